@@ -3,6 +3,8 @@
 
     python bench.py --gpus N --steps K --warmup W [--shard time|cells]      (N > 1: starts its own N ranks as a child torchrun)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...      (or under a launcher's environment)
+    python bench.py --gpus 1 --steps K --warmup W --full                    (+ CPU baseline, read ceiling, other configs, ingest)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR        (+ the last timed step's panel as DIR/<name>.npy)
 
 Workload (BASELINE.json configs[1], shapes per SURVEY.md §8d): one year of hourly ERA5-like
 2 m temperature on the 0.25 deg US-counties extent (T = 8760, 215 x 1440 = 309,600 cells,
@@ -32,11 +34,21 @@ The JSON line also carries
   roofline       the fused temporal kernel against the HBM peak: algorithmic bytes
                  (T * cells * 8 B per launch) / the kernel's mean duration,
                  measured with HIP events around every launch of the timed region; `traffic` is the
-                 PMC-measured HBM bytes per launch from profiles/traffic.json with its provenance;
+                 PMC-measured HBM bytes per launch from profiles/traffic.json with its provenance.
+A plain run stops there: set up, warm up, time the K steps, dump the outputs if asked, print the line.
+With --full (off by default) it goes on, after the timed region, to
+  read ceiling   roofline.measured_read_ceiling_GBps: a bare streaming read of the same cube (rank 0);
   cpu_baseline   the plain-C port of the reference's numba engine (oracle/c) timed on this
                  box's host cores on a bounded sample of the same workload (rank 0, N = 1);
   other_configs  (N = 1) the other four BASELINE configs, a few steps each, kernel time and roofline;
   ingest         (N = 1) the configs[0] store read from RAM into HBM, chunks decoded in HBM / on the host threads.
+--no-cpu-baseline / --no-other-configs / --no-ingest leave single parts of --full out.
+
+--dump-outputs DIR writes what the last timed step handed its caller, float64, as DIR/<name>.npy (rank 0):
+res.npy (the divided region x period panel [K, R, P]; for --shard time on N > 1 the gathered [N, K, R, P]),
+num.npy and den.npy (the weighted sums before the divide; for --shard cells summed over the ranks).  The
+inputs are seeded, so the same arguments give the same inputs on every run.  An array past its share of
+DUMP_BUDGET_BYTES is written as a fixed seeded sample of its elements (flattened) instead.
 """
 import argparse
 import hashlib
@@ -53,6 +65,20 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # RCCL across proc
 
 HBM_PEAK_GBPS = 8000.0       # MI355X spec peak (MI355X_MICROARCH.md); ~6290 GB/s measured copy rate
 VALU_PEAK_LANE_INST = 256 * 4 * 16 * 2.4e9       # fp64 VALU issue peak: 256 CUs x 4 SIMDs x 16 fp64 lanes per clock x 2.4 GHz
+DUMP_BUDGET_BYTES = 64 << 20                     # --dump-outputs: all arrays together
+
+
+def dump_outputs(out_dir, arrays):
+    """Write ``arrays`` (name -> tensor / array) as float64 ``out_dir/<name>.npy``.  An array larger than its even share of
+    DUMP_BUDGET_BYTES is written as a fixed sample of its flattened elements (seeded: the same indices on every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1) // 8
+    for name, a in arrays.items():
+        a = a.detach().double().cpu().numpy() if hasattr(a, "detach") else np.asarray(a, dtype=np.float64)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(20260101).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def c2_columns():
@@ -534,10 +560,15 @@ def main():
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--shard", default="time", choices=["time", "cells"],
                     help="N > 1: time = one year per GPU + all-gather (weak scaling); cells = latitude bands of one year + all-reduce (strong)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
-    ap.add_argument("--no-ingest", action="store_true", help="skip the store -> HBM figure (N = 1, after other_configs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: read ceiling, CPU baseline, other configs and ingest (a plain run measures the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without the other configs (and ingest)")
+    ap.add_argument("--no-ingest", action="store_true", help="--full without the store -> HBM figure (N = 1, after other_configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float64, rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -664,10 +695,10 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     kms = plan.profile_end()
-    # outside the timed region: this box's streaming-read ceiling for the very cube the kernel just read — ten back-to-back launches of
-    # the library's probe kernel (the temporal kernel's access pattern, no arithmetic: afhip_read_probe) by HIP events
+    # outside the timed region (--full): this box's streaming-read ceiling for the very cube the kernel just read — ten back-to-back
+    # launches of the library's probe kernel (the temporal kernel's access pattern, no arithmetic: afhip_read_probe) by HIP events
     probe_ms = []
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             probe_ms = hip.read_probe(cube, 10)
         except Exception as e:      # a measuring aid must never take the headline down with it
@@ -681,6 +712,13 @@ def main():
     if cells_mode and world == 1:
         if not torch.equal(torch.nan_to_num(full), torch.nan_to_num(outs[b]["res"])):
             raise SystemExit("cell arm: the divided panel differs from the plan's own result")
+    if args.dump_outputs and rank == 0:
+        if cells_mode:
+            dumped = {"res": full, "num": flat[:K * R].view(K, R, 1), "den": flat[K * R:].view(R, 1)}
+        else:
+            dumped = {"res": gathered[b] if use_flat else (torch.stack(gathered[b]) if world > 1 else outs[b]["res"]),
+                      "num": outs[b]["num"], "den": outs[b]["den"]}
+        dump_outputs(args.dump_outputs, dumped)
     tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -751,7 +789,7 @@ def main():
                                                       "frac_of_spec_peak": ceiling / HBM_PEAK_GBPS, "denominator_of_frac": "8000 GB/s spec peak"}})
         if world > 1 and len({i[:2] for i in idents}) < world:
             line["warning"] = "ranks shared a GPU (gloo rehearsal): not a scaling measurement"
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # both CPU engines of the reference, restated (oracle/): the faster one is THE baseline
             cands = []
             for fn in (cpu_baseline, cpu_baseline_dask_path):
@@ -765,7 +803,7 @@ def main():
             if cands[0]["value"] and cands[1]["value"]:
                 line["cpu_baseline"]["sample"] += (f" | the faster of two restatements of the reference's CPU engines ({cands[0]['value'] / cands[1]['value']:.1f}x the "
                                                    "other, see cpu_baseline_other_engine); a stated baseline, not the target")
-        if world == 1 and not args.no_other_configs and (T, ny, nx) == (8760, 215, 1440):
+        if world == 1 and args.full and not args.no_other_configs and (T, ny, nx) == (8760, 215, 1440):
             del cube
             torch.cuda.empty_cache()
             line["other_configs"] = run_other_configs(torch)

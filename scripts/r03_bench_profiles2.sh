@@ -12,7 +12,7 @@ done
 export AGGFLY_BENCH_ONLY=C5
 for set in "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAVES SQ_INSTS_SALU" "GRBM_GUI_ACTIVE"; do
   n=$(echo $set | cut -d' ' -f1)
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $o/pmc_bench_${tag}_c5_$n -o p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $o/pmc_bench_${tag}_c5_$n.log 2>&1 || echo "pass $n failed"
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $o/pmc_bench_${tag}_c5_$n -o p -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $o/pmc_bench_${tag}_c5_$n.log 2>&1 || echo "pass $n failed"
 done
 unset AGGFLY_BENCH_ONLY
 python3 scripts/pmc_bench_post.py $tag > $o/pmc_post_$tag.log 2>&1
@@ -26,6 +26,6 @@ for src, dst in (("$o/traffic_$tag.json", "profiles/traffic.json"), ("$o/valu_co
     except Exception as e:
         print("not merged:", src, e)
 PY
-python bench.py > $o/bench_$tag.json 2> $o/bench_$tag.err; tail -c 400 $o/bench_$tag.err; head -c 600 $o/bench_$tag.json; echo
+python bench.py --full > $o/bench_$tag.json 2> $o/bench_$tag.err; tail -c 400 $o/bench_$tag.err; head -c 600 $o/bench_$tag.json; echo
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/rp_bench_$tag -o p -- python3 bench.py --steps 20 --no-cpu-baseline --no-other-configs > $o/rp_bench_$tag.log 2>&1
 python3 scripts/pmc_bench_post.py $tag | head -12

@@ -3,7 +3,7 @@
 cfg=$1; o=gpurun_out/r03; mkdir -p $o
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 export AGGFLY_BENCH_ONLY=$cfg
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/rp_cfg_$cfg -o p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $o/rp_cfg_$cfg.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/rp_cfg_$cfg -o p -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $o/rp_cfg_$cfg.log 2>&1
 python3 - <<PY
 import pandas as pd, glob
 f = glob.glob("$o/rp_cfg_$cfg/**/*kernel_stats.csv", recursive=True)[0]

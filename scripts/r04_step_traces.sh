@@ -1,12 +1,12 @@
 #!/bin/bash
 # round 4: what a whole bench.py step of each other_configs shape runs on the closing build — rocprofv3 --kernel-trace --stats over
-# `AGGFLY_BENCH_ONLY=<shape> python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-ingest`, engine kernels only (name, calls, average ns, total ns)
+# `AGGFLY_BENCH_ONLY=<shape> python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-ingest`, engine kernels only (name, calls, average ns, total ns)
 o=gpurun_out/r04; mkdir -p $o
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=$o/step_traces.txt; : > $out
 for cfg in C1 C3 C4 C5 C5_iid DAILY REF; do
   export AGGFLY_BENCH_ONLY=$cfg
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $o/rp_cfg_$cfg -o p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-ingest > $o/rp_cfg_$cfg.log 2>&1
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $o/rp_cfg_$cfg -o p -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-ingest > $o/rp_cfg_$cfg.log 2>&1
   echo "== $cfg" >> $out
   python3 - >> $out <<PY
 import pandas as pd, glob

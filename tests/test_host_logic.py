@@ -179,12 +179,13 @@ def test_dataset_sel_keeps_every_dimension():
         ds.interior_cells(None)
 
 
-def test_transform_dataset_and_multi_dd_keys():
+def test_transform_dataset_and_multi_dd_keys(monkeypatch):
     """`transform_dataset` / `multi_dd_to_dict` (`aggregate.py:36-78,285-303`): the eager helpers run the library's
     element-wise kernel — without a GPU they fail loudly instead of computing in numpy (their numbers are checked on
     the GPU, `test_gpu_api.py::test_dataset_transforms_run_in_the_hip_library`); the key naming is host logic."""
     from aggfly_amd.aggregate import multi_dd_to_dict, transform_dataset
     from aggfly_amd.hip import HipEngineError
+    monkeypatch.setattr(hip, "device_count", lambda: 0)          # no device visible, also where the suite runs beside a GPU
     arr, time, lat, lon = gi.dataset_360_inputs()
     ds = af.Dataset(af.DataArray(arr, ["time", "latitude", "longitude"], {"time": time, "latitude": lat, "longitude": lon}))
     for kw in (dict(transform="power", exp=[np.arange(1, 4)]), dict(transform="spline"), dict(transform="interact", inter=ds)):
