@@ -62,6 +62,13 @@ def load():
         lib.afcodec_blosc_lz4_plan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                                C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                C.POINTER(C.c_int32), C.c_void_p]
+        lib.afcodec_zstd_plan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]
+        lib.afcodec_zstd_scratch_bytes.restype = C.c_int64
+        lib.afcodec_zstd_scratch_bytes.argtypes = [C.c_int64] * 5
+        lib.afcodec_zstd_emulate.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                             C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         lib.afcodec_read_packed.argtypes = [C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
                                             C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
         _lib = lib
@@ -70,7 +77,8 @@ def load():
 
 EXPORTS = ("afcodec_last_error", "afcodec_have", "afcodec_blosc_info", "afcodec_blosc_decode", "afcodec_blosc_decode_mt", "afcodec_blosc_decode_many",
            "afcodec_blosc_decode_files", "afcodec_decode_files", "afcodec_decode_ranges",
-           "afcodec_blosc_bound", "afcodec_blosc_encode_lz4", "afcodec_zstd_decode", "afcodec_zstd_bound", "afcodec_zstd_encode", "afcodec_lz4_decode", "afcodec_blosc_lz4_plan", "afcodec_read_packed")
+           "afcodec_blosc_bound", "afcodec_blosc_encode_lz4", "afcodec_zstd_decode", "afcodec_zstd_bound", "afcodec_zstd_encode", "afcodec_lz4_decode", "afcodec_blosc_lz4_plan", "afcodec_read_packed",
+           "afcodec_zstd_plan", "afcodec_zstd_scratch_bytes", "afcodec_zstd_emulate")
 
 
 def _err(lib, what):
@@ -287,3 +295,57 @@ def blosc_lz4_plan(base: np.ndarray, comp_off, comp_size, out_off, out_size, str
             raise PlanCapacityError(f"blosc_lz4_plan: {msg}")
         raise CodecError(f"blosc_lz4_plan: chunks {bad[:8]} are malformed: {msg}")
     return int(ns.value), int(nb.value), int(tmp.value), int(maxd.value), res
+
+
+# record layouts shared with libaggfly_hip (include/aggfly_hip.h: afhip_zstd_frame, afhip_zstd_block; zstd_passes.h)
+ZSTD_FRAME = np.dtype([("dst_off", "<i8"), ("base", "<i8"), ("size", "<i8"), ("first_block", "<i4"), ("n_blocks", "<i4")])
+ZSTD_BLOCK = np.dtype([("src", "<i8"), ("lit_off", "<i8"), ("seq_off", "<i8"), ("frame", "<i4"), ("btype", "<i4"), ("csize", "<i4"),
+                       ("lit_type", "<i4"), ("lit_size", "<i4"), ("lit_src", "<i4"), ("lit_csize", "<i4"), ("n_streams", "<i4"),
+                       ("huf_desc", "<i4"), ("huf_block", "<i4"), ("nseq", "<i4"), ("seq_src", "<i4"), ("mode", "<i4", 3),
+                       ("tab_desc", "<i4", 3), ("tab_block", "<i4", 3), ("pad", "<i4")])
+
+
+class ZstdPlan:
+    """What `zstd_plan` found in a batch: record counts and the sizes of the per-batch buffers."""
+
+    def __init__(self, n_frames, n_blocks, lit_bytes, n_seqs, dec_bytes, results):
+        self.n_frames, self.n_blocks, self.lit_bytes, self.n_seqs, self.dec_bytes = n_frames, n_blocks, lit_bytes, n_seqs, dec_bytes
+        self.results = results
+
+    def scratch_bytes(self) -> int:
+        return int(load().afcodec_zstd_scratch_bytes(self.n_blocks, self.n_frames, self.lit_bytes, self.n_seqs, self.dec_bytes))
+
+
+def zstd_plan(base: np.ndarray, comp_off, comp_size, out_off, out_size, frames: np.ndarray, blocks: np.ndarray, strict: bool = True):
+    """Plan the GPU-side decode of Zstandard frames that sit in ``base`` (uint8; chunk i = ``comp_size[i]`` bytes at
+    ``comp_off[i]``, decoded to ``out_off[i]`` of the output, ``out_size[i]`` bytes): fills ``frames`` (dtype `ZSTD_FRAME`)
+    and ``blocks`` (dtype `ZSTD_BLOCK`) for `hip.zstd_decode`.  -> `ZstdPlan`; ``results[i]`` = decoded size, or
+    `E_UNSUPPORTED` for a frame the GPU route does not take (decode it on the host); malformed frames raise `CodecError`
+    (``strict=False``: they are only marked negative in ``results``)."""
+    lib = load()
+    n = len(comp_off)
+    co, cs, oo, osz = (np.ascontiguousarray(a, dtype=np.int64) for a in (comp_off, comp_size, out_off, out_size))
+    res = np.zeros(n, dtype=np.int64)
+    nf, nb, lit, nsq, dec = (C.c_int64(0) for _ in range(5))
+    assert frames.dtype == ZSTD_FRAME and blocks.dtype == ZSTD_BLOCK and base.dtype == np.uint8
+    rc = lib.afcodec_zstd_plan(base.ctypes.data, n, co.ctypes.data, cs.ctypes.data, oo.ctypes.data, osz.ctypes.data,
+                               frames.ctypes.data, len(frames), C.byref(nf), blocks.ctypes.data, len(blocks), C.byref(nb),
+                               C.byref(lit), C.byref(nsq), C.byref(dec), res.ctypes.data)
+    bad = [int(i) for i in np.nonzero((res < 0) & (res != E_UNSUPPORTED))[0]]
+    if rc and "list too small" in lib.afcodec_last_error().decode() and not bad:
+        raise PlanCapacityError(f"zstd_plan: {lib.afcodec_last_error().decode()}")
+    if strict and bad:
+        raise CodecError(f"zstd_plan: chunks {bad[:8]} are malformed: {lib.afcodec_last_error().decode()}")
+    return ZstdPlan(int(nf.value), int(nb.value), int(lit.value), int(nsq.value), int(dec.value), res)
+
+
+def zstd_emulate(base: np.ndarray, frames: np.ndarray, blocks: np.ndarray, plan: ZstdPlan, out: np.ndarray):
+    """Run the passes of the GPU decode (`hip.zstd_decode`) on this thread — the host reference of the GPU algorithm, for
+    tests.  -> (errors, pointer-jump rounds)."""
+    lib = load()
+    scratch = np.zeros(plan.scratch_bytes(), dtype=np.uint8)
+    err, rounds = C.c_int32(0), C.c_int32(0)
+    lib.afcodec_zstd_emulate(base.ctypes.data, base.nbytes, frames.ctypes.data, plan.n_frames, blocks.ctypes.data, plan.n_blocks,
+                             plan.lit_bytes, plan.n_seqs, plan.dec_bytes, scratch.ctypes.data, out.ctypes.data, C.byref(err),
+                             C.byref(rounds))
+    return int(err.value), int(rounds.value)

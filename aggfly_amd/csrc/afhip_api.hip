@@ -23,6 +23,7 @@
 #include "afhip_kernels.h"
 #include "afhip_panel_kernels.h"
 #include "afhip_lz4_kernels.h"
+#include "afhip_zstd_kernels.h"
 #include "afhip_variants.h"
 #include "afhip_sine_p2_table.h"
 
@@ -600,6 +601,54 @@ extern "C" int afhip_lz4_decode_streams(const void* comp_dev, const afhip_lz4_st
         return AFHIP_OK;
     }
     hipLaunchKernelGGL((k_lz4_streams_vec<LZ4_NEAR, false>), g, b, 0, st, c, sr, (uint8_t*)tmp_dev, (uint8_t*)out_dev, errors_dev, (long long*)nullptr);
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
+extern "C" int64_t afhip_zstd_scratch_bytes(int64_t n_blocks, int64_t n_frames, int64_t lit_bytes, int64_t n_seqs, int64_t dec_bytes) {
+    if (n_blocks < 0 || n_frames < 0 || lit_bytes < 0 || n_seqs < 0 || dec_bytes < 0) return fail(AFHIP_E_INVALID, "zstd_scratch_bytes: negative size");
+    int64_t o[9];
+    return afz_layout(n_blocks, n_frames, lit_bytes, n_seqs, dec_bytes, o);
+}
+
+extern "C" int afhip_zstd_decode(const void* comp_dev, int64_t comp_bytes, const afhip_zstd_frame* frames_dev, int64_t n_frames,
+                                 const afhip_zstd_block* blocks_dev, int64_t n_blocks, int64_t lit_bytes, int64_t n_seqs, int64_t dec_bytes,
+                                 void* scratch_dev, int64_t scratch_bytes, void* out_dev, int32_t* errors_dev, int32_t* rounds_dev,
+                                 void* stream) {
+    static_assert(sizeof(afhip_zstd_block) == sizeof(afz_block) && sizeof(afhip_zstd_frame) == sizeof(afz_frame), "record layouts");
+    if (!comp_dev || !frames_dev || !blocks_dev || !scratch_dev || !out_dev || !errors_dev || comp_bytes < 0 || n_frames < 0 ||
+        n_blocks < 0 || lit_bytes < 0 || n_seqs < 0 || dec_bytes < 0)
+        return fail(AFHIP_E_INVALID, "zstd_decode: NULL argument or negative size");
+    if (dec_bytes > 0x7fffffff || lit_bytes > 0x7fffffff || n_blocks > 0x7fffffff - 64)
+        return fail(AFHIP_E_INVALID, "zstd_decode: more than 2 GiB decoded in one batch");
+    if (scratch_bytes < afhip_zstd_scratch_bytes(n_blocks, n_frames, lit_bytes, n_seqs, dec_bytes))
+        return fail(AFHIP_E_INVALID, "zstd_decode: scratch smaller than afhip_zstd_scratch_bytes()");
+    if (n_frames == 0) return AFHIP_OK;
+    GUARD_DEVICE(pointer_device(out_dev));
+    hipStream_t st = (hipStream_t)stream;
+    afz_ctx c;
+    memset(&c, 0, sizeof c);
+    c.comp = (const uint8_t*)comp_dev; c.comp_bytes = comp_bytes;
+    c.frames = (const afz_frame*)frames_dev; c.n_frames = n_frames;
+    c.blocks = (const afz_block*)blocks_dev; c.n_blocks = n_blocks;
+    afz_bind(&c, (uint8_t*)scratch_dev, n_blocks, n_frames, lit_bytes, n_seqs, dec_bytes);
+    c.out = (uint8_t*)out_dev; c.errors = errors_dev;
+    HIP_TRY(hipMemsetAsync(c.bad, 0, (size_t)(n_frames + 64) * 4, st));
+    auto waves = [](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n + ZSTD_WG - 1) / ZSTD_WG)); };
+    hipLaunchKernelGGL(k_zstd_tables, waves(n_blocks + 1), dim3(ZSTD_WG), 0, st, c);
+    if (n_blocks) {
+        hipLaunchKernelGGL(k_zstd_literals, waves(4 * n_blocks), dim3(ZSTD_WG), 0, st, c);
+        hipLaunchKernelGGL(k_zstd_sequences, waves(n_blocks), dim3(ZSTD_WG), 0, st, c);
+    }
+    hipLaunchKernelGGL(k_zstd_frames, waves(n_frames), dim3(ZSTD_WG), 0, st, c);
+    const int R = afz_rounds_host(dec_bytes);
+    if (n_blocks) {
+        hipLaunchKernelGGL(k_zstd_fill, dim3((unsigned)n_blocks), dim3(ZSTD_WG), 0, st, c);
+        const unsigned jg = (unsigned)std::max<int64_t>(1, std::min<int64_t>((dec_bytes + ZSTD_JUMP_WG - 1) / ZSTD_JUMP_WG, 16384));
+        for (int r = 0; r < R; ++r) hipLaunchKernelGGL(k_zstd_jump, dim3(jg), dim3(ZSTD_JUMP_WG), 0, st, c, r);
+        hipLaunchKernelGGL(k_zstd_gather, dim3((unsigned)n_blocks), dim3(ZSTD_WG), 0, st, c);
+    }
+    if (rounds_dev) hipLaunchKernelGGL(k_zstd_rounds, dim3(1), dim3(ZSTD_WG), 0, st, c, R, rounds_dev);
     HIP_TRY(hipGetLastError());
     return AFHIP_OK;
 }

@@ -913,3 +913,207 @@ int64_t afcodec_zstd_encode(const void* src, int64_t n, int level, void* dst, in
     if (p_zstd_iserr(got)) return fail(AFCODEC_E_CODEC, "zstd compression failed");
     return (int64_t)got;
 }
+
+/* ---- plan of a GPU-side Zstandard decode (include/aggfly_codec.h: afcodec_zstd_plan) ----
+ * Walks the frame header, the block headers and, in compressed blocks, the literals and sequences section headers (RFC
+ * 8878 §3.1.1); of the entropy descriptions it reads only as much as gives their sizes (an FSE table description has to be
+ * walked to find where the next one begins).  Building the tables and decoding is the GPU's (zstd_passes.h). */
+#include "zstd_passes.h"
+
+static int zstd_literals_header(const uint8_t* q, int64_t bs, afz_block* k) {
+    if (bs < 1) return -1;
+    const int lt = q[0] & 3, sf = (q[0] >> 2) & 3;
+    int64_t hs, regen, comp = 0;
+    k->lit_type = lt; k->n_streams = 1; k->huf_desc = -1; k->lit_csize = 0;
+    if (lt < 2) {
+        hs = (sf & 1) == 0 ? 1 : (sf == 1 ? 2 : 3);
+        if (hs > bs) return -1;
+        regen = hs == 1 ? q[0] >> 3 : (hs == 2 ? (q[0] >> 4) + (q[1] << 4) : (q[0] >> 4) + (q[1] << 4) + ((int64_t)q[2] << 12));
+        comp = lt == 0 ? regen : 1;
+        k->lit_src = (int32_t)hs;
+    } else {
+        hs = sf < 2 ? 3 : sf + 2;
+        if (hs > bs) return -1;
+        const uint64_t h = (uint64_t)q[0] | ((uint64_t)q[1] << 8) | ((uint64_t)q[2] << 16) | (hs > 3 ? (uint64_t)q[3] << 24 : 0) |
+                           (hs > 4 ? (uint64_t)q[4] << 32 : 0);
+        const int bits = hs == 3 ? 10 : (hs == 4 ? 14 : 18);
+        regen = (int64_t)((h >> 4) & ((1u << bits) - 1));
+        comp = (int64_t)((h >> (4 + bits)) & ((1u << bits) - 1));
+        k->n_streams = sf == 0 ? 1 : 4;
+        if (hs + comp > bs) return -1;
+        int64_t desc = 0;
+        if (lt == 2) {
+            if (comp < 1) return -1;
+            const int hb = q[hs];
+            desc = hb < 128 ? 1 + hb : 1 + (hb - 127 + 1) / 2;
+            k->huf_desc = (int32_t)hs;
+        }
+        k->lit_src = (int32_t)(hs + desc);
+        k->lit_csize = (int32_t)(comp - desc);
+        if (k->lit_csize < (k->n_streams == 4 ? 10 : 1)) return -1;
+    }
+    if (regen > AFZ_BLOCK_MAX || hs + comp > bs) return -1;
+    k->lit_size = (int32_t)regen;
+    return (int)(hs + comp);
+}
+
+int afcodec_zstd_plan(const void* base, int64_t n, const int64_t* comp_off, const int64_t* comp_size, const int64_t* out_off,
+                      const int64_t* out_size, void* frames_v, int64_t cap_frames, int64_t* n_frames, void* blocks_v, int64_t cap_blocks,
+                      int64_t* n_blocks, int64_t* lit_bytes, int64_t* n_seqs, int64_t* dec_bytes, int64_t* results) {
+    afz_frame* frames = (afz_frame*)frames_v;
+    afz_block* blocks = (afz_block*)blocks_v;
+    int64_t nf = 0, nb = 0, lit = 0, nsq = 0, dec = 0;
+    int rc_all = AFCODEC_OK;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint8_t* c = (const uint8_t*)base + comp_off[i];
+        const int64_t csz = comp_size[i];
+        const int64_t nb0 = nb, lit0 = lit, nsq0 = nsq;
+        int bad = 0;
+        const char* why = "malformed frame";
+        results[i] = 0;
+#define ZBAD(code, msg) do { bad = (code); why = (msg); goto done; } while (0)
+        if (csz < 4) ZBAD(AFCODEC_E_FORMAT, "shorter than a frame header");
+        const uint32_t magic = le32(c);
+        if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) ZBAD(AFCODEC_E_UNSUPPORTED, "skippable frame: decode on the host");
+        if (magic != 0xFD2FB528u) ZBAD(AFCODEC_E_FORMAT, "not a Zstandard frame");
+        if (csz < 6) ZBAD(AFCODEC_E_FORMAT, "truncated frame header");
+        {
+            const int fhd = c[4], fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, did_flag = fhd & 3;
+            if (fhd & 0x08) ZBAD(AFCODEC_E_FORMAT, "reserved frame header bit set");
+            int64_t pos = 5 + (single ? 0 : 1);
+            const int did_size = did_flag == 0 ? 0 : (did_flag == 1 ? 1 : (did_flag == 2 ? 2 : 4));
+            const int fcs_size = fcs_flag == 0 ? (single ? 1 : 0) : (fcs_flag == 1 ? 2 : (fcs_flag == 2 ? 4 : 8));
+            if (pos + did_size + fcs_size > csz) ZBAD(AFCODEC_E_FORMAT, "truncated frame header");
+            uint64_t did = 0, fcs = 0;
+            for (int j = 0; j < did_size; ++j) did |= (uint64_t)c[pos + j] << (8 * j);
+            pos += did_size;
+            for (int j = 0; j < fcs_size; ++j) fcs |= (uint64_t)c[pos + j] << (8 * j);
+            pos += fcs_size;
+            if (fcs_size == 2) fcs += 256;
+            if (did) ZBAD(AFCODEC_E_UNSUPPORTED, "frame needs a dictionary: decode on the host");
+            if (!fcs_size) ZBAD(AFCODEC_E_UNSUPPORTED, "frame without Frame_Content_Size: decode on the host");
+            if (fhd & 0x04) ZBAD(AFCODEC_E_UNSUPPORTED, "frame with a content checksum: decode on the host");
+            if ((int64_t)fcs != out_size[i] || fcs > 0x7fffffffu)
+                ZBAD(AFCODEC_E_UNSUPPORTED, "Frame_Content_Size differs from the chunk size: decode on the host");
+            if (nf >= cap_frames) return fail(AFCODEC_E_SIZE, "frame list too small");
+            int32_t huf = -1, tmode[3] = {-1, -1, -1}, tsym[3] = {0, 0, 0}, tblk[3] = {0, 0, 0}, tdesc[3] = {0, 0, 0};
+            for (;;) {
+                if (pos + 3 > csz) ZBAD(AFCODEC_E_FORMAT, "truncated block header");
+                const uint32_t bh = (uint32_t)c[pos] | ((uint32_t)c[pos + 1] << 8) | ((uint32_t)c[pos + 2] << 16);
+                const int last = bh & 1, bt = (bh >> 1) & 3;
+                const int64_t bs = bh >> 3;
+                if (bt == 3) ZBAD(AFCODEC_E_FORMAT, "reserved block type");
+                if (bs > AFZ_BLOCK_MAX) ZBAD(AFCODEC_E_FORMAT, "block larger than 128 KiB");
+                const int64_t csize = bt == 1 ? 1 : bs;
+                pos += 3;
+                if (pos + csize > csz) ZBAD(AFCODEC_E_FORMAT, "block beyond the chunk");
+                if (nb >= cap_blocks) return fail(AFCODEC_E_SIZE, "block list too small");
+                afz_block k;
+                memset(&k, 0, sizeof k);
+                k.src = comp_off[i] + pos; k.frame = (int32_t)nf; k.btype = bt; k.csize = (int32_t)csize;
+                k.huf_desc = -1; k.huf_block = -1; k.n_streams = 1;
+                if (bt < 2) {
+                    k.lit_type = bt; k.lit_size = (int32_t)bs; k.lit_src = 0;
+                } else {
+                    const uint8_t* q = c + pos;
+                    const int ls = zstd_literals_header(q, bs, &k);
+                    if (ls < 0) ZBAD(AFCODEC_E_FORMAT, "malformed literals section header");
+                    if (k.lit_type == 2) huf = (int32_t)nb;
+                    if (k.lit_type >= 2) {
+                        if (huf < 0) ZBAD(AFCODEC_E_FORMAT, "treeless literals without an earlier Huffman table");
+                        k.huf_block = huf;
+                    }
+                    int64_t s = ls;
+                    if (s >= bs) ZBAD(AFCODEC_E_FORMAT, "no sequences section");
+                    const int b0 = q[s];
+                    if (b0 == 0) { k.nseq = 0; s += 1; if (s != bs) ZBAD(AFCODEC_E_FORMAT, "bytes after an empty sequences section"); }
+                    else {
+                        if (b0 < 128) { k.nseq = b0; s += 1; }
+                        else if (b0 < 255) { if (s + 2 > bs) ZBAD(AFCODEC_E_FORMAT, "truncated sequences header"); k.nseq = ((b0 - 128) << 8) + q[s + 1]; s += 2; }
+                        else { if (s + 3 > bs) ZBAD(AFCODEC_E_FORMAT, "truncated sequences header"); k.nseq = q[s + 1] + (q[s + 2] << 8) + 0x7F00; s += 3; }
+                        if (k.nseq > AFZ_BLOCK_MAX / 3) ZBAD(AFCODEC_E_FORMAT, "more sequences than a block holds");
+                        if (s >= bs) ZBAD(AFCODEC_E_FORMAT, "truncated sequences header");
+                        const int modes = q[s++];
+                        if (modes & 3) ZBAD(AFCODEC_E_FORMAT, "reserved bits of the compression modes set");
+                        for (int t = 0; t < 3; ++t) {
+                            const int m = (modes >> (6 - 2 * t)) & 3;
+                            if (m == 0) { tmode[t] = 0; }
+                            else if (m == 1) {
+                                if (s >= bs) ZBAD(AFCODEC_E_FORMAT, "truncated RLE symbol");
+                                if (q[s] > afz_max_sym[t]) ZBAD(AFCODEC_E_FORMAT, "RLE symbol out of range");
+                                tmode[t] = 1; tsym[t] = q[s++];
+                            } else if (m == 2) {
+                                int16_t norm[64];
+                                int nsym, lg;
+                                const int used = afz_read_ncount(q + s, bs - s, norm, afz_max_sym[t], afz_max_log[t], &nsym, &lg);
+                                if (used < 0) ZBAD(AFCODEC_E_FORMAT, "malformed FSE table description");
+                                tmode[t] = 2; tblk[t] = (int32_t)nb; tdesc[t] = (int32_t)s;
+                                s += used;
+                            } else if (tmode[t] < 0) ZBAD(AFCODEC_E_FORMAT, "repeat mode without an earlier table");
+                            k.mode[t] = tmode[t];
+                            k.tab_desc[t] = tmode[t] == 1 ? tsym[t] : (tmode[t] == 2 ? tdesc[t] : 0);
+                            k.tab_block[t] = tmode[t] == 2 ? tblk[t] : -1;
+                        }
+                        if (s >= bs) ZBAD(AFCODEC_E_FORMAT, "no sequences bitstream");
+                    }
+                    k.seq_src = (int32_t)s;
+                }
+                k.lit_off = lit; k.seq_off = nsq;
+                lit += k.lit_size; nsq += k.nseq;
+                if (lit - lit0 + 3 * (nsq - nsq0) > (int64_t)fcs)      /* (every sequence adds a match of 3 bytes or more) */
+                    ZBAD(AFCODEC_E_FORMAT, "more literals and sequences than Frame_Content_Size holds");
+                blocks[nb++] = k;
+                pos += csize;
+                if (last) break;
+            }
+            if (pos != csz) ZBAD(AFCODEC_E_UNSUPPORTED, "bytes after the frame (another frame?): decode on the host");
+            frames[nf++] = (afz_frame){out_off[i], dec, (int64_t)fcs, (int32_t)nb0, (int32_t)(nb - nb0)};
+            dec += (int64_t)fcs;
+            results[i] = (int64_t)fcs;
+        }
+    done:
+#undef ZBAD
+        if (bad) {
+            nb = nb0; lit = lit0; nsq = nsq0;
+            results[i] = bad;
+            rc_all = fail(bad, why);
+        }
+    }
+    *n_frames = nf; *n_blocks = nb; *lit_bytes = lit; *n_seqs = nsq; *dec_bytes = dec;
+    return rc_all;
+}
+
+int64_t afcodec_zstd_scratch_bytes(int64_t n_blocks, int64_t n_frames, int64_t lit_bytes, int64_t n_seqs, int64_t dec_bytes) {
+    int64_t o[9];
+    return afz_layout(n_blocks, n_frames, lit_bytes, n_seqs, dec_bytes, o);
+}
+
+/* The passes of the GPU decode (zstd_passes.h) run in order on this thread: the host reference of afhip_zstd_decode. */
+int afcodec_zstd_emulate(const void* comp, int64_t comp_bytes, const void* frames, int64_t n_frames, const void* blocks,
+                         int64_t n_blocks, int64_t lit_bytes, int64_t n_seqs, int64_t dec_bytes, void* scratch, void* out,
+                         int32_t* errors, int32_t* rounds) {
+    afz_ctx x;
+    memset(&x, 0, sizeof x);
+    x.comp = (const uint8_t*)comp; x.comp_bytes = comp_bytes;
+    x.frames = (const afz_frame*)frames; x.n_frames = n_frames;
+    x.blocks = (const afz_block*)blocks; x.n_blocks = n_blocks;
+    afz_bind(&x, (uint8_t*)scratch, n_blocks, n_frames, lit_bytes, n_seqs, dec_bytes);
+    x.out = (uint8_t*)out; x.errors = errors;
+    memset(x.bad, 0, (size_t)(n_frames + 64) * 4);
+    for (int64_t b = 0; b <= n_blocks; ++b) afz_pass_tables(&x, b);
+    for (int64_t b = 0; b < n_blocks; ++b)
+        for (int q = 0; q < 4; ++q) afz_pass_literals(&x, b, q, NULL);
+    for (int64_t b = 0; b < n_blocks; ++b) afz_pass_sequences(&x, b);
+    for (int64_t f = 0; f < n_frames; ++f) afz_pass_frame(&x, f);
+    for (int64_t b = 0; b < n_blocks; ++b) afz_pass_fill(&x, b, 0, 1);
+    const int R = afz_rounds_host(dec_bytes);
+    int r = 0;
+    for (; r < R && x.flags[r]; ++r) {
+        int more = 0;
+        for (int64_t p = 0; p < dec_bytes; ++p) more |= afz_jump(&x, p);
+        x.flags[r + 1] = more;
+    }
+    for (int64_t b = 0; b < n_blocks; ++b) afz_pass_gather(&x, b, 0, 1);
+    if (rounds) *rounds = r;
+    return AFCODEC_OK;
+}

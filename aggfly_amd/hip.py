@@ -35,6 +35,7 @@ EXPORTS = (
     "afhip_plan_create", "afhip_plan_destroy", "afhip_plan_workspace_bytes", "afhip_plan_run_workspace_bytes",
     "afhip_plan_describe", "afhip_plan_run_temporal", "afhip_plan_run",
     "afhip_plan_profile_begin", "afhip_plan_profile_end", "afhip_plan_bind_inter", "afhip_csr_device", "afhip_plan_device", "afhip_transform", "afhip_panel_divide", "afhip_lz4_decode_streams", "afhip_unshuffle_blocks", "afhip_read_probe",
+    "afhip_zstd_scratch_bytes", "afhip_zstd_decode",
 )
 
 
@@ -112,6 +113,9 @@ def load():
     lib.afhip_panel_divide.argtypes = [vp, vp, vp, i64, i64, i64, vp]
     lib.afhip_lz4_decode_streams.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
     lib.afhip_unshuffle_blocks.argtypes = [vp, vp, vp, i64, i32, vp]
+    lib.afhip_zstd_scratch_bytes.restype = i64
+    lib.afhip_zstd_scratch_bytes.argtypes = [i64] * 5
+    lib.afhip_zstd_decode.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, i64, vp, i64, vp, vp, vp, vp]
     lib.afhip_plan_profile_begin.argtypes = [vp, i64]
     lib.afhip_plan_profile_end.argtypes = [vp, C.POINTER(C.c_float), i64]
     lib.afhip_plan_profile_end.restype = i64
@@ -175,6 +179,24 @@ def lz4_decode_streams(comp, streams, n_streams: int, max_dsize: int, tmp, out, 
     streams bump the int32 HBM counter ``errors``."""
     _check(load().afhip_lz4_decode_streams(comp.data_ptr(), streams.data_ptr(), int(n_streams), int(max_dsize),
                                            tmp.data_ptr() if tmp is not None else None, out.data_ptr(), errors.data_ptr(), _stream_ptr(comp)))
+
+
+def zstd_scratch_bytes(plan) -> int:
+    """`afhip_zstd_scratch_bytes` for a `codec.ZstdPlan`."""
+    n = int(load().afhip_zstd_scratch_bytes(plan.n_blocks, plan.n_frames, plan.lit_bytes, plan.n_seqs, plan.dec_bytes))
+    if n < 0:
+        _check(n)
+    return n
+
+
+def zstd_decode(comp, comp_bytes: int, frames, blocks, plan, scratch, out, errors, rounds=None):
+    """`afhip_zstd_decode`: decode the Zstandard frames planned by `codec.zstd_plan` (``frames`` / ``blocks``: uint8 HBM tensors
+    holding the records, ``comp``: the batch's compressed bytes in HBM) into ``out``; ``scratch``: a uint8 HBM tensor of
+    `zstd_scratch_bytes(plan)` bytes; damaged frames count in ``errors`` (int32), ``rounds`` (int32, optional) receives the
+    pointer-jump rounds that had work."""
+    _check(load().afhip_zstd_decode(comp.data_ptr(), int(comp_bytes), frames.data_ptr(), plan.n_frames, blocks.data_ptr(), plan.n_blocks,
+                                    plan.lit_bytes, plan.n_seqs, plan.dec_bytes, scratch.data_ptr(), scratch.numel(), out.data_ptr(),
+                                    errors.data_ptr(), rounds.data_ptr() if rounds is not None else None, _stream_ptr(comp)))
 
 
 def unshuffle_blocks(tmp, out, blocks, n_blocks: int, max_bsize: int):

@@ -538,8 +538,8 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
             return _stream_chunks_scatter(za, device, threads, slab_bytes, post if need_post else None, out_np, t_range, yx_box), za
         if not whole_rows and za.native_kind is not None:
             return _stream_chunks_scatter(za, device, threads, slab_bytes, post if need_post else None, out_np), za
-        if za.native_kind == "blosc" and _gpu_decodable(za, T * ny * nx * za.dtype.itemsize):
-            # Blosc-LZ4 chunks cross PCIe compressed and are decoded in HBM: the scatter route, whatever the chunk grid
+        if za.native_kind in ("blosc", "zstd") and _gpu_decodable(za, T * ny * nx * za.dtype.itemsize):
+            # Blosc-LZ4 / Zstandard chunks cross PCIe compressed and are decoded in HBM: the scatter route, whatever the chunk grid
             return _stream_chunks_scatter(za, device, threads, slab_bytes, post if need_post else None, out_np), za
         return stream_to_device(T, (ny, nx), za.dtype, read, slab, device, post if need_post else None, out_np), za
     finally:
@@ -549,6 +549,7 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
 
 GPU_DECODE_AUTO_BYTES = 96 << 20                  # requests this large take the decode-in-HBM route (round 2: 256 MB) ...
 GPU_DECODE_AUTO_BYTES_WHOLE_ROWS = 256 << 20      # ... also when every chunk holds whole time steps of the grid (round 2: 768 MB; see _gpu_decodable)
+GPU_DECODE_AUTO_BYTES_ZSTD = 100 << 20            # Zstandard stores: requests this large (any chunk grid; profiles/zstd_ingest.txt)
 
 
 def _gpu_decodable(za, request_bytes: int = 0) -> bool:
@@ -564,8 +565,10 @@ def _gpu_decodable(za, request_bytes: int = 0) -> bool:
     16 host threads; a small request is over before the decode kernel's ~2 ms (one wave walks one stream) are."""
     mode = os.environ.get("AGGFLY_HIP_GPU_DECODE", "auto")
     whole_rows = len(za.shape) == 3 and tuple(za.chunks[1:]) == tuple(za.shape[1:])
-    if mode == "0" or za.native_kind != "blosc" or (mode != "1" and request_bytes < (GPU_DECODE_AUTO_BYTES_WHOLE_ROWS if whole_rows
-                                                                                      else GPU_DECODE_AUTO_BYTES)):
+    # plain Zstandard frames (`hip.zstd_decode`): from `GPU_DECODE_AUTO_BYTES_ZSTD` on under auto, chunks below 1 GiB (a batch's bound)
+    zstd = za.native_kind == "zstd"
+    auto_bytes = GPU_DECODE_AUTO_BYTES_ZSTD if zstd else (GPU_DECODE_AUTO_BYTES_WHOLE_ROWS if whole_rows else GPU_DECODE_AUTO_BYTES)
+    if mode == "0" or za.native_kind not in ("blosc", "zstd") or (mode != "1" and request_bytes < auto_bytes) or (zstd and za.chunk_nbytes >= 1 << 30):
         return False
     hit = getattr(za, "_gpu_decodable", None)
     if hit is not None:
@@ -578,8 +581,10 @@ def _gpu_decodable(za, request_bytes: int = 0) -> bool:
                 continue
             with open(loc[0], "rb") as f:
                 f.seek(loc[1])
-                h = f.read(16)
-            if len(h) == 16 and h[0] == 2:
+                h = f.read(18 if zstd else 16)
+            if zstd:
+                ok = _zstd_frame_taken(h, za.chunk_nbytes)
+            elif len(h) == 16 and h[0] == 2:
                 flags, ts = h[2], h[3]
                 nbytes, blocksize = int.from_bytes(h[4:8], "little"), int.from_bytes(h[8:12], "little")
                 ok = bool(flags & 0x02) or (((flags >> 5) & 7) == 1 and not (flags & 0x04) and blocksize > 0 and nbytes == za.chunk_nbytes
@@ -593,6 +598,23 @@ def _gpu_decodable(za, request_bytes: int = 0) -> bool:
     except AttributeError:
         pass
     return ok
+
+
+def _zstd_frame_taken(h: bytes, nbytes: int) -> bool:
+    """A Zstandard frame header (the first 18 bytes of a chunk) that `afcodec_zstd_plan` takes: no checksum, no dictionary,
+    a Frame_Content_Size equal to the chunk's decoded size."""
+    if len(h) < 6 or int.from_bytes(h[:4], "little") != 0xFD2FB528:
+        return False
+    fhd = h[4]
+    fcs_flag, single, did_flag = fhd >> 6, (fhd >> 5) & 1, fhd & 3
+    if fhd & 0x0C or did_flag:
+        return False
+    fcs_size = (1 if single else 0) if fcs_flag == 0 else (2, 4, 8)[fcs_flag - 1]
+    pos = 5 + (0 if single else 1)
+    if fcs_size == 0 or len(h) < pos + fcs_size:
+        return False
+    fcs = int.from_bytes(h[pos:pos + fcs_size], "little") + (256 if fcs_size == 2 else 0)
+    return fcs == nbytes
 
 
 class _ScatterJob:
@@ -750,7 +772,8 @@ def _scatter_host_decode(job: _ScatterJob, threads: int, slab_bytes: int, post):
     return job.cube
 
 
-def _decode_batches(n_chunks: int, cb: int, nblk: int, whole_steps: bool):
+def _decode_batches(n_chunks: int, cb: int, nblk: int, whole_steps: bool, max_per: int = 4096, target_bytes: int = 144 << 20,
+                    max_bytes: int = 512 << 20):
     """How `_scatter_gpu_decode` cuts a request of ``n_chunks`` chunks (``cb`` decoded bytes, ``nblk`` Blosc blocks each):
     -> (cuts: batch boundaries over the chunks that cross PCIe compressed, per: chunks of the largest batch, n_tail: chunks at the
     request's end that the host threads decode)."""
@@ -776,9 +799,9 @@ def _decode_batches(n_chunks: int, cb: int, nblk: int, whole_steps: bool):
         n_tail = 0
     n = n_chunks - n_tail                                 # chunks that cross PCIe compressed
     total = n * cb
-    n_batches = min(16, max(1, -(-total // (144 << 20))))
-    batch_bytes = (int(env_mb) << 20) if env_mb else min(-(-total // n_batches), 512 << 20)
-    per = max(1, min(-(-batch_bytes // cb), 65535 // nblk, 4096, max(n, 1)))
+    n_batches = min(16, max(1, -(-total // target_bytes)))
+    batch_bytes = (int(env_mb) << 20) if env_mb else min(-(-total // n_batches), max_bytes)
+    per = max(1, min(-(-batch_bytes // cb), 65535 // nblk, max_per, max(n, 1)))
     n_batches = max(1, -(-n // per))
     cuts = sorted(set(int(round(i * n / n_batches)) for i in range(n_batches + 1)))
     per = max([b - a for a, b in zip(cuts, cuts[1:])] or [1])
@@ -789,28 +812,130 @@ def _decode_batches(n_chunks: int, cb: int, nblk: int, whole_steps: bool):
     return cuts, per, n_tail
 
 
+class _Lz4Route:
+    """The codec half of the decode-in-HBM route for Blosc-1 chunks of LZ4 streams: the record lists of
+    `codec.blosc_lz4_plan` (streams, shuffled blocks), `hip.lz4_decode_streams` + `hip.unshuffle_blocks`."""
+
+    what = "LZ4 stream(s)"
+
+    def __init__(self, job):
+        bsz, self.tsz = getattr(job.za, "_blosc_geometry", (65536, 1))
+        self.cb = job.cb
+        self.nblk = max(1, -(-job.cb // bsz))
+        self.max_per, self.target_bytes, self.max_bytes = 4096, 144 << 20, 512 << 20
+
+    def size(self, per, nstage, device):
+        import torch
+        from . import codec
+        cb, nblk = self.cb, self.nblk
+        self.cmax = (int(codec.load().afcodec_blosc_bound(cb, 0)) + 63) // 64 * 64
+        self.cap_streams = per * (nblk * self.tsz + cb // 65536 + 2)          # one stream per byte plane of a block; stored chunks in 64 KiB pieces
+        self.cap_blocks = per * nblk
+        self.rec_bytes = self.cap_streams * codec.LZ4_STREAM.itemsize + self.cap_blocks * codec.SHUFFLE_BLOCK.itemsize
+        self.tmp_dev = [torch.empty(per * (cb + 16 * nblk + 16), dtype=torch.uint8, device=device) for _ in range(nstage)]
+
+    def plan(self, k, hall, rec0, offs, sizes, present, out_offs):
+        """Records of a batch into the page-locked slot behind its compressed bytes -> the byte ranges of the slot to upload."""
+        from . import codec
+        streams = hall[rec0:rec0 + self.cap_streams * codec.LZ4_STREAM.itemsize].view(codec.LZ4_STREAM)
+        bl0 = rec0 + streams.nbytes
+        blocks = hall[bl0:bl0 + self.cap_blocks * codec.SHUFFLE_BLOCK.itemsize].view(codec.SHUFFLE_BLOCK)
+        try:
+            n_st, n_bl, tmp_bytes, max_d, pres = codec.blosc_lz4_plan(hall, offs[:-1][present], sizes[present], out_offs,
+                                                                        np.full(len(present), self.cb, dtype=np.int64), streams, blocks)
+        except codec.PlanCapacityError:
+            raise _NotForTheGpuRoute() from None
+        if (pres == codec.E_UNSUPPORTED).any() or tmp_bytes > self.tmp_dev[k].numel() or n_st > self.cap_streams or n_bl > self.cap_blocks:
+            # a chunk the GPU decoder does not take (aggfly_codec.h: "decode it on the host"), or one whose geometry differs
+            # from the first chunk's, which sized the buffers: the request falls back to the host route
+            raise _NotForTheGpuRoute()
+        self.rec0, self.bl0, self.n_st, self.n_bl, self.max_d = rec0, bl0, n_st, n_bl, max_d
+        self.max_bsize = int(blocks["bsize"][:n_bl].max()) if n_bl else 0
+        ranges = [(0, rec0 + n_st * codec.LZ4_STREAM.itemsize)]                              # compressed bytes + stream records: one copy
+        if n_bl:
+            ranges.append((bl0, bl0 + n_bl * codec.SHUFFLE_BLOCK.itemsize))
+        return pres, ranges
+
+    def decode(self, k, comp, target, errors):
+        from . import hip
+        if self.n_st:
+            hip.lz4_decode_streams(comp, comp[self.rec0:], self.n_st, self.max_d, self.tmp_dev[k], target, errors)
+        if self.n_bl:
+            hip.unshuffle_blocks(self.tmp_dev[k], target, comp[self.bl0:], self.n_bl, self.max_bsize)
+
+
+class _ZstdRoute:
+    """The codec half of the decode-in-HBM route for plain Zstandard frames: the frame and block records of
+    `codec.zstd_plan`, `hip.zstd_decode` with a scratch per slot (grown on the slot's stream when a batch needs more).
+    Batches decode at most 1 GiB (the scratch's byte map is ~4 bytes per decoded byte)."""
+
+    what = "Zstandard frame(s)"
+
+    def __init__(self, job):
+        self.cb = job.cb
+        self.nblk = 1
+        # large batches: every pass is a thread (or a wave) per block, latency-bound, and a batch of one 265 MB frame fills
+        # only ~125 waves of the card (profiles/zstd_ingest.txt)
+        self.max_per = max(1, min(4096, (1 << 30) // job.cb))
+        self.target_bytes = self.max_bytes = 1 << 30
+
+    def size(self, per, nstage, device):
+        from . import codec
+        cb = self.cb
+        self.cmax = (int(codec.load().afcodec_zstd_bound(cb)) + 63) // 64 * 64
+        self.cap_frames = per
+        self.cap_blocks = per * (cb // 16384 + 4)          # libzstd writes 128 KiB blocks: 8x headroom, more goes to the host
+        self.rec_bytes = (self.cap_frames * codec.ZSTD_FRAME.itemsize + 63) // 64 * 64 + self.cap_blocks * codec.ZSTD_BLOCK.itemsize
+        self.device = device
+        self.scratch = [None] * nstage
+        self.rounds = None
+
+    def plan(self, k, hall, rec0, offs, sizes, present, out_offs):
+        from . import codec
+        frames = hall[rec0:rec0 + self.cap_frames * codec.ZSTD_FRAME.itemsize].view(codec.ZSTD_FRAME)
+        bl0 = rec0 + (frames.nbytes + 63) // 64 * 64
+        blocks = hall[bl0:bl0 + self.cap_blocks * codec.ZSTD_BLOCK.itemsize].view(codec.ZSTD_BLOCK)
+        try:
+            pl = codec.zstd_plan(hall, offs[:-1][present], sizes[present], out_offs, np.full(len(present), self.cb, dtype=np.int64),
+                                 frames, blocks)
+        except codec.PlanCapacityError:
+            raise _NotForTheGpuRoute() from None
+        if (pl.results == codec.E_UNSUPPORTED).any():
+            raise _NotForTheGpuRoute()             # a checksum, a dictionary, another frame: aggfly_codec.h's "decode it on the host"
+        self.plan_, self.rec0, self.bl0 = pl, rec0, bl0
+        return pl.results, [(0, rec0 + pl.n_frames * codec.ZSTD_FRAME.itemsize), (bl0, bl0 + pl.n_blocks * codec.ZSTD_BLOCK.itemsize)]
+
+    def decode(self, k, comp, target, errors):
+        import torch
+        from . import hip
+        need = hip.zstd_scratch_bytes(self.plan_)
+        if self.scratch[k] is None or self.scratch[k].numel() < need:
+            self.scratch[k] = None
+            self.scratch[k] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if self.rounds is None and os.environ.get("AGGFLY_HIP_INGEST_TRACE") == "1":
+            self.rounds = torch.zeros(1, dtype=torch.int32, device=self.device)
+        hip.zstd_decode(comp, self.rec0, comp[self.rec0:], comp[self.bl0:], self.plan_, self.scratch[k], target, errors, self.rounds)
+
+
 def _scatter_gpu_decode(job: _ScatterJob, threads: int, post):
-    """Blosc-LZ4 chunks cross PCIe compressed: per batch the host reads the chunk files as they are into a
-    page-locked slot and parses the containers into the record lists (`codec.blosc_lz4_plan`); one upload carries the
-    compressed bytes and the records; `hip.lz4_decode_streams` + `hip.unshuffle_blocks` decode on the slot's stream —
-    straight into the cube when every chunk of the batch holds whole time steps of the window, else into a staging
-    buffer that `job.place` empties.  The page-locked slot is free again when its upload is over; the device-side one
-    is handed from the kernels to the slot's next upload by an event."""
+    """Blosc-LZ4 chunks or Zstandard frames cross PCIe compressed: per batch the host reads the chunk files as
+    they are into a page-locked slot and walks their headers into the codec's record lists (`_Lz4Route`, `_ZstdRoute`); one
+    upload carries the compressed bytes and the records; the codec's kernels decode on the slot's stream — straight into the
+    cube when every chunk of the batch holds whole time steps of the window, else into a staging buffer that `job.place`
+    empties.  The page-locked slot is free again when its upload is over; the device-side one is handed from the kernels to
+    the slot's next upload by an event."""
     import torch
-    from . import codec, hip
+    from . import codec
     za, device, cb, idxs, cube = job.za, job.device, job.cb, job.idxs, job.cube
-    bsz, tsz = getattr(za, "_blosc_geometry", (65536, 1))
-    nblk = max(1, -(-cb // bsz))
-    cuts, per, n_tail = _decode_batches(len(idxs), cb, nblk, job.whole_steps)
+    route = _ZstdRoute(job) if za.native_kind == "zstd" else _Lz4Route(job)
+    cuts, per, n_tail = _decode_batches(len(idxs), cb, route.nblk, job.whole_steps, route.max_per, route.target_bytes, route.max_bytes)
     all_idxs, idxs = idxs, idxs[:len(idxs) - n_tail]
     # staging slots in flight: 4 (3 measured 7 % slower), 6 when every batch is one big chunk (the converter's 265 MB chunks)
     nstage = max(1, min(int(os.environ.get("AGGFLY_HIP_GPU_DECODE_SLOTS", "6" if per == 1 else "4")), len(cuts) - 1))
     cube_bytes = cube.view(torch.uint8).reshape(-1) if job.whole_steps else None
-    # compressed bytes + the two record lists of a batch share one page-locked slot and one upload
-    cmax = (int(codec.load().afcodec_blosc_bound(cb, 0)) + 63) // 64 * 64
-    cap_streams = per * (nblk * tsz + cb // 65536 + 2)          # one stream per byte plane of a block; stored chunks in 64 KiB pieces
-    cap_blocks = per * nblk
-    rec_bytes = cap_streams * codec.LZ4_STREAM.itemsize + cap_blocks * codec.SHUFFLE_BLOCK.itemsize
+    # compressed bytes + the record lists of a batch share one page-locked slot and one upload
+    route.size(per, nstage, device)
+    cmax, rec_bytes = route.cmax, route.rec_bytes
     # (the page-locked buffers are cached per size class: the tail's is one MORE of the slots' class when the two coincide)
     cls = lambda n: 1 << max(20, (int(n) - 1).bit_length())
     shared = n_tail > 0 and cls(n_tail * cb) == cls(per * cmax + rec_bytes)
@@ -818,7 +943,6 @@ def _scatter_gpu_decode(job: _ScatterJob, threads: int, post):
     thost = host[nstage] if shared else (_pinned_stage(n_tail * cb, 1, device)[0] if n_tail else None)
     host = host[:nstage]
     comp_dev = [torch.empty(per * cmax + rec_bytes, dtype=torch.uint8, device=device) for _ in range(nstage)]
-    tmp_dev = [torch.empty(per * (cb + 16 * nblk + 16), dtype=torch.uint8, device=device) for _ in range(nstage)]
     staged = [None] * nstage                             # decoded chunks of batches that cannot go straight into the cube
     errors = torch.zeros(1, dtype=torch.int32, device=device)
     copy_stream = torch.cuda.Stream(device=device)
@@ -844,7 +968,7 @@ def _scatter_gpu_decode(job: _ScatterJob, threads: int, post):
             ws.synchronize()
 
     try:
-        _gpu_decode_batches(job, threads, cuts, per, cmax, cap_streams, cap_blocks, nstage, host, comp_dev, tmp_dev, staged, errors,
+        _gpu_decode_batches(job, threads, cuts, per, cmax, route, nstage, host, comp_dev, staged, errors,
                             copy_stream, work_streams, done, uploaded, trace, cube_bytes)
         if n_tail:
             tail = all_idxs[len(idxs):]
@@ -872,19 +996,20 @@ def _scatter_gpu_decode(job: _ScatterJob, threads: int, post):
     last.synchronize()
     copy_stream.synchronize()
     trace.drained()
-    trace.report(origin, gpu_decode=True, batches=len(cuts) - 1, chunks_per_batch=per)
+    extra = {"zstd_jump_rounds": int(route.rounds.item())} if getattr(route, "rounds", None) is not None else {}
+    trace.report(origin, gpu_decode=True, batches=len(cuts) - 1, chunks_per_batch=per, **extra)
     if int(errors.item()):
-        raise codec.CodecError(f"{int(errors.item())} LZ4 stream(s) of {za.path} are malformed (GPU decode); "
+        raise codec.CodecError(f"{int(errors.item())} {route.what} of {za.path} are malformed (GPU decode); "
                                "AGGFLY_HIP_GPU_DECODE=0 decodes on the host and names the chunk")
     torch.cuda.current_stream(device).wait_stream(last)
     return cube
 
 
-def _gpu_decode_batches(job, threads, cuts, per, cmax, cap_streams, cap_blocks, nstage, host, comp_dev, tmp_dev, staged, errors,
+def _gpu_decode_batches(job, threads, cuts, per, cmax, route, nstage, host, comp_dev, staged, errors,
                         copy_stream, work_streams, done, uploaded, trace, cube_bytes):
     """The batch loop of `_scatter_gpu_decode` (which drains the streams if anything here raises)."""
     import torch
-    from . import codec, hip
+    from . import codec
     za, device, cb, idxs = job.za, job.device, job.cb, job.idxs
     for b, (lo, hi) in enumerate(zip(cuts[:-1], cuts[1:])):
         batch = idxs[lo:hi]
@@ -900,21 +1025,10 @@ def _gpu_decode_batches(job, threads, cuts, per, cmax, cap_streams, cap_blocks, 
         trace.lap("read")
         present = np.nonzero(sizes != -100)[0]
         rec0 = int(offs[-1])
-        streams = hall[rec0:rec0 + cap_streams * codec.LZ4_STREAM.itemsize].view(codec.LZ4_STREAM)
-        bl0 = rec0 + streams.nbytes
-        blocks = hall[bl0:bl0 + cap_blocks * codec.SHUFFLE_BLOCK.itemsize].view(codec.SHUFFLE_BLOCK)
         direct = job.whole_steps and all(job.inside(it) for it, _, _ in batch)
         out_offs = (np.array([batch[i][0] * job.tc - job.ka for i in present], dtype=np.int64) * job.step_bytes if direct
                     else present.astype(np.int64) * cb)
-        try:
-            n_st, n_bl, tmp_bytes, max_d, pres = codec.blosc_lz4_plan(hall, offs[:-1][present], sizes[present], out_offs,
-                                                                        np.full(len(present), cb, dtype=np.int64), streams, blocks)
-        except codec.PlanCapacityError:
-            raise _NotForTheGpuRoute() from None
-        if (pres == codec.E_UNSUPPORTED).any() or tmp_bytes > tmp_dev[k].numel() or n_st > cap_streams or n_bl > cap_blocks:
-            # a chunk the GPU decoder does not take (aggfly_codec.h: "decode it on the host"), or one whose geometry differs
-            # from the first chunk's, which sized the buffers: the request falls back to the host route
-            raise _NotForTheGpuRoute()
+        pres, ranges = route.plan(k, hall, rec0, offs, sizes, present, out_offs)
         if (pres != cb).any():
             badc = [za.chunk_locator(batch[int(present[i])])[0] for i in np.nonzero(pres != cb)[0][:4]]
             raise codec.CodecError(f"chunks {badc} are damaged or decode to another size than {cb} bytes")
@@ -927,11 +1041,9 @@ def _gpu_decode_batches(job, threads, cuts, per, cmax, cap_streams, cap_blocks, 
                 trace.batches.append({"batch": b, "chunks": len(batch), "host_read_done_ms": (trace.clock() - trace.t0) * 1e3,
                                       **{n: torch.cuda.Event(enable_timing=True) for n in ("h2d0", "h2d1", "k1")}})
                 trace.batches[-1]["h2d0"].record(copy_stream)
-            n1 = rec0 + n_st * codec.LZ4_STREAM.itemsize                                        # compressed bytes + stream records: one copy
-            comp_dev[k][:n1].copy_(host[k][:n1], non_blocking=True)
-            if n_bl:
-                n2 = n_bl * codec.SHUFFLE_BLOCK.itemsize
-                comp_dev[k][bl0:bl0 + n2].copy_(host[k][bl0:bl0 + n2], non_blocking=True)
+            for a_, b_ in ranges:
+                if b_ > a_:
+                    comp_dev[k][a_:b_].copy_(host[k][a_:b_], non_blocking=True)
             uploaded[k] = torch.cuda.Event()
             uploaded[k].record(copy_stream)
             if trace.on:
@@ -941,10 +1053,7 @@ def _gpu_decode_batches(job, threads, cuts, per, cmax, cap_streams, cap_blocks, 
             if not direct and staged[k] is None:
                 staged[k] = torch.empty(per * cb, dtype=torch.uint8, device=device)
             target = cube_bytes if direct else staged[k]
-            if n_st:
-                hip.lz4_decode_streams(comp_dev[k], comp_dev[k][rec0:], n_st, max_d, tmp_dev[k], target, errors)
-            if n_bl:
-                hip.unshuffle_blocks(tmp_dev[k], target, comp_dev[k][bl0:], n_bl, int(blocks["bsize"][:n_bl].max()))
+            route.decode(k, comp_dev[k], target, errors)
             job.place(batch, res, staged[k], skip_present=direct)
             done[k] = torch.cuda.Event()
             done[k].record(work_streams[k])

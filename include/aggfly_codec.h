@@ -54,6 +54,28 @@ int afcodec_blosc_lz4_plan(const void* base, int64_t n, const int64_t* comp_off,
                            const int64_t* out_size, void* streams, int64_t cap_streams, int64_t* n_streams, void* blocks,
                            int64_t cap_blocks, int64_t* n_blocks, int64_t* tmp_bytes, int32_t* max_dsize, int64_t* results);
 
+/* Plan of a GPU-side Zstandard decode (libaggfly_hip: afhip_zstd_decode, include/aggfly_hip.h): n plain Zstandard frames —
+ * chunk i = comp_size[i] bytes at base + comp_off[i], decoded to offset out_off[i] of the output (out_size[i] bytes) — have
+ * their frame, block, literals and sequences headers walked on the host (FSE table descriptions only as far as their sizes)
+ * into one afhip_zstd_frame record per frame and one afhip_zstd_block record per block: offsets of the literals, of the
+ * Huffman description and of the sequences bitstream, literal type and sizes, stream count, number of sequences, the LL / OF
+ * / ML modes with Repeat_Mode and treeless literals resolved to the block whose table is meant, and each block's place in the
+ * batch's literal and sequence buffers (*lit_bytes bytes, *n_seqs sequences; *dec_bytes = all frames' decoded bytes).
+ * results[i] = the frame's decoded size, or < 0: AFCODEC_E_UNSUPPORTED marks a frame the GPU route does not take (content
+ * checksum, dictionary, no Frame_Content_Size or one other than out_size[i], skippable frame, more than one frame) — decode
+ * it on the host; malformed frames give AFCODEC_E_FORMAT and no record.  Every record lies inside its chunk, the batch's
+ * buffers and the frame's destination.  Nothing is decoded here. */
+int afcodec_zstd_plan(const void* base, int64_t n, const int64_t* comp_off, const int64_t* comp_size, const int64_t* out_off,
+                      const int64_t* out_size, void* frames, int64_t cap_frames, int64_t* n_frames, void* blocks, int64_t cap_blocks,
+                      int64_t* n_blocks, int64_t* lit_bytes, int64_t* n_seqs, int64_t* dec_bytes, int64_t* results);
+/* Scratch of one batch (== afhip_zstd_scratch_bytes). */
+int64_t afcodec_zstd_scratch_bytes(int64_t n_blocks, int64_t n_frames, int64_t lit_bytes, int64_t n_seqs, int64_t dec_bytes);
+/* The passes of afhip_zstd_decode run in order on the calling thread (host reference of the GPU algorithm, for tests): the
+ * same arguments with host pointers; *errors = damaged frames, *rounds = pointer-jump rounds that had work. */
+int afcodec_zstd_emulate(const void* comp, int64_t comp_bytes, const void* frames, int64_t n_frames, const void* blocks,
+                         int64_t n_blocks, int64_t lit_bytes, int64_t n_seqs, int64_t dec_bytes, void* scratch, void* out,
+                         int32_t* errors, int32_t* rounds);
+
 /* Chunk files of one codec kind (0 raw, 1 Blosc-1, 2 Zstandard frame, 3 zlib or gzip stream, 4 numcodecs LZ4;
  * kind + 16 * element_size adds a byte-unshuffle after the codec: HDF5 / netCDF-4 shuffle + deflate chunks): read and
  * decoded paths[i] -> dsts[i], one chunk per OpenMP thread. */

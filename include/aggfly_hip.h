@@ -190,6 +190,25 @@ int afhip_lz4_decode_streams(const void* comp_dev, const afhip_lz4_stream* strea
 int afhip_unshuffle_blocks(const void* tmp_dev, void* out_dev, const afhip_shuffle_block* blocks_dev, int64_t n_blocks,
                            int32_t max_bsize, void* stream);
 
+/* Zstandard frames decoded in HBM (Zarr v2 compressor "zstd", Zarr v3 bytes -> zstd, shards too).  The host walks the frame,
+ * block and section headers (afcodec_zstd_plan, include/aggfly_codec.h) into one record per frame and per block, which
+ * travel to HBM with the compressed bytes; the tables are built, literals and sequences decoded and the LZ matches resolved
+ * on the GPU, in launch-ordered passes over all blocks of the batch (aggfly_amd/csrc/zstd_passes.h).  Frame f's
+ * Frame_Content_Size bytes go to out_dev + dst_off.  scratch_dev: afhip_zstd_scratch_bytes(...) bytes, caller-owned (~4 bytes
+ * per decoded byte + 11 KiB per block).  A damaged frame writes nothing outside its own destination and the scratch, and
+ * adds 1 to *errors_dev; rounds_dev (may be NULL) receives the number of pointer-jump rounds that had work.  Nothing
+ * allocates or synchronises; all pointers are device memory. */
+typedef struct afhip_zstd_frame { int64_t dst_off, base, size; int32_t first_block, n_blocks; } afhip_zstd_frame;
+typedef struct afhip_zstd_block {
+    int64_t src, lit_off, seq_off;
+    int32_t frame, btype, csize, lit_type, lit_size, lit_src, lit_csize, n_streams, huf_desc, huf_block, nseq, seq_src;
+    int32_t mode[3], tab_desc[3], tab_block[3], pad;
+} afhip_zstd_block;
+int64_t afhip_zstd_scratch_bytes(int64_t n_blocks, int64_t n_frames, int64_t lit_bytes, int64_t n_seqs, int64_t dec_bytes);
+int afhip_zstd_decode(const void* comp_dev, int64_t comp_bytes, const afhip_zstd_frame* frames_dev, int64_t n_frames,
+                      const afhip_zstd_block* blocks_dev, int64_t n_blocks, int64_t lit_bytes, int64_t n_seqs, int64_t dec_bytes,
+                      void* scratch_dev, int64_t scratch_bytes, void* out_dev, int32_t* errors_dev, int32_t* rounds_dev, void* stream);
+
 /* Replaces the body of SpatialAggregator.compute (spatial.py:110-133) for K names:
  * shared validity (all K non-NaN), den = W.valid, num_k = W.where(valid, x_k, 0),
  * res = num/den where den != 0 else NaN.
