@@ -136,11 +136,29 @@ def menu(kind):
                     for kmax in (2, 6):
                         add(dtype, 0, vec, stat, 0, kmax, 8, pair=1, ss=1, rag=1)
                         add(dtype, 0, vec, stat, 0, kmax, 8, pair=1, ss=1, rag=1, rf=1)
-    # `full` = what the planner can pick; the tuning arms of the headline shapes (kbench.py / r03_arms.py `tuning=`; not production:
-    # 74 kernels) are compiled by `make MENU=arms` only
+    # kernels the planner can never pick at tuning 0 are tuning arms, not production (twins go with their plain variants)
+    out = [v[:8] + (0,) if v[8] and not pickable(v) else v for v in out]
+    # `full` = what the planner can pick; the tuning arms of the headline shapes (kbench.py / r03_arms.py `tuning=`; not production)
+    # and the unpickable kernels above are compiled by `make MENU=arms` only
     if kind != "arms":
         out = [v for v in out if v[8]]
     return out
+
+
+def pickable(v):
+    """False for a kernel that no plan can select by afhip_plan_create's default rules (afhip_api.hip), whatever its shape."""
+    dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod = v
+    short = feat & (128 | 1024 | 4096 | 8192)                   # a short-group form; 4096 / 8192: three rows / mixed lengths
+    if kmax == 2 and (nthr == 16 or (nthr == 4 and stat in (1, 2))):
+        return False      # every column adds at most one threshold slot, so slots <= K, and <= K - 1 beside a mean / sum / min / max /
+        #                   sine_dd source (stat 3 may come from a non-integer pow on a threshold column: s3_t4_k2 stays)
+    if dtype == 0 and pipe == 0 and vec == 2 and nthr == 16:
+        return False      # want_vec = 2 needs fewer than four slots (and an LDS-histogram plan takes one cell per lane)
+    if dtype == 0 and pipe == 0 and vec == 2 and stat == 1 and nthr == 0 and kmax == 2:
+        return False      # want_vec = 1 for light float32 plans: stat <= 1, no slot, K <= 2
+    if short and stat == 1 and kmax == 2 and (not (feat & (1024 | 4096 | 8192)) or (dtype == 0 and feat & (4096 | 8192))):
+        return False      # stat-1 short-group plans need K >= min_k: 3 for two-row groups, and for float32 three-row / mixed groups
+    return True
 
 
 def name_of(v):

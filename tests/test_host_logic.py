@@ -509,6 +509,59 @@ def test_kernel_menu_shape():
         assert info["variants"] == len(full) and info["arms"] == 0 and info["region_fused_twins"] == len(twins)
 
 
+def test_every_production_variant_has_a_recipe_at_its_template_edge():
+    """tests/test_gpu_variant_menu.py runs one plan per production kernel (`variant_recipes.recipe`): every entry of the menu has one
+    (a new entry without one fails here, before a GPU run), and its Python-visible shape is the variant's — columns and distinct
+    threshold slots in the kernel's tier, as many as the spec grammar lets fill it, the inner-group form, one period per group for
+    `sl`, a contiguous equal-width partition for `hb`, several periods and no exact order for a region-fused twin."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import variant_recipes as vr
+    menu = vr.production_menu("full")
+    assert len(menu) == len(vr.gen_variants().menu("full"))
+    tiers = {2: (1, 2), 6: (3, 6), 16: (7, 16)}
+    slot_tiers = {0: (0, 0), 1: (1, 1), 4: (2, 4), 16: (5, 16)}
+    for t in menu:
+        v = vr.variant(t)
+        r = vr.recipe(t)
+        cols = r.columns
+        K, n = len(cols), vr.slots_of(cols)
+        assert tiers[v.kmax][0] <= K <= tiers[v.kmax][1] and slot_tiers[v.nthr][0] <= n <= slot_tiers[v.nthr][1], (v.name, K, n)
+        two = v.dtype == vr.F32 and v.pipe == 0 and v.vec == 2                   # two cells per lane: K < 8, fewer than 4 slots
+        assert K == (min(v.kmax, 7) if two else v.kmax), (v.name, K)
+        assert n == min(v.nthr, K - (v.stat in (1, 2)), 3 if two else 16), (v.name, K, n)      # stat 3: a fractional pow on a slot
+        stats = {"mean": 1, "sum": 1, "min": 2, "max": 2, "sine_dd": 2, "nanmean": 3}
+        frac = any(c.get("transform") == "pow" and not float(c["transform_arg"]).is_integer() for c in cols)
+        assert max([stats.get(c["inner"], 0) for c in cols] + [3 if frac else 0]) == v.stat, v.name
+        assert r.n_cells % v.vec == 0 and r.n_cells % (vr.WG * v.vec) != 0 and r.n_cells > vr.WG * v.vec, v.name
+        lens = np.diff(r.inner_bounds)
+        assert r.inner_bounds[0] == 0 and r.inner_bounds[-1] == r.T and (lens >= 0).all(), v.name
+        form = {"pair": {2}, "quad": {4}, "tri": {3}, "rag": {1, 2, 3, 4}}.get(v.form)
+        if form:
+            assert set(lens.tolist()) == form and (v.form != "tri" or len(lens) % 2 == 1), v.name
+        else:
+            assert (lens == 0).any() and not set(lens.tolist()) <= {1, 2, 3, 4}, v.name                 # an empty group
+            assert (r.T / len(lens) < (8 if v.dtype == vr.F32 else 4)) == (v.pipe == 1), v.name       # short groups: the ring
+        assert (lens % v.depth != 0).any(), v.name
+        P = len(r.outer_bounds) - 1
+        if v.has(vr.SL):
+            assert P == len(lens) and all(c["outer"] == "identity" for c in cols), v.name
+        else:
+            assert P >= 2 and (np.diff(r.outer_bounds) == 0).any(), v.name                           # an empty period
+        if v.has(vr.TKI):
+            assert all(c["inner"] != "dd" for c in cols), v.name
+        elif v.nthr:
+            assert any(c["inner"] == "dd" for c in cols), v.name
+        rows = sorted({tuple(c["inner_args"]) for c in cols if c["inner"] == "bins"})
+        partition = len(rows) >= 4 and all(a[1] == b[0] for a, b in zip(rows, rows[1:])) and \
+            np.allclose(np.diff([a[0] for a in rows]), rows[0][1] - rows[0][0], rtol=1e-9, atol=0)
+        assert partition == v.has(vr.HB), v.name
+        if v.has(vr.HB):
+            exact = all(float(x).is_integer() for row in rows for x in row[:2])
+            assert exact == v.has(vr.HA), v.name
+        assert r.exact_order == (not v.has(vr.RF)) and r.region_fused == v.has(vr.RF), v.name
+        assert r.tuning == (204 if v.dtype == vr.F32 and v.vec == 2 and v.depth == 4 and not v.form else 0), v.name   # depth 4: large grids
+
+
 def test_every_name_the_reference_package_exports_exists_here():
     """`aggfly/__init__.py:1-27` re-exports 27 names; a script written against it must import unchanged (`import aggfly_amd as af`).
     The weights PRODUCERS (geopandas / rasterio work, CPU-side per the north_star) exist as names that point to the supported way in:
