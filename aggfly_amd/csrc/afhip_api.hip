@@ -1,17 +1,11 @@
-// afhip_api.hip — C-ABI entry points, plan lowering and kernel dispatch (include/aggfly_hip.h).
+// afhip_api.hip — C-ABI entry points and kernel dispatch (include/aggfly_hip.h).
 //
-// Lowering (afhip_plan_create) turns the column list into
-//   * one inner accumulator set (STAT mode) + deduplicated threshold slots evaluated on
-//     raw data, + one ColOp per column (source, transform, outer reducer);
-//   * a chunk table over time: chunks are ranges of whole inner groups; a chunk either
-//     holds whole outer periods (each emits its final value) or is a piece of one long
-//     period (it emits a partial that k_combine_slots merges in time order);
-//   * the kernel variant (dtype, LDS-DMA or direct loads, STAT, slots, columns).
+// A plan is built by the host-only planner (afhip_planner.cpp: build_plan — column lowering, kernel variant, chunk table,
+// workspace sizes); afhip_plan_create here hands it the device's facts and uploads the tables it made.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,24 +18,13 @@
 #include "afhip_panel_kernels.h"
 #include "afhip_lz4_kernels.h"
 #include "afhip_zstd_kernels.h"
+#include "afhip_planner.h"
 #include "afhip_variants.h"
 #include "afhip_sine_p2_table.h"
 
 using namespace afhip;
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
 
 #define HIP_TRY(expr)                                                                        \
     do {                                                                                     \
@@ -326,54 +309,21 @@ static afhip_csr::RfTab* rf_table(afhip_csr* csr, int vec) {
     return &t;
 }
 
-struct afhip_plan {
+struct afhip_plan : PlanLayout {             // what the planner made (afhip_planner.h) + device tables, scratch and run state
     int device = 0;                       // the device the plan's tables and scratch live on (current device at afhip_plan_create)
-    bool has_sine = false;                // a column is sine_dd: launches carry the acos table and its LDS
-    afhip_plan_desc desc{};
-    std::vector<int64_t> ib, ob;          // host copies
-    std::vector<afhip_column> columns;
-    // lowering
-    int stat = 0, nthr = 0, K = 0;
-    std::vector<ThrSlot> thr;
-    std::vector<ColOp> cols;               // cols[j].inter / inter_f32 are set by afhip_plan_bind_inter
-    std::vector<ChunkDesc> chunks;
-    std::vector<int32_t> emit;
-    std::vector<int64_t> gtab;            // {(end step) << 1 | emit, bits of 1.0/len} per inner group, padded by one
-    std::vector<int32_t> slot_ptr;        // [P+1]
-    int64_t n_slots = 0;
-    const Variant* variant = nullptr;
-    const Variant* variant_rf = nullptr;   // its twin with the region-fused period ends compiled in (null: none in the menu)
-    bool rf_plan_ok = false;               // the plan's columns and slots allow the route (the table decides the rest at run time)
     int last_route = 0;                    // 1: the last afhip_plan_run took the region-fused route (afhip_plan_describe tells)
     int last_counts_lanes = -1;            // lanes per (row, period) pair of the last run's packed-count gather (1, 4, 8, 16; -1: it did not run)
-    int64_t tiles = 0;
-    int wg = WG;                          // threads per workgroup (64 for small grids, else 256)
-    int hb_n = 0; double hb_c1 = 0, hb_c0 = 0;                          // LDS-histogram bins
-    bool hb_arith = false; double hb_w = 0, hb_lo0 = 0, hb_gl = 0, hb_gh = 0, hb_c0b = 0;   // ... with exactly representable edges (+ the biased guess constant)
-    int xcd_remap = 1;        // measured +0.2..1 % on configs[1] (profiles/r01_xcd_remap.txt): harmless, kept on
-    bool counts_spmm = true;  // packed-count plans: gather the records directly when no per-cell output is asked for
-    bool packed = false;      // single-level, all columns plain bin counts: partial holds packed records (FusedArgs::packed)
-    PackFmt pk{};             // their format; pk_bw = bits per count
-    int hb_bin_of_slot[MAX_THR] = {0};
-    double hb_edge[MAX_THR + 1] = {0};
     // device tables
     DevBuf<int64_t> d_ob;
     DevBuf<int64_t> d_gtab;
     DevBuf<ChunkDesc> d_chunks;
     DevBuf<int32_t> d_slot_ptr;
     // workspace
-    int64_t ws_partial = 0, ws_panel = 0;   // byte sizes
     void* own_ws = nullptr;                 // plan-owned scratch (callers that hand no workspace): grown by a new hipMalloc, the
     int64_t own_ws_bytes = 0;               // outgrown block is `retired` until the plan is destroyed — no hipFree (a device-wide
     std::vector<void*> retired;             // synchronisation) ever sits on the run path
     double* sums = nullptr;                 // [rows][P][K + 1] of the current run: behind partial + panel in the run's workspace
     int last_ws = 0;                        // 1: the last run used a caller-owned workspace, 2: plan-owned (afhip_plan_describe tells)
-    // experiment knobs, read once when the plan is created (never on the run path)
-    bool no_slot_spmm = false, no_slots_divide = false, no_counts_divide = false;
-    int rf_layout = -1;                               // AFHIP_RF_LAYOUT=slot|run: layout of the run sums forced (rf_run_major)
-    int rf_reduce_order = -1;                         // AFHIP_RF_REDUCE_ORDER=r|p: k_rf_reduce's (region, period) pairs region-major / period-major
-    int slot_spmm_sub = 0, slot_spmm_order = -1;      // AFHIP_SLOT_SPMM_ORDER=v|p: SlotSpmmArgs::p_major forced off / on
-    int counts_spmm_sub = -1;                         // AFHIP_COUNTS_SPMM_SUB=0|4|8|16: lanes per (row, period) pair of the packed-count gather (0: one, table order)
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     // per-launch profiling ring (afhip_plan_profile_*): event pairs around the temporal kernel
     std::vector<hipEvent_t> prof_ev;
@@ -389,7 +339,7 @@ struct afhip_plan {
 // ---------------------------------------------------------------------------------------
 // misc
 // ---------------------------------------------------------------------------------------
-extern "C" const char* afhip_last_error(void) { return g_err.c_str(); }
+extern "C" const char* afhip_last_error(void) { return last_error(); }
 extern "C" int afhip_abi_version(void) { return AFHIP_ABI_VERSION; }
 
 extern "C" int afhip_build_info(char* buf, int buf_len) {
@@ -777,615 +727,29 @@ extern "C" int afhip_spatial_wavg(const afhip_csr* csr, const double* x_dev, int
 }
 
 // ---------------------------------------------------------------------------------------
-// plan lowering
+// plans
 // ---------------------------------------------------------------------------------------
-static bool is_stat(int c) { return c >= AFHIP_MEAN && c <= AFHIP_NANMEAN; }
-
-static int add_thr_slot(std::vector<ThrSlot>& thr, const double* a3, bool bins) {
-    ThrSlot s{};
-    s.t0 = a3[0]; s.t1 = a3[1];
-    const bool base_is_t0 = (a3[2] == 0.0);                 // nb_kernels.py:167
-    if (bins) { s.A = 0.0; s.B = 1.0; }
-    else if (base_is_t0) { s.A = 1.0; s.B = -a3[0]; }
-    else { s.A = -1.0; s.B = a3[1]; }
-    // float thresholds equivalent to the double compares for float inputs
-    s.t0f = (float)a3[0]; if ((double)s.t0f > a3[0]) s.t0f = std::nextafterf(s.t0f, -INFINITY);
-    s.t1f = (float)a3[1]; if ((double)s.t1f < a3[1]) s.t1f = std::nextafterf(s.t1f, INFINITY);
-    s.nan_poisons = bins ? 0 : 1;
-    for (size_t i = 0; i < thr.size(); ++i)
-        if (!memcmp(&thr[i], &s, sizeof s)) return (int)i;
-    thr.push_back(s);
-    return (int)thr.size() - 1;
-}
-
-static int lower_columns(afhip_plan* pl) {
-    const int K = pl->desc.K;
-    int stat = 0;
-    pl->thr.clear(); pl->cols.clear();
-    pl->has_sine = false;
-    for (int j = 0; j < K; ++j) {
-        const afhip_column& c = pl->columns[j];
-        ColOp co{};
-        co.rounding = c.rounding;
-        switch (c.inner) {
-            case AFHIP_MEAN: co.src = SRC_MEAN; stat = std::max(stat, 1); break;
-            case AFHIP_SUM: co.src = SRC_SUM; stat = std::max(stat, 1); break;
-            case AFHIP_MIN: co.src = SRC_MIN; stat = std::max(stat, 2); break;
-            case AFHIP_MAX: co.src = SRC_MAX; stat = std::max(stat, 2); break;
-            case AFHIP_NANMEAN: co.src = SRC_NANMEAN; stat = 3; break;
-            case AFHIP_DD: co.src = SRC_THR; co.src_idx = add_thr_slot(pl->thr, c.inner_args, false); break;
-            case AFHIP_BINS: co.src = SRC_THR; co.src_idx = add_thr_slot(pl->thr, c.inner_args, true); break;
-            case AFHIP_SINE_DD:
-                co.src = SRC_SINE; stat = std::max(stat, 2);
-                co.s0 = c.inner_args[0]; co.s1 = c.inner_args[1];
-                co.s0x2 = 2.0 * co.s0; co.s1x2 = 2.0 * co.s1;
-                {   // the pair-mode window tests on float data compare in float: s rounded down / up (afhip_kernels.h: ColOp)
-                    auto dn = [](double t) { float f = (float)t; return (double)f > t ? std::nextafterf(f, -INFINITY) : f; };
-                    auto up = [](double t) { float f = (float)t; return (double)f < t ? std::nextafterf(f, INFINITY) : f; };
-                    co.s0dn = dn(co.s0); co.s0up = up(co.s0); co.s1dn = dn(co.s1); co.s1up = up(co.s1);
-                }
-                co.swidth = co.s1 - co.s0; co.swidth2 = 2.0 * co.swidth;
-                pl->has_sine = true;
-                if (c.inner_args[2] != 0.0 && c.inner_args[2] != 1.0)
-                    return fail(AFHIP_E_INVALID, "column %d: sine_dd flag must be 0 or 1 (temporal.py:324)", j);
-                co.skind = (int)c.inner_args[2];
-                break;
-            default: return fail(AFHIP_E_INVALID, "column %d: unknown inner reducer %d", j, c.inner);
-        }
-        switch (c.transform) {
-            case AFHIP_TF_NONE: co.tf = TF_NONE; break;
-            case AFHIP_TF_POW: {
-                const double e = c.transform_arg;
-                if (e == std::floor(e) && std::fabs(e) <= 64.0) { co.tf = TF_POWI; co.tf_iarg = (int)e; }
-                else { co.tf = TF_POW; co.tf_arg = e; }
-                break;
-            }
-            case AFHIP_TF_HINGE: co.tf = TF_HINGE; co.tf_arg = c.transform_arg; break;
-            case AFHIP_TF_INTER: co.tf = TF_INTER; break;
-            default: return fail(AFHIP_E_INVALID, "column %d: unknown transform %d", j, c.transform);
-        }
-        // pow() and `inter` are compiled into the all-purpose (STAT 3) variants only (FEAT bit 1)
-        if (co.tf == TF_POW || co.tf == TF_INTER) stat = 3;
-        switch (c.outer) {
-            case AFHIP_IDENTITY: co.outer = OUT_FIRST; break;
-            case AFHIP_SUM: co.outer = OUT_SUM; break;
-            case AFHIP_MEAN: co.outer = OUT_MEAN; break;
-            case AFHIP_MIN: co.outer = OUT_MIN; break;
-            case AFHIP_MAX: co.outer = OUT_MAX; break;
-            case AFHIP_DD:
-            case AFHIP_BINS:
-                co.outer = c.outer == AFHIP_DD ? OUT_DD : OUT_BINS;
-                co.o0 = c.outer_args[0]; co.o1 = c.outer_args[1];
-                co.obase = (c.outer_args[2] == 0.0) ? c.outer_args[0] : c.outer_args[1];
-                break;
-            default:
-                return fail(AFHIP_E_UNSUPPORTED, "column %d: outer reducer %d is not fused (use the staged path)", j, c.outer);
-        }
-        pl->cols.push_back(co);
-    }
-    if ((int)pl->thr.size() > MAX_THR) return fail(AFHIP_E_UNSUPPORTED, "more than %d threshold slots in one pass", MAX_THR);
-    if (K > MAX_COLS) return fail(AFHIP_E_UNSUPPORTED, "more than %d columns in one pass", MAX_COLS);
-    pl->stat = stat;
-    pl->nthr = (int)pl->thr.size();
-    pl->K = K;
-    return AFHIP_OK;
-}
-
-// the variant with the region-fused period ends compiled in and every other field equal (null: the menu has none)
-static const Variant* twin_of(const Variant* v) {
+// workgroups of kernel `fn` one CU holds at once (registers, LDS, wave slots)
+static int resident_wgs_per_cu(const void* fn, int wg, size_t lds) {
     int n = 0;
-    const Variant* tab = variants_table(&n);
-    for (int i = 0; i < n; ++i) {
-        const Variant& t = tab[i];
-        if (t.rf && t.dtype == v->dtype && t.pipe == v->pipe && t.vec == v->vec && t.stat == v->stat && t.nthr == v->nthr && t.kmax == v->kmax &&
-            t.depth == v->depth && t.nt == v->nt && t.tki == v->tki && t.sl == v->sl && t.hb == v->hb && t.ha == v->ha && t.pair == v->pair &&
-            t.ss == v->ss && t.quad == v->quad)
-            return &t;
-    }
-    return nullptr;
-}
-
-// Chunking.  target_len = time steps a workgroup should stream; a long period is cut on
-// inner-group boundaries into pieces (each emits a partial), short consecutive periods are
-// packed into one chunk (each emits its own final value).
-static int lay_chunks(afhip_plan* pl, int64_t want_chunks);
-
-// dynamic LDS of a launch of the plan's variant with pl->wg threads per workgroup
-static size_t plan_lds_bytes(const afhip_plan* pl) {
-    size_t lds = pl->variant->pipe == 1 ? (size_t)(pl->wg / 64) * pl->variant->depth * 1024 : 0;
-    if (pl->has_sine) lds += (pl->variant->pair && !pl->variant->quad) ? SINE_P2_BYTES : SINE_TAB_BYTES;      // the variant's sine table, behind the ring
-    if (pl->variant->hb) lds = (size_t)HB_TABLE_BYTES + (size_t)(pl->hb_n + 2) * pl->variant->vec * pl->wg * 4;
-    return lds;
-}
-
-// workgroups of the plan's variant one CU holds at once (registers, LDS, wave slots)
-static int resident_wgs_per_cu(const afhip_plan* pl) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pl->variant->fn, pl->wg, plan_lds_bytes(pl)) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, wg, lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
     return n;
-}
-
-static int build_chunks(afhip_plan* pl, int vec) {
-    const auto& ib = pl->ib;
-    const auto& ob = pl->ob;
-    const int64_t G1 = pl->desc.G1, P = pl->desc.P, T = pl->desc.T, C = pl->desc.n_cells;
-    // single-wave workgroups when 256-thread tiles cannot give every CU a few workgroups — and on large grids too, unless every
-    // workgroup copies a sine table into LDS first (pair-mode sine_dd at 64 threads: 3.23 -> 5.80 ms).  The bare streaming read of
-    // this access shape is fastest in single-wave workgroups (scripts/probe/read_bw.hip: 7.02 against 6.69 TB/s at four rows in
-    // flight, profiles/r03_read_ceiling.txt) and the plans follow it by less: configs[1] f64 3.142 -> 3.131 ms, f32 1.713 -> 1.693,
-    // C1 f32 1.577 -> 1.558, the reference's benchmark shape 5.336 -> 5.281 (same box, arms alternated; 128 threads: 3.234).
-    pl->wg = ((C + (int64_t)WG * vec - 1) / ((int64_t)WG * vec) < (int64_t)cu_count(pl->device) || !pl->has_sine) ? 64 : WG;
-    // the LDS-histogram kernel: single-wave workgroups and MANY time chunks.  It is short of bytes in flight (waves park 65 % of
-    // their cycles on memory at 4.2 waves per SIMD, VALU and LDS far from busy: profiles/r03_c4_bound_pmc.txt), and the more,
-    // smaller workgroups the grid offers the fuller the CUs stay: configs[3] f32 3.15 ms (7 chunks of 256 threads) -> 2.84 ms
-    // (126 chunks of 64), f64 5.86 -> 5.58 (profiles/r03_sweep_chunks_depth.txt).  Round 1 had measured 4-wave workgroups
-    // ahead — at the few chunks of that time.
-    const bool hist = pl->variant && pl->variant->hb;
-    if (hist) pl->wg = 64;
-    if (const char* e = getenv("AFHIP_FORCE_WG")) { int w = atoi(e); if (w == 64 || w == 128 || w == 256) pl->wg = w; }   // experiment knob
-    pl->tiles = (C + (int64_t)pl->wg * vec - 1) / ((int64_t)pl->wg * vec);
-    // aim for ~4 workgroups per CU over the whole grid, never streaming fewer than 64 steps
-    int per_cu = 4;      // measured (profiles/r01_sweep_chunks.txt, r03_sweep_chunks_depth.txt): the fewer time chunks the better once every CU has ~4 workgroups
-    if (hist) per_cu = 96;   // ... except for the histogram kernel (above)
-    if (const char* e = getenv("AFHIP_WGS_PER_CU")) per_cu = std::max(1, atoi(e));   // experiment knob
-    const int64_t want_wgs = (int64_t)cu_count(pl->device) * per_cu * (WG / pl->wg);
-    int64_t want_chunks = std::max<int64_t>(1, (want_wgs + pl->tiles - 1) / pl->tiles);
-    // Plans with several output periods: up to one time chunk per period.  Cutting ON period boundaries adds no slot and no traffic
-    // (the "fewer chunks are better" of round 1 was measured at P = 1, where every cut adds a slot), and the period-end stores are
-    // what such plans pay for: with the stores compiled out the configs[1] plan runs P = 12 and P = 73 exactly as fast as P = 1
-    // (3.14 ms), with them 3.69 and 4.30 — 150 MB of stores for 0.55 ms, box-dependent (0.22 ms on another box).  The more chunks, the
-    // fewer period ends a workgroup carries in the middle of its stream: P = 365 5.24 -> 4.94 ms, P = 73 3.76 -> 3.46, weekly f32
-    // 1.72 -> 1.67, the reference's own benchmark shape 5.64 -> 5.53 (profiles/r03_period_end_stores.txt).  lay_chunks still
-    // packs periods shorter than 64 steps together; the histogram kernel keeps its own rule.
-    // Plans that already get eight chunks or more keep them (configs[2]'s shape, 14 chunks for 40 years: 40 measured 0.5 % behind).
-    bool period_chunks = false;
-    if (P > 1 && !hist && want_chunks < 8 && !getenv("AFHIP_WGS_PER_CU") && !getenv("AFHIP_NO_PERIOD_CHUNKS")) {
-        int64_t wg_cap = 262144;                                    // workgroups a period-chunked launch may have
-        if (const char* e = getenv("AFHIP_PERIOD_CHUNK_WGS")) wg_cap = std::max<int64_t>(1024, atoll(e));      // experiment knob
-        const int64_t by_period = std::min<int64_t>(P, std::max<int64_t>(1, wg_cap / std::max<int64_t>(pl->tiles, 1)));
-        // (a handful of period chunks makes a handful of occupancy rounds with a costly last one: P = 4 measured 2-4 % behind one chunk)
-        if (by_period >= 8) { want_chunks = by_period; period_chunks = true; }
-    }
-    int rc = lay_chunks(pl, want_chunks);
-    if (rc) return rc;
-    // Rounds.  A CU holds `resident` workgroups of this variant at once; a grid of more workgroups than the chip holds runs in
-    // "rounds", and a last round that is mostly empty is paid in full: the reference's own benchmark shape (global 0.25 deg,
-    // 2,028 tiles as ONE chunk against 1,536 resident workgroups = 1.32 rounds) ran at 0.65 of the HBM peak, as three chunks
-    // (3.96 rounds) at 0.79 (profiles/r03_ref_shape_arms.txt).  When the grid does not fit the chip at once, take the chunk
-    // count (of the next few) whose last round is fullest; a grid that fits keeps the fewest chunks, which measured best.
-    // (period-aligned chunks are many and short: their last round weighs little, and the search below would cut periods to fill it)
-    if (!period_chunks && !getenv("AFHIP_NO_ROUND_FILL") && !getenv("AFHIP_WGS_PER_CU")) {
-        const int64_t capacity = (int64_t)resident_wgs_per_cu(pl) * cu_count(pl->device);
-        auto fill = [&](int64_t total) { const int64_t rounds = (total + capacity - 1) / capacity; return (double)total / (double)(rounds * capacity); };
-        int64_t total = pl->tiles * (int64_t)pl->chunks.size();
-        if (capacity > 0 && total > capacity && fill(total) < 0.92) {
-            int64_t best_c = want_chunks;
-            double best = fill(total);
-            size_t last_n = pl->chunks.size();
-            for (int64_t c = want_chunks + 1; c <= want_chunks + 12 && best < 0.92; ++c) {
-                if ((rc = lay_chunks(pl, c))) return rc;
-                if (pl->chunks.size() == last_n) continue;         // (period boundaries: not every count exists)
-                last_n = pl->chunks.size();
-                const double f = fill(pl->tiles * (int64_t)pl->chunks.size());
-                if (f > best + 1e-9) { best = f; best_c = c; }
-            }
-            if ((rc = lay_chunks(pl, best_c))) return rc;
-        }
-    }
-    return AFHIP_OK;
-}
-
-// Chunk table for ~want_chunks time chunks (see build_chunks).
-static int lay_chunks(afhip_plan* pl, int64_t want_chunks) {
-    const auto& ib = pl->ib;
-    const auto& ob = pl->ob;
-    const int64_t G1 = pl->desc.G1, P = pl->desc.P, T = pl->desc.T;
-    const int64_t target_len = std::max<int64_t>(64, T / std::max<int64_t>(want_chunks, 1));
-    // splitting a period adds partial traffic (16 B per extra slot, column and cell, write +
-    // read); keep it under ~5 % of the cube: extra_slots*K*16 <= 0.05*T*elem.  (2 % starved the
-    // CONUS-window f32 plan of workgroups: 9 chunks 0.229 ms, 22 chunks 0.151 ms.)
-    const int64_t elem = pl->desc.dtype == AFHIP_F32 ? 4 : 8;
-    double split_frac = 0.05;
-    if (const char* e = getenv("AFHIP_SPLIT_FRAC")) split_frac = atof(e);   // experiment knob
-    int64_t split_budget = std::max<int64_t>(1, (int64_t)(split_frac * (double)T * (double)elem / (16.0 * std::max(1, pl->K))));
-    const bool any_first = std::any_of(pl->cols.begin(), pl->cols.end(), [](const ColOp& c) { return c.outer == OUT_FIRST; });
-    const bool may_split = !pl->desc.exact_order && !any_first;
-
-    pl->chunks.clear();
-    pl->emit.assign((size_t)std::max<int64_t>(G1, 1), 0);
-    pl->slot_ptr.assign((size_t)P + 1, 0);
-    int64_t slot = 0;
-
-    auto steps_of = [&](int64_t p) { return ib[(size_t)ob[(size_t)p + 1]] - ib[(size_t)ob[(size_t)p]]; };
-    auto groups_of = [&](int64_t p) { return ob[(size_t)p + 1] - ob[(size_t)p]; };
-    auto splittable = [&](int64_t p) {
-        return may_split && split_budget > 0 && groups_of(p) >= 2 && steps_of(p) >= 2 * target_len;
-    };
-    auto push_chunk = [&](int64_t g_lo, int64_t g_hi, int64_t slot_base) {
-        ChunkDesc c{};
-        c.k_lo = ib[(size_t)g_lo]; c.k_hi = ib[(size_t)g_hi];
-        c.g_lo = (int32_t)g_lo; c.g_hi = (int32_t)g_hi; c.slot_base = (int32_t)slot_base;
-        pl->chunks.push_back(c);
-    };
-
-    int64_t p = 0;
-    while (p < P) {
-        const int64_t g0 = ob[(size_t)p], g1 = ob[(size_t)p + 1];
-        if (g1 == g0) {  // empty resample bin: no slot, the combine kernel writes NaN
-            pl->slot_ptr[(size_t)p] = (int32_t)slot;
-            ++p;
-            continue;
-        }
-        if (splittable(p)) {
-            const int64_t steps = steps_of(p);
-            const int64_t pieces = std::max<int64_t>(2, std::min<int64_t>({steps / target_len, g1 - g0, split_budget + 1}));
-            pl->slot_ptr[(size_t)p] = (int32_t)slot;
-            int64_t g = g0, made = 0;
-            for (int64_t i = 1; i <= pieces && g < g1; ++i) {
-                int64_t ge;
-                if (i == pieces) {
-                    ge = g1;
-                } else {
-                    const int64_t k_goal = ib[(size_t)g0] + (steps * i) / pieces;
-                    ge = (int64_t)(std::lower_bound(ib.begin() + g + 1, ib.begin() + g1, k_goal) - ib.begin());
-                    ge = std::min(ge, g1);
-                }
-                if (ge <= g) continue;
-                push_chunk(g, ge, slot);
-                pl->emit[(size_t)ge - 1] = 1;
-                ++slot; ++made;
-                g = ge;
-            }
-            split_budget -= std::max<int64_t>(0, made - 1);
-            ++p;
-            continue;
-        }
-        // pack whole periods until the chunk holds ~target_len steps
-        const int64_t cg0 = g0, slot_base = slot;
-        int64_t acc_steps = 0, cg1 = g0;
-        bool first = true;
-        while (p < P) {
-            const int64_t a0 = ob[(size_t)p], a1 = ob[(size_t)p + 1];
-            const int64_t st = steps_of(p);
-            if (!first && (acc_steps + st > target_len || splittable(p))) break;
-            pl->slot_ptr[(size_t)p] = (int32_t)slot;
-            if (a1 > a0) { pl->emit[(size_t)a1 - 1] = 1; ++slot; cg1 = a1; }
-            acc_steps += st;
-            first = false;
-            ++p;
-        }
-        push_chunk(cg0, cg1, slot_base);
-    }
-    pl->slot_ptr[(size_t)P] = (int32_t)slot;
-    pl->n_slots = slot;
-    if (pl->chunks.size() > 65535)
-        return fail(AFHIP_E_UNSUPPORTED, "plan needs %zu chunks (> 65535 grid.y)", pl->chunks.size());
-    return AFHIP_OK;
-}
-
-static int validate_desc(const afhip_plan_desc* d) {
-    if (!d) return fail(AFHIP_E_INVALID, "plan_create: desc is NULL");
-    if (d->T < 0 || d->n_cells <= 0 || d->K <= 0 || d->G1 < 0 || d->P < 0)
-        return fail(AFHIP_E_INVALID, "plan_create: bad sizes (T=%lld n_cells=%lld K=%d G1=%lld P=%lld)",
-                    (long long)d->T, (long long)d->n_cells, d->K, (long long)d->G1, (long long)d->P);
-    if (d->dtype != AFHIP_F32 && d->dtype != AFHIP_F64) return fail(AFHIP_E_INVALID, "plan_create: dtype must be AFHIP_F32 or AFHIP_F64");
-    if (!d->inner_bounds || !d->outer_bounds || !d->columns) return fail(AFHIP_E_INVALID, "plan_create: NULL table");
-    if (d->inner_bounds[0] != 0 || d->inner_bounds[d->G1] != d->T)
-        return fail(AFHIP_E_INVALID, "plan_create: inner_bounds must run from 0 to T");
-    for (int64_t g = 0; g < d->G1; ++g)
-        if (d->inner_bounds[g + 1] < d->inner_bounds[g]) return fail(AFHIP_E_INVALID, "plan_create: inner_bounds not monotone (time index must be monotonic increasing)");
-    if (d->outer_bounds[0] != 0 || d->outer_bounds[d->P] != d->G1)
-        return fail(AFHIP_E_INVALID, "plan_create: outer_bounds must run from 0 to G1");
-    for (int64_t p = 0; p < d->P; ++p)
-        if (d->outer_bounds[p + 1] < d->outer_bounds[p]) return fail(AFHIP_E_INVALID, "plan_create: outer_bounds not monotone");
-    if (d->G1 > INT32_MAX - 2) return fail(AFHIP_E_INVALID, "plan_create: too many inner groups");
-    return AFHIP_OK;
 }
 
 extern "C" int afhip_plan_create(const afhip_plan_desc* desc, afhip_plan** out) {
     if (!out) return fail(AFHIP_E_INVALID, "plan_create: out is NULL");
     *out = nullptr;
-    int rc = validate_desc(desc);
-    if (rc) return rc;
     auto* pl = new afhip_plan();
     pl->device = current_device();
-    pl->desc = *desc;
-    pl->ib.assign(desc->inner_bounds, desc->inner_bounds + desc->G1 + 1);
-    pl->ob.assign(desc->outer_bounds, desc->outer_bounds + desc->P + 1);
-    pl->columns.assign(desc->columns, desc->columns + desc->K);
-    pl->desc.inner_bounds = nullptr; pl->desc.outer_bounds = nullptr; pl->desc.columns = nullptr;
-    if ((rc = lower_columns(pl))) { delete pl; return rc; }
-
-    // variant: the load path that measured fastest for the dtype and grid size
-    // (profiles/r01_sweep_load_arms.txt), subject to row alignment.
-    const int64_t C_ = desc->n_cells;
-    int want_pipe = 0, want_vec = 1;
-    if (desc->dtype == AFHIP_F64) {
-        // one cell per lane, direct loads — on small grids too: round 1 had the LDS-DMA ring ahead there (6.1 vs 5.4 TB/s on
-        // 104x236), the re-sweep on round 2's kernel has it behind (5.99 vs 6.67 TB/s; profiles/r02_kbench_resweep.txt)
-    } else {
-        // two cells per lane, unless the plan carries many accumulators (register pressure):
-        // one cell per lane measured 1.6x faster on the 13-bin plan (profiles/r01_kbench_c4_f32.json)
-        if (C_ % 2 == 0 && pl->nthr < 4 && pl->K < 8) want_vec = 2;
-        // ... and unless it is a light one (one or two mean / sum columns, no threshold slots): one cell per lane then keeps
-        // more waves resident and measured 6.6 % faster on configs[0] at 215x1440 (6,534 -> 6,966 GB/s), level on the 104x236
-        // window (profiles/r02_kbench_light_f32_plans.txt)
-        if (pl->stat <= 1 && pl->nthr == 0 && pl->K <= 2) want_vec = 1;
-    }
-    // short inner groups: the direct path keeps DEPTH rows in flight only INSIDE a group, the LDS-DMA ring
-    // prefetches across group ends.  Measured (mean plan, 721x1440 / 1801x3600): 2-step groups f64 4.5 vs
-    // 6.0 TB/s, f32 3.5 vs 4.3; 4-step groups f32 4.4 vs 5.6, f64 equal; 8 steps and longer: equal.
-    // every inner group exactly two rows ((tmin, tmax) pairs) and min / max / sine columns: the pair-mode variants of the
-    // direct-load path keep DEPTH / 2 whole groups in flight, so they need no ring either
-    // ... and the same for groups of exactly four rows (6-hourly data), in the lean form only (FEAT bit 10)
-    int glen = 0;
-    if (desc->G1 > 0 && pl->nthr == 0 && (pl->stat == 1 || pl->stat == 2) && !getenv("AFHIP_NO_PAIR_MODE")) {
-        for (int L : {2, 3, 4}) {
-            bool all = desc->T == (int64_t)L * desc->G1;
-            for (int64_t g = 0; all && g < desc->G1; ++g) all = pl->ib[(size_t)g + 1] - pl->ib[(size_t)g] == L;
-            if (all) glen = L;
-        }
-        // mixed lengths of one to four rows (a sub-daily series with missing steps): the four-row form with a length per group
-        // (FEAT bit 13); a series of single rows throughout is not a short-group plan
-        if (glen == 0 && desc->T > desc->G1 && !getenv("AFHIP_NO_RAGGED_MODE")) {
-            bool all = true;
-            for (int64_t g = 0; all && g < desc->G1; ++g) {
-                const int64_t L = pl->ib[(size_t)g + 1] - pl->ib[(size_t)g];
-                all = L >= 1 && L <= 4;
-            }
-            if (all) glen = 5;
-        }
-    }
-    if (glen >= 3 && getenv("AFHIP_NO_QUAD_MODE")) glen = 0;
-    // (its loads address a row by a 32-bit byte offset per lane: rows of 4 GiB and more take the general path)
-    if ((uint64_t)desc->n_cells * (desc->dtype == AFHIP_F64 ? 8u : 4u) >= (1ull << 32)) glen = 0;
-    bool pairs = glen >= 2;                              // short-group mode (two-, three- or four-row groups)
-    const bool quad_len = glen >= 3;                     // three / four / mixed rows: the lean form only, general sine closed forms
-    const int glcode = glen == 5 ? 3 : (glen == 4 ? 1 : (glen == 3 ? 2 : 0));      // Variant::quad
-    // pair plans whose columns are all  mean | sum | min | max | sine_dd -> (integer power) -> sum | mean  without float32 rounding
-    // take the lean group end (FEAT bit 8); when every column is a plain sine_dd, its tightest form (FEAT bit 9).  A sine_dd
-    // column there needs s0 < s1: its two max() terms are one clamp of width s1 - s0.
-    bool lean = pairs && !getenv("AFHIP_NO_LEAN_PAIRS"), lean_sine = lean && pl->K <= 2 && !quad_len;
-    for (const ColOp& c : pl->cols) {
-        const bool sine_ok = c.src == SRC_SINE && c.s0 < c.s1 && std::isfinite(c.swidth);
-        const bool src_ok = c.src == SRC_MEAN || c.src == SRC_SUM || c.src == SRC_MIN || c.src == SRC_MAX || sine_ok;
-        lean = lean && src_ok && (c.tf == TF_NONE || (c.tf == TF_POWI && c.tf_iarg >= 1)) && c.rounding == 0 && (c.outer == OUT_SUM || c.outer == OUT_MEAN);
-        lean_sine = lean_sine && sine_ok && c.tf == TF_NONE;
-    }
-    lean_sine = lean_sine && lean;
-    // four-row groups exist in the lean form only, for as many columns as its variants hold
-    if (quad_len && !(lean && find_variant(desc->dtype, 0, pl->stat, 0, pl->K, 0, 0, false, false, false, false, false, 1, 0, glcode)))
-        pairs = lean = false;
-    // mean / sum columns alone (no min, max or sine): the pair path exists in the lean form only, and a light plan (one or two
-    // columns) streams faster through the LDS-DMA ring, whose prefetch runs across the two-row groups (5.99 vs 5.44 TB/s on
-    // 1801 x 3600 f32); with more columns the lean group end wins (profiles/r03_pairs_mean_poly.txt)
-    // (four-row groups: the lean form measured ahead of the ring at every column count, profiles/r03_quad_groups.txt)
-    if (pairs && pl->stat == 1) {
-        // (three-row groups on float32: one- and two-column plans stream faster through the ring, 4.59 / 4.94 against 4.93 / 5.04 ms on
-        // 1801 x 3600; from three columns on, and on float64 at every count, the lean form is ahead: profiles/r04_three_row_groups.txt)
-        // (mixed lengths likewise: 6.25 / 6.39 against 6.89 / 6.83 ms, float64 level; profiles/r04_mixed_short_groups.txt)
-        int min_k = quad_len ? (((glen == 3 || glen == 5) && desc->dtype == AFHIP_F32) ? 3 : 1) : 3;
-        if (const char* e = getenv("AFHIP_LEAN_STAT1_MIN_K")) min_k = atoi(e);      // experiment knob
-        if (!lean || pl->K < min_k) pairs = lean = lean_sine = false;
-    }
-    if (!pairs) {
-        const double avg_group = desc->G1 > 0 ? (double)desc->T / (double)desc->G1 : 0.0;
-        const int vec16 = desc->dtype == AFHIP_F64 ? 2 : 4;
-        bool sine = false;                          // sine_dd on short windows is fp64-VALU-bound: direct loads measured 4 % faster
-        for (const ColOp& c : pl->cols) sine = sine || c.src == SRC_SINE;
-        if (!sine && avg_group > 0 && avg_group < (desc->dtype == AFHIP_F64 ? 4.0 : 8.0) && C_ % vec16 == 0) { want_pipe = 1; want_vec = vec16; }
-    }
-    int tuning = desc->tuning;
-    if (tuning > 0) {
-        const int tvec = ((tuning % 10000) % 1000) / 100;
-        if (tvec <= 0 || C_ % tvec != 0) tuning = 0;          // a vector arm needs rows that are multiples of it
-    }
-    // specialisations the lowered plan qualifies for
-    bool all_bins = pl->nthr > 0;
-    for (const ThrSlot& t : pl->thr) all_bins = all_bins && t.nan_poisons == 0;
-    bool single_level = desc->P == desc->G1;
-    for (int64_t p = 0; single_level && p <= desc->P; ++p) single_level = pl->ob[(size_t)p] == p;
-    for (const ColOp& c : pl->cols) single_level = single_level && c.outer == OUT_FIRST;
-    // contiguous equal-width partition?  (sorted by t0, t1[b] == t0[b+1], constant width)
-    pl->hb_n = 0;
-    if (all_bins && pl->nthr >= 4) {
-        std::vector<int> order((size_t)pl->nthr);
-        for (int i = 0; i < pl->nthr; ++i) order[(size_t)i] = i;
-        std::sort(order.begin(), order.end(), [&](int x, int y) { return pl->thr[(size_t)x].t0 < pl->thr[(size_t)y].t0; });
-        const double e0 = pl->thr[(size_t)order[0]].t0;
-        const double w = pl->thr[(size_t)order[0]].t1 - e0;
-        bool ok = w > 0 && std::isfinite(e0) && std::isfinite(w);
-        for (int b = 0; ok && b < pl->nthr; ++b) {
-            const ThrSlot& t = pl->thr[(size_t)order[(size_t)b]];
-            ok = std::fabs(t.t0 - (e0 + b * w)) <= 1e-9 * w && std::fabs(t.t1 - (e0 + (b + 1) * w)) <= 1e-9 * w;
-            if (ok && b + 1 < pl->nthr) ok = t.t1 == pl->thr[(size_t)order[(size_t)b + 1]].t0;
-        }
-        // the in-kernel guess floor(v / w - e0 / w) is computed in the INPUT precision and may be off by
-        // one bin at most: the bins must not be narrower than ~2^20 (f32) / 2^48 (f64) ulps of the edges
-        const double emax = std::max(std::fabs(e0), std::fabs(e0 + pl->nthr * w));
-        const double eps = desc->dtype == AFHIP_F32 ? 1.2e-7 : 2.3e-16;
-        ok = ok && emax * eps * 16.0 < w;
-        if (ok) {
-            pl->hb_n = pl->nthr; pl->hb_c1 = 1.0 / w; pl->hb_c0 = 1.0 - e0 / w;      // + 1: bin 0 is the lower guard bin
-            for (int b = 0; b < pl->nthr; ++b) {
-                pl->hb_bin_of_slot[order[(size_t)b]] = b;
-                pl->hb_edge[b] = pl->thr[(size_t)order[(size_t)b]].t0;
-            }
-            pl->hb_edge[pl->nthr] = pl->thr[(size_t)order[(size_t)pl->nthr - 1]].t1;
-            // arithmetic edges: E[g] = lo0 + g * w must come out EXACTLY, in the input precision and by the very fma the
-            // kernel executes, for every bin of the guarded partition; the clamp points must lie inside the guard bins
-            const int n = pl->nthr;
-            const double lo0 = e0 - w, gl = e0 - 0.5 * w, gh = pl->hb_edge[n] + 0.5 * w;
-            bool ex = true;
-            if (desc->dtype == AFHIP_F32) {
-                const float wf = (float)w, lo0f = (float)lo0, e0f = (float)e0, glf = (float)gl, ghf = (float)gh;
-                ex = (double)wf == w && (double)lo0f == lo0 && (double)e0f == e0 && lo0f + wf == e0f;
-                for (int g = 0; ex && g <= n + 1; ++g) {
-                    const double lo_want = g == 0 ? lo0 : pl->hb_edge[g - 1];
-                    const double hi_want = g == n + 1 ? pl->hb_edge[n] + w : pl->hb_edge[g];
-                    ex = (double)fmaf((float)g, wf, lo0f) == lo_want && (double)fmaf((float)g, wf, e0f) == hi_want;
-                }
-                ex = ex && (double)glf > lo0 && (double)glf < e0 && (double)ghf > pl->hb_edge[n] && (double)ghf < pl->hb_edge[n] + w;
-            } else {
-                ex = lo0 + w == e0;
-                for (int g = 0; ex && g <= n + 1; ++g) {
-                    const double lo_want = g == 0 ? lo0 : pl->hb_edge[g - 1];
-                    const double hi_want = g == n + 1 ? pl->hb_edge[n] + w : pl->hb_edge[g];
-                    ex = fma((double)g, w, lo0) == lo_want && fma((double)g, w, e0) == hi_want;
-                }
-                ex = ex && gl > lo0 && gl < e0 && gh > pl->hb_edge[n] && gh < pl->hb_edge[n] + w;
-            }
-            // the one-sided guess (ha_update): the guess constant biased down by the smallest delta of a ladder for which, with the
-            // kernel's own fma in the input precision, every edge E[k] of the guarded partition guesses bin k - 1 and the clamp
-            // points guess their guard bins.  fma and floor are monotone in v, so every value of [E[t], E[t+1]) then guesses t - 1
-            // or t.  No delta fits (bins of a few ulps): the table form.
-            double c0b = 0.0;
-            if (ex) {
-                const double c1 = pl->hb_c1, c0 = pl->hb_c0;
-                bool found = false;
-                for (int k = (desc->dtype == AFHIP_F32 ? 22 : 50); !found && k >= 8; --k) {
-                    const double delta = std::ldexp(1.0, -k);
-                    bool okd = true;
-                    if (desc->dtype == AFHIP_F32) {
-                        const float c1f = (float)c1, cbf = (float)(c0 - delta);
-                        auto guess = [&](double v) { return (double)floorf(fmaf((float)v, c1f, cbf)); };
-                        for (int g = 1; okd && g <= n + 1; ++g) okd = guess(pl->hb_edge[g - 1]) == (double)(g - 1);
-                        okd = okd && guess(gl) == 0.0 && guess(gh) == (double)(n + 1);
-                        if (okd) c0b = (double)cbf;
-                    } else {
-                        const double cb = c0 - delta;
-                        auto guess = [&](double v) { return floor(fma(v, c1, cb)); };
-                        for (int g = 1; okd && g <= n + 1; ++g) okd = guess(pl->hb_edge[g - 1]) == (double)(g - 1);
-                        okd = okd && guess(gl) == 0.0 && guess(gh) == (double)(n + 1);
-                        if (okd) c0b = cb;
-                    }
-                    found = okd;
-                }
-                ex = found;
-            }
-            // (these variants address a row by a 32-bit byte offset per lane)
-            if ((uint64_t)desc->n_cells * (desc->dtype == AFHIP_F64 ? 8u : 4u) >= (1ull << 32)) ex = false;
-            if (getenv("AFHIP_NO_ARITH_EDGES")) ex = false;       // experiment knob: force the table form
-            pl->hb_arith = ex; pl->hb_w = w; pl->hb_lo0 = lo0; pl->hb_gl = gl; pl->hb_gh = gh; pl->hb_c0b = c0b;
-        }
-    }
-    if (pl->hb_n > 0 && tuning == 0) { want_pipe = 0; want_vec = 1; }   // the LDS histogram lives on the direct-load path
-    const bool partition = pl->hb_n > 0 && want_pipe == 0;
-    const bool arith = partition && pl->hb_arith;
-    pairs = pairs && want_pipe == 0;
-    lean = lean && pairs; lean_sine = lean_sine && pairs;
-    // rows in flight per lane on the direct-load path: f64 four, f32 eight — but four for f32 plans with two cells per lane on
-    // grids large enough for 256-thread workgroups (the multi-column plans; see gen_variants.py)
-    int depth_hint = desc->dtype == AFHIP_F64 ? 4 : 8;
-    if (desc->dtype == AFHIP_F32 && want_pipe == 0 && want_vec == 2 && !pairs && pl->hb_n == 0 &&
-        (C_ + (int64_t)WG * 2 - 1) / ((int64_t)WG * 2) >= (int64_t)cu_count(pl->device))
-        depth_hint = 4;
-    if (const char* e = getenv("AFHIP_DEPTH_HINT")) depth_hint = atoi(e);      // experiment knob
-    const int quads = (pairs && quad_len) ? glcode : 0;
-    const bool twos = pairs && !quad_len;
-    if (quads) depth_hint = glen == 3 ? 6 : 8;           // two groups per block
-    const int lean_code = lean ? (lean_sine ? 2 : 1) : 0;
-    const Variant* v = find_variant(desc->dtype, want_pipe, pl->stat, pl->nthr, pl->K, tuning, want_vec, all_bins, single_level, partition, arith, twos, lean_code, depth_hint, quads);
-    if (!v && tuning > 0)   // a tuning arm is a hint: arms are compiled for the headline plan shapes only
-        v = find_variant(desc->dtype, want_pipe, pl->stat, pl->nthr, pl->K, 0, want_vec, all_bins, single_level, partition, arith, twos, lean_code, depth_hint, quads);
-    if (!v) v = find_variant(desc->dtype, 0, pl->stat, pl->nthr, pl->K, 0, 1, all_bins, single_level, pl->hb_n > 0, pl->hb_n > 0 && pl->hb_arith, twos, lean_code, depth_hint, quads);
-    if (!v) {
-        delete pl;
-        return fail(AFHIP_E_UNSUPPORTED, "no kernel variant for dtype=%d stat=%d slots=%d columns=%d", desc->dtype, pl->stat, pl->nthr, pl->K);
-    }
-    // A single-level plan takes an `sl` variant when the menu has one (no outer accumulators: cheaper) — but those have no region-fused
-    // twin, and a plan that stores one value per group, column and cell (a daily panel of several degree-day columns) then writes and
-    // re-reads period values worth a sizeable share of the cube.  From 5 % on the general two-level variant (outer = first) with its twin
-    // is taken instead; packed bin counts (16-byte records, gathered directly) stay where they are.
-    if (v->sl && !v->tki && tuning == 0 && !desc->exact_order && !getenv("AFHIP_NO_REGION_FUSED") &&
-        (double)desc->P * pl->K * 8.0 >= 0.05 * (double)desc->T * (desc->dtype == AFHIP_F32 ? 4.0 : 8.0)) {
-        const Variant* v2 = find_variant(desc->dtype, want_pipe, pl->stat, pl->nthr, pl->K, 0, want_vec, false, false, false, false, twos, lean_code, depth_hint, quads);
-        if (v2 && v2->pipe == 0 && !v2->tki && !v2->hb && twin_of(v2)) v = v2;
-    }
-    pl->variant = v;
-    if ((rc = build_chunks(pl, v->vec))) { delete pl; return rc; }
-    // Region-fused period ends (FusedArgs::rf_w): the twin variant, if the menu has one, and what the plan itself must satisfy —
-    // two-level columns without float32 rounding of the final value (the period value must enter the weighted sum as it leaves
-    // the accumulator; an outer mean's division by the period's group count is applied to the region sums, k_rf_reduce), at most one slot per period (shared validity needs the whole period's value), several periods
-    // (with one the stores sit at the kernel's end and cost nothing: the headline stays on the route it was measured on).
-    {
-        pl->variant_rf = twin_of(v);
-        bool ok = pl->variant_rf != nullptr && !desc->exact_order && desc->P >= 2 && !getenv("AFHIP_NO_REGION_FUSED");
-        for (const ColOp& c : pl->cols) ok = ok && !(c.rounding & AFHIP_ROUND_FINAL);      // (identity outers too: a daily panel of daily means)
-        for (int64_t p = 0; ok && p < desc->P; ++p) ok = pl->slot_ptr[(size_t)p + 1] - pl->slot_ptr[(size_t)p] <= 1;
-        // ... and per-cell period values that would be a noticeable share of the traffic: P K 8 bytes per cell against T elem.  Below
-        // ~0.2 % there is nothing to win and the emit still costs: configs[2]'s shape (40 annual values of 2 columns from 350,640
-        // hourly steps: 0.05 %) measured 0.25 % behind, the one-period headline (0.06 %) 0.6 %; the shapes that gain sit at 0.5 % and up.
-        const double share = (double)desc->P * pl->K * 8.0 / std::max(1.0, (double)desc->T * (desc->dtype == AFHIP_F32 ? 4.0 : 8.0));
-        const bool forced = getenv("AFHIP_FORCE_REGION_FUSED") != nullptr;
-        if (ok && !forced) ok = share >= 0.002;
-        // Which forms gain was measured, not derived (profiles/r03_region_fused.txt: an occupancy rule could not tell them apart): float64
-        // forms and float32 forms without threshold slots gain 3 - 50 % from two periods on; the lean four-row forms and the six-column
-        // lean pair form likewise (6-hourly monthly polynomial: step 0.97 against 1.13 - 1.33 ms).
-        // Round 4 (the scan form of the period end; twins for threshold-only plans and every short-group form; profiles/r04_region_fused_scan.txt):
-        // the float32-with-a-threshold-slot forms are level from 12 periods and ahead from there, a degree-day column alone gains 6 % at
-        // 12 and 52 periods and 22-25 % on a daily panel — one rule for all of them: period values of 0.2 % of the cube and more.  The
-        // two-row forms other than the six-column lean one (sine_dd from (tmin, tmax) pairs: a period end every few rows) pay only where
-        // the per-cell route's own traffic decides: monthly 4.44 against 3.77 ms (behind), weekly 5.80 against 6.20, daily 17.7 against
-        // 21.5 — from period values of 5 % of the cube.
-        const bool two_row_light = v->pair && !v->quad && !(v->ss == 1 && v->kmax == 6);
-        if (ok && !forced && two_row_light) {
-            double min_share = 0.05;
-            if (const char* e = getenv("AFHIP_RF_MIN_SHARE")) min_share = atof(e);      // experiment knob
-            ok = share >= min_share;
-        }
-        pl->rf_plan_ok = ok;
-    }
-
-    pl->gtab.assign(2 * ((size_t)desc->G1 + 2), 0);
-    for (int64_t g = 0; g < desc->G1; ++g) {
-        const int64_t len = pl->ib[(size_t)g + 1] - pl->ib[(size_t)g];
-        const double inv = len > 0 ? 1.0 / (double)len : 0.0;     // correctly rounded: div_by() then equals s / n exactly
-        int64_t bits;
-        memcpy(&bits, &inv, 8);
-        pl->gtab[2 * (size_t)g] = (pl->ib[(size_t)g + 1] << 1) | (pl->emit[(size_t)g] ? 1 : 0);
-        pl->gtab[2 * (size_t)g + 1] = bits;
-    }
-    if ((rc = pl->d_ob.upload(pl->ob)) || (rc = pl->d_gtab.upload(pl->gtab)) ||
+    DeviceFacts dev;
+    dev.cu_count = cu_count(pl->device);
+    dev.resident_wgs = resident_wgs_per_cu;
+    int rc;
+    if ((rc = build_plan(desc, dev, pl)) || (rc = pl->d_ob.upload(pl->ob)) || (rc = pl->d_gtab.upload(pl->gtab)) ||
         (rc = pl->d_chunks.upload(pl->chunks)) || (rc = pl->d_slot_ptr.upload(pl->slot_ptr))) {
         delete pl;
         return rc;
     }
-    const int64_t C = desc->n_cells, K = desc->K, P = desc->P;
-    auto a256 = [](int64_t b) { return (b + 255) / 256 * 256; };
-    // packed counts: integer-bin single-level variant, every column a plain bin count, no period longer than a
-    // 16-bit counter holds (0xFFFF is the NaN mark)
-    // experiment knobs, read once per plan (never on the run path)
-    if (const char* e = getenv("AFHIP_XCD_REMAP")) pl->xcd_remap = atoi(e) ? 1 : 0;
-    pl->counts_spmm = !getenv("AFHIP_NO_COUNTS_SPMM");
-    if (const char* e = getenv("AFHIP_COUNTS_SPMM_SUB")) pl->counts_spmm_sub = atoi(e);
-    pl->no_slot_spmm = env_flag("AFHIP_NO_SLOT_SPMM");            // keep k_combine_slots + k_csr_spmm on every route
-    pl->no_slots_divide = getenv("AFHIP_NO_SLOTS_DIVIDE") != nullptr;
-    pl->no_counts_divide = getenv("AFHIP_NO_COUNTS_DIVIDE") != nullptr;
-    if (const char* e = getenv("AFHIP_RF_LAYOUT")) pl->rf_layout = (e[0] == 'r') ? 1 : 0;
-    if (const char* e = getenv("AFHIP_RF_REDUCE_ORDER")) pl->rf_reduce_order = (e[0] == 'p') ? 1 : 0;
-    if (const char* e = getenv("AFHIP_SLOT_SPMM_ORDER")) pl->slot_spmm_order = (e[0] == 'p') ? 1 : 0;
-    if (const char* e = getenv("AFHIP_SLOT_SPMM_SUB")) { const int sb = atoi(e); if (sb == 8 || sb == 16 || sb == 32 || sb == 64) pl->slot_spmm_sub = sb; }
-    pl->packed = v->tki && v->sl && K <= 16 && !getenv("AFHIP_NO_PACKED_COUNTS");
-    for (const ColOp& c : pl->cols)
-        pl->packed = pl->packed && c.src == SRC_THR && c.tf == TF_NONE && c.rounding == 0 && c.outer == OUT_FIRST;
-    int64_t maxlen = 0;
-    for (int64_t g = 0; g < desc->G1; ++g) maxlen = std::max(maxlen, pl->ib[(size_t)g + 1] - pl->ib[(size_t)g]);
-    pl->packed = pl->packed && maxlen < 65535;
-    if (pl->packed) {
-        // the narrowest field that holds the longest period's count and keeps all ones free for NaN; 16-byte records when
-        // K such fields fit two words (daily data, annual bins: 13 x 9 bits), else 16-bit fields in 32 bytes
-        int bw = 1;
-        while (((int64_t)1 << bw) - 1 <= maxlen) ++bw;
-        int f = 64 / bw;
-        pl->pk.nw = 2;
-        if (K > 2 * f || getenv("AFHIP_PACK32")) { bw = 16; f = 4; pl->pk.nw = 4; }
-        pl->pk.mask = (uint32_t)(((uint64_t)1 << bw) - 1);
-        for (int j = 0; j < MAX_COLS; ++j) { pl->pk.word[j] = (uint8_t)(j / f); pl->pk.shift[j] = (uint8_t)((j % f) * bw); }
-    }
-    pl->ws_partial = pl->packed ? a256(std::max<int64_t>(pl->n_slots, 1) * C * pl->pk.nw * 8)
-                                : a256(std::max<int64_t>(pl->n_slots, 1) * K * C * 8);
-    pl->ws_panel = a256(C * (K + 1) * std::max<int64_t>(P, 1) * 8);
     *out = pl;
     return AFHIP_OK;
 }
@@ -1481,7 +845,7 @@ static int launch_temporal(afhip_plan* pl, const void* cube, double* partial, hi
     fa.gtab = pl->d_gtab.p; fa.chunks = pl->d_chunks.p;
     fa.partial = partial; fa.K = pl->K; fa.nthr = pl->nthr;
     fa.n_tiles = (int32_t)pl->tiles;
-    fa.xcd_remap = pl->xcd_remap;
+    fa.xcd_remap = 1;        // measured +0.2..1 % on configs[1] (profiles/r01_xcd_remap.txt): harmless, kept on
     fa.sine_tab = nullptr;
     if (pl->has_sine) {
         int rc = sine_table_dev(pl->device, pl->variant->pair != 0 && pl->variant->quad == 0, &fa.sine_tab);
@@ -1573,7 +937,7 @@ static int launch_spmm_slots(afhip_plan* pl, const afhip_csr* csr, const double*
     sa.nseg = csr->nseg; sa.P = P; sa.C = pl->desc.n_cells; sa.K = (int32_t)K;
     sa.p_major = pl->slot_spmm_order >= 0 ? pl->slot_spmm_order : (P >= 8 ? 1 : 0);
     // no row of the table is cut: a segment IS a region, and the lane that holds its K + 1 sums finishes the panel (no divide kernel)
-    *divided = csr->n_split == 0 && csr->nseg == csr->R && !pl->no_slots_divide;
+    *divided = csr->n_split == 0 && csr->nseg == csr->R;
     if (*divided) { sa.num = num_dev; sa.den = den_dev; sa.res = res_dev; sa.R = csr->R; }
     for (int j = 0; j < pl->K; ++j) {
         sa.outer[j] = pl->cols[(size_t)j].outer;
@@ -1702,7 +1066,7 @@ extern "C" int afhip_plan_run(afhip_plan* plan, const void* cube_dev, const afhi
                                plan->d_slot_ptr.p, plan->d_ob.p, mean_mask, (const double*)(partial + plan->n_slots * rf->n_runs * (K + 1)), rf->n_xcells,
                                rf->xreg_ptr.p, rf->xcell.p, rf->xw.p, plan->sums, csr->R, P, (int)(K + 1), rf->n_runs,
                                rf_run_major(plan, rf) ? (int64_t)(K + 1) : rf->n_runs * (K + 1), rf_run_major(plan, rf) ? plan->n_slots * (K + 1) : (int64_t)(K + 1),
-                               plan->rf_reduce_order >= 0 ? plan->rf_reduce_order : ((!rf_run_major(plan, rf) && P >= 8) ? 1 : 0));
+                               (!rf_run_major(plan, rf) && P >= 8) ? 1 : 0);
             HIP_TRY(hipGetLastError());
         }
     } else if (plan->packed && !cells_dev && plan->n_slots <= P && plan->counts_spmm) {
@@ -1711,7 +1075,7 @@ extern "C" int afhip_plan_run(afhip_plan* plan, const void* cube_dev, const afhi
         const int64_t nv = exact ? csr->R : csr->nseg, nq = nv * P;
         if (nq) {
             // rows that are never cut (exact order, or a table without long rows): the gather finishes the panel itself, no divide kernel
-            divided = (exact || csr->n_split == 0) && nv == csr->R && !plan->no_counts_divide;
+            divided = (exact || csr->n_split == 0) && nv == csr->R;
             // lanes per pair: one (the table's order: `exact_order`), or a group of lanes over the row's entries with the pairs dealt period-major
             // (one lane per pair leaves a job of few periods with few threads, each walking its row alone: annual bins on 3,100 county-sized
             // regions 0.365 ms against 0.030 with sixteen lanes per pair; many periods turn it around — the group's lanes idle on short

@@ -1,0 +1,725 @@
+// afhip_planner.cpp — plan building (afhip_planner.h).  Host code only: compiled as C++, no HIP header, no hip* call.
+//
+// build_plan turns the column list into
+//   * one inner accumulator set (STAT mode) + deduplicated threshold slots evaluated on
+//     raw data, + one ColOp per column (source, transform, outer reducer);
+//   * a chunk table over time: chunks are ranges of whole inner groups; a chunk either
+//     holds whole outer periods (each emits its final value) or is a piece of one long
+//     period (it emits a partial that k_combine_slots merges in time order);
+//   * the kernel variant (dtype, LDS-DMA or direct loads, STAT, slots, columns).
+// One function per decision, in the order build_plan calls them; each takes what it reads as parameters and returns its
+// result as a small value.
+#include "afhip_planner.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+namespace afhip {
+
+namespace {
+thread_local std::string g_err;
+}
+
+int fail(int code, const char* fmt, ...) {
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+
+const char* last_error() { return g_err.c_str(); }
+
+// ---- knobs ----
+PlanKnobs read_knobs() {
+    auto set = [](const char* name) { return getenv(name) != nullptr; };
+    PlanKnobs k;
+    if (const char* e = getenv("AFHIP_FORCE_WG")) { int w = atoi(e); if (w == 64 || w == 128 || w == 256) k.force_wg = w; }
+    if (const char* e = getenv("AFHIP_WGS_PER_CU")) k.wgs_per_cu = std::max(1, atoi(e));
+    k.no_period_chunks = set("AFHIP_NO_PERIOD_CHUNKS");
+    k.no_round_fill = set("AFHIP_NO_ROUND_FILL");
+    k.no_pair_mode = set("AFHIP_NO_PAIR_MODE");
+    k.no_quad_mode = set("AFHIP_NO_QUAD_MODE");
+    k.no_ragged_mode = set("AFHIP_NO_RAGGED_MODE");
+    k.no_region_fused = set("AFHIP_NO_REGION_FUSED");
+    k.counts_spmm = !set("AFHIP_NO_COUNTS_SPMM");
+    if (const char* e = getenv("AFHIP_COUNTS_SPMM_SUB")) k.counts_spmm_sub = atoi(e);
+    if (const char* e = getenv("AFHIP_NO_SLOT_SPMM")) k.no_slot_spmm = atoi(e) != 0;
+    if (const char* e = getenv("AFHIP_RF_LAYOUT")) k.rf_layout = (e[0] == 'r') ? 1 : 0;
+    if (const char* e = getenv("AFHIP_SLOT_SPMM_ORDER")) k.slot_spmm_order = (e[0] == 'p') ? 1 : 0;
+    if (const char* e = getenv("AFHIP_SLOT_SPMM_SUB")) { const int sb = atoi(e); if (sb == 8 || sb == 16 || sb == 32 || sb == 64) k.slot_spmm_sub = sb; }
+    return k;
+}
+
+// ---- 1. column lowering ----
+static int add_thr_slot(std::vector<ThrSlot>& thr, const double* a3, bool bins) {
+    ThrSlot s{};
+    s.t0 = a3[0]; s.t1 = a3[1];
+    const bool base_is_t0 = (a3[2] == 0.0);                 // nb_kernels.py:167
+    if (bins) { s.A = 0.0; s.B = 1.0; }
+    else if (base_is_t0) { s.A = 1.0; s.B = -a3[0]; }
+    else { s.A = -1.0; s.B = a3[1]; }
+    // float thresholds equivalent to the double compares for float inputs
+    s.t0f = (float)a3[0]; if ((double)s.t0f > a3[0]) s.t0f = std::nextafterf(s.t0f, -INFINITY);
+    s.t1f = (float)a3[1]; if ((double)s.t1f < a3[1]) s.t1f = std::nextafterf(s.t1f, INFINITY);
+    s.nan_poisons = bins ? 0 : 1;
+    for (size_t i = 0; i < thr.size(); ++i)
+        if (!memcmp(&thr[i], &s, sizeof s)) return (int)i;
+    thr.push_back(s);
+    return (int)thr.size() - 1;
+}
+
+static int lower_columns(PlanLayout* pl) {
+    const int K = pl->desc.K;
+    int stat = 0;
+    pl->thr.clear(); pl->cols.clear();
+    pl->has_sine = false;
+    for (int j = 0; j < K; ++j) {
+        const afhip_column& c = pl->columns[j];
+        ColOp co{};
+        co.rounding = c.rounding;
+        switch (c.inner) {
+            case AFHIP_MEAN: co.src = SRC_MEAN; stat = std::max(stat, 1); break;
+            case AFHIP_SUM: co.src = SRC_SUM; stat = std::max(stat, 1); break;
+            case AFHIP_MIN: co.src = SRC_MIN; stat = std::max(stat, 2); break;
+            case AFHIP_MAX: co.src = SRC_MAX; stat = std::max(stat, 2); break;
+            case AFHIP_NANMEAN: co.src = SRC_NANMEAN; stat = 3; break;
+            case AFHIP_DD: co.src = SRC_THR; co.src_idx = add_thr_slot(pl->thr, c.inner_args, false); break;
+            case AFHIP_BINS: co.src = SRC_THR; co.src_idx = add_thr_slot(pl->thr, c.inner_args, true); break;
+            case AFHIP_SINE_DD:
+                co.src = SRC_SINE; stat = std::max(stat, 2);
+                co.s0 = c.inner_args[0]; co.s1 = c.inner_args[1];
+                co.s0x2 = 2.0 * co.s0; co.s1x2 = 2.0 * co.s1;
+                {   // the pair-mode window tests on float data compare in float: s rounded down / up (afhip_plan_types.h: ColOp)
+                    auto dn = [](double t) { float f = (float)t; return (double)f > t ? std::nextafterf(f, -INFINITY) : f; };
+                    auto up = [](double t) { float f = (float)t; return (double)f < t ? std::nextafterf(f, INFINITY) : f; };
+                    co.s0dn = dn(co.s0); co.s0up = up(co.s0); co.s1dn = dn(co.s1); co.s1up = up(co.s1);
+                }
+                co.swidth = co.s1 - co.s0; co.swidth2 = 2.0 * co.swidth;
+                pl->has_sine = true;
+                if (c.inner_args[2] != 0.0 && c.inner_args[2] != 1.0)
+                    return fail(AFHIP_E_INVALID, "column %d: sine_dd flag must be 0 or 1 (temporal.py:324)", j);
+                co.skind = (int)c.inner_args[2];
+                break;
+            default: return fail(AFHIP_E_INVALID, "column %d: unknown inner reducer %d", j, c.inner);
+        }
+        switch (c.transform) {
+            case AFHIP_TF_NONE: co.tf = TF_NONE; break;
+            case AFHIP_TF_POW: {
+                const double e = c.transform_arg;
+                if (e == std::floor(e) && std::fabs(e) <= 64.0) { co.tf = TF_POWI; co.tf_iarg = (int)e; }
+                else { co.tf = TF_POW; co.tf_arg = e; }
+                break;
+            }
+            case AFHIP_TF_HINGE: co.tf = TF_HINGE; co.tf_arg = c.transform_arg; break;
+            case AFHIP_TF_INTER: co.tf = TF_INTER; break;
+            default: return fail(AFHIP_E_INVALID, "column %d: unknown transform %d", j, c.transform);
+        }
+        // pow() and `inter` are compiled into the all-purpose (STAT 3) variants only (FEAT bit 1)
+        if (co.tf == TF_POW || co.tf == TF_INTER) stat = 3;
+        switch (c.outer) {
+            case AFHIP_IDENTITY: co.outer = OUT_FIRST; break;
+            case AFHIP_SUM: co.outer = OUT_SUM; break;
+            case AFHIP_MEAN: co.outer = OUT_MEAN; break;
+            case AFHIP_MIN: co.outer = OUT_MIN; break;
+            case AFHIP_MAX: co.outer = OUT_MAX; break;
+            case AFHIP_DD:
+            case AFHIP_BINS:
+                co.outer = c.outer == AFHIP_DD ? OUT_DD : OUT_BINS;
+                co.o0 = c.outer_args[0]; co.o1 = c.outer_args[1];
+                co.obase = (c.outer_args[2] == 0.0) ? c.outer_args[0] : c.outer_args[1];
+                break;
+            default:
+                return fail(AFHIP_E_UNSUPPORTED, "column %d: outer reducer %d is not fused (use the staged path)", j, c.outer);
+        }
+        pl->cols.push_back(co);
+    }
+    if ((int)pl->thr.size() > MAX_THR) return fail(AFHIP_E_UNSUPPORTED, "more than %d threshold slots in one pass", MAX_THR);
+    if (K > MAX_COLS) return fail(AFHIP_E_UNSUPPORTED, "more than %d columns in one pass", MAX_COLS);
+    pl->stat = stat;
+    pl->nthr = (int)pl->thr.size();
+    pl->K = K;
+    return AFHIP_OK;
+}
+
+// (rows of 4 GiB and more: the short-group and arithmetic-edge variants address a row by a 32-bit byte offset per lane)
+static bool rows_fit_32bit(const afhip_plan_desc& d) {
+    return (uint64_t)d.n_cells * (d.dtype == AFHIP_F64 ? 8u : 4u) < (1ull << 32);
+}
+
+// ---- 2. short-group form ----
+struct GroupForm {
+    int glen = 0;           // length class of the inner groups: 2 / 3 / 4 rows throughout, 5 = mixed one to four rows, 0 = none of these
+    bool pairs = false;     // short-group mode (two-, three- or four-row groups)
+    bool lean = false, lean_sine = false;      // the lean group end (FEAT bit 8), its sine-only form (FEAT bit 9)
+    bool quad_len() const { return glen >= 3; }      // three / four / mixed rows: the lean form only, general sine closed forms
+    int glcode() const { return glen == 5 ? 3 : (glen == 4 ? 1 : (glen == 3 ? 2 : 0)); }      // Variant::quad
+};
+
+// short inner groups: the direct path keeps DEPTH rows in flight only INSIDE a group, the LDS-DMA ring
+// prefetches across group ends.  Measured (mean plan, 721x1440 / 1801x3600): 2-step groups f64 4.5 vs
+// 6.0 TB/s, f32 3.5 vs 4.3; 4-step groups f32 4.4 vs 5.6, f64 equal; 8 steps and longer: equal.
+// every inner group exactly two rows ((tmin, tmax) pairs) and min / max / sine columns: the pair-mode variants of the
+// direct-load path keep DEPTH / 2 whole groups in flight, so they need no ring either
+// ... and the same for groups of exactly four rows (6-hourly data), in the lean form only (FEAT bit 10)
+static int group_length_class(const PlanLayout& pl, const PlanKnobs& knobs) {
+    const afhip_plan_desc* desc = &pl.desc;
+    int glen = 0;
+    if (desc->G1 > 0 && pl.nthr == 0 && (pl.stat == 1 || pl.stat == 2) && !knobs.no_pair_mode) {
+        for (int L : {2, 3, 4}) {
+            bool all = desc->T == (int64_t)L * desc->G1;
+            for (int64_t g = 0; all && g < desc->G1; ++g) all = pl.ib[(size_t)g + 1] - pl.ib[(size_t)g] == L;
+            if (all) glen = L;
+        }
+        // mixed lengths of one to four rows (a sub-daily series with missing steps): the four-row form with a length per group
+        // (FEAT bit 13); a series of single rows throughout is not a short-group plan
+        if (glen == 0 && desc->T > desc->G1 && !knobs.no_ragged_mode) {
+            bool all = true;
+            for (int64_t g = 0; all && g < desc->G1; ++g) {
+                const int64_t L = pl.ib[(size_t)g + 1] - pl.ib[(size_t)g];
+                all = L >= 1 && L <= 4;
+            }
+            if (all) glen = 5;
+        }
+    }
+    if (glen >= 3 && knobs.no_quad_mode) glen = 0;
+    // (its loads address a row by a 32-bit byte offset per lane: rows of 4 GiB and more take the general path)
+    if (!rows_fit_32bit(*desc)) glen = 0;
+    return glen;
+}
+
+static GroupForm short_group_form(const PlanLayout& pl, const PlanKnobs& knobs) {
+    const afhip_plan_desc* desc = &pl.desc;
+    GroupForm f;
+    f.glen = group_length_class(pl, knobs);
+    f.pairs = f.glen >= 2;
+    // pair plans whose columns are all  mean | sum | min | max | sine_dd -> (integer power) -> sum | mean  without float32 rounding
+    // take the lean group end (FEAT bit 8); when every column is a plain sine_dd, its tightest form (FEAT bit 9).  A sine_dd
+    // column there needs s0 < s1: its two max() terms are one clamp of width s1 - s0.
+    f.lean = f.pairs; f.lean_sine = f.lean && pl.K <= 2 && !f.quad_len();
+    for (const ColOp& c : pl.cols) {
+        const bool sine_ok = c.src == SRC_SINE && c.s0 < c.s1 && std::isfinite(c.swidth);
+        const bool src_ok = c.src == SRC_MEAN || c.src == SRC_SUM || c.src == SRC_MIN || c.src == SRC_MAX || sine_ok;
+        f.lean = f.lean && src_ok && (c.tf == TF_NONE || (c.tf == TF_POWI && c.tf_iarg >= 1)) && c.rounding == 0 && (c.outer == OUT_SUM || c.outer == OUT_MEAN);
+        f.lean_sine = f.lean_sine && sine_ok && c.tf == TF_NONE;
+    }
+    f.lean_sine = f.lean_sine && f.lean;
+    // four-row groups exist in the lean form only, for as many columns as its variants hold
+    if (f.quad_len()) {
+        VariantQuery q;
+        q.dtype = desc->dtype; q.stat = pl.stat; q.K = pl.K; q.lean = 1; q.quads = f.glcode();
+        if (!(f.lean && find_variant(q))) f.pairs = f.lean = false;
+    }
+    // mean / sum columns alone (no min, max or sine): the pair path exists in the lean form only, and a light plan (one or two
+    // columns) streams faster through the LDS-DMA ring, whose prefetch runs across the two-row groups (5.99 vs 5.44 TB/s on
+    // 1801 x 3600 f32); with more columns the lean group end wins (profiles/r03_pairs_mean_poly.txt)
+    // (four-row groups: the lean form measured ahead of the ring at every column count, profiles/r03_quad_groups.txt)
+    if (f.pairs && pl.stat == 1) {
+        // (three-row groups on float32: one- and two-column plans stream faster through the ring, 4.59 / 4.94 against 4.93 / 5.04 ms on
+        // 1801 x 3600; from three columns on, and on float64 at every count, the lean form is ahead: profiles/r04_three_row_groups.txt)
+        // (mixed lengths likewise: 6.25 / 6.39 against 6.89 / 6.83 ms, float64 level; profiles/r04_mixed_short_groups.txt)
+        const int min_k = f.quad_len() ? (((f.glen == 3 || f.glen == 5) && desc->dtype == AFHIP_F32) ? 3 : 1) : 3;
+        if (!f.lean || pl.K < min_k) f.pairs = f.lean = f.lean_sine = false;
+    }
+    return f;
+}
+
+// a short-group form lives on the direct-load path (load_path takes the LDS-DMA ring only for plans that have none: this keeps the two in step)
+static GroupForm on_load_path(GroupForm f, int pipe) {
+    f.pairs = f.pairs && pipe == 0;
+    f.lean = f.lean && f.pairs; f.lean_sine = f.lean_sine && f.pairs;
+    return f;
+}
+
+// ---- 3. load path ----
+struct LoadPath {
+    int pipe = 0;      // 0 direct loads, 1 LDS-DMA ring
+    int vec = 1;       // cells per lane
+};
+
+// variant: the load path that measured fastest for the dtype and grid size
+// (profiles/r01_sweep_load_arms.txt), subject to row alignment.
+static LoadPath load_path(const PlanLayout& pl, bool pairs) {
+    const afhip_plan_desc* desc = &pl.desc;
+    const int64_t C_ = desc->n_cells;
+    LoadPath p;
+    if (desc->dtype == AFHIP_F64) {
+        // one cell per lane, direct loads — on small grids too: round 1 had the LDS-DMA ring ahead there (6.1 vs 5.4 TB/s on
+        // 104x236), the re-sweep on round 2's kernel has it behind (5.99 vs 6.67 TB/s; profiles/r02_kbench_resweep.txt)
+    } else {
+        // two cells per lane, unless the plan carries many accumulators (register pressure):
+        // one cell per lane measured 1.6x faster on the 13-bin plan (profiles/r01_kbench_c4_f32.json)
+        if (C_ % 2 == 0 && pl.nthr < 4 && pl.K < 8) p.vec = 2;
+        // ... and unless it is a light one (one or two mean / sum columns, no threshold slots): one cell per lane then keeps
+        // more waves resident and measured 6.6 % faster on configs[0] at 215x1440 (6,534 -> 6,966 GB/s), level on the 104x236
+        // window (profiles/r02_kbench_light_f32_plans.txt)
+        if (pl.stat <= 1 && pl.nthr == 0 && pl.K <= 2) p.vec = 1;
+    }
+    // short inner groups that are no short-group plan: the LDS-DMA ring (see group_length_class)
+    if (!pairs) {
+        const double avg_group = desc->G1 > 0 ? (double)desc->T / (double)desc->G1 : 0.0;
+        const int vec16 = desc->dtype == AFHIP_F64 ? 2 : 4;
+        bool sine = false;                          // sine_dd on short windows is fp64-VALU-bound: direct loads measured 4 % faster
+        for (const ColOp& c : pl.cols) sine = sine || c.src == SRC_SINE;
+        if (!sine && avg_group > 0 && avg_group < (desc->dtype == AFHIP_F64 ? 4.0 : 8.0) && C_ % vec16 == 0) { p.pipe = 1; p.vec = vec16; }
+    }
+    return p;
+}
+
+// the tuning arm of the description, or 0 when the rows do not allow it
+static int usable_tuning(const afhip_plan_desc& d) {
+    int tuning = d.tuning;
+    if (tuning > 0) {
+        const int tvec = ((tuning % 10000) % 1000) / 100;
+        if (tvec <= 0 || d.n_cells % tvec != 0) tuning = 0;          // a vector arm needs rows that are multiples of it
+    }
+    return tuning;
+}
+
+// ---- 4. histogram partition ----
+// The float32 / float64 checks below are one template over the input type T: std::fma / std::floor on T are fmaf / floorf for
+// float and fma / floor for double, the very operations the kernel executes on its input precision.
+// arithmetic edges: E[g] = lo0 + g * w must come out EXACTLY, in the input precision and by the very fma the
+// kernel executes, for every bin of the guarded partition; the clamp points must lie inside the guard bins
+template <typename T>
+static bool edges_exact(const HistPartition& h, int n, double e0) {
+    const double w = h.hb_w, lo0 = h.hb_lo0, gl = h.hb_gl, gh = h.hb_gh;
+    const T wt = (T)w, lo0t = (T)lo0, e0t = (T)e0, glt = (T)gl, ght = (T)gh;
+    bool ex = (double)wt == w && (double)lo0t == lo0 && (double)e0t == e0 && lo0t + wt == e0t;
+    for (int g = 0; ex && g <= n + 1; ++g) {
+        const double lo_want = g == 0 ? lo0 : h.hb_edge[g - 1];
+        const double hi_want = g == n + 1 ? h.hb_edge[n] + w : h.hb_edge[g];
+        ex = (double)std::fma((T)g, wt, lo0t) == lo_want && (double)std::fma((T)g, wt, e0t) == hi_want;
+    }
+    return ex && (double)glt > lo0 && (double)glt < e0 && (double)ght > h.hb_edge[n] && (double)ght < h.hb_edge[n] + w;
+}
+
+// the one-sided guess (ha_update): the guess constant biased down by the smallest delta of a ladder for which, with the
+// kernel's own fma in the input precision, every edge E[k] of the guarded partition guesses bin k - 1 and the clamp
+// points guess their guard bins.  fma and floor are monotone in v, so every value of [E[t], E[t+1]) then guesses t - 1
+// or t.  No delta fits (bins of a few ulps): the table form.
+template <typename T>
+static bool biased_guess(const HistPartition& h, int n, int k_first, double* c0b) {
+    const double c1 = h.hb_c1, c0 = h.hb_c0;
+    bool found = false;
+    for (int k = k_first; !found && k >= 8; --k) {
+        const double delta = std::ldexp(1.0, -k);
+        const T c1t = (T)c1, cbt = (T)(c0 - delta);
+        auto guess = [&](double v) { return (double)std::floor(std::fma((T)v, c1t, cbt)); };
+        bool okd = true;
+        for (int g = 1; okd && g <= n + 1; ++g) okd = guess(h.hb_edge[g - 1]) == (double)(g - 1);
+        okd = okd && guess(h.hb_gl) == 0.0 && guess(h.hb_gh) == (double)(n + 1);
+        if (okd) *c0b = (double)cbt;
+        found = okd;
+    }
+    return found;
+}
+
+// contiguous equal-width partition?  (sorted by t0, t1[b] == t0[b+1], constant width)
+static HistPartition find_partition(const PlanLayout& pl, bool all_bins) {
+    const afhip_plan_desc* desc = &pl.desc;
+    HistPartition h;
+    if (!(all_bins && pl.nthr >= 4)) return h;
+    std::vector<int> order((size_t)pl.nthr);
+    for (int i = 0; i < pl.nthr; ++i) order[(size_t)i] = i;
+    std::sort(order.begin(), order.end(), [&](int x, int y) { return pl.thr[(size_t)x].t0 < pl.thr[(size_t)y].t0; });
+    const double e0 = pl.thr[(size_t)order[0]].t0;
+    const double w = pl.thr[(size_t)order[0]].t1 - e0;
+    bool ok = w > 0 && std::isfinite(e0) && std::isfinite(w);
+    for (int b = 0; ok && b < pl.nthr; ++b) {
+        const ThrSlot& t = pl.thr[(size_t)order[(size_t)b]];
+        ok = std::fabs(t.t0 - (e0 + b * w)) <= 1e-9 * w && std::fabs(t.t1 - (e0 + (b + 1) * w)) <= 1e-9 * w;
+        if (ok && b + 1 < pl.nthr) ok = t.t1 == pl.thr[(size_t)order[(size_t)b + 1]].t0;
+    }
+    // the in-kernel guess floor(v / w - e0 / w) is computed in the INPUT precision and may be off by
+    // one bin at most: the bins must not be narrower than ~2^20 (f32) / 2^48 (f64) ulps of the edges
+    const double emax = std::max(std::fabs(e0), std::fabs(e0 + pl.nthr * w));
+    const double eps = desc->dtype == AFHIP_F32 ? 1.2e-7 : 2.3e-16;
+    ok = ok && emax * eps * 16.0 < w;
+    if (!ok) return h;
+    const int n = pl.nthr;
+    h.hb_n = n; h.hb_c1 = 1.0 / w; h.hb_c0 = 1.0 - e0 / w;      // + 1: bin 0 is the lower guard bin
+    for (int b = 0; b < n; ++b) {
+        h.hb_bin_of_slot[order[(size_t)b]] = b;
+        h.hb_edge[b] = pl.thr[(size_t)order[(size_t)b]].t0;
+    }
+    h.hb_edge[n] = pl.thr[(size_t)order[(size_t)n - 1]].t1;
+    h.hb_w = w; h.hb_lo0 = e0 - w; h.hb_gl = e0 - 0.5 * w; h.hb_gh = h.hb_edge[n] + 0.5 * w;
+    const bool f32 = desc->dtype == AFHIP_F32;
+    bool ex = f32 ? edges_exact<float>(h, n, e0) : edges_exact<double>(h, n, e0);
+    if (ex) ex = f32 ? biased_guess<float>(h, n, 22, &h.hb_c0b) : biased_guess<double>(h, n, 50, &h.hb_c0b);
+    // (these variants address a row by a 32-bit byte offset per lane)
+    if (!rows_fit_32bit(*desc)) ex = false;
+    h.hb_arith = ex;
+    return h;
+}
+
+// ---- 5. variant choice ----
+// the variant with the region-fused period ends compiled in and every other field equal (null: the menu has none)
+static const Variant* twin_of(const Variant* v) {
+    int n = 0;
+    const Variant* tab = variants_table(&n);
+    for (int i = 0; i < n; ++i) {
+        const Variant& t = tab[i];
+        if (t.rf && t.dtype == v->dtype && t.pipe == v->pipe && t.vec == v->vec && t.stat == v->stat && t.nthr == v->nthr && t.kmax == v->kmax &&
+            t.depth == v->depth && t.nt == v->nt && t.tki == v->tki && t.sl == v->sl && t.hb == v->hb && t.ha == v->ha && t.pair == v->pair &&
+            t.ss == v->ss && t.quad == v->quad)
+            return &t;
+    }
+    return nullptr;
+}
+
+// `form0` and `path0` are the short-group form and the load path the plan would take by the default rules.  Null: the menu holds
+// no variant that covers the plan.
+static const Variant* choose_variant(const PlanLayout& pl, const GroupForm& form0, const LoadPath& path0, const HistPartition& hist, bool all_bins,
+                                     int tuning, const PlanKnobs& knobs, int cu_count) {
+    const afhip_plan_desc* desc = &pl.desc;
+    // specialisations the lowered plan qualifies for
+    bool single_level = desc->P == desc->G1;
+    for (int64_t p = 0; single_level && p <= desc->P; ++p) single_level = pl.ob[(size_t)p] == p;
+    for (const ColOp& c : pl.cols) single_level = single_level && c.outer == OUT_FIRST;
+    const LoadPath path = (hist.hb_n > 0 && tuning == 0) ? LoadPath{0, 1} : path0;   // the LDS histogram lives on the direct-load path
+    const GroupForm form = on_load_path(form0, path.pipe);
+    // rows in flight per lane on the direct-load path: f64 four, f32 eight — but four for f32 plans with two cells per lane on
+    // grids large enough for 256-thread workgroups (the multi-column plans; see gen_variants.py)
+    int depth_hint = desc->dtype == AFHIP_F64 ? 4 : 8;
+    if (desc->dtype == AFHIP_F32 && path.pipe == 0 && path.vec == 2 && !form.pairs && hist.hb_n == 0 &&
+        (desc->n_cells + (int64_t)WG * 2 - 1) / ((int64_t)WG * 2) >= (int64_t)cu_count)
+        depth_hint = 4;
+    VariantQuery q;
+    q.dtype = desc->dtype; q.pipe = path.pipe; q.vec = path.vec; q.stat = pl.stat; q.nthr = pl.nthr; q.K = pl.K; q.tuning = tuning;
+    q.all_bins = all_bins; q.single_level = single_level;
+    q.partition = hist.hb_n > 0 && path.pipe == 0;
+    q.arith = q.partition && hist.hb_arith;
+    q.quads = (form.pairs && form.quad_len()) ? form.glcode() : 0;
+    q.pairs = form.pairs && !form.quad_len();
+    if (q.quads) depth_hint = form.glen == 3 ? 6 : 8;           // two groups per block
+    q.depth_hint = depth_hint;
+    q.lean = form.lean ? (form.lean_sine ? 2 : 1) : 0;
+    const Variant* v = find_variant(q);
+    VariantQuery untuned = q;
+    untuned.tuning = 0;
+    if (!v && tuning > 0) v = find_variant(untuned);   // a tuning arm is a hint: arms are compiled for the headline plan shapes only
+    if (!v) {      // direct loads, one cell per lane
+        VariantQuery d = untuned;
+        d.pipe = 0; d.vec = 1; d.partition = hist.hb_n > 0; d.arith = hist.hb_n > 0 && hist.hb_arith;
+        v = find_variant(d);
+    }
+    if (!v) return nullptr;
+    // A single-level plan takes an `sl` variant when the menu has one (no outer accumulators: cheaper) — but those have no region-fused
+    // twin, and a plan that stores one value per group, column and cell (a daily panel of several degree-day columns) then writes and
+    // re-reads period values worth a sizeable share of the cube.  From 5 % on the general two-level variant (outer = first) with its twin
+    // is taken instead; packed bin counts (16-byte records, gathered directly) stay where they are.
+    if (v->sl && !v->tki && tuning == 0 && !desc->exact_order && !knobs.no_region_fused &&
+        (double)desc->P * pl.K * 8.0 >= 0.05 * (double)desc->T * (desc->dtype == AFHIP_F32 ? 4.0 : 8.0)) {
+        VariantQuery two = untuned;
+        two.all_bins = two.single_level = two.partition = two.arith = false;
+        const Variant* v2 = find_variant(two);
+        if (v2 && v2->pipe == 0 && !v2->tki && !v2->hb && twin_of(v2)) v = v2;
+    }
+    return v;
+}
+
+// ---- 6. chunking ----
+size_t plan_lds_bytes(const PlanLayout* pl) {
+    size_t lds = pl->variant->pipe == 1 ? (size_t)(pl->wg / 64) * pl->variant->depth * 1024 : 0;
+    if (pl->has_sine) lds += (pl->variant->pair && !pl->variant->quad) ? SINE_P2_BYTES : SINE_TAB_BYTES;      // the variant's sine table, behind the ring
+    if (pl->variant->hb) lds = (size_t)HB_TABLE_BYTES + (size_t)(pl->hb_n + 2) * pl->variant->vec * pl->wg * 4;
+    return lds;
+}
+
+// Chunking.  target_len = time steps a workgroup should stream; a long period is cut on
+// inner-group boundaries into pieces (each emits a partial), short consecutive periods are
+// packed into one chunk (each emits its own final value).
+static int lay_chunks(PlanLayout* pl, int64_t want_chunks);
+
+static int build_chunks(PlanLayout* pl, int vec, const PlanKnobs& knobs, const DeviceFacts& dev) {
+    const int64_t P = pl->desc.P, C = pl->desc.n_cells;
+    // single-wave workgroups when 256-thread tiles cannot give every CU a few workgroups — and on large grids too, unless every
+    // workgroup copies a sine table into LDS first (pair-mode sine_dd at 64 threads: 3.23 -> 5.80 ms).  The bare streaming read of
+    // this access shape is fastest in single-wave workgroups (scripts/probe/read_bw.hip: 7.02 against 6.69 TB/s at four rows in
+    // flight, profiles/r03_read_ceiling.txt) and the plans follow it by less: configs[1] f64 3.142 -> 3.131 ms, f32 1.713 -> 1.693,
+    // C1 f32 1.577 -> 1.558, the reference's benchmark shape 5.336 -> 5.281 (same box, arms alternated; 128 threads: 3.234).
+    pl->wg = ((C + (int64_t)WG * vec - 1) / ((int64_t)WG * vec) < (int64_t)dev.cu_count || !pl->has_sine) ? 64 : WG;
+    // the LDS-histogram kernel: single-wave workgroups and MANY time chunks.  It is short of bytes in flight (waves park 65 % of
+    // their cycles on memory at 4.2 waves per SIMD, VALU and LDS far from busy: profiles/r03_c4_bound_pmc.txt), and the more,
+    // smaller workgroups the grid offers the fuller the CUs stay: configs[3] f32 3.15 ms (7 chunks of 256 threads) -> 2.84 ms
+    // (126 chunks of 64), f64 5.86 -> 5.58 (profiles/r03_sweep_chunks_depth.txt).  Round 1 had measured 4-wave workgroups
+    // ahead — at the few chunks of that time.
+    const bool hist = pl->variant && pl->variant->hb;
+    if (hist) pl->wg = 64;
+    if (knobs.force_wg) pl->wg = knobs.force_wg;   // experiment knob
+    pl->tiles = (C + (int64_t)pl->wg * vec - 1) / ((int64_t)pl->wg * vec);
+    // aim for ~4 workgroups per CU over the whole grid, never streaming fewer than 64 steps
+    int per_cu = 4;      // measured (profiles/r01_sweep_chunks.txt, r03_sweep_chunks_depth.txt): the fewer time chunks the better once every CU has ~4 workgroups
+    if (hist) per_cu = 96;   // ... except for the histogram kernel (above)
+    if (knobs.wgs_per_cu) per_cu = knobs.wgs_per_cu;   // experiment knob
+    const int64_t want_wgs = (int64_t)dev.cu_count * per_cu * (WG / pl->wg);
+    int64_t want_chunks = std::max<int64_t>(1, (want_wgs + pl->tiles - 1) / pl->tiles);
+    // Plans with several output periods: up to one time chunk per period.  Cutting ON period boundaries adds no slot and no traffic
+    // (the "fewer chunks are better" of round 1 was measured at P = 1, where every cut adds a slot), and the period-end stores are
+    // what such plans pay for: with the stores compiled out the configs[1] plan runs P = 12 and P = 73 exactly as fast as P = 1
+    // (3.14 ms), with them 3.69 and 4.30 — 150 MB of stores for 0.55 ms, box-dependent (0.22 ms on another box).  The more chunks, the
+    // fewer period ends a workgroup carries in the middle of its stream: P = 365 5.24 -> 4.94 ms, P = 73 3.76 -> 3.46, weekly f32
+    // 1.72 -> 1.67, the reference's own benchmark shape 5.64 -> 5.53 (profiles/r03_period_end_stores.txt).  lay_chunks still
+    // packs periods shorter than 64 steps together; the histogram kernel keeps its own rule.
+    // Plans that already get eight chunks or more keep them (configs[2]'s shape, 14 chunks for 40 years: 40 measured 0.5 % behind).
+    bool period_chunks = false;
+    if (P > 1 && !hist && want_chunks < 8 && !knobs.wgs_per_cu && !knobs.no_period_chunks) {
+        const int64_t wg_cap = 262144;                              // workgroups a period-chunked launch may have
+        const int64_t by_period = std::min<int64_t>(P, std::max<int64_t>(1, wg_cap / std::max<int64_t>(pl->tiles, 1)));
+        // (a handful of period chunks makes a handful of occupancy rounds with a costly last one: P = 4 measured 2-4 % behind one chunk)
+        if (by_period >= 8) { want_chunks = by_period; period_chunks = true; }
+    }
+    int rc = lay_chunks(pl, want_chunks);
+    if (rc) return rc;
+    // Rounds.  A CU holds `resident` workgroups of this variant at once; a grid of more workgroups than the chip holds runs in
+    // "rounds", and a last round that is mostly empty is paid in full: the reference's own benchmark shape (global 0.25 deg,
+    // 2,028 tiles as ONE chunk against 1,536 resident workgroups = 1.32 rounds) ran at 0.65 of the HBM peak, as three chunks
+    // (3.96 rounds) at 0.79 (profiles/r03_ref_shape_arms.txt).  When the grid does not fit the chip at once, take the chunk
+    // count (of the next few) whose last round is fullest; a grid that fits keeps the fewest chunks, which measured best.
+    // (period-aligned chunks are many and short: their last round weighs little, and the search below would cut periods to fill it)
+    if (!period_chunks && !knobs.no_round_fill && !knobs.wgs_per_cu) {
+        const int64_t capacity = (int64_t)dev.resident_wgs(pl->variant->fn, pl->wg, plan_lds_bytes(pl)) * dev.cu_count;
+        auto fill = [&](int64_t total) { const int64_t rounds = (total + capacity - 1) / capacity; return (double)total / (double)(rounds * capacity); };
+        int64_t total = pl->tiles * (int64_t)pl->chunks.size();
+        if (capacity > 0 && total > capacity && fill(total) < 0.92) {
+            int64_t best_c = want_chunks;
+            double best = fill(total);
+            size_t last_n = pl->chunks.size();
+            for (int64_t c = want_chunks + 1; c <= want_chunks + 12 && best < 0.92; ++c) {
+                if ((rc = lay_chunks(pl, c))) return rc;
+                if (pl->chunks.size() == last_n) continue;         // (period boundaries: not every count exists)
+                last_n = pl->chunks.size();
+                const double f = fill(pl->tiles * (int64_t)pl->chunks.size());
+                if (f > best + 1e-9) { best = f; best_c = c; }
+            }
+            if ((rc = lay_chunks(pl, best_c))) return rc;
+        }
+    }
+    return AFHIP_OK;
+}
+
+// Chunk table for ~want_chunks time chunks (see build_chunks).
+static int lay_chunks(PlanLayout* pl, int64_t want_chunks) {
+    const auto& ib = pl->ib;
+    const auto& ob = pl->ob;
+    const int64_t G1 = pl->desc.G1, P = pl->desc.P, T = pl->desc.T;
+    const int64_t target_len = std::max<int64_t>(64, T / std::max<int64_t>(want_chunks, 1));
+    // splitting a period adds partial traffic (16 B per extra slot, column and cell, write +
+    // read); keep it under ~5 % of the cube: extra_slots*K*16 <= 0.05*T*elem.  (2 % starved the
+    // CONUS-window f32 plan of workgroups: 9 chunks 0.229 ms, 22 chunks 0.151 ms.)
+    const int64_t elem = pl->desc.dtype == AFHIP_F32 ? 4 : 8;
+    const double split_frac = 0.05;
+    int64_t split_budget = std::max<int64_t>(1, (int64_t)(split_frac * (double)T * (double)elem / (16.0 * std::max(1, pl->K))));
+    const bool any_first = std::any_of(pl->cols.begin(), pl->cols.end(), [](const ColOp& c) { return c.outer == OUT_FIRST; });
+    const bool may_split = !pl->desc.exact_order && !any_first;
+
+    pl->chunks.clear();
+    pl->emit.assign((size_t)std::max<int64_t>(G1, 1), 0);
+    pl->slot_ptr.assign((size_t)P + 1, 0);
+    int64_t slot = 0;
+
+    auto steps_of = [&](int64_t p) { return ib[(size_t)ob[(size_t)p + 1]] - ib[(size_t)ob[(size_t)p]]; };
+    auto groups_of = [&](int64_t p) { return ob[(size_t)p + 1] - ob[(size_t)p]; };
+    auto splittable = [&](int64_t p) {
+        return may_split && split_budget > 0 && groups_of(p) >= 2 && steps_of(p) >= 2 * target_len;
+    };
+    auto push_chunk = [&](int64_t g_lo, int64_t g_hi, int64_t slot_base) {
+        ChunkDesc c{};
+        c.k_lo = ib[(size_t)g_lo]; c.k_hi = ib[(size_t)g_hi];
+        c.g_lo = (int32_t)g_lo; c.g_hi = (int32_t)g_hi; c.slot_base = (int32_t)slot_base;
+        pl->chunks.push_back(c);
+    };
+
+    int64_t p = 0;
+    while (p < P) {
+        const int64_t g0 = ob[(size_t)p], g1 = ob[(size_t)p + 1];
+        if (g1 == g0) {  // empty resample bin: no slot, the combine kernel writes NaN
+            pl->slot_ptr[(size_t)p] = (int32_t)slot;
+            ++p;
+            continue;
+        }
+        if (splittable(p)) {
+            const int64_t steps = steps_of(p);
+            const int64_t pieces = std::max<int64_t>(2, std::min<int64_t>({steps / target_len, g1 - g0, split_budget + 1}));
+            pl->slot_ptr[(size_t)p] = (int32_t)slot;
+            int64_t g = g0, made = 0;
+            for (int64_t i = 1; i <= pieces && g < g1; ++i) {
+                int64_t ge;
+                if (i == pieces) {
+                    ge = g1;
+                } else {
+                    const int64_t k_goal = ib[(size_t)g0] + (steps * i) / pieces;
+                    ge = (int64_t)(std::lower_bound(ib.begin() + g + 1, ib.begin() + g1, k_goal) - ib.begin());
+                    ge = std::min(ge, g1);
+                }
+                if (ge <= g) continue;
+                push_chunk(g, ge, slot);
+                pl->emit[(size_t)ge - 1] = 1;
+                ++slot; ++made;
+                g = ge;
+            }
+            split_budget -= std::max<int64_t>(0, made - 1);
+            ++p;
+            continue;
+        }
+        // pack whole periods until the chunk holds ~target_len steps
+        const int64_t cg0 = g0, slot_base = slot;
+        int64_t acc_steps = 0, cg1 = g0;
+        bool first = true;
+        while (p < P) {
+            const int64_t a0 = ob[(size_t)p], a1 = ob[(size_t)p + 1];
+            const int64_t st = steps_of(p);
+            if (!first && (acc_steps + st > target_len || splittable(p))) break;
+            pl->slot_ptr[(size_t)p] = (int32_t)slot;
+            if (a1 > a0) { pl->emit[(size_t)a1 - 1] = 1; ++slot; cg1 = a1; }
+            acc_steps += st;
+            first = false;
+            ++p;
+        }
+        push_chunk(cg0, cg1, slot_base);
+    }
+    pl->slot_ptr[(size_t)P] = (int32_t)slot;
+    pl->n_slots = slot;
+    if (pl->chunks.size() > 65535)
+        return fail(AFHIP_E_UNSUPPORTED, "plan needs %zu chunks (> 65535 grid.y)", pl->chunks.size());
+    return AFHIP_OK;
+}
+
+// ---- 7. region-fused eligibility (after chunking: it reads the slots of the periods) ----
+// Region-fused period ends (FusedArgs::rf_w): the twin variant, if the menu has one, and what the plan itself must satisfy —
+// two-level columns without float32 rounding of the final value (the period value must enter the weighted sum as it leaves
+// the accumulator; an outer mean's division by the period's group count is applied to the region sums, k_rf_reduce), at most one slot per period (shared validity needs the whole period's value), several periods
+// (with one the stores sit at the kernel's end and cost nothing: the headline stays on the route it was measured on).
+static bool rf_plan_ok(const PlanLayout& pl, const PlanKnobs& knobs) {
+    const afhip_plan_desc* desc = &pl.desc;
+    const Variant* v = pl.variant;
+    bool ok = pl.variant_rf != nullptr && !desc->exact_order && desc->P >= 2 && !knobs.no_region_fused;
+    for (const ColOp& c : pl.cols) ok = ok && !(c.rounding & AFHIP_ROUND_FINAL);      // (identity outers too: a daily panel of daily means)
+    for (int64_t p = 0; ok && p < desc->P; ++p) ok = pl.slot_ptr[(size_t)p + 1] - pl.slot_ptr[(size_t)p] <= 1;
+    // ... and per-cell period values that would be a noticeable share of the traffic: P K 8 bytes per cell against T elem.  Below
+    // ~0.2 % there is nothing to win and the emit still costs: configs[2]'s shape (40 annual values of 2 columns from 350,640
+    // hourly steps: 0.05 %) measured 0.25 % behind, the one-period headline (0.06 %) 0.6 %; the shapes that gain sit at 0.5 % and up.
+    const double share = (double)desc->P * pl.K * 8.0 / std::max(1.0, (double)desc->T * (desc->dtype == AFHIP_F32 ? 4.0 : 8.0));
+    if (ok) ok = share >= 0.002;
+    // Which forms gain was measured, not derived (profiles/r03_region_fused.txt: an occupancy rule could not tell them apart): float64
+    // forms and float32 forms without threshold slots gain 3 - 50 % from two periods on; the lean four-row forms and the six-column
+    // lean pair form likewise (6-hourly monthly polynomial: step 0.97 against 1.13 - 1.33 ms).
+    // Round 4 (the scan form of the period end; twins for threshold-only plans and every short-group form; profiles/r04_region_fused_scan.txt):
+    // the float32-with-a-threshold-slot forms are level from 12 periods and ahead from there, a degree-day column alone gains 6 % at
+    // 12 and 52 periods and 22-25 % on a daily panel — one rule for all of them: period values of 0.2 % of the cube and more.  The
+    // two-row forms other than the six-column lean one (sine_dd from (tmin, tmax) pairs: a period end every few rows) pay only where
+    // the per-cell route's own traffic decides: monthly 4.44 against 3.77 ms (behind), weekly 5.80 against 6.20, daily 17.7 against
+    // 21.5 — from period values of 5 % of the cube.
+    const bool two_row_light = v->pair && !v->quad && !(v->ss == 1 && v->kmax == 6);
+    if (ok && two_row_light) ok = share >= 0.05;
+    return ok;
+}
+
+// ---- 8. group table, packed-count format, workspace sizes ----
+static std::vector<int64_t> group_table(const PlanLayout& pl) {
+    const int64_t G1 = pl.desc.G1;
+    std::vector<int64_t> gtab(2 * ((size_t)G1 + 2), 0);
+    for (int64_t g = 0; g < G1; ++g) {
+        const int64_t len = pl.ib[(size_t)g + 1] - pl.ib[(size_t)g];
+        const double inv = len > 0 ? 1.0 / (double)len : 0.0;     // correctly rounded: div_by() then equals s / n exactly
+        int64_t bits;
+        memcpy(&bits, &inv, 8);
+        gtab[2 * (size_t)g] = (pl.ib[(size_t)g + 1] << 1) | (pl.emit[(size_t)g] ? 1 : 0);
+        gtab[2 * (size_t)g + 1] = bits;
+    }
+    return gtab;
+}
+
+// packed counts: integer-bin single-level variant, every column a plain bin count, no period longer than a
+// 16-bit counter holds (0xFFFF is the NaN mark).  nw = 0: the plan is not packed.
+static PackFmt packed_format(const PlanLayout& pl) {
+    const int64_t K = pl.desc.K;
+    PackFmt pk{};
+    bool packed = pl.variant->tki && pl.variant->sl && K <= 16;
+    for (const ColOp& c : pl.cols)
+        packed = packed && c.src == SRC_THR && c.tf == TF_NONE && c.rounding == 0 && c.outer == OUT_FIRST;
+    int64_t maxlen = 0;
+    for (int64_t g = 0; g < pl.desc.G1; ++g) maxlen = std::max(maxlen, pl.ib[(size_t)g + 1] - pl.ib[(size_t)g]);
+    packed = packed && maxlen < 65535;
+    if (!packed) return pk;
+    // the narrowest field that holds the longest period's count and keeps all ones free for NaN; 16-byte records when
+    // K such fields fit two words (daily data, annual bins: 13 x 9 bits), else 16-bit fields in 32 bytes
+    int bw = 1;
+    while (((int64_t)1 << bw) - 1 <= maxlen) ++bw;
+    int f = 64 / bw;
+    pk.nw = 2;
+    if (K > 2 * f) { bw = 16; f = 4; pk.nw = 4; }
+    pk.mask = (uint32_t)(((uint64_t)1 << bw) - 1);
+    for (int j = 0; j < MAX_COLS; ++j) { pk.word[j] = (uint8_t)(j / f); pk.shift[j] = (uint8_t)((j % f) * bw); }
+    return pk;
+}
+
+static void workspace_sizes(PlanLayout* pl) {
+    const int64_t C = pl->desc.n_cells, K = pl->desc.K, P = pl->desc.P;
+    auto a256 = [](int64_t b) { return (b + 255) / 256 * 256; };
+    pl->ws_partial = pl->packed ? a256(std::max<int64_t>(pl->n_slots, 1) * C * pl->pk.nw * 8)
+                                : a256(std::max<int64_t>(pl->n_slots, 1) * K * C * 8);
+    pl->ws_panel = a256(C * (K + 1) * std::max<int64_t>(P, 1) * 8);
+}
+
+// ---- the planner ----
+static int validate_desc(const afhip_plan_desc* d) {
+    if (!d) return fail(AFHIP_E_INVALID, "plan_create: desc is NULL");
+    if (d->T < 0 || d->n_cells <= 0 || d->K <= 0 || d->G1 < 0 || d->P < 0)
+        return fail(AFHIP_E_INVALID, "plan_create: bad sizes (T=%lld n_cells=%lld K=%d G1=%lld P=%lld)",
+                    (long long)d->T, (long long)d->n_cells, d->K, (long long)d->G1, (long long)d->P);
+    if (d->dtype != AFHIP_F32 && d->dtype != AFHIP_F64) return fail(AFHIP_E_INVALID, "plan_create: dtype must be AFHIP_F32 or AFHIP_F64");
+    if (!d->inner_bounds || !d->outer_bounds || !d->columns) return fail(AFHIP_E_INVALID, "plan_create: NULL table");
+    if (d->inner_bounds[0] != 0 || d->inner_bounds[d->G1] != d->T)
+        return fail(AFHIP_E_INVALID, "plan_create: inner_bounds must run from 0 to T");
+    for (int64_t g = 0; g < d->G1; ++g)
+        if (d->inner_bounds[g + 1] < d->inner_bounds[g]) return fail(AFHIP_E_INVALID, "plan_create: inner_bounds not monotone (time index must be monotonic increasing)");
+    if (d->outer_bounds[0] != 0 || d->outer_bounds[d->P] != d->G1)
+        return fail(AFHIP_E_INVALID, "plan_create: outer_bounds must run from 0 to G1");
+    for (int64_t p = 0; p < d->P; ++p)
+        if (d->outer_bounds[p + 1] < d->outer_bounds[p]) return fail(AFHIP_E_INVALID, "plan_create: outer_bounds not monotone");
+    if (d->G1 > INT32_MAX - 2) return fail(AFHIP_E_INVALID, "plan_create: too many inner groups");
+    return AFHIP_OK;
+}
+
+int build_plan(const afhip_plan_desc* desc, const DeviceFacts& dev, PlanLayout* pl) {
+    int rc = validate_desc(desc);
+    if (rc) return rc;
+    const PlanKnobs knobs = read_knobs();
+    static_cast<RunKnobs&>(*pl) = knobs;
+    pl->desc = *desc;
+    pl->ib.assign(desc->inner_bounds, desc->inner_bounds + desc->G1 + 1);
+    pl->ob.assign(desc->outer_bounds, desc->outer_bounds + desc->P + 1);
+    pl->columns.assign(desc->columns, desc->columns + desc->K);
+    pl->desc.inner_bounds = nullptr; pl->desc.outer_bounds = nullptr; pl->desc.columns = nullptr;
+    if ((rc = lower_columns(pl))) return rc;
+
+    const GroupForm form = short_group_form(*pl, knobs);
+    const LoadPath path = load_path(*pl, form.pairs);
+    const int tuning = usable_tuning(pl->desc);
+    bool all_bins = pl->nthr > 0;
+    for (const ThrSlot& t : pl->thr) all_bins = all_bins && t.nan_poisons == 0;
+    static_cast<HistPartition&>(*pl) = find_partition(*pl, all_bins);
+    pl->variant = choose_variant(*pl, form, path, *pl, all_bins, tuning, knobs, dev.cu_count);
+    if (!pl->variant)
+        return fail(AFHIP_E_UNSUPPORTED, "no kernel variant for dtype=%d stat=%d slots=%d columns=%d", desc->dtype, pl->stat, pl->nthr, pl->K);
+    if ((rc = build_chunks(pl, pl->variant->vec, knobs, dev))) return rc;
+    pl->variant_rf = twin_of(pl->variant);
+    pl->rf_plan_ok = rf_plan_ok(*pl, knobs);
+    pl->gtab = group_table(*pl);
+    pl->pk = packed_format(*pl);
+    pl->packed = pl->pk.nw != 0;
+    workspace_sizes(pl);
+    return AFHIP_OK;
+}
+
+}  // namespace afhip

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "afhip_numerics.h"
+#include "afhip_plan_types.h"      // SINE_ROWS, SINE_TAB_BYTES, SINE_P2_N, SINE_P2_BYTES
 
 namespace afhip {
 
@@ -29,8 +30,6 @@ namespace afhip {
 // 11 fp64 + 3 integer instructions and two LDS reads.  Checked on the host against the reference's libm form by
 // scripts/fit/arc_table_emulation.py (1.9e-13 absolute on values of order 1-30) and on the device by scripts/sine_accuracy.py.
 constexpr int SINE_SCALE = 256;
-constexpr int SINE_ROWS = 184;                  // rows per half: k <= 181 for u <= 0.70711; the last rows are guards
-constexpr int SINE_TAB_BYTES = 2 * SINE_ROWS * 32;
 struct alignas(32) SineRow { double C, S, TH, pad; };
 typedef const __attribute__((address_space(3))) SineRow* sine_tab_t;
 
@@ -81,8 +80,6 @@ __device__ __forceinline__ double sine_arc(double d, double x, double alpha, sin
 // integer instructions (and the degree-14 asin of round 2, 44).  It is better conditioned, too: no cancellation g - a theta next
 // to a = 1.  Three layouts of the table were built in round 3: rows in a (centred cubics, 17 + rsq), rows in x = 4 (1 - a)
 // (absolute cubics, 13 + rsq) and — the one in the tree — rows in th = 2 sqrt(1 - a), 512 on [0, 2] (11 + rsq; sine_pair_g).
-constexpr int SINE_P2_N = 512;                                   // = AFHIP_SINE_P2_N of the generated table
-constexpr int SINE_P2_BYTES = (SINE_P2_N + 1) * 32 + 32;         // (+ a pad row: multiple of 64 bytes)
 struct alignas(32) SineP2Row { double c0, c1, c2, c3; };
 typedef const __attribute__((address_space(3))) SineP2Row* sine_p2_t;
 // max(x, DBL_MIN): 1 - a may come out 0 or a rounding error below it (a = |d| / alpha next to 1): t = sqrt(.) is then ~1e-154,

@@ -35,12 +35,31 @@ struct Variant {
 const Variant* variants_table(int* n);   // generated (variants_table.hip)
 const char* variants_menu();             // "full" (the production menu), "arms" (+ the tuning arms) or "dev"
 
+// What a lowered plan asks of the menu (afhip_planner.cpp: choose_variant).  A fallback is the same query with a field changed.
 // tuning: 0 = the default choice below; otherwise an explicit arm
 //         pipe*1000 + vec*100 + depth  (+10000: default cache policy instead of nt)
 //         e.g. 1404 LDS ring, 4 cells per lane, depth 4;  108 direct loads, 1 cell per lane, 8 rows in flight
-inline const Variant* find_variant(int dtype, int pipe, int stat, int nthr, int K, int tuning, int vec = 0,
-                                   bool all_bins = false, bool single_level = false, bool partition = false, bool arith = false,
-                                   bool pairs = false, int lean = 0, int depth_hint = 0, int quads = 0, bool rf = false) {
+struct VariantQuery {
+    int dtype = 0;              // AFHIP_F32 / AFHIP_F64
+    int pipe = 0;               // 0 direct loads, 1 LDS-DMA ring
+    int stat = 0, nthr = 0, K = 0;      // what the columns need: STAT mode, threshold slots, columns
+    int tuning = 0;
+    int vec = 0;                // cells per lane (0: any)
+    bool all_bins = false;      // every threshold slot is a bin count
+    bool single_level = false;  // one inner group per period, every outer `first`
+    bool partition = false;     // the slots are a contiguous equal-width partition (LDS histogram)
+    bool arith = false;         // ... with exactly representable edges
+    bool pairs = false;         // every inner group holds exactly two rows
+    int lean = 0;               // lean group end the plan qualifies for: 0 none, 1 lean, 2 sine-only (Variant::ss)
+    int depth_hint = 0;         // among equals, the burst depth to prefer (0: none)
+    int quads = 0;              // Variant::quad of a four- / three-row / mixed short-group plan
+    bool rf = false;            // the region-fused twins instead of the plain variants
+};
+
+inline const Variant* find_variant(const VariantQuery& q) {
+    const int dtype = q.dtype, pipe = q.pipe, stat = q.stat, nthr = q.nthr, K = q.K, tuning = q.tuning, vec = q.vec, lean = q.lean,
+              depth_hint = q.depth_hint, quads = q.quads;
+    const bool all_bins = q.all_bins, single_level = q.single_level, partition = q.partition, arith = q.arith, pairs = q.pairs, rf = q.rf;
     const Variant* best = nullptr;
     long best_cost = 0;
     int n = 0;

@@ -118,7 +118,7 @@ def menu(kind):
     # region-fused period ends (FEAT bit 11): twins of the production two-level variants on the direct-load path.  Round 3 built the
     # twins that gain from two periods on (up to six columns and four threshold slots, with a statistic; of the short-group forms
     # every lean four-row form and the six-column lean pair form); round 4 adds threshold-only plans (a daily panel of degree days) and
-    # every short-group form incl. the sine-only pair form (afhip_api.hip: rf_plan_ok says when the planner takes them).  Plans of
+    # every short-group form incl. the sine-only pair form (afhip_planner.cpp: rf_plan_ok says when the planner takes them).  Plans of
     # more than six columns or four threshold slots are bound by their arithmetic and measured level with or behind the per-cell route
     # (13 degree-day columns, daily panel: 20.7 against 21.1 ms; monthly: 15.5 against 14.5): no twins.  Single-level (`sl`),
     # integer-bin and histogram variants have none either.
@@ -146,18 +146,18 @@ def menu(kind):
 
 
 def pickable(v):
-    """False for a kernel that no plan can select by afhip_plan_create's default rules (afhip_api.hip), whatever its shape."""
+    """False for a kernel that no plan can select by the planner's default rules (afhip_planner.cpp: the stage named in each comment), whatever its shape."""
     dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod = v
     short = feat & (128 | 1024 | 4096 | 8192)                   # a short-group form; 4096 / 8192: three rows / mixed lengths
     if kmax == 2 and (nthr == 16 or (nthr == 4 and stat in (1, 2))):
         return False      # every column adds at most one threshold slot, so slots <= K, and <= K - 1 beside a mean / sum / min / max /
-        #                   sine_dd source (stat 3 may come from a non-integer pow on a threshold column: s3_t4_k2 stays)
+        #                   sine_dd source (stat 3 may come from a non-integer pow on a threshold column: s3_t4_k2 stays) — lower_columns
     if dtype == 0 and pipe == 0 and vec == 2 and nthr == 16:
-        return False      # want_vec = 2 needs fewer than four slots (and an LDS-histogram plan takes one cell per lane)
+        return False      # load_path: two cells per lane need fewer than four slots (and an LDS-histogram plan takes one cell per lane: choose_variant)
     if dtype == 0 and pipe == 0 and vec == 2 and stat == 1 and nthr == 0 and kmax == 2:
-        return False      # want_vec = 1 for light float32 plans: stat <= 1, no slot, K <= 2
+        return False      # load_path: one cell per lane for light float32 plans: stat <= 1, no slot, K <= 2
     if short and stat == 1 and kmax == 2 and (not (feat & (1024 | 4096 | 8192)) or (dtype == 0 and feat & (4096 | 8192))):
-        return False      # stat-1 short-group plans need K >= min_k: 3 for two-row groups, and for float32 three-row / mixed groups
+        return False      # short_group_form: stat-1 short-group plans need K >= min_k: 3 for two-row groups, and for float32 three-row / mixed groups
     return True
 
 

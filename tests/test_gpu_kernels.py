@@ -593,7 +593,7 @@ def test_many_periods_and_grid_limits(torch_cuda):
 def test_many_period_plans_take_one_time_chunk_per_period(torch_cuda, monkeypatch):
     """Plans with eight or more output periods on a grid that would otherwise stream as a few long chunks are cut into one time
     chunk per period (no extra slot: whole periods stay together, so every per-cell value is bit-identical to the few-chunk
-    layout); fewer periods keep round 2's rule (`afhip_api.hip:build_chunks`, profiles/r03_period_end_stores.txt)."""
+    layout); fewer periods keep round 2's rule (`afhip_planner.cpp:build_chunks`, profiles/r03_period_end_stores.txt)."""
     from aggfly_amd import hip
     torch = torch_cuda
     T, ny, nx = 12 * 64, 512, 512                                   # 512 tiles of 256 threads x 2 cells: round 2's rule makes two chunks

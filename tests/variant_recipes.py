@@ -6,7 +6,7 @@ runs each one against the oracle.  A recipe leaves the planner its default choic
 one exception: the float32 two-cells-per-lane kernels with four rows in flight (depth 4), which the planner takes only on grids
 of at least cu_count * 2 * WG cells, are pinned with tuning=204 (direct loads, two cells per lane, depth 4).
 
-How a recipe selects its variant (afhip_api.hip, afhip_plan_create):
+How a recipe selects its variant (afhip_planner.cpp: build_plan and its stages):
   statistic tier   stat 3: a `nanmean` source;  stat 2: `min` / `max` / `sine_dd`;  stat 1: `mean` / `sum`;  stat 0: thresholds only
   slot tier        distinct `dd` / `bins` argument rows (each column adds at most one, so nthr <= K; nthr <= K - 1 beside a mean /
                    sum / min / max / sine_dd source).  Stat 3 with every column a threshold: a non-integer pow on one of them
@@ -269,7 +269,7 @@ def variant_of(v: Variant, feat) -> Variant:
 
 
 def slots_of(columns):
-    """Distinct threshold slots a column list lowers to (afhip_api.hip: add_thr_slot)."""
+    """Distinct threshold slots a column list lowers to (afhip_planner.cpp: add_thr_slot)."""
     return len({(c["inner"], tuple(c["inner_args"])) for c in columns if c["inner"] in ("dd", "bins")})
 
 
