@@ -265,15 +265,11 @@ static afhip_csr::RfTab* rf_table(afhip_csr* csr, int vec) {
             }
             int need = n_at > 0 ? 128 : 0;
             // the lane a step reads (k_fused_temporal: dpp64): steps 0 - 3 the lane 1, 2, 4, 8 to the left inside its row of 16; step 4
-            // the last lane of the row before (rows 1 and 3); step 5 lane 31 (rows 2 and 3).  (AFHIP_RF_DPP=0 builds: l - 2^st.)
+            // the last lane of the row before (rows 1 and 3); step 5 lane 31 (rows 2 and 3).
             auto src_of = [](int st, int l) -> int {
-#if AFHIP_RF_DPP
                 if (st < 4) return (l & 15) >= (1 << st) ? l - (1 << st) : -1;
                 if (st == 4) return ((l >> 4) & 1) ? (l & ~15) - 1 : -1;
                 return l >= 32 ? 31 : -1;
-#else
-                return l >= (1 << st) ? l - (1 << st) : -1;
-#endif
             };
             for (int st = 0; st < 6; ++st) {
                 bool Fn[64];
@@ -345,7 +341,7 @@ extern "C" int afhip_abi_version(void) { return AFHIP_ABI_VERSION; }
 extern "C" int afhip_build_info(char* buf, int buf_len) {
     int n = 0, arms = 0, rf = 0;
     const Variant* tab = variants_table(&n);
-    for (int i = 0; i < n; ++i) { arms += tab[i].production ? 0 : 1; rf += tab[i].rf ? 1 : 0; }
+    for (int i = 0; i < n; ++i) { arms += tab[i].production ? 0 : 1; rf += tab[i].rf() ? 1 : 0; }
     char tmp[160];
     const int len = snprintf(tmp, sizeof tmp, "menu=%s variants=%d arms=%d region_fused_twins=%d abi=%d", variants_menu(), n, arms, rf, AFHIP_ABI_VERSION);
     if (buf && buf_len > 0) snprintf(buf, buf_len, "%s", tmp);
@@ -832,7 +828,7 @@ extern "C" int afhip_plan_describe(const afhip_plan* plan, char* buf, int buf_le
 // 3.21 -> 2.96) and on the general forms nowhere below 5e8 (float64 daily configs[1] panel 4.49 -> 4.87, float32 2.76 -> 2.90).
 static bool rf_run_major(const afhip_plan* pl, const afhip_csr::RfTab* rf) {
     if (pl->rf_layout >= 0) return pl->rf_layout == 1;
-    return (double)rf->n_runs * (double)pl->desc.P * (double)(pl->K + 1) >= (pl->variant->pair ? 5e7 : 5e8);
+    return (double)rf->n_runs * (double)pl->desc.P * (double)(pl->K + 1) >= (pl->variant->pair() ? 5e7 : 5e8);
 }
 
 static int launch_temporal(afhip_plan* pl, const void* cube, double* partial, hipStream_t st, const afhip_csr::RfTab* rf = nullptr) {
@@ -848,7 +844,7 @@ static int launch_temporal(afhip_plan* pl, const void* cube, double* partial, hi
     fa.xcd_remap = 1;        // measured +0.2..1 % on configs[1] (profiles/r01_xcd_remap.txt): harmless, kept on
     fa.sine_tab = nullptr;
     if (pl->has_sine) {
-        int rc = sine_table_dev(pl->device, pl->variant->pair != 0 && pl->variant->quad == 0, &fa.sine_tab);
+        int rc = sine_table_dev(pl->device, pl->variant->sine_p2(), &fa.sine_tab);
         if (rc) return rc;
     }
     for (int i = 0; i < pl->nthr; ++i) fa.thr[i] = pl->thr[(size_t)i];
@@ -873,14 +869,14 @@ static int launch_temporal(afhip_plan* pl, const void* cube, double* partial, hi
         fn = pl->variant_rf->fn;
         lds = (lds + 15) / 16 * 16;
         fa.rf_lds_off = (int32_t)lds;
-        lds += (size_t)pl->wg * (size_t)(pl->variant->vec * 16 + 16);      // RF_LANE_BYTES of afhip_kernels.h
+        lds += (size_t)pl->wg * (size_t)rf_lane_bytes(pl->variant->vec);
         fa.rf_w = rf->w2.p; fa.rf_lane = rf->lane.p; fa.rf_tile = rf->tile.p; fa.rf_out = partial;
         fa.rf_slot_stride = rf_run_major(pl, rf) ? (int64_t)(pl->K + 1) : rf->n_runs * (pl->K + 1);
         fa.rf_run_stride = rf_run_major(pl, rf) ? pl->n_slots * (pl->K + 1) : (int64_t)(pl->K + 1);
         fa.rf_x = rf->n_xcells ? rf->xidx.p : nullptr; fa.rf_nx = rf->n_xcells;
         fa.rf_ex = partial + pl->n_slots * rf->n_runs * (pl->K + 1);           // behind the run sums
     }
-    if (pl->variant->hb) {
+    if (pl->variant->hb()) {
         fa.hb_n = pl->hb_n; fa.hb_c1 = pl->hb_c1; fa.hb_c0 = pl->hb_c0;
         fa.hb_c1f = (float)pl->hb_c1; fa.hb_c0f = (float)pl->hb_c0;
         fa.hb_shift = pl->wg == 64 ? 6 : (pl->wg == 128 ? 7 : 8);

@@ -41,7 +41,7 @@ struct FusedArgs {
     int32_t K, nthr;
     int32_t xcd_remap, n_tiles;    // 1: give each XCD a contiguous range of cell tiles (speed only)
     const double* sine_tab;        // device [2][SINE_ROWS][4]: rows of the acos table (sine_theta), or null when no column is sine_dd
-    // LDS-histogram bins (FEAT bit 5): the threshold slots form a contiguous partition of equal
+    // LDS-histogram bins (FEAT_HIST): the threshold slots form a contiguous partition of equal
     // width with edges hb_edge[0..hb_n]; hb_bin_of_slot[slot] = position of that slot's bin.
     // guess bin (shifted by one guard bin) = floor(v * hb_c1 + hb_c0); hb_dn / hb_up are the edges
     // rounded down / up to float, so a float v compares exactly:  v > t <=> v > dn,  v < t <=> v < up.
@@ -51,7 +51,7 @@ struct FusedArgs {
     int32_t hb_bin_of_slot[MAX_THR];
     double hb_edge[MAX_THR + 1];
     float hb_dn[MAX_THR + 1], hb_up[MAX_THR + 1];
-    // arithmetic edges (FEAT bit 6): every edge is EXACTLY hb_lo0 + g * hb_w in the input precision (host-checked with
+    // arithmetic edges (FEAT_ARITH_EDGES): every edge is EXACTLY hb_lo0 + g * hb_w in the input precision (host-checked with
     // the same fma), so the two edges around a guess are two fmas instead of an LDS table read; hb_gl / hb_gh sit
     // inside the lower / upper guard bin: values (and NaN) are clamped onto them first.
     // packed != 0 (single-level plans whose columns are all bin counts): the period's K counts leave as small
@@ -129,78 +129,34 @@ namespace afhip {
 //
 //   STAT 0 none | 1 sum | 2 sum+min+max | 3 sum+count+min+max with NaN skipping (nanmean)
 // ---------------------------------------------------------------------------------------
-//   FEAT bit 0: single-sine degree days compiled in (needs STAT >= 2)
-//        bit 1: the general transforms compiled in: pow() with a non-integer exponent, and `inter` (Dataset.interact,
-//               dataset.py:483-518,547-563: the inner value times the matching element of a second cube)
-// Both are bulky once inlined per column, so only the variants that need them carry them.
+// FEAT: the feature bits FEAT_* of afhip_plan_types.h, which says what each one compiles in.
 //
 // The workgroup size is a launch parameter (64 or 256 threads): waves never talk to each
 // other, so small grids are launched as single-wave workgroups for a finer tail.
-#ifndef AFHIP_RF_DPP
-#define AFHIP_RF_DPP 1             // the period end's scan moves its values by DPP (1) or by ds_bpermute (0: the Hillis-Steele steps of round 4's first forms)
-#endif
-#ifndef AFHIP_RF_WAVES
-#define AFHIP_RF_WAVES 1           // waves per SIMD the region-fused twins are compiled for (1 = no constraint)
-#endif
 template <typename TIn, int PIPE, int VEC, int STAT, int NTHR, int KMAX, int DEPTH, int FEAT>
-__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((FEAT & 2048) ? AFHIP_RF_WAVES : 1))) void k_fused_temporal(const FusedArgs a) {
-    constexpr int AUX = (FEAT & 4) ? 2 : 0;   // FEAT bit 2: non-temporal (nt) cache policy on the streaming loads
-    // FEAT bit 3: every threshold slot is a bin count -> 32-bit integer counters (one
-    //             v_addc per slot and element instead of fma + select + f64 add)
-    // FEAT bit 4: single-level plan (every inner group is an output period, every column
-    //             passes its inner value through): no outer accumulators at all
-    // FEAT bit 5: the bins are a contiguous equal-width partition -> per-lane histogram in LDS.
-    //             One fma + floor in the INPUT precision guesses the bin (off by one at most, host-
-    //             checked); the two edges around the guess come from an LDS table and four exact
-    //             compares move the guess up / down or reject a value that sits on an edge (strict
-    //             inequalities, like the reference); one ds_add_u32 bumps the lane's private
-    //             counter.  A guard bin on either side absorbs out-of-range values, so there is no
-    //             range test and no data-dependent branch.  ~13 VALU + 2 LDS ops per element
-    //             instead of 3 VALU per bin.
-    constexpr bool TKI = (FEAT & 8) != 0;
-    constexpr bool SL = (FEAT & 16) != 0;
-    constexpr bool HB = (FEAT & 32) != 0;
-    // FEAT bit 6: histogram with arithmetic edges — exactly representable equal-width edges (5 degC bins from -20 ...):
-    //             the edge pair of the guessed bin is computed (2 fma) instead of read from the LDS table, which takes an
-    //             LDS round trip out of every element's dependent chain; a value on an edge is recognised by equality.
-    constexpr bool HA = (FEAT & 64) != 0;
-    // FEAT bit 7: every inner group holds exactly TWO rows ((tmin, tmax) pairs per day, configs[4]): a block of DEPTH rows is
-    //             DEPTH / 2 whole groups — all of them in flight at once instead of one group's two rows — and a group's
-    //             statistics are min / max / sum of the pair, taken in the input precision, without the per-row accumulators.
-    constexpr bool PAIR = (FEAT & 128) != 0;
-    // FEAT bit 8: pair mode with the LEAN group end: every column is   mean | sum | min | max | sine_dd  ->  (nothing | integer
-    //             power)  ->  sum | mean,   without float32 rounding (configs[4]'s sine_dd -> sum; the daily mean of (tmin, tmax)
-    //             and its polynomial).  The group end is then the column's value, its power chain and one add — no per-group walk
-    //             through the column records' source / transform / reducer switches (that walk is ~90 scalar instructions per wave
-    //             and group, as many as the vector ones that do the arithmetic: profiles/r03_kbench_c5_table_arc.txt); the records
-    //             are loop-invariant kernel arguments and stay in scalar registers; a NaN pair is remembered in a lane mask (scalar
-    //             OR) and applied when the period's sum leaves the kernel, since NaN is sticky under + anyway.
-    constexpr bool LEAN = (FEAT & 256) != 0;
-    // FEAT bit 9: ... and every column is a plain sine_dd (no power): nothing but the closed forms in the group end
-    constexpr bool LEAN_SINE = (FEAT & 512) != 0;
-    static_assert(!LEAN_SINE || (LEAN && (FEAT & 1) && KMAX <= 2), "the sine-only lean form: at most two columns");
-    // FEAT bit 10: the same mode for inner groups of exactly FOUR rows (6-hourly data): GL rows per group, DEPTH / GL groups per block;
-    //              lean form only.  The sum runs in time order ((u0 + u1) + u2) + u3, the mean is s / 4 = s * 0.25 exactly, min / max
-    //              are taken in the input precision; sine_dd columns use the general closed forms (tavg is not the mid-range of four
-    //              steps), so these variants read the acos table.
-    // FEAT bit 12: ... and of exactly THREE rows (8-hourly data): the sum runs (u0 + u1) + u2, the mean is the correctly rounded s / 3
-    //              (div_by with the correctly rounded reciprocal: bit-identical to the reference's division), otherwise like four rows.
-    // FEAT bit 13: ... and of MIXED lengths one to four rows (a 6-hourly series with missing steps, a 12-hourly one joined to a
-    //              6-hourly one): every group owns four row registers and fills as many as it is long; its length is a scalar read from
-    //              the group table, the loads and the statistics' tail rows sit under scalar branches on it, the mean is div_by's
-    //              correctly rounded s / n (n = 2, 4: exact anyway).  Otherwise the four-row form.
-    constexpr bool RAG = (FEAT & 8192) != 0;
-    constexpr int GL = ((FEAT & 1024) || RAG) ? 4 : ((FEAT & 4096) ? 3 : 2);
-    static_assert(!(FEAT & (1024 | 4096 | 8192)) || (PAIR && LEAN && !LEAN_SINE), "three- / four-row / mixed groups: a lean short-group form");
-    static_assert(((FEAT & 1024) != 0) + ((FEAT & 4096) != 0) + ((FEAT & 8192) != 0) <= 1, "one group length rule per variant");
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_fused_temporal(const FusedArgs a) {
+    // ---- everything the body asks of FEAT ----
+    constexpr bool SINE = feat_has(FEAT, FEAT_SINE), GENERAL_TF = feat_has(FEAT, FEAT_GENERAL_TF);
+    constexpr int AUX = feat_has(FEAT, FEAT_NT) ? 2 : 0;
+    constexpr bool TKI = feat_has(FEAT, FEAT_INT_BINS), SL = feat_has(FEAT, FEAT_SINGLE_LEVEL);
+    constexpr bool HB = feat_has(FEAT, FEAT_HIST), HA = feat_has(FEAT, FEAT_ARITH_EDGES);
+    constexpr bool PAIR = feat_has(FEAT, FEAT_SHORT_GROUP);
+    // (the lean group end skips a per-group walk of ~90 scalar instructions per wave and group, as many as the vector ones that do the
+    // arithmetic: profiles/r03_kbench_c5_table_arc.txt)
+    constexpr bool LEAN = feat_lean_level(FEAT) >= 1, LEAN_SINE = feat_lean_level(FEAT) == 2;
+    constexpr bool RAG = feat_has(FEAT, FEAT_MIXED);
+    constexpr int GL = feat_group_rows(FEAT);
+    constexpr bool RF = feat_has(FEAT, FEAT_REGION_FUSED);
+    constexpr int SINE_BYTES = feat_sine_bytes(FEAT);              // the sine table this variant copies into LDS
+    static_assert(!LEAN_SINE || (feat_has(FEAT, FEAT_LEAN) && SINE && KMAX <= 2), "the sine-only lean form: at most two columns");
+    static_assert(feat_group_form(FEAT) == 0 || (PAIR && LEAN && !LEAN_SINE), "three- / four-row / mixed groups: a lean short-group form");
+    static_assert(feat_has(FEAT, FEAT_FOUR_ROW) + feat_has(FEAT, FEAT_THREE_ROW) + feat_has(FEAT, FEAT_MIXED) <= 1, "one group length rule per variant");
     static_assert(!PAIR || (PIPE == 0 && (STAT == 2 || (STAT == 1 && LEAN)) && NTHR == 0 && DEPTH % GL == 0),
                   "short-group mode: direct loads, sum (+ min + max), no threshold slots");
     static_assert(!LEAN || PAIR, "the lean group end is a short-group form");
-    // FEAT bit 11: region-fused period ends compiled in (FusedArgs::rf_w).  A twin of the plain variant: the staging code at the
-    // period end raises the register count by ~7 (one wave per SIMD less on the float32 two-cell forms), so only plans that take
-    // the route run it; with rf_w == null it behaves like its twin.
-    constexpr bool RF = (FEAT & 2048) != 0;
     static_assert(!RF || !(SL || HB), "region-fused period ends: two-level plans only");
+    static_assert(!(HB && SINE), "histogram variants carry no sine_dd code");
+    static_assert(!RF || VEC <= 2, "region-fused period ends: one or two cells per lane");
     const int64_t C = a.C;
     const int K = a.K;
     const int lane = threadIdx.x & 63;
@@ -258,19 +214,17 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((FEAT & 2048
     int* hcnt = (int*)(dynlds + HB_TABLE_BYTES);
     const int bd = blockDim.x, tid = threadIdx.x;
     // sine_dd plans: every workgroup copies the acos table (sine_theta) into LDS, behind the LDS-DMA ring if there is one
-    static_assert(!(HB && (FEAT & 1)), "histogram variants carry no sine_dd code");
-    // (pair-mode variants: the G table of sine_pair_g; the others: the acos table of sine_theta — the host hands over the one
-    // the variant reads)
+    // (feat_sine_p2 variants — two-row groups: the P2 table of sine_pair_g; the others: the acos table of sine_theta — the host
+    // hands over the one the variant reads)
     sine_tab_t sine_tab = nullptr;
     sine_p2_t sine_p2 = nullptr;
-    if constexpr ((FEAT & 1) != 0) {
-        unsigned char* base = dynlds + (PIPE == 1 ? (size_t)(bd >> 6) * DEPTH * 1024 : (size_t)0);
+    if constexpr (SINE) {
+        unsigned char* base = dynlds + lds_sine_offset(PIPE, bd >> 6, DEPTH);
         if (a.sine_tab != nullptr) {            // uniform: the host sets it iff a column is sine_dd (and then sizes the LDS for it)
             typedef double d2 __attribute__((ext_vector_type(2)));
-            constexpr int bytes = ((FEAT & 128) != 0 && (FEAT & (1024 | 4096)) == 0) ? SINE_P2_BYTES : SINE_TAB_BYTES;
             // (the sine-only lean form works in DOUBLED units — clamp, arcs and the column's sum — and halves once per period end:
             // its copy of the table is 2 H, every step an exact scaling of the undoubled one)
-            for (int e = tid; e < bytes / 16; e += bd) {
+            for (int e = tid; e < SINE_BYTES / 16; e += bd) {
                 d2 t = ((const d2*)a.sine_tab)[e];
                 if constexpr (LEAN_SINE) t *= 2.0;
                 ((d2*)base)[e] = t;
@@ -314,7 +268,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((FEAT & 2048
     }
     auto reset_outer = [&]() {
         if (SL) return;
-        if constexpr ((FEAT & 256) != 0) {          // lean forms: every outer reducer is sum | mean — no per-column identity, no j < K masks
+        if constexpr (LEAN) {          // lean forms: every outer reducer is sum | mean — no per-column identity, no j < K masks
 #pragma unroll
             for (int j = 0; j < KMAX; ++j)
 #pragma unroll
@@ -345,21 +299,14 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((FEAT & 2048
     //   rf_first[e] first run of (tile, e) in rf_out
     //   rf_need[e]  (uniform) bit s: some lane of the wave adds in step s — steps no run of this tile is long enough for are skipped;
     //               bit 6: some run ends at a lane's first cell (two cells per lane); bit 7: the tile has runs of entry e at all
-    static_assert(!RF || VEC <= 2, "region-fused period ends: one or two cells per lane");
-#ifndef AFHIP_RF_CB
-#define AFHIP_RF_CB 2
-#endif
-    // columns per block of the period end's scan (registers against overlap).  The general two-cell forms of six columns take ONE (AFHIP_RF_SLIM):
+    // columns per block of the period end's scan (registers against overlap): two.  The general two-cell forms of six columns take ONE (RF_SLIM):
     // they are held by their bytes in flight, and with the weights re-read per block and the store addresses formed at the stores the twin fits six waves per SIMD
-#ifndef AFHIP_RF_SLIM
-#define AFHIP_RF_SLIM 1
-#endif
-    constexpr bool RF_SLIM = AFHIP_RF_SLIM && VEC == 2 && KMAX == 6 && !(FEAT & 128) && sizeof(TIn) == 4;
-    constexpr int RF_CB = RF_SLIM ? 1 : AFHIP_RF_CB;
+    constexpr bool RF_SLIM = VEC == 2 && KMAX == 6 && !PAIR && sizeof(TIn) == 4;
+    constexpr int RF_CB = RF_SLIM ? 1 : 2;
     // The lane's weights and words are PARKED in LDS (a wave-private block behind the variant's other LDS: RF_LANE_BYTES per lane) and
     // read back at every period end: held in registers they cost the twins ten VGPRs for the whole kernel — 103 against the plain
     // variant's 74 on the float32 configs[1] plan, four waves per SIMD instead of six, for a kernel that is bound by bytes in flight.
-    constexpr int RF_LANE_BYTES = VEC * 16 + 16;      // (a multiple of 16: the block is read and written in 16-byte pieces)
+    constexpr int RF_LANE_BYTES = rf_lane_bytes(VEC);
     typedef __attribute__((address_space(3))) unsigned char* rf_lds_t;
     rf_lds_t rf_park = nullptr;
     int rf_first[2] = {0, 0}, rf_need[2] = {0, 0};
@@ -435,11 +382,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((FEAT & 2048
         b += (vc > hi) ? 1 : 0;                                     // (a carry-in add)
         if (vc != hi) {
             int* p = (int*)((char*)hcnt + (b << hb_sh) + hb_lane[i]);
-#ifdef HA_PLAIN_RMW
-            *p = *p + 1;                                              // the counter is private to this lane
-#else
-            __hip_atomic_fetch_add(p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-#endif
+            __hip_atomic_fetch_add(p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);     // the counter is private to this lane: one ds_add_u32
         }
     };
     auto consume = [&](const RawVec<TIn, VEC>& rv, bool hb_inline = true) {
@@ -530,15 +473,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((FEAT & 2048
         // compile time — the validity weight first, then val[0 .. KMAX) — so nothing inside the scan branches on K: columns beyond K
         // carry whatever their registers hold through the shuffles and only their stores are skipped (the weight is stored at index K
         // of the record).  Per block: products, the lane's own stretch, the scan steps some run of the tile needs (a shuffle = two
-        // ds_bpermute on an address formed once per step; the adds run under the lanes' take / start / end bits as branches on lane
+        // DPP moves, dpp64 below; the adds run under the lanes' take / start / end bits as branches on lane
         // conditions, i.e. EXEC masks, not selects), the sums of the runs that end in this lane.
         constexpr int CB = RF_CB, NCOL = KMAX + 1;
-        auto shfl64 = [&](double x, int addr) -> double {
-            const int lo = __builtin_amdgcn_ds_bpermute(addr, __double2loint(x));
-            const int hi = __builtin_amdgcn_ds_bpermute(addr, __double2hiint(x));
-            return __hiloint2double(hi, lo);
-        };
-#if AFHIP_RF_DPP
         // the scan's data movement as DPP moves (no LDS round trip): steps 0 - 3 shift by 1, 2, 4, 8 lanes inside each row of 16
         // (row_shr), step 4 hands every row's last lane to the next row (row_bcast:15 -> rows 1 and 3), step 5 lane 31 to rows 2 and 3
         // (row_bcast:31); `carried` is the whole wave shifted by one lane (wave_shr:1).  Lanes without a source keep 0 — they never add.
@@ -562,7 +499,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((FEAT & 2048
             }
             return __hiloint2double(hi, lo);
         };
-#endif
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             int need = rf_need[e];
@@ -614,14 +550,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((FEAT & 2048
                 for (int st = 0; st < 6; ++st) {
                     if (!((need >> st) & 1)) continue;               // (uniform)
                     double pv[CB];
-#if AFHIP_RF_DPP
 #pragma unroll
                     for (int qq = 0; qq < CB; ++qq) pv[qq] = q0 + qq < NCOL ? dpp64(v[qq], st) : 0.0;
-#else
-                    const int addr = ((lane - (1 << st)) & 63) << 2;
-#pragma unroll
-                    for (int qq = 0; qq < CB; ++qq) pv[qq] = q0 + qq < NCOL ? shfl64(v[qq], addr) : 0.0;
-#endif
                     if ((bits >> st) & 1u) {
                         KEEP_BRANCH();
 #pragma unroll
@@ -632,14 +562,12 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((FEAT & 2048
                 // record index of list position q: the weight at K, val[q - 1] at q - 1 (stored when q - 1 < K)
                 if constexpr (VEC == 2) {
                     if (need & 64) {                                 // (uniform) a run ends at some lane's FIRST cell: what the previous lanes
-                        const int addr = ((lane - 1) & 63) << 2;     // carried (unless the cell starts a stretch) + the cell
-                        double carried[CB];
+                        double carried[CB];                          // carried (unless the cell starts a stretch) + the cell
+                        // (names `lane` and nothing else: the closure's layout, and with it the register allocation of the float32 two-cell
+                        // twins, hangs on this lambda capturing it here — profiles/feature_bits_refactor.txt)
+                        (void)lane;
 #pragma unroll
-#if AFHIP_RF_DPP
                         for (int qq = 0; qq < CB; ++qq) carried[qq] = q0 + qq < NCOL ? dpp64(v[qq], 6) : 0.0;
-#else
-                        for (int qq = 0; qq < CB; ++qq) carried[qq] = q0 + qq < NCOL ? shfl64(v[qq], addr) : 0.0;
-#endif
                         if (end0) {
                             KEEP_BRANCH();
                             if (!fresh) {
@@ -816,10 +744,10 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((FEAT & 2048
                         asm volatile("" : "+s"(cc));
 #endif
                         const int src = (int)(cc & 15u);
-                        if ((FEAT & 1) && src == SRC_SINE) {
+                        if (SINE && src == SRC_SINE) {
                             KEEP_BRANCH();
                             // (the full record of a sine_dd column is read where it is used: zoff is 0, but only known at run time)
-                            if constexpr ((FEAT & 1) != 0) { const ColOp co = a.cols[KMAX > 2 ? j + zoff : j]; sine_column(co, x); }
+                            if constexpr (SINE) { const ColOp co = a.cols[KMAX > 2 ? j + zoff : j]; sine_column(co, x); }
                         } else if constexpr (STAT == 1) {
                             // mean | sum: s / n with n = 2 or 4 is s * (1 / n) exactly; one multiply by a scalar either way (n = 3: the
                             // correctly rounded quotient, already in mean[])
@@ -933,9 +861,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((FEAT & 2048
                 // float round trip, 1/x for negative exponents) and runs them on every group end.
                 double x[VEC];
                 const int src = co.src;
-                if ((FEAT & 1) && STAT >= 2 && src == SRC_SINE) {
+                if (SINE && STAT >= 2 && src == SRC_SINE) {
                     KEEP_BRANCH();
-                    if constexpr ((FEAT & 1) && STAT >= 2) sine_column(co, x);
+                    if constexpr (SINE && STAT >= 2) sine_column(co, x);
                 } else
 #pragma unroll
                 for (int i = 0; i < VEC; ++i) {
@@ -981,10 +909,10 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((FEAT & 2048
 #pragma unroll
                         for (int i = 0; i < VEC; ++i) x[i] = ((x[i] > co.tf_arg) ? 1.0 : 0.0) * (x[i] - co.tf_arg);
                     }
-                } else if ((FEAT & 2) && tf == TF_POW) {
+                } else if (GENERAL_TF && tf == TF_POW) {
 #pragma unroll
                     for (int i = 0; i < VEC; ++i) x[i] = pow(x[i], co.tf_arg);
-                } else if ((FEAT & 2) && tf == TF_INTER) {
+                } else if (GENERAL_TF && tf == TF_INTER) {
                     // np.multiply(block, other) (dataset.py:563): this group's value times other[g][cell]; lanes beyond the
                     // grid re-read valid cells (c_ld) and are never stored
                     KEEP_BRANCH();
@@ -1375,7 +1303,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((FEAT & 2048
         unsigned char* ring = dynlds;                                         // waves * DEPTH KiB
         const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         const uint32_t ring_lds = (uint32_t)(uintptr_t)(lds_ptr_t)ring;
-        const uint32_t wave_lds = __builtin_amdgcn_readfirstlane(ring_lds + (uint32_t)wave * (DEPTH * 1024u));
+        const uint32_t wave_lds = __builtin_amdgcn_readfirstlane(ring_lds + (uint32_t)wave * (uint32_t)lds_ring_bytes_per_wave(DEPTH));
         const uint32_t rd_lane = wave_lds + (uint32_t)lane * 16u;
         const int last = rows - 1;
         const int64_t row_bytes = C * (int64_t)sizeof(TIn);

@@ -1,6 +1,7 @@
 // afhip_plan_types.h — what the host planner (afhip_planner.cpp) and the device code (afhip_kernels.h) share: launch constants,
-// the column / slot / chunk records that FusedArgs copies by value, and the LDS sizes of the sine tables.  Plain C++: no HIP.
+// the column / slot / chunk records that FusedArgs copies by value, the feature bits of k_fused_temporal and its LDS layout.  Plain C++: no HIP.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace afhip {
@@ -62,5 +63,87 @@ constexpr int SINE_ROWS = 184;                  // rows per half: k <= 181 for u
 constexpr int SINE_TAB_BYTES = 2 * SINE_ROWS * 32;
 constexpr int SINE_P2_N = 512;                                   // = AFHIP_SINE_P2_N of the generated table
 constexpr int SINE_P2_BYTES = (SINE_P2_N + 1) * 32 + 32;         // (+ a pad row: multiple of 64 bytes)
+
+// ---------------------------------------------------------------------------------------
+// The feature bits of k_fused_temporal's template parameter FEAT: what each one compiles in.  The one definition — the kernel,
+// the variant table, the planner and the launcher all read it; gen_variants.py's table is held equal by static_asserts in the
+// generated variants_table.hip.
+// ---------------------------------------------------------------------------------------
+enum : int {
+    // single-sine degree days (needs STAT >= 2).  Bulky once inlined per column, like the next bit: only the variants that need
+    // them carry them
+    FEAT_SINE = 1,
+    // the general transforms: pow() with a non-integer exponent, and `inter` (Dataset.interact, dataset.py:483-518,547-563: the
+    // inner value times the matching element of a second cube)
+    FEAT_GENERAL_TF = 2,
+    // non-temporal (nt) cache policy on the streaming loads
+    FEAT_NT = 4,
+    // every threshold slot is a bin count -> 32-bit integer counters (one v_addc per slot and element instead of fma + select +
+    // f64 add)
+    FEAT_INT_BINS = 8,
+    // single-level plan (every inner group is an output period, every column passes its inner value through): no outer
+    // accumulators at all
+    FEAT_SINGLE_LEVEL = 16,
+    // the bins are a contiguous equal-width partition -> per-lane histogram in LDS.  One fma + floor in the INPUT precision
+    // guesses the bin (off by one at most, host-checked); the two edges around the guess come from an LDS table and four exact
+    // compares move the guess up / down or reject a value that sits on an edge (strict inequalities, like the reference); one
+    // ds_add_u32 bumps the lane's private counter.  A guard bin on either side absorbs out-of-range values, so there is no range
+    // test and no data-dependent branch.  ~13 VALU + 2 LDS ops per element instead of 3 VALU per bin.
+    FEAT_HIST = 32,
+    // histogram with arithmetic edges — exactly representable equal-width edges (5 degC bins from -20 ...): the edge pair of the
+    // guessed bin is computed (2 fma) instead of read from the LDS table, which takes an LDS round trip out of every element's
+    // dependent chain; a value on an edge is recognised by equality
+    FEAT_ARITH_EDGES = 64,
+    // short-group mode: every inner group holds exactly TWO rows ((tmin, tmax) pairs per day, configs[4]) unless one of the three
+    // length bits below says otherwise.  A block of DEPTH rows is DEPTH / 2 whole groups — all of them in flight at once instead
+    // of one group's two rows — and a group's statistics are min / max / sum of the pair, taken in the input precision, without
+    // the per-row accumulators
+    FEAT_SHORT_GROUP = 128,
+    // short-group mode with the LEAN group end: every column is   mean | sum | min | max | sine_dd  ->  (nothing | integer power)
+    // ->  sum | mean,   without float32 rounding (configs[4]'s sine_dd -> sum; the daily mean of (tmin, tmax) and its polynomial).
+    // The group end is then the column's value, its power chain and one add — no per-group walk through the column records'
+    // source / transform / reducer switches; the records are loop-invariant kernel arguments and stay in scalar registers; a NaN
+    // pair is remembered in a lane mask (scalar OR) and applied when the period's sum leaves the kernel, since NaN is sticky under
+    // + anyway
+    FEAT_LEAN = 256,
+    // ... and every column is a plain sine_dd (no power), at most two of them: nothing but the closed forms in the group end
+    FEAT_LEAN_SINE = 512,
+    // the lean short-group form for inner groups of exactly FOUR rows (6-hourly data).  The sum runs in time order
+    // ((u0 + u1) + u2) + u3, the mean is s / 4 = s * 0.25 exactly, min / max are taken in the input precision; sine_dd columns use
+    // the general closed forms (tavg is not the mid-range of four steps), so these variants read the acos table
+    FEAT_FOUR_ROW = 1024,
+    // region-fused period ends (FusedArgs::rf_w).  A twin of the plain variant: the staging code at the period end raises the
+    // register count by ~7 (one wave per SIMD less on the float32 two-cell forms), so only plans that take the route run it; with
+    // rf_w == null it behaves like its twin
+    FEAT_REGION_FUSED = 2048,
+    // ... of exactly THREE rows (8-hourly data): the sum runs (u0 + u1) + u2, the mean is the correctly rounded s / 3 (div_by with
+    // the correctly rounded reciprocal: bit-identical to the reference's division), otherwise like four rows
+    FEAT_THREE_ROW = 4096,
+    // ... of MIXED lengths one to four rows (a 6-hourly series with missing steps, a 12-hourly one joined to a 6-hourly one):
+    // every group owns four row registers and fills as many as it is long; its length is a scalar read from the group table, the
+    // loads and the statistics' tail rows sit under scalar branches on it, the mean is div_by's correctly rounded s / n (n = 2, 4:
+    // exact anyway).  Otherwise the four-row form
+    FEAT_MIXED = 8192,
+};
+
+// what follows from the bits
+constexpr bool feat_has(int feat, int bits) { return (feat & bits) != 0; }
+// rows a short-group variant gives each group (k_fused_temporal: GL)
+constexpr int feat_group_rows(int feat) { return feat_has(feat, FEAT_FOUR_ROW | FEAT_MIXED) ? 4 : (feat_has(feat, FEAT_THREE_ROW) ? 3 : 2); }
+// lean group end: 0 none, 1 lean, 2 its sine-only form
+constexpr int feat_lean_level(int feat) { return feat_has(feat, FEAT_LEAN_SINE) ? 2 : (feat_has(feat, FEAT_LEAN) ? 1 : 0); }
+// group-length rule of a short-group variant: 0 two rows (or not a short-group variant), 1 four, 2 three, 3 mixed one to four
+constexpr int feat_group_form(int feat) { return feat_has(feat, FEAT_FOUR_ROW) ? 1 : (feat_has(feat, FEAT_THREE_ROW) ? 2 : (feat_has(feat, FEAT_MIXED) ? 3 : 0)); }
+// sine_dd reads the P2 table of sine_pair_g (tavg is the mid-range: two-row groups only), otherwise the acos table of sine_theta
+constexpr bool feat_sine_p2(int feat) { return feat_has(feat, FEAT_SHORT_GROUP) && feat_group_form(feat) == 0; }
+constexpr int feat_sine_bytes(int feat) { return feat_sine_p2(feat) ? SINE_P2_BYTES : SINE_TAB_BYTES; }
+
+// The kernel's dynamic LDS, front to back: the LDS-DMA ring (PIPE 1: one block of DEPTH rows of 1 KiB per wave), then the sine
+// table of a plan with a sine_dd column; histogram variants (direct loads, no sine_dd) hold their edge tables and counters there
+// instead; the parking blocks of a region-fused launch come last (FusedArgs::rf_lds_off).
+constexpr size_t lds_ring_bytes_per_wave(int depth) { return (size_t)depth * 1024; }
+constexpr size_t lds_sine_offset(int pipe, int waves, int depth) { return pipe == 1 ? (size_t)waves * lds_ring_bytes_per_wave(depth) : (size_t)0; }
+constexpr size_t lds_hist_bytes(int bins, int vec, int wg) { return (size_t)HB_TABLE_BYTES + (size_t)bins * vec * wg * 4; }    // counters [bins * vec][wg]; bins = hb_n + 2 with the guards
+constexpr int rf_lane_bytes(int vec) { return vec * 16 + 16; }     // a lane's parking block: its cells' weight pairs + its two lane words (a multiple of 16: read and written in 16-byte pieces)
 
 }  // namespace afhip

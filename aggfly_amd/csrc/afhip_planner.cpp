@@ -122,7 +122,7 @@ static int lower_columns(PlanLayout* pl) {
             case AFHIP_TF_INTER: co.tf = TF_INTER; break;
             default: return fail(AFHIP_E_INVALID, "column %d: unknown transform %d", j, c.transform);
         }
-        // pow() and `inter` are compiled into the all-purpose (STAT 3) variants only (FEAT bit 1)
+        // pow() and `inter` are compiled into the all-purpose (STAT 3) variants only (FEAT_GENERAL_TF)
         if (co.tf == TF_POW || co.tf == TF_INTER) stat = 3;
         switch (c.outer) {
             case AFHIP_IDENTITY: co.outer = OUT_FIRST; break;
@@ -158,9 +158,9 @@ static bool rows_fit_32bit(const afhip_plan_desc& d) {
 struct GroupForm {
     int glen = 0;           // length class of the inner groups: 2 / 3 / 4 rows throughout, 5 = mixed one to four rows, 0 = none of these
     bool pairs = false;     // short-group mode (two-, three- or four-row groups)
-    bool lean = false, lean_sine = false;      // the lean group end (FEAT bit 8), its sine-only form (FEAT bit 9)
+    bool lean = false, lean_sine = false;      // the lean group end (FEAT_LEAN), its sine-only form (FEAT_LEAN_SINE)
     bool quad_len() const { return glen >= 3; }      // three / four / mixed rows: the lean form only, general sine closed forms
-    int glcode() const { return glen == 5 ? 3 : (glen == 4 ? 1 : (glen == 3 ? 2 : 0)); }      // Variant::quad
+    int glcode() const { return glen == 5 ? 3 : (glen == 4 ? 1 : (glen == 3 ? 2 : 0)); }      // feat_group_form
 };
 
 // short inner groups: the direct path keeps DEPTH rows in flight only INSIDE a group, the LDS-DMA ring
@@ -168,7 +168,7 @@ struct GroupForm {
 // 6.0 TB/s, f32 3.5 vs 4.3; 4-step groups f32 4.4 vs 5.6, f64 equal; 8 steps and longer: equal.
 // every inner group exactly two rows ((tmin, tmax) pairs) and min / max / sine columns: the pair-mode variants of the
 // direct-load path keep DEPTH / 2 whole groups in flight, so they need no ring either
-// ... and the same for groups of exactly four rows (6-hourly data), in the lean form only (FEAT bit 10)
+// ... and the same for groups of exactly four rows (6-hourly data), in the lean form only (FEAT_FOUR_ROW)
 static int group_length_class(const PlanLayout& pl, const PlanKnobs& knobs) {
     const afhip_plan_desc* desc = &pl.desc;
     int glen = 0;
@@ -179,7 +179,7 @@ static int group_length_class(const PlanLayout& pl, const PlanKnobs& knobs) {
             if (all) glen = L;
         }
         // mixed lengths of one to four rows (a sub-daily series with missing steps): the four-row form with a length per group
-        // (FEAT bit 13); a series of single rows throughout is not a short-group plan
+        // (FEAT_MIXED); a series of single rows throughout is not a short-group plan
         if (glen == 0 && desc->T > desc->G1 && !knobs.no_ragged_mode) {
             bool all = true;
             for (int64_t g = 0; all && g < desc->G1; ++g) {
@@ -201,7 +201,7 @@ static GroupForm short_group_form(const PlanLayout& pl, const PlanKnobs& knobs) 
     f.glen = group_length_class(pl, knobs);
     f.pairs = f.glen >= 2;
     // pair plans whose columns are all  mean | sum | min | max | sine_dd -> (integer power) -> sum | mean  without float32 rounding
-    // take the lean group end (FEAT bit 8); when every column is a plain sine_dd, its tightest form (FEAT bit 9).  A sine_dd
+    // take the lean group end (FEAT_LEAN); when every column is a plain sine_dd, its tightest form (FEAT_LEAN_SINE).  A sine_dd
     // column there needs s0 < s1: its two max() terms are one clamp of width s1 - s0.
     f.lean = f.pairs; f.lean_sine = f.lean && pl.K <= 2 && !f.quad_len();
     for (const ColOp& c : pl.cols) {
@@ -368,9 +368,8 @@ static const Variant* twin_of(const Variant* v) {
     const Variant* tab = variants_table(&n);
     for (int i = 0; i < n; ++i) {
         const Variant& t = tab[i];
-        if (t.rf && t.dtype == v->dtype && t.pipe == v->pipe && t.vec == v->vec && t.stat == v->stat && t.nthr == v->nthr && t.kmax == v->kmax &&
-            t.depth == v->depth && t.nt == v->nt && t.tki == v->tki && t.sl == v->sl && t.hb == v->hb && t.ha == v->ha && t.pair == v->pair &&
-            t.ss == v->ss && t.quad == v->quad)
+        if (t.feat == (v->feat | FEAT_REGION_FUSED) && t.dtype == v->dtype && t.pipe == v->pipe && t.vec == v->vec && t.stat == v->stat && t.nthr == v->nthr &&
+            t.kmax == v->kmax && t.depth == v->depth)
             return &t;
     }
     return nullptr;
@@ -417,22 +416,21 @@ static const Variant* choose_variant(const PlanLayout& pl, const GroupForm& form
     // twin, and a plan that stores one value per group, column and cell (a daily panel of several degree-day columns) then writes and
     // re-reads period values worth a sizeable share of the cube.  From 5 % on the general two-level variant (outer = first) with its twin
     // is taken instead; packed bin counts (16-byte records, gathered directly) stay where they are.
-    if (v->sl && !v->tki && tuning == 0 && !desc->exact_order && !knobs.no_region_fused &&
+    if (v->sl() && !v->tki() && tuning == 0 && !desc->exact_order && !knobs.no_region_fused &&
         (double)desc->P * pl.K * 8.0 >= 0.05 * (double)desc->T * (desc->dtype == AFHIP_F32 ? 4.0 : 8.0)) {
         VariantQuery two = untuned;
         two.all_bins = two.single_level = two.partition = two.arith = false;
         const Variant* v2 = find_variant(two);
-        if (v2 && v2->pipe == 0 && !v2->tki && !v2->hb && twin_of(v2)) v = v2;
+        if (v2 && v2->pipe == 0 && !v2->tki() && !v2->hb() && twin_of(v2)) v = v2;
     }
     return v;
 }
 
 // ---- 6. chunking ----
 size_t plan_lds_bytes(const PlanLayout* pl) {
-    size_t lds = pl->variant->pipe == 1 ? (size_t)(pl->wg / 64) * pl->variant->depth * 1024 : 0;
-    if (pl->has_sine) lds += (pl->variant->pair && !pl->variant->quad) ? SINE_P2_BYTES : SINE_TAB_BYTES;      // the variant's sine table, behind the ring
-    if (pl->variant->hb) lds = (size_t)HB_TABLE_BYTES + (size_t)(pl->hb_n + 2) * pl->variant->vec * pl->wg * 4;
-    return lds;
+    const Variant& v = *pl->variant;
+    if (v.hb()) return lds_hist_bytes(pl->hb_n + 2, v.vec, pl->wg);
+    return lds_sine_offset(v.pipe, pl->wg / 64, v.depth) + (pl->has_sine ? (size_t)feat_sine_bytes(v.feat) : 0);      // the variant's sine table, behind the ring
 }
 
 // Chunking.  target_len = time steps a workgroup should stream; a long period is cut on
@@ -453,7 +451,7 @@ static int build_chunks(PlanLayout* pl, int vec, const PlanKnobs& knobs, const D
     // smaller workgroups the grid offers the fuller the CUs stay: configs[3] f32 3.15 ms (7 chunks of 256 threads) -> 2.84 ms
     // (126 chunks of 64), f64 5.86 -> 5.58 (profiles/r03_sweep_chunks_depth.txt).  Round 1 had measured 4-wave workgroups
     // ahead — at the few chunks of that time.
-    const bool hist = pl->variant && pl->variant->hb;
+    const bool hist = pl->variant && pl->variant->hb();
     if (hist) pl->wg = 64;
     if (knobs.force_wg) pl->wg = knobs.force_wg;   // experiment knob
     pl->tiles = (C + (int64_t)pl->wg * vec - 1) / ((int64_t)pl->wg * vec);
@@ -619,7 +617,7 @@ static bool rf_plan_ok(const PlanLayout& pl, const PlanKnobs& knobs) {
     // two-row forms other than the six-column lean one (sine_dd from (tmin, tmax) pairs: a period end every few rows) pay only where
     // the per-cell route's own traffic decides: monthly 4.44 against 3.77 ms (behind), weekly 5.80 against 6.20, daily 17.7 against
     // 21.5 — from period values of 5 % of the cube.
-    const bool two_row_light = v->pair && !v->quad && !(v->ss == 1 && v->kmax == 6);
+    const bool two_row_light = v->pair() && !v->group_form() && !(v->lean() == 1 && v->kmax == 6);
     if (ok && two_row_light) ok = share >= 0.05;
     return ok;
 }
@@ -644,7 +642,7 @@ static std::vector<int64_t> group_table(const PlanLayout& pl) {
 static PackFmt packed_format(const PlanLayout& pl) {
     const int64_t K = pl.desc.K;
     PackFmt pk{};
-    bool packed = pl.variant->tki && pl.variant->sl && K <= 16;
+    bool packed = pl.variant->tki() && pl.variant->sl() && K <= 16;
     for (const ColOp& c : pl.cols)
         packed = packed && c.src == SRC_THR && c.tf == TF_NONE && c.rounding == 0 && c.outer == OUT_FIRST;
     int64_t maxlen = 0;

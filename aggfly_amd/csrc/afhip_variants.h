@@ -6,6 +6,7 @@
 // below; find_variant() picks the cheapest instantiation that covers a lowered plan.
 #pragma once
 #include <stdint.h>
+#include "afhip_plan_types.h"
 
 namespace afhip {
 
@@ -17,19 +18,21 @@ struct Variant {
     int nthr;     // threshold slots
     int kmax;     // columns
     int depth;    // LDS ring depth in rows (pipe 1)
-    int nt;       // 1: non-temporal cache policy on the streaming loads
+    int feat;     // FEAT_* bits (afhip_plan_types.h): what else the kernel has compiled in
     int production;   // 1: part of the default menu; 0: tuning arm only
-    int tki;          // 1: integer bin counters (all threshold slots must be bins)
-    int sl;           // 1: single-level plans only (no outer accumulators)
-    int hb;           // 1: LDS-histogram bins (contiguous equal-width partition)
-    int ha;           // 1: ... whose edges are exactly representable: computed, not read from the LDS table
-    int pair;         // 1: plans whose inner groups all hold exactly two rows ((tmin, tmax) pairs)
-    int ss;           // ... with the lean group end: 1 = columns mean | sum | min | max | sine_dd -> (integer power) -> sum | mean;
-                      //     2 = every column a plain sine_dd -> sum | mean (the tightest form)
-    int quad;         // 1: ... for inner groups of exactly FOUR rows (6-hourly data) instead of two, 2: of exactly THREE rows (8-hourly), 3: of one to four rows, mixed; lean form only
-    int rf;           // 1: region-fused period ends compiled in (the twin of the variant with the same other fields)
     const void* fn;
     const char* name;
+
+    bool nt() const { return feat_has(feat, FEAT_NT); }
+    bool tki() const { return feat_has(feat, FEAT_INT_BINS); }            // integer bin counters (all threshold slots must be bins)
+    bool sl() const { return feat_has(feat, FEAT_SINGLE_LEVEL); }         // single-level plans only
+    bool hb() const { return feat_has(feat, FEAT_HIST); }                 // LDS-histogram bins
+    bool ha() const { return feat_has(feat, FEAT_ARITH_EDGES); }          // ... with computed edges
+    bool pair() const { return feat_has(feat, FEAT_SHORT_GROUP); }        // a short-group form (two rows per inner group unless group_form() says otherwise)
+    int lean() const { return feat_lean_level(feat); }                    // its lean group end: 0 none, 1 lean, 2 sine-only
+    int group_form() const { return feat_group_form(feat); }              // 1 four rows, 2 three rows, 3 mixed one to four; lean form only
+    bool rf() const { return feat_has(feat, FEAT_REGION_FUSED); }         // the region-fused twin of the variant with the same other fields and bits
+    bool sine_p2() const { return feat_sine_p2(feat); }                   // sine_dd plans: the P2 table instead of the acos table
 };
 
 const Variant* variants_table(int* n);   // generated (variants_table.hip)
@@ -50,9 +53,9 @@ struct VariantQuery {
     bool partition = false;     // the slots are a contiguous equal-width partition (LDS histogram)
     bool arith = false;         // ... with exactly representable edges
     bool pairs = false;         // every inner group holds exactly two rows
-    int lean = 0;               // lean group end the plan qualifies for: 0 none, 1 lean, 2 sine-only (Variant::ss)
+    int lean = 0;               // lean group end the plan qualifies for: 0 none, 1 lean, 2 sine-only (Variant::lean)
     int depth_hint = 0;         // among equals, the burst depth to prefer (0: none)
-    int quads = 0;              // Variant::quad of a four- / three-row / mixed short-group plan
+    int quads = 0;              // Variant::group_form of a four- / three-row / mixed short-group plan
     bool rf = false;            // the region-fused twins instead of the plain variants
 };
 
@@ -72,17 +75,17 @@ inline const Variant* find_variant(const VariantQuery& q) {
     }
     for (int i = 0; i < n; ++i) {
         const Variant& v = tab[i];
-        if (v.dtype != dtype || v.stat < stat || v.nthr < nthr || v.kmax < K || (v.rf != 0) != rf) continue;
-        if ((v.tki && !(all_bins && nthr > 0)) || (v.sl && !single_level) || (v.hb && !partition) || (v.ha && !arith)) continue;
-        if (v.pair && !((pairs || quads) && nthr == 0)) continue;
-        if ((v.pair && v.quad != quads) || (quads && !v.pair)) continue;    // a three- / four-row plan takes the variants of its group length only, and vice versa
-        if (v.ss > lean) continue;                      // a lean variant needs a plan that qualifies for its form (2 implies 1)
-        if (v.pipe != want_pipe || v.nt != want_nt) continue;
+        if (v.dtype != dtype || v.stat < stat || v.nthr < nthr || v.kmax < K || v.rf() != rf) continue;
+        if ((v.tki() && !(all_bins && nthr > 0)) || (v.sl() && !single_level) || (v.hb() && !partition) || (v.ha() && !arith)) continue;
+        if (v.pair() && !((pairs || quads) && nthr == 0)) continue;
+        if ((v.pair() && v.group_form() != quads) || (quads && !v.pair())) continue;    // a three- / four-row plan takes the variants of its group length only, and vice versa
+        if (v.lean() > lean) continue;                      // a lean variant needs a plan that qualifies for its form (2 implies 1)
+        if (v.pipe != want_pipe || (int)v.nt() != want_nt) continue;
         if (tuning > 0) {
             if (v.vec != want_vec || v.depth != want_depth) continue;
         } else if (!v.production || (vec > 0 && v.vec != vec)) continue;
         // specialised forms (integer bins, single level) are cheaper than the general one
-        const long cost = (long)v.nthr * 1000 + (long)v.kmax * 10 + v.stat - (v.tki ? 400 : 0) - (v.sl ? 5 : 0) - (v.hb ? 300 : 0) - (v.ha ? 50 : 0) - (v.pair ? 5 : 0) - 3 * v.ss
+        const long cost = (long)v.nthr * 1000 + (long)v.kmax * 10 + v.stat - (v.tki() ? 400 : 0) - (v.sl() ? 5 : 0) - (v.hb() ? 300 : 0) - (v.ha() ? 50 : 0) - (v.pair() ? 5 : 0) - 3 * v.lean()
                           + ((depth_hint > 0 && v.depth != depth_hint) ? 1 : 0);      // among equals, the burst depth that measured best for the shape
         if (!best || cost < best_cost) { best = &v; best_cost = cost; }
     }

@@ -13,16 +13,45 @@ import sys
 CT = {0: "float", 1: "double"}
 
 
+class Feat:
+    """The bits of k_fused_temporal's FEAT; afhip_plan_types.h says what each compiles in (FEAT_<name> there: the generated
+    variants_table.hip asserts that the two agree)."""
+    SINE = 1
+    GENERAL_TF = 2
+    NT = 4
+    INT_BINS = 8
+    SINGLE_LEVEL = 16
+    HIST = 32
+    ARITH_EDGES = 64
+    SHORT_GROUP = 128
+    LEAN = 256
+    LEAN_SINE = 512
+    FOUR_ROW = 1024
+    REGION_FUSED = 2048
+    THREE_ROW = 4096
+    MIXED = 8192
+
+
+FEAT_NAMES = [n for n in vars(Feat) if n.isupper()]
+GROUP_LENGTH = Feat.FOUR_ROW | Feat.THREE_ROW | Feat.MIXED      # the short-group forms of other than two rows
+# name suffixes, in name order (`_ss` instead of `_lean` for the sine-only lean form)
+SUFFIXES = ((Feat.NT, "_nt"), (Feat.INT_BINS, "_ibins"), (Feat.SINGLE_LEVEL, "_sl"), (Feat.HIST, "_hist"), (Feat.ARITH_EDGES, "_arith"),
+            (Feat.SHORT_GROUP, "_pair"), (Feat.LEAN, "_lean"), (Feat.FOUR_ROW, "_quad"), (Feat.THREE_ROW, "_tri"), (Feat.MIXED, "_rag"),
+            (Feat.REGION_FUSED, "_rf"))
+
+
 def menu(kind):
     """(dtype, pipe, vec, stat, nthr, kmax, depth, feat, production)"""
     out = []
     vec16 = {0: 4, 1: 2}
 
     def add(dtype, pipe, vec, stat, nthr, kmax, depth, nt=1, prod=1, tki=0, sl=0, hb=0, ha=0, pair=0, ss=0, quad=0, rf=0, tri=0, rag=0):
-        # sine degree days ride on the min/max accumulators; generic pow() only in the
-        # all-purpose (STAT 3) variants; bit 2 = nt cache policy on the streaming loads;
-        # bit 3 = integer bin counters; bit 4 = single-level plan (no outer accumulators)
-        feat = {0: 0, 1: 0, 2: 1, 3: 3}[stat] | (4 if nt else 0) | (8 if tki else 0) | (16 if sl else 0) | (32 if hb else 0) | (64 if ha else 0) | (128 if pair else 0) | (256 if ss else 0) | (512 if ss == 2 else 0) | (1024 if quad else 0) | (2048 if rf else 0) | (4096 if tri else 0) | (8192 if rag else 0)
+        # sine degree days ride on the min/max accumulators; generic pow() only in the all-purpose (STAT 3) variants
+        feat = {0: 0, 1: 0, 2: Feat.SINE, 3: Feat.SINE | Feat.GENERAL_TF}[stat]
+        for on, bit in ((nt, Feat.NT), (tki, Feat.INT_BINS), (sl, Feat.SINGLE_LEVEL), (hb, Feat.HIST), (ha, Feat.ARITH_EDGES), (pair, Feat.SHORT_GROUP),
+                        (ss, Feat.LEAN), (ss == 2, Feat.LEAN_SINE), (quad, Feat.FOUR_ROW), (rf, Feat.REGION_FUSED), (tri, Feat.THREE_ROW), (rag, Feat.MIXED)):
+            if on:
+                feat |= bit
         key = (dtype, pipe, vec, stat, nthr, kmax, depth, feat)
         for i, v in enumerate(out):
             if v[:8] == key:
@@ -95,7 +124,7 @@ def menu(kind):
         if dtype == 0:
             for (stat, nthr, kmax) in [(st, nt_, km) for st in (0, 1, 3) for nt_ in (0, 1) for km in (2, 6) if not (st == 0 and nt_ == 0)] + [(2, 0, 2), (2, 0, 6)]:
                 add(dtype, 0, 2, stat, nthr, kmax, 4)
-        # (tmin, tmax) pairs with the lean group end (FEAT bit 8): sine_dd / min / max sources (stat 2) and mean / sum alone (stat 1)
+        # (tmin, tmax) pairs with the lean group end (Feat.LEAN): sine_dd / min / max sources (stat 2) and mean / sum alone (stat 1)
         for (vec, depth) in (((1, 4), (1, 8)) if dtype == 1 else ((2, 8), (1, 8), (2, 4))):
             prod = 1 if (vec, depth) in ((1, 4), (2, 8), (1, 8)) and not (dtype == 1 and depth == 8) else 0
             add(dtype, 0, vec, 2, 0, 2, depth, pair=1, ss=2, prod=prod)      # every column a plain sine_dd (configs[4])
@@ -104,18 +133,18 @@ def menu(kind):
             add(dtype, 0, vec, 1, 0, 2, depth, pair=1, ss=1, prod=prod)
             add(dtype, 0, vec, 1, 0, 6, depth, pair=1, ss=1, prod=prod)
         # (four cells per lane — half the per-wave scalar work per cell — measured level with two: 4.28 vs 4.25 ms on C5; not kept)
-        # inner groups of exactly four rows (6-hourly data): the lean short-group form (FEAT bit 10)
+        # inner groups of exactly four rows (6-hourly data): the lean short-group form (Feat.FOUR_ROW)
         for (vec, depth) in (((1, 8), (1, 4)) if dtype == 1 else ((2, 8), (1, 8))):
             prod = 0 if (dtype == 1 and depth == 4) else 1
             for stat in (1, 2):
                 for kmax in (2, 6):
                     add(dtype, 0, vec, stat, 0, kmax, depth, pair=1, ss=1, quad=1, prod=prod)
-        # inner groups of exactly three rows (8-hourly data): the same lean form (FEAT bit 12), two groups per block of six rows
+        # inner groups of exactly three rows (8-hourly data): the same lean form (Feat.THREE_ROW), two groups per block of six rows
         for vec in ((1,) if dtype == 1 else (2, 1)):
             for stat in (1, 2):
                 for kmax in (2, 6):
                     add(dtype, 0, vec, stat, 0, kmax, 6, pair=1, ss=1, tri=1)
-    # region-fused period ends (FEAT bit 11): twins of the production two-level variants on the direct-load path.  Round 3 built the
+    # region-fused period ends (Feat.REGION_FUSED): twins of the production two-level variants on the direct-load path.  Round 3 built the
     # twins that gain from two periods on (up to six columns and four threshold slots, with a statistic; of the short-group forms
     # every lean four-row form and the six-column lean pair form); round 4 adds threshold-only plans (a daily panel of degree days) and
     # every short-group form incl. the sine-only pair form (afhip_planner.cpp: rf_plan_ok says when the planner takes them).  Plans of
@@ -125,9 +154,9 @@ def menu(kind):
     # — appended, so that the translation units above keep their contents
     for v in list(out):
         dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod = v
-        if prod and pipe == 0 and kmax <= 6 and nthr <= 4 and not (feat & (8 | 16 | 32)):
-            out.append((dtype, pipe, vec, stat, nthr, kmax, depth, feat | 2048, prod))
-    # inner groups of MIXED lengths one to four rows (FEAT bit 13; a sub-daily series with missing steps): the four-row form with a
+        if prod and pipe == 0 and kmax <= 6 and nthr <= 4 and not (feat & (Feat.INT_BINS | Feat.SINGLE_LEVEL | Feat.HIST)):
+            out.append((dtype, pipe, vec, stat, nthr, kmax, depth, feat | Feat.REGION_FUSED, prod))
+    # inner groups of MIXED lengths one to four rows (Feat.MIXED; a sub-daily series with missing steps): the four-row form with a
     # scalar trip count per group, and its region-fused twins — appended likewise
     if kind != "dev":
         for dtype in (0, 1):
@@ -148,7 +177,7 @@ def menu(kind):
 def pickable(v):
     """False for a kernel that no plan can select by the planner's default rules (afhip_planner.cpp: the stage named in each comment), whatever its shape."""
     dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod = v
-    short = feat & (128 | 1024 | 4096 | 8192)                   # a short-group form; 4096 / 8192: three rows / mixed lengths
+    short = feat & (Feat.SHORT_GROUP | GROUP_LENGTH)            # a short-group form
     if kmax == 2 and (nthr == 16 or (nthr == 4 and stat in (1, 2))):
         return False      # every column adds at most one threshold slot, so slots <= K, and <= K - 1 beside a mean / sum / min / max /
         #                   sine_dd source (stat 3 may come from a non-integer pow on a threshold column: s3_t4_k2 stays) — lower_columns
@@ -156,15 +185,15 @@ def pickable(v):
         return False      # load_path: two cells per lane need fewer than four slots (and an LDS-histogram plan takes one cell per lane: choose_variant)
     if dtype == 0 and pipe == 0 and vec == 2 and stat == 1 and nthr == 0 and kmax == 2:
         return False      # load_path: one cell per lane for light float32 plans: stat <= 1, no slot, K <= 2
-    if short and stat == 1 and kmax == 2 and (not (feat & (1024 | 4096 | 8192)) or (dtype == 0 and feat & (4096 | 8192))):
+    if short and stat == 1 and kmax == 2 and (not (feat & GROUP_LENGTH) or (dtype == 0 and feat & (Feat.THREE_ROW | Feat.MIXED))):
         return False      # short_group_form: stat-1 short-group plans need K >= min_k: 3 for two-row groups, and for float32 three-row / mixed groups
     return True
 
 
 def name_of(v):
     dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod = v
-    return (f"{'f32' if dtype == 0 else 'f64'}_p{pipe}_v{vec}_s{stat}_t{nthr}_k{kmax}_d{depth}" + ("_nt" if feat & 4 else "")
-            + ("_ibins" if feat & 8 else "") + ("_sl" if feat & 16 else "") + ("_hist" if feat & 32 else "") + ("_arith" if feat & 64 else "") + ("_pair" if feat & 128 else "") + ("_ss" if feat & 512 else ("_lean" if feat & 256 else "")) + ("_quad" if feat & 1024 else "") + ("_tri" if feat & 4096 else "") + ("_rag" if feat & 8192 else "") + ("_rf" if feat & 2048 else ""))
+    return (f"{'f32' if dtype == 0 else 'f64'}_p{pipe}_v{vec}_s{stat}_t{nthr}_k{kmax}_d{depth}"
+            + "".join("_ss" if bit == Feat.LEAN and feat & Feat.LEAN_SINE else sfx for bit, sfx in SUFFIXES if feat & bit))
 
 
 def inst(v):
@@ -227,13 +256,15 @@ def main():
             f.write(f"int register_variants_{idx:02d}(Variant* out) {{\n    int n = 0;\n")
             for v in group:
                 dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod = v
-                f.write(f"    out[n++] = Variant{{{dtype}, {pipe}, {vec}, {stat}, {nthr}, {kmax}, {depth}, {1 if feat & 4 else 0}, {prod}, {1 if feat & 8 else 0}, {1 if feat & 16 else 0}, {1 if feat & 32 else 0}, {1 if feat & 64 else 0}, {1 if feat & 128 else 0}, {2 if feat & 512 else (1 if feat & 256 else 0)}, {1 if feat & 1024 else (2 if feat & 4096 else (3 if feat & 8192 else 0))}, {1 if feat & 2048 else 0}, (const void*)&{inst(v)}, \"{name_of(v)}\"}};\n")
+                f.write(f"    out[n++] = Variant{{{dtype}, {pipe}, {vec}, {stat}, {nthr}, {kmax}, {depth}, {feat}, {prod}, (const void*)&{inst(v)}, \"{name_of(v)}\"}};\n")
             f.write("    return n;\n}\n}\n")
         files.append(fn)
     with _KeepIfSame(os.path.join(outdir, "variants_table.hip")) as f:
         f.write("// generated by gen_variants.py — do not edit\n")
         f.write('#include "afhip_variants.h"\n')
         f.write("namespace afhip {\n")
+        for name in FEAT_NAMES:
+            f.write(f'static_assert(FEAT_{name} == {getattr(Feat, name)}, "gen_variants.py and afhip_plan_types.h disagree on a FEAT bit");\n')
         for g in range(ngroups):
             f.write(f"int register_variants_{g:02d}(Variant* out);\n")
         f.write(f"static Variant g_table[{len(vs)}];\nstatic int g_count = -1;\n")

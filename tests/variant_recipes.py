@@ -33,9 +33,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WG = 256                     # afhip_kernels.h
 F32, F64 = 0, 1              # include/aggfly_hip.h
 
-# FEAT bits (gen_variants.py)
-NT, TKI, SL, HB, HA, PAIR, LEAN, SS2, QUAD, RF, TRI, RAG = 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192
-
 
 def gen_variants():
     path = os.path.join(ROOT, "aggfly_amd", "csrc")
@@ -43,6 +40,12 @@ def gen_variants():
         sys.path.insert(0, path)
     import gen_variants as gv
     return gv
+
+
+# FEAT bits (gen_variants.py)
+_F = gen_variants().Feat
+NT, TKI, SL, HB, HA, PAIR, LEAN, SS2 = _F.NT, _F.INT_BINS, _F.SINGLE_LEVEL, _F.HIST, _F.ARITH_EDGES, _F.SHORT_GROUP, _F.LEAN, _F.LEAN_SINE
+QUAD, RF, TRI, RAG = _F.FOUR_ROW, _F.REGION_FUSED, _F.THREE_ROW, _F.MIXED
 
 
 def production_menu(kind="full"):
