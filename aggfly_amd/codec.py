@@ -69,6 +69,12 @@ def load():
         lib.afcodec_zstd_scratch_bytes.argtypes = [C.c_int64] * 5
         lib.afcodec_zstd_emulate.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                              C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        lib.afcodec_inflate_plan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                             C.POINTER(C.c_int64), C.c_void_p, C.c_int64] + [C.POINTER(C.c_int64)] * 6 + [C.c_void_p]
+        lib.afcodec_inflate_scratch_bytes.restype = C.c_int64
+        lib.afcodec_inflate_scratch_bytes.argtypes = [C.c_int64] * 6
+        lib.afcodec_inflate_emulate.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int64] * 6 + [
+            C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         lib.afcodec_read_packed.argtypes = [C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
                                             C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
         _lib = lib
@@ -78,7 +84,8 @@ def load():
 EXPORTS = ("afcodec_last_error", "afcodec_have", "afcodec_blosc_info", "afcodec_blosc_decode", "afcodec_blosc_decode_mt", "afcodec_blosc_decode_many",
            "afcodec_blosc_decode_files", "afcodec_decode_files", "afcodec_decode_ranges",
            "afcodec_blosc_bound", "afcodec_blosc_encode_lz4", "afcodec_zstd_decode", "afcodec_zstd_bound", "afcodec_zstd_encode", "afcodec_lz4_decode", "afcodec_blosc_lz4_plan", "afcodec_read_packed",
-           "afcodec_zstd_plan", "afcodec_zstd_scratch_bytes", "afcodec_zstd_emulate")
+           "afcodec_zstd_plan", "afcodec_zstd_scratch_bytes", "afcodec_zstd_emulate",
+           "afcodec_inflate_plan", "afcodec_inflate_scratch_bytes", "afcodec_inflate_emulate")
 
 
 def _err(lib, what):
@@ -348,4 +355,64 @@ def zstd_emulate(base: np.ndarray, frames: np.ndarray, blocks: np.ndarray, plan:
     lib.afcodec_zstd_emulate(base.ctypes.data, base.nbytes, frames.ctypes.data, plan.n_frames, blocks.ctypes.data, plan.n_blocks,
                              plan.lit_bytes, plan.n_seqs, plan.dec_bytes, scratch.ctypes.data, out.ctypes.data, C.byref(err),
                              C.byref(rounds))
+    return int(err.value), int(rounds.value)
+
+
+# record layout shared with libaggfly_hip (include/aggfly_hip.h: afhip_inflate_stream; inflate_passes.h)
+INFLATE_STREAM = np.dtype([("src", "<i8"), ("dst_off", "<i8"), ("base", "<i8"), ("seq_off", "<i8"), ("csize", "<i4"), ("dsize", "<i4"),
+                           ("to_out", "<i4"), ("first_block", "<i4"), ("n_blocks", "<i4"), ("first_piece", "<i4")])
+
+
+class InflatePlan:
+    """What `inflate_plan` found in a batch: record counts and the sizes of the per-batch buffers."""
+
+    def __init__(self, n_streams, n_shuf, n_pblocks, n_seqs, n_pieces, dec_bytes, tmp_bytes, max_bsize, results):
+        self.n_streams, self.n_shuf, self.n_pblocks, self.n_seqs, self.n_pieces = n_streams, n_shuf, n_pblocks, n_seqs, n_pieces
+        self.dec_bytes, self.tmp_bytes, self.max_bsize, self.results = dec_bytes, tmp_bytes, max_bsize, results
+
+    def sizes(self):
+        return self.n_streams, self.n_pblocks, self.n_seqs, self.n_pieces, self.dec_bytes, self.tmp_bytes
+
+    def scratch_bytes(self) -> int:
+        return int(load().afcodec_inflate_scratch_bytes(*self.sizes()))
+
+
+def inflate_plan(base: np.ndarray, comp_off, comp_size, out_off, out_size, streams: np.ndarray, shuf: np.ndarray, typesize=1,
+                 strict: bool = True):
+    """Plan the GPU-side decode of zlib streams that sit in ``base`` (uint8; chunk i = ``comp_size[i]`` bytes at ``comp_off[i]``,
+    decoded to ``out_off[i]`` of the output, ``out_size[i]`` bytes; ``typesize`` — one for all chunks, or one per chunk — > 1: byte-unshuffled there, HDF5's
+    shuffle + deflate): fills ``streams`` (dtype `INFLATE_STREAM`) and ``shuf`` (dtype `SHUFFLE_BLOCK`) for `hip.inflate_decode`.
+    -> `InflatePlan`; ``results[i]`` = decoded size, or `E_UNSUPPORTED` for a chunk the GPU route does not take (preset
+    dictionary, gzip member, 1 GiB or more: decode it on the host); other header bytes raise `CodecError` (``strict=False``: they
+    are only marked negative in ``results``)."""
+    lib = load()
+    n = len(comp_off)
+    co, cs, oo, osz = (np.ascontiguousarray(a, dtype=np.int64) for a in (comp_off, comp_size, out_off, out_size))
+    res = np.zeros(n, dtype=np.int64)
+    ns, nsh, nb, nsq, npc, dec, tmp = (C.c_int64(0) for _ in range(7))
+    assert streams.dtype == INFLATE_STREAM and shuf.dtype == SHUFFLE_BLOCK and base.dtype == np.uint8
+    ts = np.ascontiguousarray(np.broadcast_to(np.asarray(typesize, dtype=np.int32), (n,)))
+    rc = lib.afcodec_inflate_plan(base.ctypes.data, n, co.ctypes.data, cs.ctypes.data, oo.ctypes.data, osz.ctypes.data, ts.ctypes.data,
+                                  streams.ctypes.data, len(streams), C.byref(ns), shuf.ctypes.data, len(shuf), C.byref(nsh), C.byref(nb),
+                                  C.byref(nsq), C.byref(npc), C.byref(dec), C.byref(tmp), res.ctypes.data)
+    bad = [int(i) for i in np.nonzero((res < 0) & (res != E_UNSUPPORTED))[0]]
+    if rc and not bad and ("list too small" in lib.afcodec_last_error().decode() or "2 GiB" in lib.afcodec_last_error().decode()):
+        raise PlanCapacityError(f"inflate_plan: {lib.afcodec_last_error().decode()}")
+    if rc == -3:
+        raise _err(lib, "inflate_plan")
+    if strict and bad:
+        raise CodecError(f"inflate_plan: chunks {bad[:8]} are malformed: {lib.afcodec_last_error().decode()}")
+    max_b = int(shuf["bsize"][:nsh.value].max()) if nsh.value else 0
+    return InflatePlan(int(ns.value), int(nsh.value), int(nb.value), int(nsq.value), int(npc.value), int(dec.value), int(tmp.value), max_b, res)
+
+
+def inflate_emulate(base: np.ndarray, streams: np.ndarray, shuf: np.ndarray, plan: InflatePlan, out: np.ndarray):
+    """Run the passes of the GPU decode (`hip.inflate_decode`) on this thread — the host reference of the GPU algorithm, for
+    tests.  -> (errors, pointer-jump rounds)."""
+    lib = load()
+    scratch = np.zeros(plan.scratch_bytes(), dtype=np.uint8)
+    err, rounds = C.c_int32(0), C.c_int32(0)
+    lib.afcodec_inflate_emulate(base.ctypes.data, base.nbytes, streams.ctypes.data, plan.n_streams, shuf.ctypes.data, plan.n_shuf,
+                                plan.n_pblocks, plan.n_seqs, plan.n_pieces, plan.dec_bytes, plan.tmp_bytes, scratch.ctypes.data,
+                                out.ctypes.data, C.byref(err), C.byref(rounds))
     return int(err.value), int(rounds.value)

@@ -18,6 +18,7 @@
 #include "afhip_panel_kernels.h"
 #include "afhip_lz4_kernels.h"
 #include "afhip_zstd_kernels.h"
+#include "afhip_inflate_kernels.h"
 #include "afhip_planner.h"
 #include "afhip_variants.h"
 #include "afhip_sine_p2_table.h"
@@ -595,6 +596,58 @@ extern "C" int afhip_zstd_decode(const void* comp_dev, int64_t comp_bytes, const
         hipLaunchKernelGGL(k_zstd_gather, dim3((unsigned)n_blocks), dim3(ZSTD_WG), 0, st, c);
     }
     if (rounds_dev) hipLaunchKernelGGL(k_zstd_rounds, dim3(1), dim3(ZSTD_WG), 0, st, c, R, rounds_dev);
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
+extern "C" int64_t afhip_inflate_scratch_bytes(int64_t n_streams, int64_t n_pblocks, int64_t n_seqs, int64_t n_pieces, int64_t dec_bytes,
+                                               int64_t tmp_bytes) {
+    if (n_streams < 0 || n_pblocks < 0 || n_seqs < 0 || n_pieces < 0 || dec_bytes < 0 || tmp_bytes < 0)
+        return fail(AFHIP_E_INVALID, "inflate_scratch_bytes: negative size");
+    int64_t o[9];
+    return afi_layout(n_streams, n_pblocks, n_seqs, n_pieces, dec_bytes, tmp_bytes, o);
+}
+
+extern "C" int afhip_inflate_decode(const void* comp_dev, int64_t comp_bytes, const afhip_inflate_stream* streams_dev, int64_t n_streams,
+                                    const afhip_shuffle_block* shuf_dev, int64_t n_shuf, int32_t max_bsize, int64_t n_pblocks, int64_t n_seqs,
+                                    int64_t n_pieces, int64_t dec_bytes, int64_t tmp_bytes, void* scratch_dev, int64_t scratch_bytes,
+                                    void* out_dev, int32_t* errors_dev, int32_t* rounds_dev, void* stream) {
+    static_assert(sizeof(afhip_inflate_stream) == sizeof(afi_stream) && sizeof(afhip_shuffle_block) == sizeof(ShufBlock), "record layouts");
+    if (!comp_dev || !streams_dev || !scratch_dev || !out_dev || !errors_dev || (n_shuf && !shuf_dev) || comp_bytes < 0 || n_streams < 0 ||
+        n_shuf < 0 || max_bsize < 0 || n_pblocks < 0 || n_seqs < 0 || n_pieces < 0 || dec_bytes < 0 || tmp_bytes < 0)
+        return fail(AFHIP_E_INVALID, "inflate_decode: NULL argument or negative size");
+    if (dec_bytes > 0x7fffffff || n_pblocks > 0x7fffffff - 64 || n_streams > 0x7fffffff - 64 || n_pieces > 0x7fffffff - 64)
+        return fail(AFHIP_E_INVALID, "inflate_decode: more than 2 GiB decoded in one batch");
+    if (scratch_bytes < afhip_inflate_scratch_bytes(n_streams, n_pblocks, n_seqs, n_pieces, dec_bytes, tmp_bytes))
+        return fail(AFHIP_E_INVALID, "inflate_decode: scratch smaller than afhip_inflate_scratch_bytes()");
+    if (n_streams == 0) return AFHIP_OK;
+    GUARD_DEVICE(pointer_device(out_dev));
+    hipStream_t st = (hipStream_t)stream;
+    afi_ctx c;
+    memset(&c, 0, sizeof c);
+    c.comp = (const uint8_t*)comp_dev; c.comp_bytes = comp_bytes;
+    c.streams = (const afi_stream*)streams_dev; c.n_streams = n_streams;
+    c.n_blocks = n_pblocks; c.n_seqs = n_seqs; c.n_pieces = n_pieces; c.dec_bytes = dec_bytes; c.tmp_bytes = tmp_bytes;
+    afi_bind(&c, (uint8_t*)scratch_dev);
+    c.out = (uint8_t*)out_dev; c.errors = errors_dev;
+    HIP_TRY(hipMemsetAsync(c.bad, 0, (size_t)(n_streams + 64) * 4, st));
+    auto waves = [](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n + INFLATE_WG - 1) / INFLATE_WG)); };
+    hipLaunchKernelGGL(k_inflate_front, dim3((unsigned)n_streams), dim3(INFLATE_WG), 0, st, c);
+    const int R = afz_rounds_host(dec_bytes);
+    const afz_ctx z = afi_jump_view(&c);
+    if (n_pblocks && dec_bytes) {
+        hipLaunchKernelGGL(k_inflate_fill, dim3((unsigned)n_pblocks), dim3(INFLATE_WG), 0, st, c);
+        const unsigned jg = (unsigned)std::max<int64_t>(1, std::min<int64_t>((dec_bytes + ZSTD_JUMP_WG - 1) / ZSTD_JUMP_WG, 16384));
+        for (int r = 0; r < R; ++r) hipLaunchKernelGGL(k_zstd_jump, dim3(jg), dim3(ZSTD_JUMP_WG), 0, st, z, r);
+        hipLaunchKernelGGL(k_inflate_gather, dim3((unsigned)n_pblocks), dim3(INFLATE_WG), 0, st, c);
+    }
+    if (n_pieces) hipLaunchKernelGGL(k_inflate_adler, dim3((unsigned)n_pieces), dim3(INFLATE_WG), 0, st, c);
+    hipLaunchKernelGGL(k_inflate_check, waves(n_streams), dim3(INFLATE_WG), 0, st, c);
+    const unsigned tiles = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)max_bsize / 2 + 255) / 256));
+    for (int64_t b0 = 0; b0 < n_shuf; b0 += 65535)       // (a launch unshuffles at most 65,535 blocks)
+        hipLaunchKernelGGL(k_unshuffle_blocks, dim3(tiles, (unsigned)std::min<int64_t>(65535, n_shuf - b0)), dim3(256), 0, st,
+                           (const uint8_t*)c.tmp, (uint8_t*)out_dev, (const ShufBlock*)shuf_dev + b0);
+    if (rounds_dev) hipLaunchKernelGGL(k_zstd_rounds, dim3(1), dim3(ZSTD_WG), 0, st, z, R, rounds_dev);
     HIP_TRY(hipGetLastError());
     return AFHIP_OK;
 }

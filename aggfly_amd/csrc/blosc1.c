@@ -1117,3 +1117,101 @@ int afcodec_zstd_emulate(const void* comp, int64_t comp_bytes, const void* frame
     if (rounds) *rounds = r;
     return AFCODEC_OK;
 }
+
+/* ---- plan of a GPU-side zlib decode (include/aggfly_codec.h: afcodec_inflate_plan) ----
+ * Only the zlib wrapper is read (RFC 1950 §2.2): deflate's block boundaries are found by decoding, which is the GPU's
+ * (inflate_passes.h). */
+#include "inflate_passes.h"
+
+int afcodec_inflate_plan(const void* base, int64_t n, const int64_t* comp_off, const int64_t* comp_size, const int64_t* out_off,
+                         const int64_t* out_size, const int32_t* typesize, void* streams_v, int64_t cap_streams, int64_t* n_streams, void* shuf_v,
+                         int64_t cap_shuf, int64_t* n_shuf, int64_t* n_pblocks, int64_t* n_seqs, int64_t* n_pieces, int64_t* dec_bytes,
+                         int64_t* tmp_bytes, int64_t* results) {
+    typedef struct { int64_t tmp_off, out_off; int32_t bsize, typesize; } shuf_rec;      /* == afhip_shuffle_block */
+    afi_stream* streams = (afi_stream*)streams_v;
+    shuf_rec* shuf = (shuf_rec*)shuf_v;
+    int64_t ns = 0, nsh = 0, nb = 0, nsq = 0, np = 0, dec = 0, tmp = 0;
+    int rc_all = AFCODEC_OK;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint8_t* c = (const uint8_t*)base + comp_off[i];
+        const int64_t csz = comp_size[i], dsz = out_size[i];
+        const int ts = typesize ? typesize[i] : 1;
+        int bad = 0;
+        const char* why = "";
+        if (ts < 1 || ts > 255) return fail(AFCODEC_E_SIZE, "inflate_plan: element size out of range");
+        if (csz < 2) { bad = AFCODEC_E_FORMAT; why = "shorter than a zlib header"; }
+        else if (c[0] == 0x1f && c[1] == 0x8b) { bad = AFCODEC_E_UNSUPPORTED; why = "gzip member: decode on the host"; }
+        else if ((c[0] & 15) != 8 || (c[0] >> 4) > 7 || ((c[0] << 8) | c[1]) % 31) { bad = AFCODEC_E_FORMAT; why = "not a zlib stream"; }
+        else if (c[1] & 0x20) { bad = AFCODEC_E_UNSUPPORTED; why = "zlib stream with a preset dictionary: decode on the host"; }
+        else if (dsz < 0 || dsz >= ((int64_t)1 << 30) || csz > 0x7fffffff) { bad = AFCODEC_E_UNSUPPORTED; why = "chunk of 1 GiB or more: decode on the host"; }
+        else if (dec + dsz > 0x7fffffff) return fail(AFCODEC_E_SIZE, "inflate_plan: more than 2 GiB decoded in one batch");
+        if (bad) {
+            results[i] = bad;
+            rc_all = fail(bad, why);
+            continue;
+        }
+        const int shuffled = ts > 1 && dsz >= ts;
+        if (ns >= cap_streams || (shuffled && nsh >= cap_shuf)) return fail(AFCODEC_E_SIZE, "stream list too small");
+        afi_stream s;
+        memset(&s, 0, sizeof s);
+        s.src = comp_off[i]; s.csize = (int32_t)csz; s.dsize = (int32_t)dsz;
+        s.base = dec; s.seq_off = nsq;
+        s.first_block = (int32_t)nb; s.n_blocks = (int32_t)(dsz / AFI_PBLOCK_MIN + 1);
+        s.first_piece = (int32_t)np;
+        if (shuffled) {
+            s.to_out = 0; s.dst_off = tmp;
+            shuf[nsh++] = (shuf_rec){tmp, out_off[i], (int32_t)dsz, ts};
+            tmp += (dsz + 15) & ~(int64_t)15;
+        } else {
+            s.to_out = 1; s.dst_off = out_off[i];
+        }
+        streams[ns++] = s;
+        nb += s.n_blocks; nsq += dsz / 3 + 1; np += (dsz + AFI_PIECE - 1) / AFI_PIECE; dec += dsz;
+        results[i] = dsz;
+    }
+    *n_streams = ns; *n_shuf = nsh; *n_pblocks = nb; *n_seqs = nsq; *n_pieces = np; *dec_bytes = dec; *tmp_bytes = tmp;
+    return rc_all;
+}
+
+int64_t afcodec_inflate_scratch_bytes(int64_t n_streams, int64_t n_pblocks, int64_t n_seqs, int64_t n_pieces, int64_t dec_bytes,
+                                      int64_t tmp_bytes) {
+    int64_t o[9];
+    return afi_layout(n_streams, n_pblocks, n_seqs, n_pieces, dec_bytes, tmp_bytes, o);
+}
+
+/* The passes of the GPU decode (inflate_passes.h) run in order on this thread: the host reference of afhip_inflate_decode. */
+int afcodec_inflate_emulate(const void* comp, int64_t comp_bytes, const void* streams, int64_t n_streams, const void* shuf_v,
+                            int64_t n_shuf, int64_t n_pblocks, int64_t n_seqs, int64_t n_pieces, int64_t dec_bytes, int64_t tmp_bytes,
+                            void* scratch, void* out, int32_t* errors, int32_t* rounds) {
+    typedef struct { int64_t tmp_off, out_off; int32_t bsize, typesize; } shuf_rec;
+    const shuf_rec* shuf = (const shuf_rec*)shuf_v;
+    afi_ctx x;
+    memset(&x, 0, sizeof x);
+    x.comp = (const uint8_t*)comp; x.comp_bytes = comp_bytes;
+    x.streams = (const afi_stream*)streams; x.n_streams = n_streams;
+    x.n_blocks = n_pblocks; x.n_seqs = n_seqs; x.n_pieces = n_pieces; x.dec_bytes = dec_bytes; x.tmp_bytes = tmp_bytes;
+    afi_bind(&x, (uint8_t*)scratch);
+    x.out = (uint8_t*)out; x.errors = errors;
+    memset(x.bad, 0, (size_t)(n_streams + 64) * 4);
+    for (int64_t s = 0; s < n_streams; ++s) afi_pass_front(&x, s, NULL);
+    for (int64_t b = 0; b < n_pblocks; ++b) afi_pass_fill(&x, b, 0, 1);
+    const afz_ctx z = afi_jump_view(&x);
+    const int R = afz_rounds_host(dec_bytes);
+    int r = 0;
+    for (; r < R && x.flags[r]; ++r) {
+        int more = 0;
+        for (int64_t p = 0; p < dec_bytes; ++p) more |= afz_jump(&z, p);
+        x.flags[r + 1] = more;
+    }
+    for (int64_t b = 0; b < n_pblocks; ++b) afi_pass_gather(&x, b, 0, 1);
+    for (int64_t g = 0; g < n_pieces; ++g) {
+        uint32_t a;
+        uint64_t b;
+        afi_adler_share(&x, g, 0, 1, &a, &b);
+        afi_adler_put(&x, g, a, b);
+    }
+    for (int64_t s = 0; s < n_streams; ++s) afi_pass_check(&x, s);
+    for (int64_t i = 0; i < n_shuf; ++i) unshuffle_bytes(shuf[i].typesize, shuf[i].bsize, x.tmp + shuf[i].tmp_off, (uint8_t*)out + shuf[i].out_off);
+    if (rounds) *rounds = r;
+    return AFCODEC_OK;
+}

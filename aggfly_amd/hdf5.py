@@ -698,7 +698,9 @@ class ChunkSource:
                 self.native_kind = None                                    # a chunk written with filters skipped: host route
             self._index[tuple(o // c for o, c in zip(offs, self.chunks))] = (a, nbytes)
 
-    def chunk_locator(self, idx):
+    def chunk_locator(self, idx, probe: bool = True):
+        """(file, offset, nbytes) of chunk ``idx`` without its fletcher32 trailer, or None when it is absent (``probe`` is
+        `ZarrArray.chunk_locator`'s: the chunk index answers either way)."""
         hit = self._index.get(tuple(idx))
         return None if hit is None else (self.path, hit[0], hit[1] - self._trailer)
 

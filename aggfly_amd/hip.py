@@ -35,7 +35,7 @@ EXPORTS = (
     "afhip_plan_create", "afhip_plan_destroy", "afhip_plan_workspace_bytes", "afhip_plan_run_workspace_bytes",
     "afhip_plan_describe", "afhip_plan_run_temporal", "afhip_plan_run",
     "afhip_plan_profile_begin", "afhip_plan_profile_end", "afhip_plan_bind_inter", "afhip_csr_device", "afhip_plan_device", "afhip_transform", "afhip_panel_divide", "afhip_lz4_decode_streams", "afhip_unshuffle_blocks", "afhip_read_probe",
-    "afhip_zstd_scratch_bytes", "afhip_zstd_decode",
+    "afhip_zstd_scratch_bytes", "afhip_zstd_decode", "afhip_inflate_scratch_bytes", "afhip_inflate_decode",
 )
 
 
@@ -116,6 +116,9 @@ def load():
     lib.afhip_zstd_scratch_bytes.restype = i64
     lib.afhip_zstd_scratch_bytes.argtypes = [i64] * 5
     lib.afhip_zstd_decode.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, i64, vp, i64, vp, vp, vp, vp]
+    lib.afhip_inflate_scratch_bytes.restype = i64
+    lib.afhip_inflate_scratch_bytes.argtypes = [i64] * 6
+    lib.afhip_inflate_decode.argtypes = [vp, i64, vp, i64, vp, i64, i32, i64, i64, i64, i64, i64, vp, i64, vp, vp, vp, vp]
     lib.afhip_plan_profile_begin.argtypes = [vp, i64]
     lib.afhip_plan_profile_end.argtypes = [vp, C.POINTER(C.c_float), i64]
     lib.afhip_plan_profile_end.restype = i64
@@ -197,6 +200,25 @@ def zstd_decode(comp, comp_bytes: int, frames, blocks, plan, scratch, out, error
     _check(load().afhip_zstd_decode(comp.data_ptr(), int(comp_bytes), frames.data_ptr(), plan.n_frames, blocks.data_ptr(), plan.n_blocks,
                                     plan.lit_bytes, plan.n_seqs, plan.dec_bytes, scratch.data_ptr(), scratch.numel(), out.data_ptr(),
                                     errors.data_ptr(), rounds.data_ptr() if rounds is not None else None, _stream_ptr(comp)))
+
+
+def inflate_scratch_bytes(plan) -> int:
+    """`afhip_inflate_scratch_bytes` for a `codec.InflatePlan`."""
+    n = int(load().afhip_inflate_scratch_bytes(*plan.sizes()))
+    if n < 0:
+        _check(n)
+    return n
+
+
+def inflate_decode(comp, comp_bytes: int, streams, shuf, plan, scratch, out, errors, rounds=None):
+    """`afhip_inflate_decode`: decode the zlib streams planned by `codec.inflate_plan` (``streams`` / ``shuf``: uint8 HBM tensors
+    holding the records, ``comp``: the batch's compressed bytes in HBM) into ``out``, shuffled chunks through the scratch;
+    ``scratch``: a uint8 HBM tensor of `inflate_scratch_bytes(plan)` bytes; damaged streams count in ``errors`` (int32),
+    ``rounds`` (int32, optional) receives the pointer-jump rounds that had work."""
+    _check(load().afhip_inflate_decode(comp.data_ptr(), int(comp_bytes), streams.data_ptr(), plan.n_streams,
+                                       shuf.data_ptr() if plan.n_shuf else None, plan.n_shuf, plan.max_bsize, plan.n_pblocks, plan.n_seqs,
+                                       plan.n_pieces, plan.dec_bytes, plan.tmp_bytes, scratch.data_ptr(), scratch.numel(), out.data_ptr(),
+                                       errors.data_ptr(), rounds.data_ptr() if rounds is not None else None, _stream_ptr(comp)))
 
 
 def unshuffle_blocks(tmp, out, blocks, n_blocks: int, max_bsize: int):

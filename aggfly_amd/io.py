@@ -538,8 +538,8 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
             return _stream_chunks_scatter(za, device, threads, slab_bytes, post if need_post else None, out_np, t_range, yx_box), za
         if not whole_rows and za.native_kind is not None:
             return _stream_chunks_scatter(za, device, threads, slab_bytes, post if need_post else None, out_np), za
-        if za.native_kind in ("blosc", "zstd") and _gpu_decodable(za, T * ny * nx * za.dtype.itemsize):
-            # Blosc-LZ4 / Zstandard chunks cross PCIe compressed and are decoded in HBM: the scatter route, whatever the chunk grid
+        if (za.native_kind in ("blosc", "zstd") or _deflate_typesize(za.native_kind)) and _gpu_decodable(za, T * ny * nx * za.dtype.itemsize):
+            # Blosc-LZ4 / Zstandard / deflate chunks cross PCIe compressed and are decoded in HBM: the scatter route, whatever the chunk grid
             return _stream_chunks_scatter(za, device, threads, slab_bytes, post if need_post else None, out_np), za
         return stream_to_device(T, (ny, nx), za.dtype, read, slab, device, post if need_post else None, out_np), za
     finally:
@@ -550,6 +550,20 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
 GPU_DECODE_AUTO_BYTES = 96 << 20                  # requests this large take the decode-in-HBM route (round 2: 256 MB) ...
 GPU_DECODE_AUTO_BYTES_WHOLE_ROWS = 256 << 20      # ... also when every chunk holds whole time steps of the grid (round 2: 768 MB; see _gpu_decodable)
 GPU_DECODE_AUTO_BYTES_ZSTD = 100 << 20            # Zstandard stores: requests this large (any chunk grid; profiles/zstd_ingest.txt)
+# zlib / deflate chunks (netCDF-4, HDF5, Zarr v2 "zlib"): the smallest measured request from which the decode in HBM takes <= 0.9 x the
+# host route's time on all three layouts of profiles/deflate_ingest.txt.  None: measured 64 MiB ... 820 MiB, there is no such size — ahead
+# on 98 KB chunks at 256 / 512 MiB (0.85 / 0.57 x), 8-84 x behind on 2.4 MB and 9 MB chunks, whose few streams each keep one lane of the
+# front end busy for 0.4-1.4 s — so the route is opt-in (AGGFLY_HIP_GPU_DECODE=1)
+GPU_DECODE_AUTO_BYTES_DEFLATE = None
+
+
+def _deflate_typesize(kind):
+    """Element size of the byte unshuffle behind a deflate chunk kind — 1 for plain ``"zlib"``, n for ``("zlib", n)`` — else None."""
+    if kind == "zlib":
+        return 1
+    if isinstance(kind, tuple) and len(kind) == 2 and kind[0] == "zlib":
+        return int(kind[1])
+    return None
 
 
 def _gpu_decodable(za, request_bytes: int = 0) -> bool:
@@ -567,8 +581,13 @@ def _gpu_decodable(za, request_bytes: int = 0) -> bool:
     whole_rows = len(za.shape) == 3 and tuple(za.chunks[1:]) == tuple(za.shape[1:])
     # plain Zstandard frames (`hip.zstd_decode`): from `GPU_DECODE_AUTO_BYTES_ZSTD` on under auto, chunks below 1 GiB (a batch's bound)
     zstd = za.native_kind == "zstd"
-    auto_bytes = GPU_DECODE_AUTO_BYTES_ZSTD if zstd else (GPU_DECODE_AUTO_BYTES_WHOLE_ROWS if whole_rows else GPU_DECODE_AUTO_BYTES)
-    if mode == "0" or za.native_kind not in ("blosc", "zstd") or (mode != "1" and request_bytes < auto_bytes) or (zstd and za.chunk_nbytes >= 1 << 30):
+    # zlib streams (`hip.inflate_decode`; HDF5 / netCDF-4 deflate with or without shuffle, Zarr v2 "zlib"): from
+    # `GPU_DECODE_AUTO_BYTES_DEFLATE` on under auto — never while that is None —, chunks below 1 GiB; gzip members stay on the host
+    deflate = _deflate_typesize(za.native_kind) is not None
+    auto_bytes = (GPU_DECODE_AUTO_BYTES_DEFLATE if deflate else GPU_DECODE_AUTO_BYTES_ZSTD if zstd
+                  else (GPU_DECODE_AUTO_BYTES_WHOLE_ROWS if whole_rows else GPU_DECODE_AUTO_BYTES))
+    if (mode == "0" or not (deflate or za.native_kind in ("blosc", "zstd")) or (mode != "1" and (auto_bytes is None or request_bytes < auto_bytes))
+            or ((zstd or deflate) and za.chunk_nbytes >= 1 << 30)):
         return False
     hit = getattr(za, "_gpu_decodable", None)
     if hit is not None:
@@ -581,8 +600,10 @@ def _gpu_decodable(za, request_bytes: int = 0) -> bool:
                 continue
             with open(loc[0], "rb") as f:
                 f.seek(loc[1])
-                h = f.read(18 if zstd else 16)
-            if zstd:
+                h = f.read(2 if deflate else 18 if zstd else 16)
+            if deflate:
+                ok = _zlib_header_taken(h)
+            elif zstd:
                 ok = _zstd_frame_taken(h, za.chunk_nbytes)
             elif len(h) == 16 and h[0] == 2:
                 flags, ts = h[2], h[3]
@@ -615,6 +636,12 @@ def _zstd_frame_taken(h: bytes, nbytes: int) -> bool:
         return False
     fcs = int.from_bytes(h[pos:pos + fcs_size], "little") + (256 if fcs_size == 2 else 0)
     return fcs == nbytes
+
+
+def _zlib_header_taken(h: bytes) -> bool:
+    """The two header bytes of a zlib stream (RFC 1950) that `afcodec_inflate_plan` takes: deflate, a window of at most 32 KiB, a
+    valid check sum, no preset dictionary (a gzip member fails the first test)."""
+    return len(h) >= 2 and (h[0] & 15) == 8 and (h[0] >> 4) <= 7 and ((h[0] << 8) | h[1]) % 31 == 0 and not (h[1] & 0x20)
 
 
 class _ScatterJob:
@@ -917,9 +944,66 @@ class _ZstdRoute:
         hip.zstd_decode(comp, self.rec0, comp[self.rec0:], comp[self.bl0:], self.plan_, self.scratch[k], target, errors, self.rounds)
 
 
+class _DeflateRoute:
+    """The codec half of the decode-in-HBM route for zlib streams (HDF5 / netCDF-4 deflate chunks, Zarr v2 "zlib"): one stream
+    record per chunk and one shuffle record per shuffled chunk from `codec.inflate_plan`, `hip.inflate_decode` with a scratch per
+    slot (grown on the slot's stream when a batch needs more).  Batches decode at most 256 MiB: the scratch holds ~9 bytes per
+    decoded byte (literals, sequence records, the byte map), i.e. up to 2.3 GiB per staging slot and 9.2 GiB of HBM for a request of
+    four batches and more.  A chunk larger than a batch is a batch of its own (6 slots): 9 bytes per byte of the chunk in each,
+    54 GiB for chunks just below the 1 GiB the route takes."""
+
+    what = "zlib stream(s)"
+    rounds_key = "inflate_jump_rounds"
+
+    def __init__(self, job):
+        self.cb = job.cb
+        self.tsz = _deflate_typesize(job.za.native_kind)
+        self.nblk = 1
+        # large batches: the front end walks a stream from its first bit to its last on one lane, so a batch takes as long as its
+        # longest stream however many streams it holds — 36 ms for 98 KB, 400 ms for 2.4 MB (profiles/deflate_ingest.txt)
+        self.max_per = max(1, min(4096, (256 << 20) // job.cb))
+        self.target_bytes = self.max_bytes = 256 << 20
+
+    def size(self, per, nstage, device):
+        from . import codec
+        cb = self.cb
+        self.cmax = (cb + cb // 8 + 1024 + 63) // 64 * 64            # (deflate's worst case is stored blocks: 5 bytes per 64 KiB more)
+        self.cap = per
+        self.rec_bytes = (per * codec.INFLATE_STREAM.itemsize + 63) // 64 * 64 + per * codec.SHUFFLE_BLOCK.itemsize
+        self.device = device
+        self.scratch = [None] * nstage
+        self.rounds = None
+
+    def plan(self, k, hall, rec0, offs, sizes, present, out_offs):
+        from . import codec
+        streams = hall[rec0:rec0 + self.cap * codec.INFLATE_STREAM.itemsize].view(codec.INFLATE_STREAM)
+        sh0 = rec0 + (streams.nbytes + 63) // 64 * 64
+        shuf = hall[sh0:sh0 + self.cap * codec.SHUFFLE_BLOCK.itemsize].view(codec.SHUFFLE_BLOCK)
+        try:
+            pl = codec.inflate_plan(hall, offs[:-1][present], sizes[present], out_offs, np.full(len(present), self.cb, dtype=np.int64),
+                                    streams, shuf, typesize=self.tsz)
+        except codec.PlanCapacityError:
+            raise _NotForTheGpuRoute() from None
+        if (pl.results == codec.E_UNSUPPORTED).any():
+            raise _NotForTheGpuRoute()             # a preset dictionary, a gzip member: aggfly_codec.h's "decode it on the host"
+        self.plan_, self.rec0, self.sh0 = pl, rec0, sh0
+        return pl.results, [(0, rec0 + pl.n_streams * codec.INFLATE_STREAM.itemsize), (sh0, sh0 + pl.n_shuf * codec.SHUFFLE_BLOCK.itemsize)]
+
+    def decode(self, k, comp, target, errors):
+        import torch
+        from . import hip
+        need = hip.inflate_scratch_bytes(self.plan_)
+        if self.scratch[k] is None or self.scratch[k].numel() < need:
+            self.scratch[k] = None
+            self.scratch[k] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if self.rounds is None and os.environ.get("AGGFLY_HIP_INGEST_TRACE") == "1":
+            self.rounds = torch.zeros(1, dtype=torch.int32, device=self.device)
+        hip.inflate_decode(comp, self.rec0, comp[self.rec0:], comp[self.sh0:], self.plan_, self.scratch[k], target, errors, self.rounds)
+
+
 def _scatter_gpu_decode(job: _ScatterJob, threads: int, post):
-    """Blosc-LZ4 chunks or Zstandard frames cross PCIe compressed: per batch the host reads the chunk files as
-    they are into a page-locked slot and walks their headers into the codec's record lists (`_Lz4Route`, `_ZstdRoute`); one
+    """Blosc-LZ4 chunks, Zstandard frames or zlib streams cross PCIe compressed: per batch the host reads the chunk files as
+    they are into a page-locked slot and walks their headers into the codec's record lists (`_Lz4Route`, `_ZstdRoute`, `_DeflateRoute`); one
     upload carries the compressed bytes and the records; the codec's kernels decode on the slot's stream — straight into the
     cube when every chunk of the batch holds whole time steps of the window, else into a staging buffer that `job.place`
     empties.  The page-locked slot is free again when its upload is over; the device-side one is handed from the kernels to
@@ -927,7 +1011,8 @@ def _scatter_gpu_decode(job: _ScatterJob, threads: int, post):
     import torch
     from . import codec
     za, device, cb, idxs, cube = job.za, job.device, job.cb, job.idxs, job.cube
-    route = _ZstdRoute(job) if za.native_kind == "zstd" else _Lz4Route(job)
+    route = (_ZstdRoute(job) if za.native_kind == "zstd" else _DeflateRoute(job) if _deflate_typesize(za.native_kind) is not None
+             else _Lz4Route(job))
     cuts, per, n_tail = _decode_batches(len(idxs), cb, route.nblk, job.whole_steps, route.max_per, route.target_bytes, route.max_bytes)
     all_idxs, idxs = idxs, idxs[:len(idxs) - n_tail]
     # staging slots in flight: 4 (3 measured 7 % slower), 6 when every batch is one big chunk (the converter's 265 MB chunks)
@@ -996,7 +1081,7 @@ def _scatter_gpu_decode(job: _ScatterJob, threads: int, post):
     last.synchronize()
     copy_stream.synchronize()
     trace.drained()
-    extra = {"zstd_jump_rounds": int(route.rounds.item())} if getattr(route, "rounds", None) is not None else {}
+    extra = {getattr(route, "rounds_key", "zstd_jump_rounds"): int(route.rounds.item())} if getattr(route, "rounds", None) is not None else {}
     trace.report(origin, gpu_decode=True, batches=len(cuts) - 1, chunks_per_batch=per, **extra)
     if int(errors.item()):
         raise codec.CodecError(f"{int(errors.item())} {route.what} of {za.path} are malformed (GPU decode); "

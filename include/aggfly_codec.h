@@ -76,6 +76,29 @@ int afcodec_zstd_emulate(const void* comp, int64_t comp_bytes, const void* frame
                          int64_t n_blocks, int64_t lit_bytes, int64_t n_seqs, int64_t dec_bytes, void* scratch, void* out,
                          int32_t* errors, int32_t* rounds);
 
+/* Plan of a GPU-side zlib decode (libaggfly_hip: afhip_inflate_decode, include/aggfly_hip.h): n chunks that are one zlib stream
+ * each — chunk i = comp_size[i] bytes at base + comp_off[i], decoded to offset out_off[i] of the output (out_size[i] bytes),
+ * byte-unshuffled there when typesize[i] > 1 (HDF5's shuffle filter before deflate; typesize NULL: no chunk is) — have their two header bytes checked (CM, CINFO,
+ * the FCHECK sum) into one afhip_inflate_stream record per chunk: the source range, the destination (the output, or the shuffle
+ * scratch with one afhip_shuffle_block record: bsize = the chunk, typesize[i]), the expected size, and the stream's place in the
+ * batch's buffers (*n_pblocks pseudo-block slots, *n_seqs sequence records, *n_pieces Adler-32 pieces, *dec_bytes decoded bytes,
+ * *tmp_bytes of shuffle scratch).  results[i] = out_size[i], or < 0: AFCODEC_E_UNSUPPORTED marks a chunk the GPU route does not
+ * take (a preset dictionary — FDICT —, a gzip member, 1 GiB or more) — decode it on the host; other header bytes give
+ * AFCODEC_E_FORMAT; neither leaves a record.  Every record lies inside its chunk, the batch's buffers and the destination.
+ * Nothing is decoded here. */
+int afcodec_inflate_plan(const void* base, int64_t n, const int64_t* comp_off, const int64_t* comp_size, const int64_t* out_off,
+                         const int64_t* out_size, const int32_t* typesize, void* streams, int64_t cap_streams, int64_t* n_streams, void* shuf,
+                         int64_t cap_shuf, int64_t* n_shuf, int64_t* n_pblocks, int64_t* n_seqs, int64_t* n_pieces, int64_t* dec_bytes,
+                         int64_t* tmp_bytes, int64_t* results);
+/* Scratch of one batch (== afhip_inflate_scratch_bytes). */
+int64_t afcodec_inflate_scratch_bytes(int64_t n_streams, int64_t n_pblocks, int64_t n_seqs, int64_t n_pieces, int64_t dec_bytes,
+                                      int64_t tmp_bytes);
+/* The passes of afhip_inflate_decode run in order on the calling thread (host reference of the GPU algorithm, for tests): the
+ * same arguments with host pointers; *errors = damaged streams, *rounds = pointer-jump rounds that had work. */
+int afcodec_inflate_emulate(const void* comp, int64_t comp_bytes, const void* streams, int64_t n_streams, const void* shuf,
+                            int64_t n_shuf, int64_t n_pblocks, int64_t n_seqs, int64_t n_pieces, int64_t dec_bytes, int64_t tmp_bytes,
+                            void* scratch, void* out, int32_t* errors, int32_t* rounds);
+
 /* Chunk files of one codec kind (0 raw, 1 Blosc-1, 2 Zstandard frame, 3 zlib or gzip stream, 4 numcodecs LZ4;
  * kind + 16 * element_size adds a byte-unshuffle after the codec: HDF5 / netCDF-4 shuffle + deflate chunks): read and
  * decoded paths[i] -> dsts[i], one chunk per OpenMP thread. */

@@ -209,6 +209,27 @@ int afhip_zstd_decode(const void* comp_dev, int64_t comp_bytes, const afhip_zstd
                       const afhip_zstd_block* blocks_dev, int64_t n_blocks, int64_t lit_bytes, int64_t n_seqs, int64_t dec_bytes,
                       void* scratch_dev, int64_t scratch_bytes, void* out_dev, int32_t* errors_dev, int32_t* rounds_dev, void* stream);
 
+/* zlib streams (RFC 1950 around RFC 1951 deflate) decoded in HBM: HDF5 / netCDF-4 [deflate] and [shuffle, deflate] chunks, Zarr v2
+ * compressor "zlib".  The host reads only the two header bytes of a chunk (afcodec_inflate_plan, include/aggfly_codec.h) into one
+ * record per stream; the blocks are walked, the Huffman tables built, the LZ77 matches resolved and the Adler-32 verified on the GPU,
+ * in launch-ordered passes (aggfly_amd/csrc/inflate_passes.h), and the n_shuf chunks written with HDF5's shuffle filter are then
+ * byte-unshuffled from the scratch into out_dev (max_bsize: the largest of them).  Stream s's dsize bytes go to out_dev + dst_off
+ * (to_out) or to the scratch.  scratch_dev: afhip_inflate_scratch_bytes(...) bytes, caller-owned (~9 bytes per decoded byte + 5.25 KiB
+ * per stream).  A damaged stream — malformed, of another size than planned, or failing its Adler-32 — writes nothing outside its own
+ * destination and the scratch, and adds 1 to *errors_dev; rounds_dev (may be NULL) receives the number of pointer-jump rounds that
+ * had work.  Not taken (the planner marks them for the host): gzip members, preset dictionaries, chunks of 1 GiB and more.
+ * Nothing allocates or synchronises; all pointers are device memory. */
+typedef struct afhip_inflate_stream {
+    int64_t src, dst_off, base, seq_off;
+    int32_t csize, dsize, to_out, first_block, n_blocks, first_piece;
+} afhip_inflate_stream;
+int64_t afhip_inflate_scratch_bytes(int64_t n_streams, int64_t n_pblocks, int64_t n_seqs, int64_t n_pieces, int64_t dec_bytes,
+                                    int64_t tmp_bytes);
+int afhip_inflate_decode(const void* comp_dev, int64_t comp_bytes, const afhip_inflate_stream* streams_dev, int64_t n_streams,
+                         const afhip_shuffle_block* shuf_dev, int64_t n_shuf, int32_t max_bsize, int64_t n_pblocks, int64_t n_seqs,
+                         int64_t n_pieces, int64_t dec_bytes, int64_t tmp_bytes, void* scratch_dev, int64_t scratch_bytes, void* out_dev,
+                         int32_t* errors_dev, int32_t* rounds_dev, void* stream);
+
 /* Replaces the body of SpatialAggregator.compute (spatial.py:110-133) for K names:
  * shared validity (all K non-NaN), den = W.valid, num_k = W.where(valid, x_k, 0),
  * res = num/den where den != 0 else NaN.
