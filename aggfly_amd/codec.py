@@ -1,6 +1,7 @@
 """ctypes binding of ``libaggfly_codec.so`` (aggfly_amd/csrc/blosc1.c): the host-side chunk codecs
 of the ingestion path — Blosc-1 containers (blosclz / lz4 / lz4hc / zlib / zstd, byte- and
-bit-shuffle), plain Zstandard frames, and a Blosc-LZ4 encoder for the writer side.
+bit-shuffle), plain Zstandard frames, the planners of the decode-in-HBM routes, and a Blosc-1 encoder (LZ4 / Zstandard) for the writer
+side.
 
 The reference decodes chunks through numcodecs inside its dask graph
 (`aggfly/dataset/dataset.py:697-728`); here every chunk is decoded by native code on a host thread
@@ -51,6 +52,8 @@ def load():
         lib.afcodec_blosc_bound.argtypes = [C.c_int64, C.c_int64]
         lib.afcodec_blosc_encode_lz4.restype = C.c_int64
         lib.afcodec_blosc_encode_lz4.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64]
+        lib.afcodec_blosc_encode.restype = C.c_int64
+        lib.afcodec_blosc_encode.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64]
         lib.afcodec_lz4_decode.restype = C.c_int64
         lib.afcodec_lz4_decode.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
         lib.afcodec_zstd_decode.restype = C.c_int64
@@ -62,6 +65,8 @@ def load():
         lib.afcodec_blosc_lz4_plan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                                C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                C.POINTER(C.c_int32), C.c_void_p]
+        lib.afcodec_blosc_plan.argtypes = ([C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_void_p, C.c_int64, C.POINTER(C.c_int64)] * 5
+                                           + [C.POINTER(C.c_int64)] * 4 + [C.POINTER(C.c_int32), C.c_void_p])
         lib.afcodec_zstd_plan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]
@@ -85,7 +90,8 @@ EXPORTS = ("afcodec_last_error", "afcodec_have", "afcodec_blosc_info", "afcodec_
            "afcodec_blosc_decode_files", "afcodec_decode_files", "afcodec_decode_ranges",
            "afcodec_blosc_bound", "afcodec_blosc_encode_lz4", "afcodec_zstd_decode", "afcodec_zstd_bound", "afcodec_zstd_encode", "afcodec_lz4_decode", "afcodec_blosc_lz4_plan", "afcodec_read_packed",
            "afcodec_zstd_plan", "afcodec_zstd_scratch_bytes", "afcodec_zstd_emulate",
-           "afcodec_inflate_plan", "afcodec_inflate_scratch_bytes", "afcodec_inflate_emulate")
+           "afcodec_inflate_plan", "afcodec_inflate_scratch_bytes", "afcodec_inflate_emulate",
+           "afcodec_blosc_plan", "afcodec_blosc_encode")
 
 
 def _err(lib, what):
@@ -222,13 +228,19 @@ def blosc_decode_files(paths, outs, threads: int = 8):
     return decode_files("blosc", paths, outs, threads)
 
 
-def blosc_encode(data, typesize: int, shuffle: bool = True, blocksize: int = 0) -> bytes:
-    """Blosc-1 / LZ4 chunk of ``data`` (bytes-like or array): what numcodecs' ``Blosc(cname="lz4")`` reads."""
+BLOSC_CNAME = {"lz4": 1, "zstd": 4}
+
+
+def blosc_encode(data, typesize: int, shuffle: bool = True, blocksize: int = 0, cname: str = "lz4", bitshuffle: bool = False,
+                 level: int = 3) -> bytes:
+    """Blosc-1 chunk of ``data`` (bytes-like or array) with LZ4 or Zstandard (``cname``, ``level``: libzstd's) streams: what
+    numcodecs' ``Blosc(cname=...)`` reads.  ``bitshuffle``: Blosc's bit shuffle (``shuffle=2``) in place of the byte shuffle."""
     lib = load()
     arr = np.ascontiguousarray(data) if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), dtype=np.uint8)
     cap = lib.afcodec_blosc_bound(arr.nbytes, blocksize)
     dst = np.empty(cap, dtype=np.uint8)
-    r = lib.afcodec_blosc_encode_lz4(arr.ctypes.data, arr.nbytes, int(typesize), 1 if shuffle else 0, int(blocksize), dst.ctypes.data, cap)
+    r = lib.afcodec_blosc_encode(arr.ctypes.data, arr.nbytes, int(typesize), 2 if bitshuffle else (1 if shuffle else 0), BLOSC_CNAME[cname],
+                                 int(level), int(blocksize), dst.ctypes.data, cap)
     if r < 0:
         raise _err(lib, "blosc_encode")
     return dst[:r].tobytes()
@@ -356,6 +368,53 @@ def zstd_emulate(base: np.ndarray, frames: np.ndarray, blocks: np.ndarray, plan:
                              plan.lit_bytes, plan.n_seqs, plan.dec_bytes, scratch.ctypes.data, out.ctypes.data, C.byref(err),
                              C.byref(rounds))
     return int(err.value), int(rounds.value)
+
+
+class BloscPlan:
+    """What `blosc_plan` found in a batch: the record counts of its five lists, the shuffle scratch, and — for `hip.zstd_decode`,
+    which reads the same attributes of a `ZstdPlan` — the Zstandard totals (``n_blocks`` counts Zstandard blocks)."""
+
+    def __init__(self, n_streams, n_shuf, n_bits, n_frames, n_blocks, lit_bytes, n_seqs, dec_bytes, tmp_bytes, max_dsize, max_shuf, max_bits,
+                 results):
+        self.n_streams, self.n_shuf, self.n_bits, self.n_frames, self.n_blocks = n_streams, n_shuf, n_bits, n_frames, n_blocks
+        self.lit_bytes, self.n_seqs, self.dec_bytes, self.tmp_bytes, self.max_dsize = lit_bytes, n_seqs, dec_bytes, tmp_bytes, max_dsize
+        self.max_shuf, self.max_bits, self.results = max_shuf, max_bits, results
+
+    def scratch_bytes(self) -> int:
+        return int(load().afcodec_zstd_scratch_bytes(self.n_blocks, self.n_frames, self.lit_bytes, self.n_seqs, self.dec_bytes))
+
+
+def blosc_plan(base: np.ndarray, comp_off, comp_size, out_off, out_size, streams: np.ndarray, shuf: np.ndarray, bits: np.ndarray,
+               frames: np.ndarray, zblocks: np.ndarray, strict: bool = True):
+    """Plan the GPU-side decode of Blosc-1 chunks of any flavour the GPU takes — LZ4 / LZ4HC or Zstandard inside, shuffle none,
+    byte or bit — that sit in ``base`` (uint8; chunk i = ``comp_size[i]`` bytes at ``comp_off[i]``): fills ``streams`` (`LZ4_STREAM`)
+    for `hip.lz4_decode_streams`, ``frames`` / ``zblocks`` (`ZSTD_FRAME` / `ZSTD_BLOCK`) for `hip.zstd_decode` INTO THE SCRATCH,
+    ``shuf`` and ``bits`` (`SHUFFLE_BLOCK`) for `hip.unshuffle_blocks` / `hip.bitunshuffle_blocks`.  -> `BloscPlan`;
+    ``results[i]`` = decoded size, or `E_UNSUPPORTED` for a chunk the GPU route does not take (blosclz / zlib / snappy inside, a
+    Zstandard frame `zstd_plan` would refuse: decode it on the host); malformed containers raise `CodecError` (``strict=False``:
+    they are only marked negative in ``results``)."""
+    lib = load()
+    n = len(comp_off)
+    co, cs, oo, osz = (np.ascontiguousarray(a, dtype=np.int64) for a in (comp_off, comp_size, out_off, out_size))
+    res = np.zeros(n, dtype=np.int64)
+    ns, nsh, nbt, nf, nzb, lit, nsq, dec, tmp = (C.c_int64(0) for _ in range(9))
+    maxd = C.c_int32(0)
+    assert streams.dtype == LZ4_STREAM and shuf.dtype == SHUFFLE_BLOCK and bits.dtype == SHUFFLE_BLOCK and base.dtype == np.uint8
+    assert frames.dtype == ZSTD_FRAME and zblocks.dtype == ZSTD_BLOCK
+    rc = lib.afcodec_blosc_plan(base.ctypes.data, n, co.ctypes.data, cs.ctypes.data, oo.ctypes.data, osz.ctypes.data,
+                                streams.ctypes.data, len(streams), C.byref(ns), shuf.ctypes.data, len(shuf), C.byref(nsh),
+                                bits.ctypes.data, len(bits), C.byref(nbt), frames.ctypes.data, len(frames), C.byref(nf),
+                                zblocks.ctypes.data, len(zblocks), C.byref(nzb), C.byref(lit), C.byref(nsq), C.byref(dec), C.byref(tmp),
+                                C.byref(maxd), res.ctypes.data)
+    bad = [int(i) for i in np.nonzero((res < 0) & (res != E_UNSUPPORTED))[0]]
+    if rc and not bad and "list too small" in lib.afcodec_last_error().decode():
+        raise PlanCapacityError(f"blosc_plan: {lib.afcodec_last_error().decode()}")
+    if strict and bad:
+        raise CodecError(f"blosc_plan: chunks {bad[:8]} are malformed: {lib.afcodec_last_error().decode()}")
+    max_shuf = int(shuf["bsize"][:nsh.value].max()) if nsh.value else 0
+    max_bits = int(bits["bsize"][:nbt.value].max()) if nbt.value else 0
+    return BloscPlan(int(ns.value), int(nsh.value), int(nbt.value), int(nf.value), int(nzb.value), int(lit.value), int(nsq.value),
+                     int(dec.value), int(tmp.value), int(maxd.value), max_shuf, max_bits, res)
 
 
 # record layout shared with libaggfly_hip (include/aggfly_hip.h: afhip_inflate_stream; inflate_passes.h)

@@ -665,6 +665,20 @@ extern "C" int afhip_unshuffle_blocks(const void* tmp_dev, void* out_dev, const 
     return AFHIP_OK;
 }
 
+extern "C" int afhip_bitunshuffle_blocks(const void* tmp_dev, void* out_dev, const afhip_shuffle_block* blocks_dev, int64_t n_blocks,
+                                         int32_t max_bsize, void* stream) {
+    if (!tmp_dev || !out_dev || !blocks_dev || n_blocks < 0 || max_bsize < 0) return fail(AFHIP_E_INVALID, "bitunshuffle_blocks: bad arguments");
+    if (n_blocks == 0) return AFHIP_OK;
+    if (n_blocks > 65535) return fail(AFHIP_E_INVALID, "bitunshuffle_blocks: more than 65535 blocks in one call");
+    GUARD_DEVICE(pointer_device(out_dev));
+    // a lane takes 8 elements: one tile of 256 lanes per 8 KiB of 4-byte elements
+    const unsigned tiles = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)max_bsize / 32 + 255) / 256));
+    hipLaunchKernelGGL(k_bitunshuffle_blocks, dim3(tiles, (unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)tmp_dev,
+                       (uint8_t*)out_dev, (const ShufBlock*)blocks_dev);
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
 extern "C" int afhip_panel_divide(const double* num_dev, const double* den_dev, double* res_dev, int64_t K, int64_t R,
                                   int64_t P, void* stream) {
     if (!num_dev || !den_dev || !res_dev || K < 0 || R < 0 || P < 0) return fail(AFHIP_E_INVALID, "panel_divide: bad arguments");

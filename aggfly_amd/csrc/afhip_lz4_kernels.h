@@ -8,6 +8,8 @@
 //   k_lz4_streams_vec  one wave per LZ4 stream (a Blosc block, or one byte plane of a split block; any length), the output
 //                      written straight to its destination; see the comment at the kernel.
 //   k_unshuffle_blocks Blosc's byte shuffle undone per block: element i's byte j sits at plane j, position i.
+//   k_bitunshuffle_blocks  Blosc's bit shuffle undone per block (Blosc chunks of LZ4 or Zstandard streams under shuffle = 2; the
+//                      Zstandard streams are decoded by afhip_zstd_kernels.h into the same scratch: afcodec_blosc_plan).
 //
 // Two earlier kernels are in the history of this file (round 2): one that decoded inside a 64 KiB LDS ring (one or two waves
 // per CU: 4-5 GB/s of LZ4 output for the chip) and a scalar, sequence-by-sequence LDS-free one (~2,000 mostly scalar
@@ -420,6 +422,92 @@ __global__ __launch_bounds__(256) void k_unshuffle_blocks(const uint8_t* __restr
     }
     const int rem = b.bsize % ts;
     if (blockIdx.x == 0 && (int)threadIdx.x < rem) dst[b.bsize - rem + threadIdx.x] = src[b.bsize - rem + threadIdx.x];
+}
+
+// Blosc's bit shuffle undone (unshuffle_bits in blosc1.c).  A block of n = bsize / ts elements is stored as 8 * ts bit rows of n / 8
+// bytes: bit k of byte j of element e is bit (e % 8) of tmp[(8j + k) * (n / 8) + e / 8].  A block whose n is not a multiple of 8 was
+// left as it is by c-blosc and is copied; so are the bsize - n * ts trailing bytes.
+// grid = (tiles, blocks), like k_unshuffle_blocks; a lane takes a group of 8 elements: for each byte j of the element it reads one
+// byte of each of the 8 rows 8j .. 8j + 7 — adjacent lanes adjacent bytes, so a wave's row read is 64 contiguous bytes —, transposes
+// the 8 x 8 bit matrix in a register pair (three masked swaps, Hacker's Delight 7-3, as the host does) and holds byte j of its 8
+// elements.  The lane then writes whole elements: 8 * ts contiguous bytes (32 for f32, a wave 2 KiB in a row) with 16-byte
+// stores where the destination is 16-byte aligned, narrower ones down to the element size, else bytes.  A wave step is 512
+// elements.  No LDS.
+__device__ __forceinline__ uint64_t bit_transpose8(uint64_t x) {
+    uint64_t t;
+    t = (x ^ (x >> 7)) & 0x00AA00AA00AA00AAull;  x = x ^ t ^ (t << 7);
+    t = (x ^ (x >> 14)) & 0x0000CCCC0000CCCCull; x = x ^ t ^ (t << 14);
+    t = (x ^ (x >> 28)) & 0x00000000F0F0F0F0ull; x = x ^ t ^ (t << 28);
+    return x;
+}
+// byte m of the result = byte j of element 8g + m
+__device__ __forceinline__ uint64_t bit_rows8(const uint8_t* __restrict__ src, int64_t nrow, int j, int64_t g) {
+    uint64_t x = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x |= (uint64_t)src[((int64_t)j * 8 + k) * nrow + g] << (8 * k);
+    return bit_transpose8(x);
+}
+// TS = 1, 2, 4, 8: the 8 elements of group g assembled in registers and stored as words of W bytes (W = 16, or the element size ... 1)
+template <int TS>
+__device__ __forceinline__ void bit_group(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int64_t nrow, int64_t g, int align) {
+    uint64_t x[TS];
+#pragma unroll
+    for (int j = 0; j < TS; ++j) x[j] = bit_rows8(src, nrow, j, g);
+    uint32_t w[2 * TS];                                            // the 8 * TS output bytes, little-endian dwords
+#pragma unroll
+    for (int q = 0; q < 2 * TS; ++q) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int o = 4 * q + r;                               // output byte o = byte (o % TS) of element (o / TS)
+            v |= (uint32_t)((x[o % TS] >> (8 * (o / TS))) & 0xff) << (8 * r);
+        }
+        w[q] = v;
+    }
+    uint8_t* o = dst + g * (8 * TS);
+    if (TS >= 2 && (align & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < 2 * TS; q += 4) *(uint4*)(o + 4 * q) = make_uint4(w[q], w[q + 1], w[q + 2], w[q + 3]);
+    } else if ((align & 7) == 0) {
+#pragma unroll
+        for (int q = 0; q < 2 * TS; q += 2) *(uint2*)(o + 4 * q) = make_uint2(w[q], w[q + 1]);
+    } else if ((align & 3) == 0) {
+#pragma unroll
+        for (int q = 0; q < 2 * TS; ++q) *(uint32_t*)(o + 4 * q) = w[q];
+    } else {
+#pragma unroll
+        for (int q = 0; q < 2 * TS; ++q) { o[4 * q] = (uint8_t)w[q]; o[4 * q + 1] = (uint8_t)(w[q] >> 8); o[4 * q + 2] = (uint8_t)(w[q] >> 16); o[4 * q + 3] = (uint8_t)(w[q] >> 24); }
+    }
+}
+__global__ __launch_bounds__(256) void k_bitunshuffle_blocks(const uint8_t* __restrict__ tmp, uint8_t* __restrict__ out,
+                                                             const ShufBlock* __restrict__ blocks) {
+    const ShufBlock b = blocks[blockIdx.y];
+    const int ts = b.typesize;
+    const int64_t n = b.bsize / ts;
+    const uint8_t* __restrict__ src = tmp + b.tmp_off;
+    uint8_t* __restrict__ dst = out + b.out_off;
+    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    if (n % 8 != 0) {                                              // not shuffled: a copy
+        for (int64_t i = first; i < b.bsize; i += step) dst[i] = src[i];
+        return;
+    }
+    const int64_t nrow = n / 8;
+    const int align = (int)((uintptr_t)dst & 15);                  // (a group is 8 * ts bytes: the block's alignment is every group's, for ts 2, 4, 8)
+    for (int64_t g = first; g < nrow; g += step) {
+        if (ts == 4) bit_group<4>(src, dst, nrow, g, align);
+        else if (ts == 8) bit_group<8>(src, dst, nrow, g, align);
+        else if (ts == 2) bit_group<2>(src, dst, nrow, g, align);
+        else if (ts == 1) bit_group<1>(src, dst, nrow, g, align | (int)((g * 8) & 15));
+        else {
+            for (int j = 0; j < ts; ++j) {
+                const uint64_t x = bit_rows8(src, nrow, j, g);
+#pragma unroll
+                for (int m = 0; m < 8; ++m) dst[(g * 8 + m) * ts + j] = (uint8_t)(x >> (8 * m));
+            }
+        }
+    }
+    const int rem = b.bsize - (int)(n * ts);
+    if (blockIdx.x == 0 && (int)threadIdx.x < rem) dst[n * ts + threadIdx.x] = src[n * ts + threadIdx.x];
 }
 
 }  // namespace afhip

@@ -237,6 +237,25 @@ static void unshuffle_bits(int ts, int64_t bsize, const uint8_t* src, uint8_t* d
     if (bsize > off) memcpy(dst + off, src + off, (size_t)(bsize - off));
 }
 
+/* the inverse (writer side): the same rule for blocks that do not hold a multiple of 8 elements */
+static void shuffle_bits(int ts, int64_t bsize, const uint8_t* src, uint8_t* dst) {
+    const int64_t n = bsize / ts;
+    if (n % 8 != 0) { memcpy(dst, src, (size_t)bsize); return; }
+    const int64_t nrow = n / 8;
+    for (int64_t g = 0; g < nrow; ++g) {
+        for (int j = 0; j < ts; ++j) {
+            uint64_t x = 0, t;                              /* byte m of x = byte j of element 8g + m */
+            for (int m = 0; m < 8; ++m) x |= (uint64_t)src[(g * 8 + m) * ts + j] << (8 * m);
+            t = (x ^ (x >> 7)) & 0x00AA00AA00AA00AAULL;  x = x ^ t ^ (t << 7);
+            t = (x ^ (x >> 14)) & 0x0000CCCC0000CCCCULL; x = x ^ t ^ (t << 14);
+            t = (x ^ (x >> 28)) & 0x00000000F0F0F0F0ULL; x = x ^ t ^ (t << 28);
+            for (int k2 = 0; k2 < 8; ++k2) dst[((int64_t)j * 8 + k2) * nrow + g] = (uint8_t)(x >> (8 * k2));
+        }
+    }
+    const int64_t off = n * ts;
+    if (bsize > off) memcpy(dst + off, src + off, (size_t)(bsize - off));
+}
+
 int64_t afcodec_zstd_decode(const void* src, int64_t n, void* dst, int64_t cap);
 int64_t afcodec_blosc_decode(const void* chunk, int64_t csize, void* dstv, int64_t dstsize);
 
@@ -347,20 +366,29 @@ static int blosc_block(const blosc_ctx* x, int64_t b) {
     return AFCODEC_OK;
 }
 
-/* ---- plan of a GPU-side decode (include/aggfly_codec.h: afcodec_blosc_lz4_plan) ----
- * Parses the containers of n chunks and lists, for the kernels of libaggfly_hip (afhip_lz4_decode_streams,
- * afhip_unshuffle_blocks), every LZ4 stream with its place in the compressed bytes and in the output, and every block whose
- * byte shuffle has to be undone.  Nothing is decoded here. */
+#include "zstd_passes.h"
+typedef struct { afz_frame* frames; int64_t cap_frames, nf; afz_block* blocks; int64_t cap_blocks, nb, lit, nsq, dec; } zstd_lists;
+static int zstd_plan_frames(zstd_lists* z, const void* base, int64_t n, const int64_t* comp_off, const int64_t* comp_size, const int64_t* out_off,
+                            const int64_t* out_size, int64_t* results);
+
+/* ---- plan of a GPU-side Blosc decode (include/aggfly_codec.h: afcodec_blosc_plan, afcodec_blosc_lz4_plan) ----
+ * ONE walk of the containers of n chunks lists, for the kernels of libaggfly_hip, every LZ4 stream and every plain copy
+ * (afhip_lz4_decode_streams), every Zstandard frame with its blocks (afhip_zstd_decode, through zstd_plan_frames below) and every
+ * block whose byte shuffle (afhip_unshuffle_blocks) or bit shuffle (afhip_bitunshuffle_blocks) has to be undone.  Layout: every
+ * Zstandard frame and every stream of a shuffled block decodes into the shuffle scratch (tmp), and the block then moves tmp ->
+ * out through one of the two unshuffle lists — an unshuffled Zstandard block as a byte-shuffle record of typesize 1, which is a
+ * copy — so that one afhip_zstd_decode call with out = tmp serves a batch of any mix of flavours.  Unshuffled LZ4 streams go
+ * straight to the output, as they always have.  Nothing is decoded here.
+ * z == NULL is afcodec_blosc_lz4_plan's filter: Zstandard and bit-shuffled chunks are then E_UNSUPPORTED like the other codecs. */
 typedef struct { int64_t src_off, dst_off; int32_t csize, dsize, to_out, pad; } lz4_stream_t;
 typedef struct { int64_t tmp_off, out_off; int32_t bsize, typesize; } shuf_block_t;
 #define GPU_STREAM_MAX 65536
 
-int afcodec_blosc_lz4_plan(const void* base, int64_t n, const int64_t* comp_off, const int64_t* comp_size, const int64_t* out_off,
-                           const int64_t* out_size, void* streams_v, int64_t cap_streams, int64_t* n_streams, void* blocks_v,
-                           int64_t cap_blocks, int64_t* n_blocks, int64_t* tmp_bytes, int32_t* max_dsize, int64_t* results) {
-    lz4_stream_t* streams = (lz4_stream_t*)streams_v;
-    shuf_block_t* blocks = (shuf_block_t*)blocks_v;
-    int64_t ns = 0, nb = 0, tmp = 0;
+static int blosc_walk(const void* base, int64_t n, const int64_t* comp_off, const int64_t* comp_size, const int64_t* out_off,
+                      const int64_t* out_size, lz4_stream_t* streams, int64_t cap_streams, int64_t* n_streams, shuf_block_t* blocks,
+                      int64_t cap_blocks, int64_t* n_blocks, shuf_block_t* bits, int64_t cap_bits, int64_t* n_bits, zstd_lists* z,
+                      int64_t* tmp_bytes, int32_t* max_dsize, int64_t* results) {
+    int64_t ns = 0, nb = 0, nbit = 0, tmp = 0;
     int32_t maxd = 0;
     int rc_all = AFCODEC_OK;
     for (int64_t i = 0; i < n; ++i) {
@@ -384,25 +412,36 @@ int afcodec_blosc_lz4_plan(const void* base, int64_t n, const int64_t* comp_off,
             continue;
         }
         const int codec = (flags >> 5) & 7;
-        if (codec != 1 || (flags & 0x04)) { results[i] = AFCODEC_E_UNSUPPORTED; rc_all = fail(AFCODEC_E_UNSUPPORTED, "not an LZ4 chunk with byte shuffle or none: decode on the host"); continue; }
+        if (!z && (codec != 1 || (flags & 0x04))) { results[i] = AFCODEC_E_UNSUPPORTED; rc_all = fail(AFCODEC_E_UNSUPPORTED, "not an LZ4 chunk with byte shuffle or none: decode on the host"); continue; }
+        if (codec != 1 && codec != 4) { results[i] = AFCODEC_E_UNSUPPORTED; rc_all = fail(AFCODEC_E_UNSUPPORTED, "inner codec is neither LZ4 nor Zstandard: decode on the host"); continue; }
         if (blocksize <= 0 || ts <= 0 || blocksize > nbytes) { results[i] = rc_all = fail(AFCODEC_E_FORMAT, "bad blocksize / typesize"); continue; }
         const int64_t nblocks = (nbytes + blocksize - 1) / blocksize, leftover = nbytes % blocksize;
         if (16 + 4 * nblocks > cbytes) { results[i] = rc_all = fail(AFCODEC_E_FORMAT, "block table beyond the chunk"); continue; }
         const int dont_split = (flags >> 4) & 1, want_shuffle = (flags & 0x01) && ts > 1;
-        const int64_t ns0 = ns, nb0 = nb, tmp0 = tmp;
+        const int64_t ns0 = ns, nb0 = nb, nbit0 = nbit, tmp0 = tmp;
+        zstd_lists z0;
+        if (z) z0 = *z;
         int bad = 0;
+        const char* why = "malformed block table or stream header";
         for (int64_t b = 0; b < nblocks && !bad; ++b) {
             const int last_short = (b == nblocks - 1) && leftover > 0;
             const int64_t bsize = last_short ? leftover : blocksize;
+            const int want_bits = !want_shuffle && (flags & 0x04) && bsize >= ts;
             int nsplits = 1;
             if (!dont_split && ts <= 16 && blocksize / ts >= 128 && !last_short) nsplits = ts;
             const int64_t neblock = bsize / nsplits;
             const int64_t start = (int64_t)(int32_t)le32(c + 16 + 4 * b);
             if (start < 16 + 4 * nblocks || start >= cbytes) { bad = AFCODEC_E_FORMAT; break; }
             int64_t dst_base;
-            if (want_shuffle) {
+            const int via_tmp = want_shuffle || want_bits || codec == 4;
+            if (want_bits) {
+                if (nbit >= cap_bits) return fail(AFCODEC_E_SIZE, "bit-shuffle block list too small");
+                bits[nbit++] = (shuf_block_t){tmp, out_off[i] + b * blocksize, (int32_t)bsize, ts};
+            } else if (via_tmp) {
                 if (nb >= cap_blocks) return fail(AFCODEC_E_SIZE, "block list too small");
-                blocks[nb++] = (shuf_block_t){tmp, out_off[i] + b * blocksize, (int32_t)bsize, ts};
+                blocks[nb++] = (shuf_block_t){tmp, out_off[i] + b * blocksize, (int32_t)bsize, want_shuffle ? ts : 1};
+            }
+            if (via_tmp) {
                 dst_base = tmp;
                 tmp += (bsize + 15) & ~(int64_t)15;
             } else {
@@ -413,21 +452,59 @@ int afcodec_blosc_lz4_plan(const void* base, int64_t n, const int64_t* comp_off,
                 if (src + 4 > c + cbytes) { bad = AFCODEC_E_FORMAT; break; }
                 const int32_t sz = (int32_t)le32(src);
                 src += 4;
-                if (sz < 0 || src + sz > c + cbytes || sz > neblock + neblock / 255 + 16) { bad = AFCODEC_E_FORMAT; break; }
-                if (ns >= cap_streams) return fail(AFCODEC_E_SIZE, "stream list too small");
-                streams[ns++] = (lz4_stream_t){comp_off[i] + (src - c), dst_base + j * neblock, sz, (int32_t)neblock, want_shuffle ? 0 : 1, 0};
-                if (neblock > maxd) maxd = (int32_t)neblock;
+                if (sz < 0 || src + sz > c + cbytes) { bad = AFCODEC_E_FORMAT; break; }
+                if (codec == 1) {
+                    if (sz > neblock + neblock / 255 + 16) { bad = AFCODEC_E_FORMAT; break; }
+                    if (ns >= cap_streams) return fail(AFCODEC_E_SIZE, "stream list too small");
+                    streams[ns++] = (lz4_stream_t){comp_off[i] + (src - c), dst_base + j * neblock, sz, (int32_t)neblock, via_tmp ? 0 : 1, 0};
+                    if (neblock > maxd) maxd = (int32_t)neblock;
+                } else if (sz == neblock) {                             /* stored stream of a Zstandard chunk (blocks of up to 1 MiB): 64 KiB per wave */
+                    for (int64_t o = 0; o < neblock; o += GPU_STREAM_MAX) {
+                        const int32_t len = (int32_t)((neblock - o) < GPU_STREAM_MAX ? (neblock - o) : GPU_STREAM_MAX);
+                        if (ns >= cap_streams) return fail(AFCODEC_E_SIZE, "stream list too small");
+                        streams[ns++] = (lz4_stream_t){comp_off[i] + (src - c) + o, dst_base + j * neblock + o, len, len, 0, 0};
+                    }
+                } else {
+                    const int64_t f_off = comp_off[i] + (src - c), f_size = sz, f_dst = dst_base + j * neblock;
+                    int64_t f_res = 0;
+                    const int zrc = zstd_plan_frames(z, base, 1, &f_off, &f_size, &f_dst, &neblock, &f_res);
+                    if (zrc == AFCODEC_E_SIZE) return zrc;                          /* a list is full: the caller's capacity, not the chunk */
+                    if (zrc) { bad = zrc; why = NULL; break; }                      /* (the frame walk has left its own message) */
+                }
                 src += sz;
             }
         }
         if (bad) {
-            ns = ns0; nb = nb0; tmp = tmp0;
+            ns = ns0; nb = nb0; nbit = nbit0; tmp = tmp0;
+            if (z) *z = z0;
             results[i] = bad;
-            rc_all = fail(bad, "malformed block table or stream header");
+            rc_all = why ? fail(bad, why) : bad;
         }
     }
     *n_streams = ns; *n_blocks = nb; *tmp_bytes = tmp; *max_dsize = maxd;
+    if (n_bits) *n_bits = nbit;
     return rc_all;
+}
+
+int afcodec_blosc_lz4_plan(const void* base, int64_t n, const int64_t* comp_off, const int64_t* comp_size, const int64_t* out_off,
+                           const int64_t* out_size, void* streams_v, int64_t cap_streams, int64_t* n_streams, void* blocks_v,
+                           int64_t cap_blocks, int64_t* n_blocks, int64_t* tmp_bytes, int32_t* max_dsize, int64_t* results) {
+    return blosc_walk(base, n, comp_off, comp_size, out_off, out_size, (lz4_stream_t*)streams_v, cap_streams, n_streams,
+                      (shuf_block_t*)blocks_v, cap_blocks, n_blocks, NULL, 0, NULL, NULL, tmp_bytes, max_dsize, results);
+}
+
+int afcodec_blosc_plan(const void* base, int64_t n, const int64_t* comp_off, const int64_t* comp_size, const int64_t* out_off,
+                       const int64_t* out_size, void* streams_v, int64_t cap_streams, int64_t* n_streams, void* blocks_v,
+                       int64_t cap_blocks, int64_t* n_blocks, void* bits_v, int64_t cap_bits, int64_t* n_bits, void* frames_v,
+                       int64_t cap_frames, int64_t* n_frames, void* zblocks_v, int64_t cap_zblocks, int64_t* n_zblocks, int64_t* lit_bytes,
+                       int64_t* n_seqs, int64_t* dec_bytes, int64_t* tmp_bytes, int32_t* max_dsize, int64_t* results) {
+    zstd_lists z = {(afz_frame*)frames_v, cap_frames, 0, (afz_block*)zblocks_v, cap_zblocks, 0, 0, 0, 0};
+    *n_frames = *n_zblocks = *lit_bytes = *n_seqs = *dec_bytes = 0;
+    const int rc = blosc_walk(base, n, comp_off, comp_size, out_off, out_size, (lz4_stream_t*)streams_v, cap_streams, n_streams,
+                              (shuf_block_t*)blocks_v, cap_blocks, n_blocks, (shuf_block_t*)bits_v, cap_bits, n_bits, &z, tmp_bytes,
+                              max_dsize, results);
+    *n_frames = z.nf; *n_zblocks = z.nb; *lit_bytes = z.lit; *n_seqs = z.nsq; *dec_bytes = z.dec;
+    return rc;
 }
 
 /* Decodes one chunk into dst (capacity dstsize); returns the number of bytes written or < 0. */
@@ -821,8 +898,8 @@ int afcodec_blosc_decode_files(int64_t n, const char* const* paths, void* const*
     return afcodec_decode_files(1, n, paths, dsts, dstsizes, nthreads, results);
 }
 
-/* Encoder for the writer side (dataset_to_zarr, synthetic stores of the ingestion benchmark):
- * LZ4, byte shuffle on request, blocks never split.  Readable by any Blosc-1 decoder. */
+/* Encoder for the writer side (dataset_to_zarr, synthetic stores of the ingestion benchmarks): LZ4 or Zstandard streams, byte or
+ * bit shuffle on request.  Readable by any Blosc-1 decoder. */
 int64_t afcodec_blosc_bound(int64_t nbytes, int64_t blocksize) {
     if (blocksize <= 0) blocksize = 1 << 16;                     /* the smallest automatic block */
     /* the encoder rounds the block size DOWN to whole elements (and clamps it to the buffer): it may need up to twice the
@@ -834,15 +911,25 @@ static int64_t blosc_need(int64_t nbytes, int64_t blocksize) {           /* exac
     const int64_t nblocks = (nbytes + blocksize - 1) / blocksize;
     return 16 + nblocks * (4 + 4 * 16) + nbytes + nbytes / 255 + 64;
 }
-int64_t afcodec_blosc_encode_lz4(const void* srcv, int64_t nbytes, int typesize, int shuffle, int64_t blocksize,
-                                 void* dstv, int64_t cap) {
+/* Blosc-1 writer: inner codec LZ4 (cname 1) or Zstandard (cname 4, through the system's libzstd at `level`), shuffle 0 none / 1 byte /
+ * 2 bit.  LZ4 chunks are laid out as before (and as c-blosc lays out shuffled ones): split blocks of 64 KiB per byte plane, one
+ * stream per plane — also under the bit shuffle, c-blosc's flags 0x24.  Zstandard chunks are what c-blosc 1.21 writes: unsplit
+ * blocks (flag 0x10), one frame per block behind its int32 length, 256 KiB blocks by default (its choice at clevel 5). */
+int64_t afcodec_blosc_encode(const void* srcv, int64_t nbytes, int typesize, int shuffle, int cname, int level, int64_t blocksize,
+                             void* dstv, int64_t cap) {
     const uint8_t* src = (const uint8_t*)srcv;
     uint8_t* dst = (uint8_t*)dstv;
-    int rc = need_lz4();
+    if (cname != 1 && cname != 4) return fail(AFCODEC_E_UNSUPPORTED, "blosc_encode writes LZ4 (1) or Zstandard (4) streams");
+    if (shuffle < 0 || shuffle > 2) return fail(AFCODEC_E_SIZE, "shuffle is 0 (none), 1 (byte) or 2 (bit)");
+    int rc = cname == 1 ? need_lz4() : need_zstd();
     if (rc) return rc;
+    if (cname == 4 && !p_zstd_enc) return fail(AFCODEC_E_UNSUPPORTED, "libzstd has no ZSTD_compress");
     if (nbytes < 0 || nbytes > 0x7fffffffLL - 64 || typesize < 1 || typesize > 255) return fail(AFCODEC_E_SIZE, "bad nbytes / typesize");
-    /* like c-blosc at level 5: 64 KiB per byte plane (blocks of 64 KiB x typesize, split into one LZ4 stream per plane) */
-    if (blocksize <= 0) { blocksize = (int64_t)65536 * (typesize <= 16 ? typesize : 1); if (blocksize > (1 << 20)) blocksize = 1 << 20; }
+    if (blocksize <= 0) {
+        /* LZ4, like c-blosc at level 5: 64 KiB per byte plane (blocks of 64 KiB x typesize, split into one stream per plane) */
+        if (cname == 1) { blocksize = (int64_t)65536 * (typesize <= 16 ? typesize : 1); if (blocksize > (1 << 20)) blocksize = 1 << 20; }
+        else blocksize = 256 << 10;
+    }
     blocksize -= blocksize % typesize;
     if (blocksize < typesize) blocksize = typesize;
     if (blocksize > nbytes && nbytes > 0) blocksize = nbytes;
@@ -851,11 +938,12 @@ int64_t afcodec_blosc_encode_lz4(const void* srcv, int64_t nbytes, int typesize,
      * block — a 1001-byte buffer of 4-byte elements used to lose its last byte */
     if (blocksize > typesize) blocksize -= blocksize % typesize;
     if (cap < blosc_need(nbytes, blocksize)) return fail(AFCODEC_E_SIZE, "destination smaller than afcodec_blosc_bound()");
-    const int do_shuf = shuffle && typesize > 1;
+    const int do_shuf = shuffle == 1 && typesize > 1, do_bits = shuffle == 2;
+    const int filter = do_shuf ? 0x01 : (do_bits ? 0x04 : 0);
     dst[0] = 2; dst[1] = 1; dst[3] = (uint8_t)typesize;
     put32(dst + 4, (uint32_t)nbytes);
     if (nbytes < 128) {                                      /* tiny buffers are stored */
-        dst[2] = 0x02 | (do_shuf ? 0x01 : 0) | (1 << 5) | 0x10;
+        dst[2] = (uint8_t)(0x02 | filter | (cname << 5) | 0x10);
         put32(dst + 8, (uint32_t)(nbytes ? nbytes : typesize));
         memcpy(dst + 16, src, (size_t)nbytes);
         put32(dst + 12, (uint32_t)(16 + nbytes));
@@ -863,25 +951,32 @@ int64_t afcodec_blosc_encode_lz4(const void* srcv, int64_t nbytes, int typesize,
     }
     /* split blocks (flag 0x10 clear), as c-blosc writes LZ4 chunks: a full block of a shuffled buffer is typesize
      * streams, one per byte plane; the short last block is one stream (the reader's rule in blosc_block) */
-    dst[2] = (uint8_t)((do_shuf ? 0x01 : 0) | (do_shuf ? 0 : 0x10) | (1 << 5));
+    const int split = cname == 1 && filter != 0;
+    dst[2] = (uint8_t)(filter | (split ? 0 : 0x10) | (cname << 5));
     put32(dst + 8, (uint32_t)blocksize);
     const int64_t nblocks = (nbytes + blocksize - 1) / blocksize;
     const int64_t leftover = nbytes % blocksize;
-    uint8_t* tmp = do_shuf ? (uint8_t*)malloc((size_t)blocksize) : NULL;
-    if (do_shuf && !tmp) return fail(AFCODEC_E_SIZE, "out of memory");
+    uint8_t* tmp = filter ? (uint8_t*)malloc((size_t)blocksize) : NULL;
+    if (filter && !tmp) return fail(AFCODEC_E_SIZE, "out of memory");
     int64_t pos = 16 + 4 * nblocks;
     for (int64_t b = 0; b < nblocks; ++b) {
         const int last_short = (b == nblocks - 1) && leftover > 0;
         const int64_t bsize = last_short ? leftover : blocksize;
         const uint8_t* in = src + b * blocksize;
         if (do_shuf) { shuffle_bytes(typesize, bsize, in, tmp); in = tmp; }
+        else if (do_bits && bsize >= typesize) { shuffle_bits(typesize, bsize, in, tmp); in = tmp; }
         put32(dst + 16 + 4 * b, (uint32_t)pos);
         int nsplits = 1;
-        if (do_shuf && typesize <= 16 && blocksize / typesize >= 128 && !last_short) nsplits = typesize;
+        if (split && typesize <= 16 && blocksize / typesize >= 128 && !last_short) nsplits = typesize;
         const int64_t ne = bsize / nsplits;
         for (int j = 0; j < nsplits; ++j) {
-            int csz = p_lz4_enc((const char*)in + j * ne, (char*)dst + pos + 4, (int)ne, (int)(ne - 1));   /* 0 if it does not shrink */
-            if (csz <= 0) { memcpy(dst + pos + 4, in + j * ne, (size_t)ne); csz = (int)ne; }
+            int64_t csz = 0;                                    /* stays 0 if the stream does not shrink */
+            if (cname == 1) csz = p_lz4_enc((const char*)in + j * ne, (char*)dst + pos + 4, (int)ne, (int)(ne - 1));
+            else if (ne > 1) {
+                const size_t got = p_zstd_enc(dst + pos + 4, (size_t)(ne - 1), in + j * ne, (size_t)ne, level);
+                csz = p_zstd_iserr(got) ? 0 : (int64_t)got;
+            }
+            if (csz <= 0) { memcpy(dst + pos + 4, in + j * ne, (size_t)ne); csz = ne; }
             put32(dst + pos, (uint32_t)csz);
             pos += 4 + csz;
         }
@@ -889,6 +984,10 @@ int64_t afcodec_blosc_encode_lz4(const void* srcv, int64_t nbytes, int typesize,
     free(tmp);
     put32(dst + 12, (uint32_t)pos);
     return pos;
+}
+
+int64_t afcodec_blosc_encode_lz4(const void* src, int64_t nbytes, int typesize, int shuffle, int64_t blocksize, void* dst, int64_t cap) {
+    return afcodec_blosc_encode(src, nbytes, typesize, shuffle ? 1 : 0, 1, 0, blocksize, dst, cap);
 }
 
 /* Plain Zstandard frames (Zarr compressor id "zstd"). */
@@ -918,7 +1017,6 @@ int64_t afcodec_zstd_encode(const void* src, int64_t n, int level, void* dst, in
  * Walks the frame header, the block headers and, in compressed blocks, the literals and sequences section headers (RFC
  * 8878 §3.1.1); of the entropy descriptions it reads only as much as gives their sizes (an FSE table description has to be
  * walked to find where the next one begins).  Building the tables and decoding is the GPU's (zstd_passes.h). */
-#include "zstd_passes.h"
 
 static int zstd_literals_header(const uint8_t* q, int64_t bs, afz_block* k) {
     if (bs < 1) return -1;
@@ -957,12 +1055,14 @@ static int zstd_literals_header(const uint8_t* q, int64_t bs, afz_block* k) {
     return (int)(hs + comp);
 }
 
-int afcodec_zstd_plan(const void* base, int64_t n, const int64_t* comp_off, const int64_t* comp_size, const int64_t* out_off,
-                      const int64_t* out_size, void* frames_v, int64_t cap_frames, int64_t* n_frames, void* blocks_v, int64_t cap_blocks,
-                      int64_t* n_blocks, int64_t* lit_bytes, int64_t* n_seqs, int64_t* dec_bytes, int64_t* results) {
-    afz_frame* frames = (afz_frame*)frames_v;
-    afz_block* blocks = (afz_block*)blocks_v;
-    int64_t nf = 0, nb = 0, lit = 0, nsq = 0, dec = 0;
+/* The walk itself, for afcodec_zstd_plan (all n frames of a batch) and for the Blosc walk (n = 1: the frame of one Blosc block):
+ * records are appended to the lists and totals of *z, which a frame that fails leaves as they were. */
+static int zstd_plan_frames(zstd_lists* z, const void* base, int64_t n, const int64_t* comp_off, const int64_t* comp_size, const int64_t* out_off,
+                            const int64_t* out_size, int64_t* results) {
+    afz_frame* frames = z->frames;
+    afz_block* blocks = z->blocks;
+    const int64_t cap_frames = z->cap_frames, cap_blocks = z->cap_blocks;
+    int64_t nf = z->nf, nb = z->nb, lit = z->lit, nsq = z->nsq, dec = z->dec;
     int rc_all = AFCODEC_OK;
     for (int64_t i = 0; i < n; ++i) {
         const uint8_t* c = (const uint8_t*)base + comp_off[i];
@@ -1079,8 +1179,17 @@ int afcodec_zstd_plan(const void* base, int64_t n, const int64_t* comp_off, cons
             rc_all = fail(bad, why);
         }
     }
-    *n_frames = nf; *n_blocks = nb; *lit_bytes = lit; *n_seqs = nsq; *dec_bytes = dec;
+    z->nf = nf; z->nb = nb; z->lit = lit; z->nsq = nsq; z->dec = dec;
     return rc_all;
+}
+
+int afcodec_zstd_plan(const void* base, int64_t n, const int64_t* comp_off, const int64_t* comp_size, const int64_t* out_off,
+                      const int64_t* out_size, void* frames_v, int64_t cap_frames, int64_t* n_frames, void* blocks_v, int64_t cap_blocks,
+                      int64_t* n_blocks, int64_t* lit_bytes, int64_t* n_seqs, int64_t* dec_bytes, int64_t* results) {
+    zstd_lists z = {(afz_frame*)frames_v, cap_frames, 0, (afz_block*)blocks_v, cap_blocks, 0, 0, 0, 0};
+    const int rc = zstd_plan_frames(&z, base, n, comp_off, comp_size, out_off, out_size, results);
+    *n_frames = z.nf; *n_blocks = z.nb; *lit_bytes = z.lit; *n_seqs = z.nsq; *dec_bytes = z.dec;
+    return rc;
 }
 
 int64_t afcodec_zstd_scratch_bytes(int64_t n_blocks, int64_t n_frames, int64_t lit_bytes, int64_t n_seqs, int64_t dec_bytes) {

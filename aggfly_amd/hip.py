@@ -35,7 +35,7 @@ EXPORTS = (
     "afhip_plan_create", "afhip_plan_destroy", "afhip_plan_workspace_bytes", "afhip_plan_run_workspace_bytes",
     "afhip_plan_describe", "afhip_plan_run_temporal", "afhip_plan_run",
     "afhip_plan_profile_begin", "afhip_plan_profile_end", "afhip_plan_bind_inter", "afhip_csr_device", "afhip_plan_device", "afhip_transform", "afhip_panel_divide", "afhip_lz4_decode_streams", "afhip_unshuffle_blocks", "afhip_read_probe",
-    "afhip_zstd_scratch_bytes", "afhip_zstd_decode", "afhip_inflate_scratch_bytes", "afhip_inflate_decode",
+    "afhip_zstd_scratch_bytes", "afhip_zstd_decode", "afhip_inflate_scratch_bytes", "afhip_inflate_decode", "afhip_bitunshuffle_blocks",
 )
 
 
@@ -113,6 +113,7 @@ def load():
     lib.afhip_panel_divide.argtypes = [vp, vp, vp, i64, i64, i64, vp]
     lib.afhip_lz4_decode_streams.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
     lib.afhip_unshuffle_blocks.argtypes = [vp, vp, vp, i64, i32, vp]
+    lib.afhip_bitunshuffle_blocks.argtypes = [vp, vp, vp, i64, i32, vp]
     lib.afhip_zstd_scratch_bytes.restype = i64
     lib.afhip_zstd_scratch_bytes.argtypes = [i64] * 5
     lib.afhip_zstd_decode.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, i64, vp, i64, vp, vp, vp, vp]
@@ -185,7 +186,7 @@ def lz4_decode_streams(comp, streams, n_streams: int, max_dsize: int, tmp, out, 
 
 
 def zstd_scratch_bytes(plan) -> int:
-    """`afhip_zstd_scratch_bytes` for a `codec.ZstdPlan`."""
+    """`afhip_zstd_scratch_bytes` for a `codec.ZstdPlan` (or the Zstandard part of a `codec.BloscPlan`)."""
     n = int(load().afhip_zstd_scratch_bytes(plan.n_blocks, plan.n_frames, plan.lit_bytes, plan.n_seqs, plan.dec_bytes))
     if n < 0:
         _check(n)
@@ -224,6 +225,12 @@ def inflate_decode(comp, comp_bytes: int, streams, shuf, plan, scratch, out, err
 def unshuffle_blocks(tmp, out, blocks, n_blocks: int, max_bsize: int):
     """`afhip_unshuffle_blocks`: Blosc's byte shuffle undone per block (records in the uint8 HBM tensor ``blocks``)."""
     _check(load().afhip_unshuffle_blocks(tmp.data_ptr(), out.data_ptr(), blocks.data_ptr(), int(n_blocks), int(max_bsize), _stream_ptr(out)))
+
+
+def bitunshuffle_blocks(tmp, out, blocks, n_blocks: int, max_bsize: int):
+    """`afhip_bitunshuffle_blocks`: Blosc's bit shuffle undone per block (records in the uint8 HBM tensor ``blocks``, the second
+    unshuffle list of `codec.blosc_plan`)."""
+    _check(load().afhip_bitunshuffle_blocks(tmp.data_ptr(), out.data_ptr(), blocks.data_ptr(), int(n_blocks), int(max_bsize), _stream_ptr(out)))
 
 
 def require_gpu():

@@ -555,6 +555,10 @@ GPU_DECODE_AUTO_BYTES_ZSTD = 100 << 20            # Zstandard stores: requests t
 # on 98 KB chunks at 256 / 512 MiB (0.85 / 0.57 x), 8-84 x behind on 2.4 MB and 9 MB chunks, whose few streams each keep one lane of the
 # front end busy for 0.4-1.4 s — so the route is opt-in (AGGFLY_HIP_GPU_DECODE=1)
 GPU_DECODE_AUTO_BYTES_DEFLATE = None
+# Blosc-1 chunks beyond LZ4 + byte shuffle (`_BloscRoute`): the same rule, on the three layouts of scripts/blosc_ingest_bench.py.  None: not
+# measured yet (profiles/blosc_flavours_ingest.txt), so both flavours are opt-in (AGGFLY_HIP_GPU_DECODE=1)
+GPU_DECODE_AUTO_BYTES_BLOSC_BITSHUFFLE = None     # LZ4 / LZ4HC streams under the bit shuffle
+GPU_DECODE_AUTO_BYTES_BLOSC_ZSTD = None           # Zstandard streams, any shuffle
 
 
 def _deflate_typesize(kind):
@@ -566,9 +570,21 @@ def _deflate_typesize(kind):
     return None
 
 
+def _blosc_auto_bytes(flavour, whole_rows: bool):
+    """The auto threshold of a Blosc store by the flavour of its first chunk — (inner codec id, shuffle 0 / 1 / 2)."""
+    if flavour[0] == 4:
+        return GPU_DECODE_AUTO_BYTES_BLOSC_ZSTD
+    if flavour[1] == 2:
+        return GPU_DECODE_AUTO_BYTES_BLOSC_BITSHUFFLE
+    return GPU_DECODE_AUTO_BYTES_WHOLE_ROWS if whole_rows else GPU_DECODE_AUTO_BYTES
+
+
 def _gpu_decodable(za, request_bytes: int = 0) -> bool:
-    """Blosc-1 chunks with LZ4 streams (lz4 / lz4hc), byte shuffle or none — what `afhip_lz4_decode_streams` takes; judged
-    from the first chunk file's header.  ``AGGFLY_HIP_GPU_DECODE``: ``1`` always, ``0`` never, unset / ``auto``: for requests
+    """Whether a request of ``request_bytes`` decoded bytes on this array takes the decode-in-HBM route; the format is judged from
+    the first present chunk's header, the size by ``AGGFLY_HIP_GPU_DECODE``: ``1`` always, ``0`` never, unset / ``auto``: from the
+    flavour's threshold on — never while that threshold is None (the route is then opt-in).
+
+    Blosc-1 chunks with LZ4 streams (lz4 / lz4hc), byte shuffle or none — what `afhip_lz4_decode_streams` takes (`_Lz4Route`): requests
     of `GPU_DECODE_AUTO_BYTES` decoded bytes or more — `GPU_DECODE_AUTO_BYTES_WHOLE_ROWS` for stores whose chunks hold whole time
     steps of the grid.  The host route is at its best on those (each chunk decodes straight into its rows of the slab; 40-53 GB/s),
     and round 2 kept them on it up to 768 MB; with round 4's equal batches and host-decoded tail the decode in HBM is ahead from
@@ -576,7 +592,12 @@ def _gpu_decodable(za, request_bytes: int = 0) -> bool:
     `profiles/r04_ingest_batches.txt`); on other chunk grids (space-tiled 12 MB chunks) it is level at 50 MB and ahead from there
     on (74 MB: 4.2 against 5.2 ms, 99 MB: 5.5 against 7.6; round 2 measured 0.26 GB on its pipeline).  Measured on MI355X (`profiles/r02_gpu_decode_by_ratio*.json`,
     DESIGN.md §8) the chunks of a 0.9-3.4 GB store reach HBM at 48-85 GB/s this way against 32-53 GB/s with the decode on
-    16 host threads; a small request is over before the decode kernel's ~2 ms (one wave walks one stream) are."""
+    16 host threads; a small request is over before the decode kernel's ~2 ms (one wave walks one stream) are.
+
+    The other Blosc-1 flavours the GPU takes (`_BloscRoute`; the flavour of the first chunk is kept in ``za._blosc_flavour``): LZ4 /
+    LZ4HC under the bit shuffle from `GPU_DECODE_AUTO_BYTES_BLOSC_BITSHUFFLE` on, Zstandard streams with any shuffle from
+    `GPU_DECODE_AUTO_BYTES_BLOSC_ZSTD` on, chunks below 1 GiB (a Zstandard batch's bound); blosclz, zlib and snappy inside Blosc
+    stay on the host.  Both constants follow profiles/blosc_flavours_ingest.txt."""
     mode = os.environ.get("AGGFLY_HIP_GPU_DECODE", "auto")
     whole_rows = len(za.shape) == 3 and tuple(za.chunks[1:]) == tuple(za.shape[1:])
     # plain Zstandard frames (`hip.zstd_decode`): from `GPU_DECODE_AUTO_BYTES_ZSTD` on under auto, chunks below 1 GiB (a batch's bound)
@@ -584,14 +605,27 @@ def _gpu_decodable(za, request_bytes: int = 0) -> bool:
     # zlib streams (`hip.inflate_decode`; HDF5 / netCDF-4 deflate with or without shuffle, Zarr v2 "zlib"): from
     # `GPU_DECODE_AUTO_BYTES_DEFLATE` on under auto — never while that is None —, chunks below 1 GiB; gzip members stay on the host
     deflate = _deflate_typesize(za.native_kind) is not None
-    auto_bytes = (GPU_DECODE_AUTO_BYTES_DEFLATE if deflate else GPU_DECODE_AUTO_BYTES_ZSTD if zstd
-                  else (GPU_DECODE_AUTO_BYTES_WHOLE_ROWS if whole_rows else GPU_DECODE_AUTO_BYTES))
-    if (mode == "0" or not (deflate or za.native_kind in ("blosc", "zstd")) or (mode != "1" and (auto_bytes is None or request_bytes < auto_bytes))
+    blosc = za.native_kind == "blosc"
+    if blosc:
+        # (the flavour is in the first chunk's header: under auto no file is opened for a request below every Blosc threshold)
+        cands = [_blosc_auto_bytes(f, whole_rows) for f in ((1, 1), (1, 2), (4, 1))]
+        auto_bytes = min([c for c in cands if c is not None], default=None)
+    else:
+        auto_bytes = GPU_DECODE_AUTO_BYTES_DEFLATE if deflate else GPU_DECODE_AUTO_BYTES_ZSTD
+    if (mode == "0" or not (deflate or blosc or zstd) or (mode != "1" and (auto_bytes is None or request_bytes < auto_bytes))
             or ((zstd or deflate) and za.chunk_nbytes >= 1 << 30)):
         return False
+    def flavour_allows():
+        """Blosc: the threshold (and the Zstandard batch's 1 GiB bound) of the flavour the first chunk's header showed."""
+        if not blosc:
+            return True
+        flavour = getattr(za, "_blosc_flavour", (1, 1))
+        limit = _blosc_auto_bytes(flavour, whole_rows)
+        return (mode == "1" or (limit is not None and request_bytes >= limit)) and not (flavour[0] == 4 and za.chunk_nbytes >= 1 << 30)
+
     hit = getattr(za, "_gpu_decodable", None)
     if hit is not None:
-        return hit
+        return hit and flavour_allows()
     ok = False
     try:
         for idx in np.ndindex(*[-(-s_ // c_) for s_, c_ in zip(za.shape, za.chunks)]):
@@ -608,9 +642,12 @@ def _gpu_decodable(za, request_bytes: int = 0) -> bool:
             elif len(h) == 16 and h[0] == 2:
                 flags, ts = h[2], h[3]
                 nbytes, blocksize = int.from_bytes(h[4:8], "little"), int.from_bytes(h[8:12], "little")
-                ok = bool(flags & 0x02) or (((flags >> 5) & 7) == 1 and not (flags & 0x04) and blocksize > 0 and nbytes == za.chunk_nbytes
+                inner = (flags >> 5) & 7
+                ok = bool(flags & 0x02) or (inner in (1, 4) and blocksize > 0 and nbytes == za.chunk_nbytes
                                             and -(-nbytes // blocksize) <= 65535)      # (one launch unshuffles at most 65,535 blocks)
                 za._blosc_geometry = (max(blocksize, 1), max(ts, 1))
+                # (inner codec id, shuffle): picks the threshold and the route; a stored chunk of another codec keeps `_Lz4Route`
+                za._blosc_flavour = (inner if inner in (1, 4) else 1, 1 if flags & 0x01 and ts > 1 else 2 if flags & 0x04 else 0)
             break
     except OSError:
         ok = False
@@ -618,7 +655,7 @@ def _gpu_decodable(za, request_bytes: int = 0) -> bool:
         za._gpu_decodable = ok
     except AttributeError:
         pass
-    return ok
+    return ok and flavour_allows()
 
 
 def _zstd_frame_taken(h: bytes, nbytes: int) -> bool:
@@ -891,6 +928,90 @@ class _Lz4Route:
             hip.unshuffle_blocks(self.tmp_dev[k], target, comp[self.bl0:], self.n_bl, self.max_bsize)
 
 
+class _BloscRoute:
+    """The codec half of the decode-in-HBM route for the Blosc-1 flavours beyond `_Lz4Route`'s — Zstandard streams with any shuffle,
+    LZ4 streams under the bit shuffle; it takes `_Lz4Route`'s chunks too, so a store may mix them —: the five record lists of
+    `codec.blosc_plan`, then `hip.lz4_decode_streams`, `hip.zstd_decode` into the shuffle scratch (with a Zstandard scratch per slot,
+    grown on the slot's stream when a batch needs more), `hip.unshuffle_blocks` and `hip.bitunshuffle_blocks`.  The lists are sized
+    from the first chunk's header; a batch that needs more falls back to the host.  Zstandard batches decode at most 1 GiB."""
+
+    what = "LZ4 stream(s) / Zstandard frame(s)"
+
+    def __init__(self, job):
+        self.bsz, self.tsz = getattr(job.za, "_blosc_geometry", (65536, 1))
+        self.zstd = getattr(job.za, "_blosc_flavour", (1, 1))[0] == 4
+        self.cb = job.cb
+        self.nblk = max(1, -(-job.cb // self.bsz))
+        if self.zstd:          # as `_ZstdRoute`: the passes are a thread or a wave per Zstandard block, latency-bound
+            self.max_per = max(1, min(4096, (1 << 30) // job.cb))
+            self.target_bytes = self.max_bytes = 1 << 30
+        else:
+            self.max_per, self.target_bytes, self.max_bytes = 4096, 144 << 20, 512 << 20
+
+    def size(self, per, nstage, device):
+        import torch
+        from . import codec
+        cb, nblk = self.cb, self.nblk
+        a64 = lambda n: (n + 63) // 64 * 64
+        self.cmax = a64(int(codec.load().afcodec_blosc_bound(cb, 0)))
+        # one frame, or one stream per byte plane, per Blosc block; stored streams and chunks in 64 KiB pieces
+        self.cap_streams = per * (nblk * (1 if self.zstd else self.tsz) + cb // 65536 + nblk + 2)
+        self.cap_blocks = per * nblk                                          # each of the two unshuffle lists
+        self.cap_frames = per * nblk if self.zstd else 1
+        # libzstd writes 128 KiB blocks: 8x headroom and 4 per frame, more goes to the host (as `_ZstdRoute.size`)
+        self.cap_zblocks = per * (cb // 16384 + 4 * nblk) if self.zstd else 1
+        sizes = (self.cap_streams * codec.LZ4_STREAM.itemsize, self.cap_blocks * codec.SHUFFLE_BLOCK.itemsize,
+                 self.cap_blocks * codec.SHUFFLE_BLOCK.itemsize, self.cap_frames * codec.ZSTD_FRAME.itemsize,
+                 self.cap_zblocks * codec.ZSTD_BLOCK.itemsize)
+        self.at = [0]
+        for n in sizes:
+            self.at.append(self.at[-1] + a64(n))
+        self.rec_bytes = self.at[-1]
+        self.device = device
+        self.tmp_dev = [torch.empty(per * (cb + 16 * nblk + 16), dtype=torch.uint8, device=device) for _ in range(nstage)]
+        self.scratch = [None] * nstage
+        self.rounds = None
+
+    def plan(self, k, hall, rec0, offs, sizes, present, out_offs):
+        from . import codec
+        dts = (codec.LZ4_STREAM, codec.SHUFFLE_BLOCK, codec.SHUFFLE_BLOCK, codec.ZSTD_FRAME, codec.ZSTD_BLOCK)
+        caps = (self.cap_streams, self.cap_blocks, self.cap_blocks, self.cap_frames, self.cap_zblocks)
+        self.lo = [rec0 + a for a in self.at[:5]]
+        lists = [hall[lo:lo + cap * dt.itemsize].view(dt) for lo, cap, dt in zip(self.lo, caps, dts)]
+        try:
+            pl = codec.blosc_plan(hall, offs[:-1][present], sizes[present], out_offs, np.full(len(present), self.cb, dtype=np.int64), *lists)
+        except codec.PlanCapacityError:
+            raise _NotForTheGpuRoute() from None
+        if (pl.results == codec.E_UNSUPPORTED).any() or pl.tmp_bytes > self.tmp_dev[k].numel() or pl.dec_bytes > 0x7fffffff:
+            # a chunk the GPU decoders do not take (aggfly_codec.h: "decode it on the host"), or one whose geometry differs from
+            # the first chunk's, which sized the buffers: the request falls back to the host route
+            raise _NotForTheGpuRoute()
+        self.plan_, self.rec0 = pl, rec0
+        counts = (pl.n_streams, pl.n_shuf, pl.n_bits, pl.n_frames, pl.n_blocks)
+        ranges = [(0, self.lo[0] + counts[0] * dts[0].itemsize)]                # compressed bytes + stream records: one copy
+        ranges += [(lo, lo + n * dt.itemsize) for lo, n, dt in zip(self.lo[1:], counts[1:], dts[1:])]
+        return pl.results, ranges
+
+    def decode(self, k, comp, target, errors):
+        import torch
+        from . import hip
+        pl, lo, tmp = self.plan_, self.lo, self.tmp_dev[k]
+        if pl.n_streams:
+            hip.lz4_decode_streams(comp, comp[lo[0]:], pl.n_streams, pl.max_dsize, tmp, target, errors)
+        if pl.n_frames:
+            need = hip.zstd_scratch_bytes(pl)
+            if self.scratch[k] is None or self.scratch[k].numel() < need:
+                self.scratch[k] = None
+                self.scratch[k] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            if self.rounds is None and os.environ.get("AGGFLY_HIP_INGEST_TRACE") == "1":
+                self.rounds = torch.zeros(1, dtype=torch.int32, device=self.device)
+            hip.zstd_decode(comp, self.rec0, comp[lo[3]:], comp[lo[4]:], pl, self.scratch[k], tmp, errors, self.rounds)
+        if pl.n_shuf:
+            hip.unshuffle_blocks(tmp, target, comp[lo[1]:], pl.n_shuf, pl.max_shuf)
+        if pl.n_bits:
+            hip.bitunshuffle_blocks(tmp, target, comp[lo[2]:], pl.n_bits, pl.max_bits)
+
+
 class _ZstdRoute:
     """The codec half of the decode-in-HBM route for plain Zstandard frames: the frame and block records of
     `codec.zstd_plan`, `hip.zstd_decode` with a scratch per slot (grown on the slot's stream when a batch needs more).
@@ -1003,7 +1124,7 @@ class _DeflateRoute:
 
 def _scatter_gpu_decode(job: _ScatterJob, threads: int, post):
     """Blosc-LZ4 chunks, Zstandard frames or zlib streams cross PCIe compressed: per batch the host reads the chunk files as
-    they are into a page-locked slot and walks their headers into the codec's record lists (`_Lz4Route`, `_ZstdRoute`, `_DeflateRoute`); one
+    they are into a page-locked slot and walks their headers into the codec's record lists (`_Lz4Route`, `_BloscRoute`, `_ZstdRoute`, `_DeflateRoute`); one
     upload carries the compressed bytes and the records; the codec's kernels decode on the slot's stream — straight into the
     cube when every chunk of the batch holds whole time steps of the window, else into a staging buffer that `job.place`
     empties.  The page-locked slot is free again when its upload is over; the device-side one is handed from the kernels to
@@ -1011,8 +1132,9 @@ def _scatter_gpu_decode(job: _ScatterJob, threads: int, post):
     import torch
     from . import codec
     za, device, cb, idxs, cube = job.za, job.device, job.cb, job.idxs, job.cube
+    flavour = getattr(za, "_blosc_flavour", (1, 1))
     route = (_ZstdRoute(job) if za.native_kind == "zstd" else _DeflateRoute(job) if _deflate_typesize(za.native_kind) is not None
-             else _Lz4Route(job))
+             else _BloscRoute(job) if flavour[0] == 4 or flavour[1] == 2 else _Lz4Route(job))
     cuts, per, n_tail = _decode_batches(len(idxs), cb, route.nblk, job.whole_steps, route.max_per, route.target_bytes, route.max_bytes)
     all_idxs, idxs = idxs, idxs[:len(idxs) - n_tail]
     # staging slots in flight: 4 (3 measured 7 % slower), 6 when every batch is one big chunk (the converter's 265 MB chunks)
@@ -1242,7 +1364,8 @@ def _write_array(path, name, data, dims, chunks, attrs, compressor, zarr_format:
         v3name = {v: k for k, v in _V3_DTYPES.items()}[data.dtype.newbyteorder("<").str if data.dtype.itemsize > 1 else data.dtype.str]
         codecs = [{"name": "bytes", "configuration": {"endian": "little"}}]
         if cid == "blosc":
-            codecs.append({"name": "blosc", "configuration": {"cname": "lz4", "clevel": 5, "shuffle": "shuffle" if compressor.get("shuffle", 1) == 1 else "noshuffle",
+            codecs.append({"name": "blosc", "configuration": {"cname": compressor.get("cname", "lz4"), "clevel": compressor.get("clevel", 5),
+                                                               "shuffle": {0: "noshuffle", 1: "shuffle", 2: "bitshuffle"}[compressor.get("shuffle", 1)],
                                                                "typesize": data.dtype.itemsize, "blocksize": compressor.get("blocksize", 0)}})
         elif cid == "zstd":
             codecs.append({"name": "zstd", "configuration": {"level": compressor.get("level", 0), "checksum": False}})
@@ -1286,7 +1409,8 @@ def _write_array(path, name, data, dims, chunks, attrs, compressor, zarr_format:
         elif cid == "blosc":
             from . import codec
             raw = codec.blosc_encode(blk, data.dtype.itemsize, shuffle=compressor.get("shuffle", 1) == 1,
-                                     blocksize=compressor.get("blocksize", 0))
+                                     blocksize=compressor.get("blocksize", 0), cname=compressor.get("cname", "lz4"),
+                                     bitshuffle=compressor.get("shuffle", 1) == 2)
         elif cid == "zstd":
             from . import codec
             raw = codec.zstd_encode(blk, compressor.get("level", 3) or 3)
@@ -1357,7 +1481,9 @@ def dataset_to_zarr(dataset: Dataset, path: str, var: str = "var", chunks=None, 
                     shards=None):
     """`dataset_to_zarr` (`zarr_convert.py:50-121`): write a time-major, time-contiguous store.
     ``compress``: True / "blosc" -> Blosc-1 LZ4 + byte shuffle (what zarr-python 2 / numcodecs write by
-    default and read back), "zstd" (zarr-python 3's default codec), "zlib" -> zlib level 1, False -> raw.
+    default and read back), "blosc-zstd" / "blosc-bitshuffle" / "blosc-zstd-bitshuffle" -> Blosc-1 with Zstandard streams and the byte
+    shuffle, LZ4 streams and the bit shuffle, or both (the Zarr v3 ``blosc`` codec's default ``cname`` is zstd), "zstd" (zarr-python
+    3's default codec), "zlib" -> zlib level 1, False -> raw.
     ``zarr_format``: 2 (``.zarray``) or 3 (``zarr.json``, ``c/`` chunk keys); ``shards`` (format 3): a dict like
     ``chunks`` giving the shard shape in which the chunks are bundled (``sharding_indexed``)."""
     cube = dataset.cube()
@@ -1375,6 +1501,9 @@ def dataset_to_zarr(dataset: Dataset, path: str, var: str = "var", chunks=None, 
             json.dump({"zarr_format": 3, "node_type": "group", "attributes": {}}, f)
     if compress in (True, "blosc"):
         comp = {"id": "blosc", "cname": "lz4", "clevel": 5, "shuffle": 1, "blocksize": 0}
+    elif compress in ("blosc-zstd", "blosc-bitshuffle", "blosc-zstd-bitshuffle"):
+        comp = {"id": "blosc", "cname": "zstd" if "zstd" in compress else "lz4", "clevel": 5, "shuffle": 2 if "bitshuffle" in compress else 1,
+                "blocksize": 0}
     elif compress == "zstd":
         comp = {"id": "zstd", "level": 3}
     elif compress == "zlib":
@@ -1382,7 +1511,8 @@ def dataset_to_zarr(dataset: Dataset, path: str, var: str = "var", chunks=None, 
     elif not compress:
         comp = None
     else:
-        raise ValueError(f"compress must be True, False, 'blosc', 'zstd' or 'zlib', got {compress!r}")
+        raise ValueError("compress must be True, False, 'blosc', 'blosc-zstd', 'blosc-bitshuffle', 'blosc-zstd-bitshuffle', 'zstd' or 'zlib', "
+                         f"got {compress!r}")
     stuple = None
     if shards is not None:
         stuple = tuple(sizes[d] if shards.get(d, -1) in (-1, None) else shards[d] for d in ("time", "latitude", "longitude"))

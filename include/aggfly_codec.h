@@ -38,6 +38,12 @@ int afcodec_blosc_decode_files(int64_t n, const char* const* paths, void* const*
 int64_t afcodec_blosc_bound(int64_t nbytes, int64_t blocksize);
 int64_t afcodec_blosc_encode_lz4(const void* src, int64_t nbytes, int typesize, int shuffle, int64_t blocksize,
                                  void* dst, int64_t cap);
+/* Blosc-1 writer: cname 1 (LZ4) or 4 (Zstandard, the system's libzstd at `level`; LZ4 ignores the level); shuffle 0 none, 1 byte,
+ * 2 bit (a block whose element count is not a multiple of 8 stays unshuffled, as in c-blosc); blocksize 0 = 64 KiB x typesize for
+ * LZ4, 256 KiB for Zstandard.  Zstandard blocks are unsplit (flag 0x10), one frame per block, as c-blosc 1.21 writes them; LZ4
+ * blocks under a shuffle are split into typesize streams.  afcodec_blosc_encode_lz4(..., shuffle, ...) is cname 1, level 0. */
+int64_t afcodec_blosc_encode(const void* src, int64_t nbytes, int typesize, int shuffle, int cname, int level, int64_t blocksize,
+                             void* dst, int64_t cap);
 
 /* Plan of a GPU-side decode (libaggfly_hip: afhip_lz4_decode_streams / afhip_unshuffle_blocks, include/aggfly_hip.h): the
  * containers of n Blosc-1 chunks — chunk i = comp_size[i] bytes at base + comp_off[i], its decoded bytes wanted at offset
@@ -48,11 +54,35 @@ int64_t afcodec_blosc_encode_lz4(const void* src, int64_t nbytes, int typesize, 
  *                         stored chunks appear with csize == dsize;
  *   blocks  [*n_blocks]   afhip_shuffle_block records: blocks whose byte shuffle is undone from the scratch into the output.
  * Nothing is decoded here.  results[i] = the chunk's decoded size, or < 0: AFCODEC_E_UNSUPPORTED marks a chunk the GPU
- * route does not take (another codec than LZ4, bit shuffle) — decode it on the host; the call then returns that code too.
+ * route does not take (another codec than LZ4, bit shuffle: afcodec_blosc_plan below takes more) — decode it on the host; the call
+ * then returns that code too.
  * *max_dsize = the longest stream (sizes the kernel's LDS ring). */
 int afcodec_blosc_lz4_plan(const void* base, int64_t n, const int64_t* comp_off, const int64_t* comp_size, const int64_t* out_off,
                            const int64_t* out_size, void* streams, int64_t cap_streams, int64_t* n_streams, void* blocks,
                            int64_t cap_blocks, int64_t* n_blocks, int64_t* tmp_bytes, int32_t* max_dsize, int64_t* results);
+
+/* The same walk for every Blosc-1 chunk the GPU decodes (afcodec_blosc_lz4_plan is this walk with Zstandard and bit shuffle filtered
+ * out): inner codec LZ4 / LZ4HC or Zstandard, shuffle none, byte or bit.  Five outputs:
+ *   streams [*n_streams]  afhip_lz4_stream records: every LZ4 stream, and every plain copy (stored streams, csize == dsize — those
+ *                         of Zstandard chunks cut into pieces of at most 64 KiB — and stored chunks, flag 0x02);
+ *   frames  [*n_frames] / zblocks [*n_zblocks]  afhip_zstd_frame / afhip_zstd_block records of every Zstandard stream, by the
+ *                         per-frame walk of afcodec_zstd_plan, with the batch totals *lit_bytes, *n_seqs, *dec_bytes; their
+ *                         dst_off are offsets into the shuffle scratch: call afhip_zstd_decode with out_dev = the scratch;
+ *   blocks  [*n_blocks]   afhip_shuffle_block records for afhip_unshuffle_blocks: byte-shuffled blocks, and the unshuffled blocks
+ *                         of Zstandard chunks as typesize 1 (a copy scratch -> output);
+ *   bits    [*n_bits]     afhip_shuffle_block records for afhip_bitunshuffle_blocks: bit-shuffled blocks;
+ *   *tmp_bytes of shuffle scratch, *max_dsize (the longest LZ4 stream) and results[i] = the chunk's nbytes, or < 0:
+ *   AFCODEC_E_UNSUPPORTED for blosclz / zlib / snappy inner codecs and for an inner frame afcodec_zstd_plan would refuse — decode the
+ *   chunk on the host —, AFCODEC_E_FORMAT for malformed containers.  A chunk that fails leaves no record.
+ * Every Zstandard frame and every stream of a shuffled block decodes into the scratch and the block then moves scratch -> output
+ * through one of the two unshuffle lists; unshuffled LZ4 streams go straight to the output.  Run, in order, afhip_lz4_decode_streams,
+ * afhip_zstd_decode (out_dev = scratch), afhip_unshuffle_blocks, afhip_bitunshuffle_blocks.  Every record lies inside its chunk,
+ * the batch's buffers and the chunk's destination, whatever the input bytes are.  Nothing is decoded here. */
+int afcodec_blosc_plan(const void* base, int64_t n, const int64_t* comp_off, const int64_t* comp_size, const int64_t* out_off,
+                       const int64_t* out_size, void* streams, int64_t cap_streams, int64_t* n_streams, void* blocks,
+                       int64_t cap_blocks, int64_t* n_blocks, void* bits, int64_t cap_bits, int64_t* n_bits, void* frames,
+                       int64_t cap_frames, int64_t* n_frames, void* zblocks, int64_t cap_zblocks, int64_t* n_zblocks, int64_t* lit_bytes,
+                       int64_t* n_seqs, int64_t* dec_bytes, int64_t* tmp_bytes, int32_t* max_dsize, int64_t* results);
 
 /* Plan of a GPU-side Zstandard decode (libaggfly_hip: afhip_zstd_decode, include/aggfly_hip.h): n plain Zstandard frames —
  * chunk i = comp_size[i] bytes at base + comp_off[i], decoded to offset out_off[i] of the output (out_size[i] bytes) — have

@@ -182,13 +182,20 @@ int afhip_place_box(const void* chunk_dev, void* cube_dev, int elem_size,
  * cube itself; stored streams (csize == dsize) are copied.  max_dsize = the longest dsize of the list (checked >= 0, not
  * otherwise used since the decode left LDS).  A malformed stream writes nothing outside its own destination and adds 1 to
  * *errors_dev (read it after the next synchronisation).
- * afhip_unshuffle_blocks: Blosc's byte shuffle undone, tmp_dev -> out_dev.  All pointers are device memory. */
+ * afhip_unshuffle_blocks: Blosc's byte shuffle undone, tmp_dev -> out_dev (typesize 1: a copy).
+ * afhip_bitunshuffle_blocks: Blosc's bit shuffle undone, the same records and launch shape (at most 65,535 blocks a call): with
+ * n = bsize / typesize elements, bit k of byte j of element e is bit (e % 8) of tmp[(8j + k) * (n / 8) + e / 8]; a block whose n
+ * is not a multiple of 8 is copied as it is (c-blosc leaves it unshuffled), and so are the bsize - n * typesize trailing bytes.
+ * The other Blosc-1 flavours — Zstandard streams, the bit shuffle — are planned by afcodec_blosc_plan, whose Zstandard frames
+ * afhip_zstd_decode (below) decodes into the same tmp_dev before the two unshuffles run.  All pointers are device memory. */
 typedef struct afhip_lz4_stream { int64_t src_off, dst_off; int32_t csize, dsize, to_out, pad; } afhip_lz4_stream;
 typedef struct afhip_shuffle_block { int64_t tmp_off, out_off; int32_t bsize, typesize; } afhip_shuffle_block;
 int afhip_lz4_decode_streams(const void* comp_dev, const afhip_lz4_stream* streams_dev, int64_t n_streams, int32_t max_dsize,
                              void* tmp_dev, void* out_dev, int32_t* errors_dev, void* stream);
 int afhip_unshuffle_blocks(const void* tmp_dev, void* out_dev, const afhip_shuffle_block* blocks_dev, int64_t n_blocks,
                            int32_t max_bsize, void* stream);
+int afhip_bitunshuffle_blocks(const void* tmp_dev, void* out_dev, const afhip_shuffle_block* blocks_dev, int64_t n_blocks,
+                              int32_t max_bsize, void* stream);
 
 /* Zstandard frames decoded in HBM (Zarr v2 compressor "zstd", Zarr v3 bytes -> zstd, shards too).  The host walks the frame,
  * block and section headers (afcodec_zstd_plan, include/aggfly_codec.h) into one record per frame and per block, which
