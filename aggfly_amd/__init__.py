@@ -22,6 +22,7 @@ from .aggregate import (  # noqa: F401
 from .cfcalendar import CFDatetime, CFTimeIndex, cf_range  # noqa: F401
 from .dataarray import DataArray  # noqa: F401
 from .dataset import Dataset, Grid  # noqa: F401
+from .packed import PackedCube  # noqa: F401
 from .io import dataset_from_path, dataset_to_zarr, zarr_from_path  # noqa: F401
 from .weights import (  # noqa: F401
     CropWeights,

@@ -320,6 +320,8 @@ struct afhip_plan : PlanLayout {             // what the planner made (afhip_pla
     int64_t own_ws_bytes = 0;               // outgrown block is `retired` until the plan is destroyed — no hipFree (a device-wide
     std::vector<void*> retired;             // synchronisation) ever sits on the run path
     double* sums = nullptr;                 // [rows][P][K + 1] of the current run: behind partial + panel in the run's workspace
+    PackArgs unpack{};                      // AFHIP_I16 plans: the unpack rule (afhip_plan_bind_packing)
+    bool unpack_bound = false;
     int last_ws = 0;                        // 1: the last run used a caller-owned workspace, 2: plan-owned (afhip_plan_describe tells)
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     // per-launch profiling ring (afhip_plan_profile_*): event pairs around the temporal kernel
@@ -340,11 +342,13 @@ extern "C" const char* afhip_last_error(void) { return last_error(); }
 extern "C" int afhip_abi_version(void) { return AFHIP_ABI_VERSION; }
 
 extern "C" int afhip_build_info(char* buf, int buf_len) {
-    int n = 0, arms = 0, rf = 0;
+    int n = 0, arms = 0, rf = 0, np = 0;
     const Variant* tab = variants_table(&n);
     for (int i = 0; i < n; ++i) { arms += tab[i].production ? 0 : 1; rf += tab[i].rf() ? 1 : 0; }
-    char tmp[160];
-    const int len = snprintf(tmp, sizeof tmp, "menu=%s variants=%d arms=%d region_fused_twins=%d abi=%d", variants_menu(), n, arms, rf, AFHIP_ABI_VERSION);
+    (void)packed_variants_table(&np);
+    char tmp[200];
+    const int len = snprintf(tmp, sizeof tmp, "menu=%s variants=%d arms=%d region_fused_twins=%d abi=%d packed_variants=%d", variants_menu(), n, arms, rf,
+                             AFHIP_ABI_VERSION, np);
     if (buf && buf_len > 0) snprintf(buf, buf_len, "%s", tmp);
     return len + 1;
 }
@@ -848,6 +852,42 @@ extern "C" int afhip_plan_bind_inter(afhip_plan* plan, int column, const void* i
     return AFHIP_OK;
 }
 
+static int check_packing(const afhip_packing* p, const char* who) {
+    static_assert(sizeof(afhip_packing) == sizeof(PackArgs), "afhip_packing is PackArgs");
+    if (!p) return fail(AFHIP_E_INVALID, "%s: the packing is NULL", who);
+    if (p->n_pairs < 0 || p->n_pairs > MAX_PACK_PAIRS) return fail(AFHIP_E_INVALID, "%s: n_pairs must be 0..%d, got %d", who, MAX_PACK_PAIRS, p->n_pairs);
+    if (p->has_fill && (p->fill < INT16_MIN || p->fill > INT16_MAX)) return fail(AFHIP_E_INVALID, "%s: the fill value %d is no int16", who, p->fill);
+    return AFHIP_OK;
+}
+
+extern "C" int afhip_plan_bind_packing(afhip_plan* plan, const afhip_packing* p) {
+    if (!plan) return fail(AFHIP_E_INVALID, "plan_bind_packing: plan is NULL");
+    if (plan->desc.dtype != AFHIP_I16) return fail(AFHIP_E_INVALID, "plan_bind_packing: the plan's dtype is not AFHIP_I16");
+    int rc = check_packing(p, "plan_bind_packing");
+    if (rc) return rc;
+    memcpy(&plan->unpack, p, sizeof(PackArgs));
+    plan->unpack.has_fill = p->has_fill ? 1 : 0;
+    plan->unpack_bound = true;
+    return AFHIP_OK;
+}
+
+extern "C" int afhip_unpack_i16(const void* q_dev, int64_t n, const afhip_packing* p, float* out_dev, void* stream) {
+    if (!q_dev || !out_dev || n < 0) return fail(AFHIP_E_INVALID, "unpack_i16: NULL array or negative size");
+    int rc = check_packing(p, "unpack_i16");
+    if (rc) return rc;
+    if (n == 0) return AFHIP_OK;
+    if ((uintptr_t)q_dev % 8 != 0 || (uintptr_t)out_dev % 16 != 0) return fail(AFHIP_E_INVALID, "unpack_i16: q_dev must be 8-byte and out_dev 16-byte aligned");
+    PackArgs pa;
+    memcpy(&pa, p, sizeof pa);
+    pa.has_fill = p->has_fill ? 1 : 0;
+    const int64_t lanes = (n + 3) / 4, blocks = (lanes + WG - 1) / WG;
+    if (blocks > 0x7fffffff) return fail(AFHIP_E_INVALID, "unpack_i16: array too large for one launch");
+    GUARD_DEVICE(pointer_device(out_dev));
+    hipLaunchKernelGGL(k_unpack_i16, dim3((unsigned)blocks), dim3(WG), 0, (hipStream_t)stream, (const int16_t*)q_dev, n, pa, out_dev);
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
 extern "C" int64_t afhip_plan_workspace_bytes(const afhip_plan* plan) {
     if (!plan) return 0;
     return plan->ws_partial;
@@ -903,7 +943,10 @@ static int launch_temporal(afhip_plan* pl, const void* cube, double* partial, hi
     for (int j = 0; j < pl->K; ++j)
         if (pl->cols[(size_t)j].tf == TF_INTER && !pl->cols[(size_t)j].inter)
             return fail(AFHIP_E_INVALID, "column %d multiplies by a second array (AFHIP_TF_INTER) that was never bound: call afhip_plan_bind_inter first", j);
+    if (pl->desc.dtype == AFHIP_I16 && !pl->unpack_bound)
+        return fail(AFHIP_E_INVALID, "the plan reads an int16-packed cube (AFHIP_I16) whose packing was never bound: call afhip_plan_bind_packing first");
     FusedArgs fa{};
+    fa.unpack = pl->unpack;
     fa.cube = cube; fa.C = pl->desc.n_cells;
     fa.gtab = pl->d_gtab.p; fa.chunks = pl->d_chunks.p;
     fa.partial = partial; fa.K = pl->K; fa.nthr = pl->nthr;
@@ -1225,6 +1268,7 @@ static int run_group(const void* cube_dev, int dtype, int64_t T, int64_t n_cells
                      int64_t G, int code, const double* ddargs, int64_t D, void* out_dev, void* stream) {
     if (!cube_dev || !bounds || !out_dev) return fail(AFHIP_E_INVALID, "group kernel: NULL argument");
     if (G < 0 || D <= 0) return fail(AFHIP_E_INVALID, "group kernel: bad G/D");
+    if (dtype != AFHIP_F32 && dtype != AFHIP_F64) return fail(AFHIP_E_INVALID, "group kernel: dtype must be AFHIP_F32 or AFHIP_F64");
     if (G == 0) return AFHIP_OK;
     GUARD_DEVICE(pointer_device(cube_dev));          // the temporary plans are created, run and freed on the cube's device
     hipStream_t st = (hipStream_t)stream;

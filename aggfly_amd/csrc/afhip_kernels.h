@@ -49,7 +49,13 @@ struct FusedArgs {
     float hb_c1f, hb_c0f;
     int32_t hb_n, hb_shift;        // hb_shift = log2(blockDim): counters are laid out [bin * VEC + i][blockDim]
     int32_t hb_bin_of_slot[MAX_THR];
-    double hb_edge[MAX_THR + 1];
+    // int16-packed cubes (the PackedI16 storage) — `unpack`: how a stored integer becomes the float32 value (unpack_i16, afhip_loads.h),
+    // read by scalar loads.  It shares the histogram edges' bytes: packed cubes have no histogram form, and the record keeps its size
+    // and every field its offset (the general sixteen-column forms index `cols` at run time and hold a copy of the whole record).
+    union {
+        double hb_edge[MAX_THR + 1];
+        PackArgs unpack;
+    };
     float hb_dn[MAX_THR + 1], hb_up[MAX_THR + 1];
     // arithmetic edges (FEAT_ARITH_EDGES): every edge is EXACTLY hb_lo0 + g * hb_w in the input precision (host-checked with
     // the same fma), so the two edges around a guess are two fmas instead of an LDS table read; hb_gl / hb_gh sit
@@ -133,8 +139,13 @@ namespace afhip {
 //
 // The workgroup size is a launch parameter (64 or 256 threads): waves never talk to each
 // other, so small grids are launched as single-wave workgroups for a finer tail.
-template <typename TIn, int PIPE, int VEC, int STAT, int NTHR, int KMAX, int DEPTH, int FEAT>
+// TS: the cube's storage (afhip_loads.h: Storage) — float / double, stored as their values (TIn), or PackedI16: rows of int16 (TRaw)
+// that `consume` unpacks to float32 at the point of use, so the DEPTH loads of a burst stay in flight as 2-byte elements.
+template <typename TS, int PIPE, int VEC, int STAT, int NTHR, int KMAX, int DEPTH, int FEAT>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_fused_temporal(const FusedArgs a) {
+    typedef typename Storage<TS>::value_type TIn;
+    typedef typename Storage<TS>::raw_type TRaw;
+    constexpr bool PACKED = Storage<TS>::packed;
     // ---- everything the body asks of FEAT ----
     constexpr bool SINE = feat_has(FEAT, FEAT_SINE), GENERAL_TF = feat_has(FEAT, FEAT_GENERAL_TF);
     constexpr int AUX = feat_has(FEAT, FEAT_NT) ? 2 : 0;
@@ -157,6 +168,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
     static_assert(!RF || !(SL || HB), "region-fused period ends: two-level plans only");
     static_assert(!(HB && SINE), "histogram variants carry no sine_dd code");
     static_assert(!RF || VEC <= 2, "region-fused period ends: one or two cells per lane");
+    static_assert(!PACKED || (PIPE == 0 && !feat_has(FEAT, FEAT_SHORT_GROUP | FEAT_INT_BINS | FEAT_SINGLE_LEVEL | FEAT_HIST | FEAT_REGION_FUSED)),
+                  "int16-packed cubes: the general forms of the direct-load path only");
     const int64_t C = a.C;
     const int K = a.K;
     const int lane = threadIdx.x & 63;
@@ -182,7 +195,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
         slot = (int32_t)(sb & 0xffffffffLL);
     }
     const int rows = (int)(k_hi - k_lo);            // chunk-relative 32-bit loop control: scalar ALU only
-    const TIn* __restrict__ cube = (const TIn*)a.cube + k_lo * C + c_ld;
+    const TRaw* __restrict__ cube = (const TRaw*)a.cube + k_lo * C + c_ld;
 
     // ---- per-cell state, all in registers (compile-time indexed) ----
     double s[VEC], mn[VEC], mx[VEC];
@@ -385,10 +398,14 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
             __hip_atomic_fetch_add(p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);     // the counter is private to this lane: one ds_add_u32
         }
     };
-    auto consume = [&](const RawVec<TIn, VEC>& rv, bool hb_inline = true) {
+    auto consume = [&](const RawVec<TRaw, VEC>& rv, bool hb_inline = true) {
+        TIn upk[PACKED ? VEC : 1];
+        if constexpr (PACKED) unpack_i16<VEC>(rv.v, a.unpack, upk);      // (uniform fields of the argument record: scalar loads)
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
-            const TIn vr = rv.v[i];
+            TIn vr_;
+            if constexpr (PACKED) vr_ = upk[i]; else vr_ = rv.v[i];
+            const TIn vr = vr_;
             const double v = (double)vr;
             const bool isn = vr != vr;
             // integer-bin plans without an inner statistic never look at the NaN mask (a NaN is simply in no bin)
@@ -1216,14 +1233,14 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
         }
         }
     } else if constexpr (PIPE == 0) {
-        const TIn* p = cube;
+        const TRaw* p = cube;
         // histogram variants with arithmetic edges are issue-bound beside their stream: their rows are addressed like the short-group
         // forms' — ONE scalar row pointer in a buffer descriptor + the lane's 32-bit byte offset, no vector address arithmetic (a
         // global_load wants a 64-bit vector address: one v_lshl_add_u64 per row and lane, a fifteenth of the element's instructions);
         // the host keeps plans whose rows reach 4 GiB off these variants
-        const char* nx = (const char*)a.cube + (size_t)(k_lo * C) * sizeof(TIn);
-        const uint32_t voff = (uint32_t)((uint64_t)c_ld * sizeof(TIn));
-        const size_t rowb = (size_t)C * sizeof(TIn);
+        const char* nx = (const char*)a.cube + (size_t)(k_lo * C) * sizeof(TRaw);
+        const uint32_t voff = (uint32_t)((uint64_t)c_ld * sizeof(TRaw));
+        const size_t rowb = (size_t)C * sizeof(TRaw);
         // group table word for g is fetched one group ahead: its scalar-load latency hides behind
         // the previous group's work (matters for 1-2 step groups: daily data, tmin/tmax pairs)
         int64_t w_next = ld_uniform(&a.gtab[2 * g]), iv_next = ld_uniform(&a.gtab[2 * g + 1]);
@@ -1238,17 +1255,17 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
             // K = 5 plan — other waves already cover the gap, the extra live registers cost more.  A register
             // ring that re-arms each row's load right after the row is consumed, across group ends, was
             // measured too: f64 6.88 -> 6.48 TB/s, f32 unchanged.  Bursts of DEPTH rows per wave win.)
-            auto load_block = [&](RawVec<TIn, VEC> (&r)[DEPTH]) {
+            auto load_block = [&](RawVec<TRaw, VEC> (&r)[DEPTH]) {
                 if constexpr (HA) {
 #pragma unroll
-                    for (int d = 0; d < DEPTH; ++d) { r[d] = ld_stream_row<TIn, VEC, AUX>(nx, voff); nx += rowb; }
+                    for (int d = 0; d < DEPTH; ++d) { r[d] = ld_stream_row<TRaw, VEC, AUX>(nx, voff); nx += rowb; }
                     return;
                 }
 #pragma unroll
-                for (int d = 0; d < DEPTH; ++d) r[d] = ld_stream<TIn, VEC, AUX>(p + (int64_t)d * C);
+                for (int d = 0; d < DEPTH; ++d) r[d] = ld_stream<TRaw, VEC, AUX>(p + (int64_t)d * C);
                 p += (int64_t)DEPTH * C;
             };
-            auto use_block = [&](const RawVec<TIn, VEC> (&r)[DEPTH]) {
+            auto use_block = [&](const RawVec<TRaw, VEC> (&r)[DEPTH]) {
                 if constexpr (HA) {
 #pragma unroll
                     for (int d = 0; d < DEPTH; ++d) consume(r[d]);
@@ -1271,7 +1288,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
                 }
             };
             for (; kk + DEPTH <= gend; kk += DEPTH) {
-                RawVec<TIn, VEC> r[DEPTH];
+                RawVec<TRaw, VEC> r[DEPTH];
                 load_block(r);
                 use_block(r);
             }
@@ -1279,15 +1296,15 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
             // are issued together too — one at a time, a 4-step group ran at a quarter of the bandwidth
             if (kk < gend) {
                 const int rem = gend - kk;
-                RawVec<TIn, VEC> r[DEPTH];
+                RawVec<TRaw, VEC> r[DEPTH];
                 if constexpr (HA) {
 #pragma unroll
                     for (int d = 0; d < DEPTH - 1; ++d)
-                        if (d < rem) { r[d] = ld_stream_row<TIn, VEC, AUX>(nx, voff); nx += rowb; }
+                        if (d < rem) { r[d] = ld_stream_row<TRaw, VEC, AUX>(nx, voff); nx += rowb; }
                 } else {
 #pragma unroll
                     for (int d = 0; d < DEPTH - 1; ++d)
-                        if (d < rem) r[d] = ld_stream<TIn, VEC, AUX>(p + (int64_t)d * C);
+                        if (d < rem) r[d] = ld_stream<TRaw, VEC, AUX>(p + (int64_t)d * C);
                     p += (int64_t)rem * C;
                 }
 #pragma unroll

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "afhip_plan_types.h"
 
 namespace afhip {
 
@@ -61,6 +62,44 @@ template <> struct alignas(16) RawVec<double, 2> { double v[2]; };
 template <> struct alignas(4) RawVec<float, 1> { float v[1]; };
 template <> struct alignas(16) RawVec<float, 4> { float v[4]; };
 template <> struct alignas(8) RawVec<float, 2> { float v[2]; };
+template <> struct alignas(2) RawVec<int16_t, 1> { int16_t v[1]; };
+template <> struct alignas(4) RawVec<int16_t, 2> { int16_t v[2]; };
+template <> struct alignas(8) RawVec<int16_t, 4> { int16_t v[4]; };
+
+// What a cube is stored as, apart from the type its values have in the kernel.  k_fused_temporal's first template argument is
+// the storage: float and double are stored as their values; the tag PackedI16 is int16 storage whose values are float32
+// (unpack_i16 below) — the row registers then hold int16 (8 / 4 / 2 bytes per lane at 4 / 2 / 1 cells) and everything after the
+// unpack is the float32 body.  A tag instead of a further template parameter: the float and double instantiations keep their names.
+struct PackedI16 {};
+template <typename TS> struct Storage { typedef TS value_type; typedef TS raw_type; static constexpr bool packed = false; };
+template <> struct Storage<PackedI16> { typedef float value_type; typedef int16_t raw_type; static constexpr bool packed = true; };
+
+// The unpack rule of an int16-packed cube (PackArgs, afhip_plan_types.h), written once: k_fused_temporal applies it where a row is
+// consumed, k_unpack_i16 (afhip_panel_kernels.h) to a whole array.  Every operation rounds to float32 on its own — separate
+// statements under -ffp-contract=off, never an fma — which is what torch does to a float32 tensor one operation at a time.  The
+// number of pairs is wave-uniform (a kernel argument): N values share its scalar branches.
+template <int N>
+__device__ __forceinline__ void unpack_i16(const int16_t (&q)[N], const PackArgs& p, float (&f)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) f[i] = (float)(int)q[i];
+    static_assert(MAX_PACK_PAIRS == 3, "three pairs, written out: every field is read at a constant offset");
+    if (p.n_pairs > 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) { f[i] = f[i] * p.mul[0]; f[i] = f[i] + p.add[0]; }
+        if (p.n_pairs > 1) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) { f[i] = f[i] * p.mul[1]; f[i] = f[i] + p.add[1]; }
+            if (p.n_pairs > 2) {
+#pragma unroll
+                for (int i = 0; i < N; ++i) { f[i] = f[i] * p.mul[2]; f[i] = f[i] + p.add[2]; }
+            }
+        }
+    }
+    if (p.has_fill) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) f[i] = ((int)q[i] == p.fill) ? __uint_as_float(0x7fc00000u) : f[i];
+    }
+}
 
 // One lane's VEC cells of a row, read once: non-temporal loads keep the stream from
 // displacing the plan tables and partials in L2 / Infinity Cache.

@@ -699,6 +699,29 @@ __global__ __launch_bounds__(WG) void k_validity_panel(const double* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------
+// k_unpack_i16: an int16-packed array to its float32 values by the rule of unpack_i16 (afhip_loads.h) — the one the temporal
+// kernel applies to a packed cube.  A plain stream: a lane reads four elements (8 bytes) and writes 16; the last lane of an array
+// whose length is no multiple of four takes its elements one by one.
+__global__ __launch_bounds__(WG) void k_unpack_i16(const int16_t* __restrict__ q, int64_t n, const PackArgs p, float* __restrict__ out) {
+    const int64_t e0 = ((int64_t)blockIdx.x * WG + threadIdx.x) * 4;
+    if (e0 >= n) return;
+    if (e0 + 4 <= n) {
+        const RawVec<int16_t, 4> r = *(const RawVec<int16_t, 4>*)(q + e0);
+        float f[4];
+        unpack_i16<4>(r.v, p, f);
+        typedef float f4 __attribute__((ext_vector_type(4)));
+        *(f4*)(out + e0) = f4{f[0], f[1], f[2], f[3]};
+    } else {
+        for (int64_t e = e0; e < n; ++e) {
+            const int16_t one[1] = {q[e]};
+            float f[1];
+            unpack_i16<1>(one, p, f);
+            out[e] = f[0];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // k_transform: the element-wise transforms of the staged path on a whole array — Dataset.power (`np.power(block, exp)`,
 // dataset.py:527-543), Dataset.spline's hinge (dataset.py:475-481) and Dataset.interact (`np.multiply`, dataset.py:547-563).
 // A plain stream: read x (and other), write out; a thread handles TRANSFORM_PER_THREAD elements a block apart so that

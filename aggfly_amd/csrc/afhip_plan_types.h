@@ -52,6 +52,16 @@ struct ColOp {
     double o0, o1, obase;      // outer dd/bins thresholds
 };
 
+// How an int16-packed cube (AFHIP_I16) becomes float32 values — the layout of afhip_packing (include/aggfly_hip.h), copied by value into
+// FusedArgs.  f = (float)q, then n_pairs times  f = f * mul[i];  f = f + add[i]  with every operation rounded to float32 (no fma),
+// then NaN where q == fill.  A pair half the chain does not have is sent as its exact identity — mul 1.0f, add -0.0f (x + -0 == x
+// for every x, the sign of zero included) — so the result is bit for bit that of the operations the chain does have.
+struct PackArgs {
+    int32_t n_pairs, has_fill, fill, pad;
+    float mul[3], add[3];
+};
+constexpr int MAX_PACK_PAIRS = 3;
+
 struct ChunkDesc {
     int64_t k_lo, k_hi;        // time steps [k_lo, k_hi)
     int32_t g_lo, g_hi;        // inner groups [g_lo, g_hi); k_lo == ib[g_lo], k_hi == ib[g_hi]

@@ -150,8 +150,11 @@ static int lower_columns(PlanLayout* pl) {
 }
 
 // (rows of 4 GiB and more: the short-group and arithmetic-edge variants address a row by a 32-bit byte offset per lane)
+// bytes of one stored element
+static int elem_bytes(int dtype) { return dtype == AFHIP_F64 ? 8 : (dtype == AFHIP_I16 ? 2 : 4); }
+
 static bool rows_fit_32bit(const afhip_plan_desc& d) {
-    return (uint64_t)d.n_cells * (d.dtype == AFHIP_F64 ? 8u : 4u) < (1ull << 32);
+    return (uint64_t)d.n_cells * (uint64_t)elem_bytes(d.dtype) < (1ull << 32);
 }
 
 // ---- 2. short-group form ----
@@ -375,6 +378,19 @@ static const Variant* twin_of(const Variant* v) {
     return nullptr;
 }
 
+// int16-packed cubes (AFHIP_I16) have a table of their own (packed_variants_table) of general forms on the direct-load path: the
+// widest row piece per lane the rows allow and the menu holds for the plan's shape — four cells (8 bytes, the light shapes only), else
+// two, else one.  (Four against two cells on the light shapes is the float32 rule "8 bytes per lane" carried over; not measured on
+// packed cubes yet: profiles/packed_cube.txt.)
+static const Variant* choose_packed_variant(const PlanLayout& pl) {
+    const int64_t C = pl.desc.n_cells;
+    for (int vec : {4, 2, 1}) {
+        if (C % vec != 0) continue;
+        if (const Variant* v = find_packed_variant(vec, pl.stat, pl.nthr, pl.K)) return v;
+    }
+    return nullptr;
+}
+
 // `form0` and `path0` are the short-group form and the load path the plan would take by the default rules.  Null: the menu holds
 // no variant that covers the plan.
 static const Variant* choose_variant(const PlanLayout& pl, const GroupForm& form0, const LoadPath& path0, const HistPartition& hist, bool all_bins,
@@ -417,7 +433,7 @@ static const Variant* choose_variant(const PlanLayout& pl, const GroupForm& form
     // re-reads period values worth a sizeable share of the cube.  From 5 % on the general two-level variant (outer = first) with its twin
     // is taken instead; packed bin counts (16-byte records, gathered directly) stay where they are.
     if (v->sl() && !v->tki() && tuning == 0 && !desc->exact_order && !knobs.no_region_fused &&
-        (double)desc->P * pl.K * 8.0 >= 0.05 * (double)desc->T * (desc->dtype == AFHIP_F32 ? 4.0 : 8.0)) {
+        (double)desc->P * pl.K * 8.0 >= 0.05 * (double)desc->T * (double)elem_bytes(desc->dtype)) {
         VariantQuery two = untuned;
         two.all_bins = two.single_level = two.partition = two.arith = false;
         const Variant* v2 = find_variant(two);
@@ -514,7 +530,7 @@ static int lay_chunks(PlanLayout* pl, int64_t want_chunks) {
     // splitting a period adds partial traffic (16 B per extra slot, column and cell, write +
     // read); keep it under ~5 % of the cube: extra_slots*K*16 <= 0.05*T*elem.  (2 % starved the
     // CONUS-window f32 plan of workgroups: 9 chunks 0.229 ms, 22 chunks 0.151 ms.)
-    const int64_t elem = pl->desc.dtype == AFHIP_F32 ? 4 : 8;
+    const int64_t elem = elem_bytes(pl->desc.dtype);
     const double split_frac = 0.05;
     int64_t split_budget = std::max<int64_t>(1, (int64_t)(split_frac * (double)T * (double)elem / (16.0 * std::max(1, pl->K))));
     const bool any_first = std::any_of(pl->cols.begin(), pl->cols.end(), [](const ColOp& c) { return c.outer == OUT_FIRST; });
@@ -606,7 +622,7 @@ static bool rf_plan_ok(const PlanLayout& pl, const PlanKnobs& knobs) {
     // ... and per-cell period values that would be a noticeable share of the traffic: P K 8 bytes per cell against T elem.  Below
     // ~0.2 % there is nothing to win and the emit still costs: configs[2]'s shape (40 annual values of 2 columns from 350,640
     // hourly steps: 0.05 %) measured 0.25 % behind, the one-period headline (0.06 %) 0.6 %; the shapes that gain sit at 0.5 % and up.
-    const double share = (double)desc->P * pl.K * 8.0 / std::max(1.0, (double)desc->T * (desc->dtype == AFHIP_F32 ? 4.0 : 8.0));
+    const double share = (double)desc->P * pl.K * 8.0 / std::max(1.0, (double)desc->T * (double)elem_bytes(desc->dtype));
     if (ok) ok = share >= 0.002;
     // Which forms gain was measured, not derived (profiles/r03_region_fused.txt: an occupancy rule could not tell them apart): float64
     // forms and float32 forms without threshold slots gain 3 - 50 % from two periods on; the lean four-row forms and the six-column
@@ -675,7 +691,8 @@ static int validate_desc(const afhip_plan_desc* d) {
     if (d->T < 0 || d->n_cells <= 0 || d->K <= 0 || d->G1 < 0 || d->P < 0)
         return fail(AFHIP_E_INVALID, "plan_create: bad sizes (T=%lld n_cells=%lld K=%d G1=%lld P=%lld)",
                     (long long)d->T, (long long)d->n_cells, d->K, (long long)d->G1, (long long)d->P);
-    if (d->dtype != AFHIP_F32 && d->dtype != AFHIP_F64) return fail(AFHIP_E_INVALID, "plan_create: dtype must be AFHIP_F32 or AFHIP_F64");
+    if (d->dtype != AFHIP_F32 && d->dtype != AFHIP_F64 && d->dtype != AFHIP_I16)
+        return fail(AFHIP_E_INVALID, "plan_create: dtype must be AFHIP_F32, AFHIP_F64 or AFHIP_I16");
     if (!d->inner_bounds || !d->outer_bounds || !d->columns) return fail(AFHIP_E_INVALID, "plan_create: NULL table");
     if (d->inner_bounds[0] != 0 || d->inner_bounds[d->G1] != d->T)
         return fail(AFHIP_E_INVALID, "plan_create: inner_bounds must run from 0 to T");
@@ -701,6 +718,21 @@ int build_plan(const afhip_plan_desc* desc, const DeviceFacts& dev, PlanLayout* 
     pl->desc.inner_bounds = nullptr; pl->desc.outer_bounds = nullptr; pl->desc.columns = nullptr;
     if ((rc = lower_columns(pl))) return rc;
 
+    if (desc->dtype == AFHIP_I16) {
+        // straight to the packed table: no short-group form, no histogram partition, no packed counts, and — the table has no
+        // region-fused twins — the spatial stage is the slot gather or the table-order sums
+        pl->variant = choose_packed_variant(*pl);
+        if (!pl->variant)
+            return fail(AFHIP_E_UNSUPPORTED, "no packed kernel variant for stat=%d slots=%d columns=%d", pl->stat, pl->nthr, pl->K);
+        if ((rc = build_chunks(pl, pl->variant->vec, knobs, dev))) return rc;
+        pl->variant_rf = nullptr;
+        pl->rf_plan_ok = false;
+        pl->gtab = group_table(*pl);
+        pl->pk = PackFmt{};
+        pl->packed = false;
+        workspace_sizes(pl);
+        return AFHIP_OK;
+    }
     const GroupForm form = short_group_form(*pl, knobs);
     const LoadPath path = load_path(*pl, form.pairs);
     const int tuning = usable_tuning(pl->desc);

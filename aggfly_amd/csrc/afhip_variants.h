@@ -11,7 +11,7 @@
 namespace afhip {
 
 struct Variant {
-    int dtype;    // AFHIP_F32 / AFHIP_F64
+    int dtype;    // AFHIP_F32 / AFHIP_F64; AFHIP_I16 in the packed table
     int pipe;     // 0 direct loads, 1 LDS-DMA ring
     int vec;      // cells per lane
     int stat;     // 0 none, 1 sum, 2 sum+min+max, 3 NaN-skipping sum+count+min+max
@@ -37,6 +37,9 @@ struct Variant {
 
 const Variant* variants_table(int* n);   // generated (variants_table.hip)
 const char* variants_menu();             // "full" (the production menu), "arms" (+ the tuning arms) or "dev"
+// The kernels of int16-packed cubes (AFHIP_I16; gen_variants.py: packed_menu), a table of their own (packed_table.hip): general
+// two-level forms on the direct-load path only, so a plan's stat / slots / columns and the cells per lane are all there is to match.
+const Variant* packed_variants_table(int* n);
 
 // What a lowered plan asks of the menu (afhip_planner.cpp: choose_variant).  A fallback is the same query with a field changed.
 // tuning: 0 = the default choice below; otherwise an explicit arm
@@ -87,6 +90,21 @@ inline const Variant* find_variant(const VariantQuery& q) {
         // specialised forms (integer bins, single level) are cheaper than the general one
         const long cost = (long)v.nthr * 1000 + (long)v.kmax * 10 + v.stat - (v.tki() ? 400 : 0) - (v.sl() ? 5 : 0) - (v.hb() ? 300 : 0) - (v.ha() ? 50 : 0) - (v.pair() ? 5 : 0) - 3 * v.lean()
                           + ((depth_hint > 0 && v.depth != depth_hint) ? 1 : 0);      // among equals, the burst depth that measured best for the shape
+        if (!best || cost < best_cost) { best = &v; best_cost = cost; }
+    }
+    return best;
+}
+
+// the cheapest packed kernel with `vec` cells per lane that covers the plan (null: the menu has none at that width)
+inline const Variant* find_packed_variant(int vec, int stat, int nthr, int K) {
+    const Variant* best = nullptr;
+    long best_cost = 0;
+    int n = 0;
+    const Variant* tab = packed_variants_table(&n);
+    for (int i = 0; i < n; ++i) {
+        const Variant& v = tab[i];
+        if (v.vec != vec || v.stat < stat || v.nthr < nthr || v.kmax < K) continue;
+        const long cost = (long)v.nthr * 1000 + (long)v.kmax * 10 + v.stat;
         if (!best || cost < best_cost) { best = &v; best_cost = cost; }
     }
     return best;

@@ -5,12 +5,19 @@ Usage: gen_variants.py OUTDIR [--menu full|arms|dev] [--per-file N]      (full: 
 
 Each generated ``variants_NN.hip`` holds a handful of explicit instantiations so that
 ``make -j`` compiles them in parallel; ``variants_table.hip`` collects the table that
-``find_variant`` (afhip_variants.h) searches.
+``find_variant`` (afhip_variants.h) searches.  The kernels of int16-packed cubes (`packed_menu`) go to ``packed_NN.hip`` and a
+table of their own, ``packed_table.hip`` (``packed_variants_table``): `menu` and its table count the float kernels only.
 """
 import os
 import sys
 
-CT = {0: "float", 1: "double"}
+CT = {0: "float", 1: "double", 2: "PackedI16"}
+I16 = 2        # AFHIP_I16: int16 storage, float32 values
+# packed_menu: the (cells per lane, stat, slots, columns) it leaves out, because their kernels hold scratch memory
+# (-Rpass-analysis=kernel-resource-usage): the all-purpose (stat 3) sixteen-column forms at two cells per lane (272 bytes per lane, like
+# their float32 twins) and one four-cell form (36).  A plan of such a shape takes the next narrower kernel, which has none.
+PACKED_DROPPED = {(2, 3, nthr, 16) for nthr in (0, 1, 4, 16)} | {(4, 3, 1, 6)}
+PACKED_SHALLOW = {(1, 3, 16, 16)}      # ... and the one that keeps eight rows in flight where its width takes sixteen: 36 bytes of scratch at sixteen (and at twelve)
 
 
 class Feat:
@@ -174,6 +181,27 @@ def menu(kind):
     return out
 
 
+def packed_menu(kind):
+    """The kernels of int16-packed cubes (storage tag PackedI16), same tuples as `menu`: the general two-level forms on the direct-load
+    path with nt loads — no short-group, lean, single-level, integer-bin, histogram or region-fused form.  Every shape at two cells and
+    at one cell per lane (4 / 2 bytes per lane and row); the light shapes also at four (8 bytes, what a float32 lane reads at two cells).
+    Rows in flight: eight at four cells per lane — 64 bytes per lane, the float32 production forms' — and sixteen at two and one,
+    whose rows are half and a quarter of that (PACKED_SHALLOW: one exception).  Chosen from -Rpass-analysis=kernel-resource-usage, not from a measurement: no kernel of the menu has scratch memory
+    (PACKED_DROPPED; profiles/packed_cube.txt has the register table)."""
+    def one(vec, stat, nthr, kmax):
+        feat = {0: 0, 1: 0, 2: Feat.SINE, 3: Feat.SINE | Feat.GENERAL_TF}[stat] | Feat.NT
+        return (I16, 0, vec, stat, nthr, kmax, 8 if (vec == 4 or (vec, stat, nthr, kmax) in PACKED_SHALLOW) else 16, feat, 1)
+
+    if kind == "dev":
+        return [one(1, 3, 16, 16), one(4, 1, 1, 6)]
+    shapes_all = [(stat, nthr, kmax) for stat in (0, 1, 3) for nthr in (0, 1, 4, 16) for kmax in (2, 6, 16)
+                  if not (stat == 0 and nthr == 0)] + [(2, 0, 2), (2, 0, 6)]
+    light = [(stat, nthr, kmax) for stat in (0, 1, 3) for nthr in (0, 1) for kmax in (2, 6) if not (stat == 0 and nthr == 0)] + [(2, 0, 2), (2, 0, 6)]
+    out = [one(vec, *sh) for vec in (2, 1) for sh in shapes_all] + [one(4, *sh) for sh in light]
+    # ... and no kernel that no plan can select (`pickable`: two-column shapes with more threshold slots than two columns lower to)
+    return [v for v in out if v[2:6] not in PACKED_DROPPED and pickable(v)]
+
+
 def pickable(v):
     """False for a kernel that no plan can select by the planner's default rules (afhip_planner.cpp: the stage named in each comment), whatever its shape."""
     dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod = v
@@ -192,7 +220,7 @@ def pickable(v):
 
 def name_of(v):
     dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod = v
-    return (f"{'f32' if dtype == 0 else 'f64'}_p{pipe}_v{vec}_s{stat}_t{nthr}_k{kmax}_d{depth}"
+    return (f"{('f32', 'f64', 'i16')[dtype]}_p{pipe}_v{vec}_s{stat}_t{nthr}_k{kmax}_d{depth}"
             + "".join("_ss" if bit == Feat.LEAN and feat & Feat.LEAN_SINE else sfx for bit, sfx in SUFFIXES if feat & bit))
 
 
@@ -226,6 +254,31 @@ class _KeepIfSame:
         return False
 
 
+def write_units(outdir, vs, per_file, stem):
+    """The translation units of the kernels `vs`, `per_file` to a file: (file names, number of files)."""
+    files = []
+    ngroups = 0
+    for i in range(0, len(vs), per_file):
+        group = vs[i:i + per_file]
+        idx = i // per_file
+        ngroups += 1
+        fn = os.path.join(outdir, f"{stem}_{idx:02d}.hip")
+        with _KeepIfSame(fn) as f:
+            f.write("// generated by gen_variants.py — do not edit\n")
+            f.write('#include "afhip_kernels.h"\n#include "afhip_variants.h"\n')
+            f.write("namespace afhip {\n")
+            for v in group:
+                f.write(f"template __global__ void {inst(v)}(const FusedArgs);\n")
+            # host-only registration: kernel handles are taken in the TU that defines them
+            f.write(f"int register_{stem}_{idx:02d}(Variant* out) {{\n    int n = 0;\n")
+            for v in group:
+                dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod = v
+                f.write(f"    out[n++] = Variant{{{dtype}, {pipe}, {vec}, {stat}, {nthr}, {kmax}, {depth}, {feat}, {prod}, (const void*)&{inst(v)}, \"{name_of(v)}\"}};\n")
+            f.write("    return n;\n}\n}\n")
+        files.append(fn)
+    return files, ngroups
+
+
 def main():
     outdir = sys.argv[1]
     kind = "full"
@@ -239,26 +292,10 @@ def main():
             per_file = int(args.pop(0))
     os.makedirs(outdir, exist_ok=True)
     vs = menu(kind)
-    files = []
-    ngroups = 0
-    for i in range(0, len(vs), per_file):
-        group = vs[i:i + per_file]
-        idx = i // per_file
-        ngroups += 1
-        fn = os.path.join(outdir, f"variants_{idx:02d}.hip")
-        with _KeepIfSame(fn) as f:
-            f.write("// generated by gen_variants.py — do not edit\n")
-            f.write('#include "afhip_kernels.h"\n#include "afhip_variants.h"\n')
-            f.write("namespace afhip {\n")
-            for v in group:
-                f.write(f"template __global__ void {inst(v)}(const FusedArgs);\n")
-            # host-only registration: kernel handles are taken in the TU that defines them
-            f.write(f"int register_variants_{idx:02d}(Variant* out) {{\n    int n = 0;\n")
-            for v in group:
-                dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod = v
-                f.write(f"    out[n++] = Variant{{{dtype}, {pipe}, {vec}, {stat}, {nthr}, {kmax}, {depth}, {feat}, {prod}, (const void*)&{inst(v)}, \"{name_of(v)}\"}};\n")
-            f.write("    return n;\n}\n}\n")
-        files.append(fn)
+    files, ngroups = write_units(outdir, vs, per_file, "variants")
+    pvs = packed_menu(kind)
+    pfiles, pgroups = write_units(outdir, pvs, per_file, "packed")
+    files += pfiles
     with _KeepIfSame(os.path.join(outdir, "variants_table.hip")) as f:
         f.write("// generated by gen_variants.py — do not edit\n")
         f.write('#include "afhip_variants.h"\n')
@@ -273,7 +310,18 @@ def main():
         for g in range(ngroups):
             f.write(f"        c += register_variants_{g:02d}(g_table + c);\n")
         f.write("        g_count = c;\n    }\n    *n = g_count;\n    return g_table;\n}\n}\n")
-    print(" ".join(os.path.basename(x) for x in files + [os.path.join(outdir, 'variants_table.hip')]))
+    with _KeepIfSame(os.path.join(outdir, "packed_table.hip")) as f:
+        f.write("// generated by gen_variants.py — do not edit\n")
+        f.write('#include "afhip_variants.h"\n')
+        f.write("namespace afhip {\n")
+        for g in range(pgroups):
+            f.write(f"int register_packed_{g:02d}(Variant* out);\n")
+        f.write(f"static Variant g_packed[{max(len(pvs), 1)}];\nstatic int g_packed_count = -1;\n")
+        f.write("const Variant* packed_variants_table(int* n) {\n    if (g_packed_count < 0) {\n        int c = 0;\n")
+        for g in range(pgroups):
+            f.write(f"        c += register_packed_{g:02d}(g_packed + c);\n")
+        f.write("        g_packed_count = c;\n    }\n    *n = g_packed_count;\n    return g_packed;\n}\n}\n")
+    print(" ".join(os.path.basename(x) for x in files + [os.path.join(outdir, 'variants_table.hip'), os.path.join(outdir, 'packed_table.hip')]))
 
 
 if __name__ == "__main__":

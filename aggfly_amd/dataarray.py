@@ -21,7 +21,9 @@ from .timegroups import as_time_index
 
 
 def _is_torch(x):
-    return type(x).__module__.startswith("torch")
+    """A torch tensor — or a `packed.PackedCube`, which offers the tensor methods this module uses (views and indexing on the
+    stored integers, scalar arithmetic folded into its unpack rule, everything else on the materialised values)."""
+    return type(x).__module__.startswith("torch") or getattr(type(x), "_aggfly_packed", False)
 
 
 class DataArray:

@@ -23,6 +23,7 @@ import numpy as np
 import pandas as pd
 
 from .dataarray import DataArray, _is_torch, from_any
+from .packed import is_packed
 
 
 def lon_to_180(lon):
@@ -150,12 +151,26 @@ class Dataset:
         return da.isel(time=t.sel_positions(time_sel))       # CF calendar: year / month / day granular, like xarray
 
     # ---- the engine's view ----
+    @property
+    def is_packed(self) -> bool:
+        """The cube is held as stored int16 (`packed.PackedCube`): the kernels unpack it as they read it."""
+        return is_packed(self.da.data)
+
+    def packed_cube(self):
+        """The (time, latitude, longitude) `packed.PackedCube` of a packed dataset, C-contiguous — what the kernels stream."""
+        if not self.is_packed:
+            raise ValueError("the dataset is not packed")
+        return self.da.transpose("time", "latitude", "longitude").data.contiguous()
+
     def cube(self):
         """(time, latitude, longitude) array, C-contiguous — what the kernels stream.
 
         ``da`` is normally a permuted view of exactly that layout (stores are time-major), so
-        this is free; otherwise one copy is made."""
+        this is free; otherwise one copy is made.  A packed dataset (`is_packed`) gives its float32 VALUES, materialised in
+        HBM by every call and not kept (`packed_cube` is what its kernels read)."""
         d = self.da.transpose("time", "latitude", "longitude").data
+        if is_packed(d):
+            return d.contiguous().materialize()
         if _is_torch(d):
             return d.contiguous()
         return np.ascontiguousarray(d)
@@ -163,7 +178,7 @@ class Dataset:
     def to_device(self, device="cuda"):
         """Move the cube into HBM once (float32 / float64 kept as stored)."""
         import torch
-        d = self.cube()
+        d = self.packed_cube() if self.is_packed else self.cube()
         if not _is_torch(d):
             d = torch.from_numpy(d)      # a plain pageable copy already runs at PCIe rate here (~56 GB/s measured)
         d = d.to(device, non_blocking=True)

@@ -164,9 +164,13 @@ def lower_spec(key: str, steps):
 # device residency and caches
 # --------------------------------------------------------------------------------------
 def device_cube(dataset: Dataset):
-    """The dataset's (time, lat, lon) cube as an HBM tensor (uploaded if still on the host)."""
+    """The dataset's (time, lat, lon) cube as an HBM tensor (uploaded if still on the host) — of a packed dataset
+    (`Dataset.is_packed`) the `packed.PackedCube` itself: the plans read the stored int16."""
     import torch
     hip.require_gpu()
+    if dataset.is_packed:
+        d = dataset.packed_cube()
+        return d if d.is_cuda else d.cuda(non_blocking=True)
     d = dataset.cube()
     if not _is_torch(d):
         if d.dtype not in (np.float32, np.float64):
@@ -184,7 +188,7 @@ def dataset_device(dataset) -> int:
     cube: the device its plans and weight tables must be created on."""
     d = getattr(getattr(dataset, "da", None), "data", None)
     if d is not None and _is_torch(d) and d.is_cuda:
-        return hip._device_index(d)
+        return hip._device_index(d.device)
     return hip._device_index(None)
 
 
@@ -433,7 +437,7 @@ def _run_fused_pass(cube, cols, ib, ob, csr=None, want_cells=True, exact_order=N
     T = int(cube.shape[0])
     n_cells = int(cube[0].numel()) if T else int(np.prod(cube.shape[1:]))
     code = hip._dtype_code(cube)
-    f32_rules = config.match_reference_f32 and code == hip.F32
+    f32_rules = config.match_reference_f32 and code in (hip.F32, hip.I16)      # a packed cube's values are float32
     cdicts = [_column_dict(c, f32_rules) for c in cols]
     try:
         plan = get_plan(T, n_cells, code, ib, ob, cdicts, exact_order, device=cube.device)
@@ -448,6 +452,8 @@ def _run_fused_pass(cube, cols, ib, ob, csr=None, want_cells=True, exact_order=N
     with plan.lock:                     # bind + enqueue as one step: another thread's call on this plan binds its own second cubes
         for j, other in inters.items():
             plan.bind_inter(j, other)
+        if code == hip.I16:             # ... and its own cube's unpack rule
+            plan.bind_packing(cube.packing())
         if csr is not None:
             out = plan.run(cube, csr, want_cells=want_cells)
             return [PassResult([c.key for c in cols], None, plan, out.get("cells"), out)]

@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("AGGFLY_HIP_LIB") or os.path.join(_HERE, "libaggfly_hi
 
 # codes (include/aggfly_hip.h)
 F32, F64 = 0, 1
+I16 = 2                         # AFHIP_I16: int16 storage, float32 values (a `packed.PackedCube`; plans only)
 MEAN, SUM, MIN, MAX, NANMEAN, DD, BINS, SINE_DD, IDENTITY = range(9)
 TF_NONE, TF_POW, TF_HINGE, TF_INTER = 0, 1, 2, 3
 ROUND_INNER, ROUND_HINGE, ROUND_FINAL = 1, 2, 4
@@ -36,6 +37,7 @@ EXPORTS = (
     "afhip_plan_describe", "afhip_plan_run_temporal", "afhip_plan_run",
     "afhip_plan_profile_begin", "afhip_plan_profile_end", "afhip_plan_bind_inter", "afhip_csr_device", "afhip_plan_device", "afhip_transform", "afhip_panel_divide", "afhip_lz4_decode_streams", "afhip_unshuffle_blocks", "afhip_read_probe",
     "afhip_zstd_scratch_bytes", "afhip_zstd_decode", "afhip_inflate_scratch_bytes", "afhip_inflate_decode", "afhip_bitunshuffle_blocks",
+    "afhip_plan_bind_packing", "afhip_unpack_i16",
 )
 
 
@@ -58,6 +60,12 @@ class PlanDesc(C.Structure):
                 ("G1", C.c_int64), ("inner_bounds", C.POINTER(C.c_int64)),
                 ("P", C.c_int64), ("outer_bounds", C.POINTER(C.c_int64)),
                 ("columns", C.POINTER(Column)), ("exact_order", C.c_int32), ("tuning", C.c_int32)]
+
+
+class Packing(C.Structure):
+    """``afhip_packing``: how an int16-packed cube becomes float32 values (`packed.PackedCube.packing`)."""
+    _fields_ = [("n_pairs", C.c_int32), ("has_fill", C.c_int32), ("fill", C.c_int32), ("pad", C.c_int32),
+                ("mul", C.c_float * 3), ("add", C.c_float * 3)]
 
 
 _lib = None
@@ -125,6 +133,8 @@ def load():
     lib.afhip_plan_profile_end.restype = i64
     lib.afhip_csr_device.argtypes = [vp]
     lib.afhip_plan_device.argtypes = [vp]
+    lib.afhip_plan_bind_packing.argtypes = [vp, C.POINTER(Packing)]
+    lib.afhip_unpack_i16.argtypes = [vp, i64, C.POINTER(Packing), vp, vp]
     _lib = lib
     return lib
 
@@ -145,7 +155,8 @@ def device_count() -> int:
 
 
 def build_info() -> dict:
-    """What the loaded build holds: {"menu": "full" | "arms" | "dev", "variants", "arms", "region_fused_twins", "abi"} (`afhip_build_info`)."""
+    """What the loaded build holds: {"menu": "full" | "arms" | "dev", "variants", "arms", "region_fused_twins", "abi", "packed_variants"}
+    (`afhip_build_info`; the first three counts are of the float32 / float64 kernels, the last of those for int16-packed cubes)."""
     buf = C.create_string_buffer(256)
     load().afhip_build_info(buf, 256)
     out = dict(kv.split("=") for kv in buf.value.decode().split())
@@ -163,6 +174,8 @@ def read_probe(cube, launches: int = 10):
     """`afhip_read_probe`: per-launch ms of a bare streaming read of ``cube`` ([T, ...] HBM tensor, rows of a multiple of 8 bytes)
     with the temporal kernels' access pattern — this box's read ceiling for the shape."""
     require_gpu()
+    if _is_packed(cube):                  # the bare read of a packed cube is that of its stored integers
+        cube = cube.q
     cube, T, n_cells = _dev_cube(cube)
     ms = (C.c_float * int(launches))()
     _check(load().afhip_read_probe(cube.data_ptr(), T, n_cells * cube.element_size(), int(launches), ms, _stream_ptr(cube)))
@@ -288,8 +301,34 @@ class _on_device:
         return False
 
 
+def _is_packed(t) -> bool:
+    from .packed import PackedCube
+    return isinstance(t, PackedCube)
+
+
+def _ptr(t):
+    """Device address of a cube: a tensor's, or a `packed.PackedCube`'s integers (the holder itself has no ``data_ptr``)."""
+    return t.q.data_ptr() if _is_packed(t) else t.data_ptr()
+
+
+def unpack_i16(cube):
+    """`afhip_unpack_i16`: the float32 values of a `packed.PackedCube` as a new HBM tensor of its shape."""
+    torch = _torch()
+    require_gpu()
+    q = cube.q if cube.q.is_cuda else cube.q.cuda(non_blocking=True)
+    q = q.contiguous()
+    if q.data_ptr() % 8:                  # a view that starts inside an 8-byte piece (the kernel reads 8 bytes per lane)
+        q = q.clone()
+    out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+    p = cube.packing()
+    _check(load().afhip_unpack_i16(q.data_ptr(), q.numel(), C.byref(p), out.data_ptr(), _stream_ptr(q)))
+    return out
+
+
 def _dtype_code(t) -> int:
     torch = _torch()
+    if _is_packed(t):
+        return I16
     if t.dtype == torch.float32:
         return F32
     if t.dtype == torch.float64:
@@ -314,6 +353,8 @@ def _group(fn_name, cube, bounds, code=None, ddargs=None):
     torch = _torch()
     lib = load()
     require_gpu()
+    if _is_packed(cube):
+        raise TypeError("the grouped reducers read float32 / float64 cubes: materialize() a packed cube first, or run it through a FusedPlan")
     cube, T, n_cells = _dev_cube(cube)
     bounds = _i64(bounds)
     G = len(bounds) - 1
@@ -342,6 +383,8 @@ def transform(x, kind: str, arg: float = 0.0, other=None, out_dtype=None):
     torch = _torch()
     lib = load()
     require_gpu()
+    if _is_packed(x):
+        x = x.materialize()
     if not x.is_cuda:
         raise HipEngineError("transform: the array must be resident in HBM (a CUDA/HIP tensor)")
     x = x.contiguous()
@@ -526,6 +569,10 @@ class FusedPlan:
         _check(load().afhip_plan_bind_inter(self._h, int(column), other.data_ptr(), _dtype_code(other)))
         self._inter[int(column)] = other
 
+    def bind_packing(self, packing: Packing):
+        """Bind the unpack rule of the int16-packed cube the next runs read (``dtype_code`` `I16` plans; `afhip_plan_bind_packing`)."""
+        _check(load().afhip_plan_bind_packing(self._h, C.byref(packing)))
+
     def describe(self) -> str:
         buf = C.create_string_buffer(2048)
         load().afhip_plan_describe(self._h, buf, 2048)
@@ -568,7 +615,7 @@ class FusedPlan:
         cube = self._check_cube(cube)
         cells = torch.empty((self.K, self.P, self.n_cells), dtype=torch.float64, device=cube.device)
         ws = self._workspace(self.workspace_bytes(), cube.device)
-        _check(load().afhip_plan_run_temporal(self._h, cube.data_ptr(), cells.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(cube)))
+        _check(load().afhip_plan_run_temporal(self._h, _ptr(cube), cells.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(cube)))
         return cells
 
     def run(self, cube, csr: CSR, want_cells=False, timed=False, out=None, workspace=None):
@@ -602,7 +649,7 @@ class FusedPlan:
             elif workspace.numel() * workspace.element_size() < need or not workspace.is_cuda:
                 raise ValueError(f"workspace must be an HBM tensor of >= {need} bytes")
             ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-        _check(load().afhip_plan_run(self._h, cube.data_ptr(), csr.handle, out["num"].data_ptr(),
+        _check(load().afhip_plan_run(self._h, _ptr(cube), csr.handle, out["num"].data_ptr(),
                                      out["den"].data_ptr(), out["res"].data_ptr(), cells_ptr, ws_ptr, ws_bytes,
                                      _stream_ptr(cube), ms))
         if timed:

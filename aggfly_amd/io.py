@@ -438,15 +438,35 @@ def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: in
     return cube
 
 
-def zarr_to_device(path: str, var: str, device="cuda", threads: int = 16, slab_bytes: int = 128 << 20, t_range=None, yx_box=None):
+def zarr_to_device(path: str, var: str, device="cuda", threads: int = 16, slab_bytes: int = 128 << 20, t_range=None, yx_box=None, keep_packed=False):
     """Decode a time-major Zarr array straight into HBM.  Returns (tensor, ZarrArray)."""
-    return array_to_device(ZarrArray(os.path.join(path, var)), device, threads, slab_bytes, t_range, yx_box)
+    return array_to_device(ZarrArray(os.path.join(path, var)), device, threads, slab_bytes, t_range, yx_box, keep_packed)
 
 
-def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 << 20, t_range=None, yx_box=None):
+def keep_packed_requested(keep_packed=False) -> bool:
+    """``keep_packed=True`` of `dataset_from_path`, or AGGFLY_HIP_KEEP_PACKED=1 in the environment (the way in for the CLI)."""
+    return bool(keep_packed) or os.environ.get("AGGFLY_HIP_KEEP_PACKED", "0") == "1"
+
+
+def packing_of(za):
+    """(scale_factor, add_offset, fill value) under which a streamed array can stay packed in HBM (`packed.PackedCube`), or None:
+    int16 storage only, and a fill value — if any — that is a stored integer."""
+    if np.dtype(za.dtype) != np.dtype(np.int16):
+        return None
+    fv = _attr_fill(za.attrs)
+    if fv is not None and isinstance(fv, float) and np.isnan(fv):
+        fv = None
+    if fv is not None and (int(fv) != fv or not -32768 <= int(fv) <= 32767):
+        return None
+    sf, ao = za.attrs.get("scale_factor"), za.attrs.get("add_offset")
+    return (None if sf is None else float(sf), None if ao is None else float(ao), None if fv is None else int(fv))
+
+
+def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 << 20, t_range=None, yx_box=None, keep_packed=False):
     """Stream a chunked (time, y, x) array — a `ZarrArray` or an `hdf5.ChunkSource` — straight into HBM: each
     slab is a whole number of time chunks, decoded chunk-parallel by the native codec into page-locked memory
-    and uploaded while the next slab decodes.  Returns (tensor, source)."""
+    and uploaded while the next slab decodes.  Returns (tensor, source).  ``keep_packed`` (int16 storage, `packing_of`): the
+    tensor stays int16 as stored — the CF unpacking in HBM is skipped and left to the kernels that read a `packed.PackedCube`."""
     if len(za.shape) != 3:
         raise ValueError("zarr_to_device expects a (time, y, x) array")
     if os.environ.get("AGGFLY_HIP_SLAB_MB"):                       # tuning knob (scripts/e2e_bench.py sweeps it)
@@ -527,6 +547,8 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
             dst.add_(ao)
 
     need_post = has_fv or packed
+    if keep_packed and packing_of(za) is not None:
+        need_post, out_np = False, za.dtype
     if t_range is not None and tuple(t_range) == (0, T):
         t_range = None
     if yx_box is not None and tuple(yx_box) == (0, ny, 0, nx):
@@ -1544,10 +1566,12 @@ def _open_npz(path, var):
     return DataArray(data, dims, {"time": time, "latitude": z["latitude"], "longitude": z["longitude"]}, name=var)
 
 
-def _open_hdf5(path, var, xycoords=("longitude", "latitude"), timecoord="time"):
+def _open_hdf5(path, var, xycoords=("longitude", "latitude"), timecoord="time", keep_packed=False):
     """netCDF-4 / HDF5 containers through the built-in reader (`hdf5.py`): variable, CF mask / scale, coordinates
     by dimension name (``DIMENSION_LIST``; for plain HDF5 files without dimension scales, by matching the axis
-    lengths to the 1-D datasets named like the coordinates)."""
+    lengths to the 1-D datasets named like the coordinates).  ``keep_packed``: an int16-packed variable (`packing_of`) is
+    left as stored, in a `packed.PackedCube` on the host — for variables the streaming route does not take (contiguous
+    layout), whose one upload then moves 2 bytes per value."""
     from . import hdf5
     with hdf5.H5File(path) as f:
         if var not in f.datasets:
@@ -1564,7 +1588,11 @@ def _open_hdf5(path, var, xycoords=("longitude", "latitude"), timecoord="time"):
             dims = tuple(dims)
         attrs = {k: (v.item() if isinstance(v, np.generic) else v) for k, v in ds.attrs.items()
                  if k not in ("DIMENSION_LIST", "REFERENCE_LIST", "CLASS", "NAME", "_Netcdf4Dimid", "_Netcdf4Coordinates")}
-        data = _cf_mask_scale(ds.read(), attrs)
+        if keep_packed and packing_of(ds) is not None:
+            from .packed import PackedCube
+            data = PackedCube(np.ascontiguousarray(ds.read()), *packing_of(ds))
+        else:
+            data = _cf_mask_scale(ds.read(), attrs)
         coords = {}
         for d in dims:
             if d in f.datasets and len(f.datasets[d].shape) == 1:
@@ -1647,7 +1675,7 @@ def _band_of_box(dims, shape, xycoords, box, lat_window):
     return tuple(out)
 
 
-def _hdf5_to_device(path, var, xycoords, timecoord, time_sel, georegions, lon_is_360, device, time_window=None):
+def _hdf5_to_device(path, var, xycoords, timecoord, time_sel, georegions, lon_is_360, device, time_window=None, keep_packed=False):
     """A chunked netCDF-4 variable through the streaming route (native inflate + unshuffle, GPU-side placement);
     None when the variable does not qualify (contiguous, not time-leading, ...): the host route then reads it."""
     from . import hdf5
@@ -1670,9 +1698,12 @@ def _hdf5_to_device(path, var, xycoords, timecoord, time_sel, georegions, lon_is
             window = _time_window(coords[timecoord], time_sel) if time_sel is not None and timecoord in coords else None
         box = _clip_box(src.dims, coords, xycoords, georegions, lon_is_360) if georegions is not None else None
         try:
-            data, _ = array_to_device(src, device=device, t_range=window, yx_box=box)
+            data, _ = array_to_device(src, device=device, t_range=window, yx_box=box, keep_packed=keep_packed)
         except ValueError:
             return None
+        if keep_packed and packing_of(src) is not None:
+            from .packed import PackedCube
+            data = PackedCube(data, *packing_of(src))
         if window is not None:
             coords[timecoord] = coords[timecoord][window[0]:window[1]]
         if box is not None:
@@ -1716,7 +1747,7 @@ def _time_window(tindex, time_sel):
 def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="time", time_sel=None,
                       georegions=None, lon_is_360=True, time_fix=False, preprocess=None, name=None,
                       chunks=None, preprocess_at_load=False, parallel=True, device=None, time_window=None, lat_window=None,
-                      **kwargs) -> Dataset:
+                      keep_packed=False, **kwargs) -> Dataset:
     """`dataset_from_path` (`dataset.py:636-740`), same signature.  ``chunks`` / ``parallel``
     are accepted and ignored (there is no dask graph); a list / glob of paths is concatenated
     along time like ``open_mfdataset``.  ``device="cuda"`` (extension) streams a single float
@@ -1724,8 +1755,14 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
     (extension, streaming route only) restricts the read to those time steps — what a rank of a time-sharded
     job asks for (`distributed.aggregate_store_sharded`); ``lat_window=(j0, j1)`` (extension) keeps rows ``j0..j1`` of the
     latitude axis AFTER the clip to the regions' extent — the band of a cell-sharded job
-    (`distributed.aggregate_store_cells`); on the streaming route only the chunks that touch the band are read."""
+    (`distributed.aggregate_store_cells`); on the streaming route only the chunks that touch the band are read.
+    ``keep_packed=True`` (extension; or AGGFLY_HIP_KEEP_PACKED=1): an int16-packed variable (``scale_factor`` / ``add_offset`` /
+    ``_FillValue``) stays packed in HBM as a `packed.PackedCube` — half the memory, half the bytes the temporal kernel reads — and
+    ``preprocess`` folds into its unpack rule.  Honoured on the streaming routes (``device=``) only, for int16 storage, and for several
+    stores only when all share their packing (yearly ERA5 files usually do not: they take the float32 route); ``Dataset.is_packed``
+    tells which route was taken."""
     import glob
+    keep_packed = keep_packed_requested(keep_packed)
     if isinstance(path, str) and "://" in path:
         raise ImportError(f"remote stores ({path.split('://')[0]}://) need fsspec backends that are not available here")
     paths = sorted(glob.glob(path)) if isinstance(path, str) and "*" in path else (list(path) if isinstance(path, (list, tuple)) else [path])
@@ -1733,6 +1770,10 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
         raise FileNotFoundError(path)
     engine = kwargs.pop("engine", None)
     if device is not None and all(engine == "zarr" or (engine is None and _looks_like_zarr(p)) for p in paths):
+
+        # several stores stay packed only under ONE packing: one rule unpacks the whole concatenated cube
+        packings = {packing_of(ZarrArray(os.path.join(p_, var))) for p_ in paths} if keep_packed else {None}
+        stay_packed = len(packings) == 1 and None not in packings
 
         def part_to_device(path1):
             za = ZarrArray(os.path.join(path1, var))
@@ -1761,7 +1802,7 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
                     raise ValueError("lat_window on a non-contiguous clip goes through the host route")
             if lat_window is not None:
                 box = _band_of_box(za.dims, za.shape, xycoords, box, lat_window)
-            data, za = zarr_to_device(path1, var, device=device, t_range=window, yx_box=box)
+            data, za = zarr_to_device(path1, var, device=device, t_range=window, yx_box=box, keep_packed=stay_packed)
             if window is not None:
                 coords[timecoord] = coords[timecoord][window[0]:window[1]]
             if box is not None:
@@ -1788,12 +1829,15 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
         except ValueError:
             data = None
         if data is not None:
+            if stay_packed:
+                from .packed import PackedCube
+                data = PackedCube(data, *packings.copy().pop())
             da = DataArray(data, za.dims, coords, name=var, attrs=za.attrs)
             # a band was cut out of the already clipped box: the clip is not repeated on the band's own grid
             return Dataset(da, xycoords=xycoords, timecoord=timecoord, time_sel=time_sel, lon_is_360=lon_is_360,
                            preprocess=preprocess, georegions=None if lat_window is not None else georegions, time_fix=time_fix, name=name)
     if device is not None and lat_window is None and len(paths) == 1 and engine in (None, "netcdf4", "h5netcdf") and _is_hdf5(paths[0]):
-        got = _hdf5_to_device(paths[0], var, xycoords, timecoord, time_sel, georegions, lon_is_360, device, time_window)
+        got = _hdf5_to_device(paths[0], var, xycoords, timecoord, time_sel, georegions, lon_is_360, device, time_window, keep_packed)
         if got is not None:
             data, src, coords = got
             da = DataArray(data, src.dims, coords, name=var, attrs=src.attrs)
@@ -1806,7 +1850,8 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
         elif p.endswith(".npz"):
             da = _open_npz(p, var)
         elif _is_hdf5(p):
-            da = _open_hdf5(p, var, xycoords, timecoord)
+            # (a packed variable outside the streaming route stays packed for its one upload: a single file bound for a device)
+            da = _open_hdf5(p, var, xycoords, timecoord, keep_packed=keep_packed and device is not None and len(paths) == 1)
         else:
             da = _open_netcdf3(p, var)
         if preprocess is not None and (preprocess_at_load or len(paths) > 1):

@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+"""An int16-packed cube against its float32 unpacking, on the configs[1] shape (T = 8760 x 309,600 cells), in ONE process.
+
+The stored integers are synthesised in HBM (an ERA5-like seasonal + diurnal field in steps of 0.0017 K around 281.3 K, then
+- 273.15 as a second pair); the float32 cube is `PackedCube.materialize()` of them — what the default device route holds for the
+same store.  Three plans: the K = 5 polynomial columns of configs[1], four degree-day thresholds, thirteen 5-degree bins.  For
+each plan: the temporal kernel's ms on the packed and on the float32 cube (HIP-event pairs around the kernel,
+`afhip_plan_profile_*`; `--launches` back to back after `--warmup`; min / median / max), the bare read of each cube
+(`hip.read_probe`), the kernel variants, and the largest relative difference of the two panels.
+
+    python scripts/packed_bench.py [--out profiles/packed_cube_measured.txt]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+import aggfly_amd as af  # noqa: E402
+from aggfly_amd import hip, synth  # noqa: E402
+
+
+def plans_columns():
+    edges = np.arange(-20, 50, 5.0)
+    return {
+        "configs[1] K=5: dd[10,30] + mean -> power[1..4] -> sum": (
+            [dict(inner="dd", inner_args=(10, 30, 0), outer="sum")] +
+            [dict(inner="mean", transform="pow", transform_arg=e, outer="sum") for e in (1, 2, 3, 4)], False),
+        "4 degree-day thresholds -> sum": ([dict(inner="dd", inner_args=(float(t), float(t) + 10, 0), outer="sum") for t in (0, 8, 16, 24)], False),
+        "13 bins of 5 degC (single level)": ([dict(inner="bins", inner_args=(edges[i], edges[i + 1], 0)) for i in range(13)], True),
+    }
+
+
+def stored_cube(T, ny, nx, spd):
+    g = torch.Generator(device="cuda").manual_seed(1)
+    q = torch.empty((T, ny, nx), dtype=torch.int16, device="cuda")
+    lat = torch.linspace(0.6, 1.4, ny, device="cuda", dtype=torch.float32)[None, :, None]
+    for k0 in range(0, T, 512):
+        k1 = min(T, k0 + 512)
+        noise = torch.randn((k1 - k0, ny, nx), generator=g, device="cuda", dtype=torch.float32)
+        k = torch.arange(k0, k1, device="cuda", dtype=torch.float32)
+        base = 15.0 + 12.0 * torch.sin(2 * np.pi * torch.floor(k / spd) / 365.0) + 6.0 * torch.sin(2 * np.pi * (k % spd) / spd - np.pi / 2)
+        celsius = base[:, None, None] * lat + 3.0 * noise
+        q[k0:k1] = torch.clamp(torch.round((celsius + 273.15 - 281.3) / 0.0017), -32766, 32767).to(torch.int16)
+    return q
+
+
+def stats(ms):
+    return f"min {min(ms):.4f}  median {float(np.median(ms)):.4f}  max {max(ms):.4f} ms"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--T", type=int, default=8760)
+    ap.add_argument("--ny", type=int, default=215)
+    ap.add_argument("--nx", type=int, default=1440)
+    ap.add_argument("--spd", type=int, default=24)
+    ap.add_argument("--regions", type=int, default=3100)
+    ap.add_argument("--launches", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    C = a.ny * a.nx
+    packed = af.PackedCube(stored_cube(a.T, a.ny, a.nx, a.spd), scale_factor=0.0017, add_offset=281.3, fill_value=-32767) - 273.15
+    plain = packed.materialize()
+    say(f"cube T={a.T} x {a.ny} x {a.nx} = {C} cells: packed {packed.nbytes() / 1e9:.2f} GB (int16, pairs {packed.pairs}), "
+        f"float32 {plain.numel() * 4 / 1e9:.2f} GB; device {hip.device_info(hip._device_index(plain))['name']}; build {hip.build_info()}")
+    for name, cube in (("packed", packed), ("float32", plain)):
+        ms = hip.read_probe(cube, launches=a.launches)[a.warmup // 2:]
+        nbytes = a.T * C * (2 if name == "packed" else 4)
+        say(f"bare read, {name:8s}: {stats(ms)}   ({nbytes / min(ms) / 1e9:.2f} TB/s at the minimum)")
+    wdf = synth.weights_table(a.ny, a.nx, a.regions, seed=7)
+    R = int(wdf["index_right"].max()) + 1
+    csr = hip.CSR(wdf["index_right"].to_numpy(), wdf["cell_id"].to_numpy(), wdf["weight"].to_numpy(), R, C)
+    ib0 = synth.hourly_bounds(a.T, a.spd)
+    for title, (cols, single) in plans_columns().items():
+        ib, ob = (np.array([0, a.T]), np.array([0, 1])) if single else (ib0, np.array([0, len(ib0) - 1]))
+        say()
+        say(title)
+        med, res = {}, {}
+        for name, cube, code in (("packed", packed, hip.I16), ("float32", plain, hip.F32)):
+            p = hip.FusedPlan(a.T, C, code, ib, ob, cols)
+            if code == hip.I16:
+                p.bind_packing(cube.packing())
+            out = p.run(cube, csr)
+            for _ in range(a.warmup):
+                p.run(cube, csr, out=out)
+            torch.cuda.synchronize()
+            p.profile_begin(a.launches)
+            for _ in range(a.launches):
+                p.run(cube, csr, out=out)
+            torch.cuda.synchronize()
+            ms = p.profile_end()
+            med[name], res[name] = float(np.median(ms)), out["res"].cpu().numpy()
+            nbytes = a.T * C * (2 if code == hip.I16 else 4)
+            say(f"  {name:8s} {p.describe().split()[0]:40s} {stats(ms)}   {nbytes / med[name] / 1e9:.2f} TB/s of its own bytes at the median")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            err = np.nanmax(np.abs(res["packed"] - res["float32"]) / np.maximum(np.abs(res["float32"]), 1e-300))
+        say(f"  packed / float32 kernel time (medians): {med['packed'] / med['float32']:.3f};  panels differ by at most {err:.1e} relative")
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
