@@ -272,11 +272,36 @@ int afcodec_blosc_info(const void* chunk, int64_t size, int64_t* nbytes, int64_t
     return AFCODEC_OK;
 }
 
+/* liblz4 1.9.3's LZ4_decompress_safe does not refuse a match offset of 0: it "copies" the destination onto itself, so a damaged
+ * stream decodes, to its recorded size, into whatever the destination held (the GPU decoder counts such a stream as an error;
+ * tests/lz4_streams.py: off0_window, off0_generic).  One walk over the sequence headers finds it; anything else that is wrong
+ * with the stream ends the walk and is left to liblz4. */
+static int lz4_has_zero_offset(const uint8_t* s, int64_t n) {
+    int64_t p = 0;
+    while (p < n) {
+        const unsigned t = s[p++];
+        int64_t L = t >> 4;
+        if (L == 15) {
+            unsigned b;
+            do { if (p >= n) return 0; b = s[p++]; L += b; } while (b == 255);
+        }
+        p += L;
+        if (p + 2 > n) return 0;                            /* the final literals (or a cut stream) */
+        if ((s[p] | s[p + 1]) == 0) return 1;
+        p += 2;
+        if ((t & 15) == 15) {
+            unsigned b;
+            do { if (p >= n) return 0; b = s[p++]; } while (b == 255);
+        }
+    }
+    return 0;
+}
+
 static int decode_stream(int codec, const uint8_t* src, int32_t csize, uint8_t* dst, int32_t want) {
     int got = -1;
     switch (codec) {
         case 0: got = blosclz_decode(src, csize, dst, want); break;
-        case 1: got = p_lz4_dec((const char*)src, (char*)dst, csize, want); break;
+        case 1: got = lz4_has_zero_offset(src, csize) ? -1 : p_lz4_dec((const char*)src, (char*)dst, csize, want); break;
         case 3: { uLongf n = (uLongf)want; got = uncompress(dst, &n, src, (uLong)csize) == Z_OK ? (int)n : -1; break; }
         case 4: { size_t n = p_zstd_dec(dst, (size_t)want, src, (size_t)csize); got = p_zstd_iserr(n) ? -1 : (int)n; break; }
         default: break;
@@ -575,7 +600,7 @@ int64_t afcodec_lz4_decode(const void* srcv, int64_t n, void* dst, int64_t cap) 
     if (n < 4) return fail(AFCODEC_E_FORMAT, "lz4 chunk shorter than its size header");
     const int64_t want = (int64_t)(int32_t)le32(src);
     if (want < 0 || want > cap) return fail(AFCODEC_E_SIZE, "lz4 chunk decodes to more than its destination");
-    const int got = p_lz4_dec((const char*)src + 4, (char*)dst, (int)(n - 4), (int)want);
+    const int got = lz4_has_zero_offset(src + 4, n - 4) ? -1 : p_lz4_dec((const char*)src + 4, (char*)dst, (int)(n - 4), (int)want);
     if (got != want) return fail(AFCODEC_E_CODEC, "lz4 block failed to decode to its recorded size");
     return want;
 }

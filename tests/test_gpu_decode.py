@@ -1,6 +1,8 @@
 """Chunk decode in HBM (`afhip_lz4_decode_streams` + `afhip_unshuffle_blocks`, planned by `afcodec_blosc_lz4_plan`):
 every LZ4 chunk the real c-blosc 1.21 wrote decodes bit-exact on the GPU; damaged streams are counted, never followed out of
-bounds; stores read through `dataset_from_path(device="cuda")` give the same cube with the decode on the GPU or on the host."""
+bounds; stores read through `dataset_from_path(device="cuda")` give the same cube with the decode on the GPU or on the host.
+What the encoders here never write — the shapes `k_lz4_streams_vec` branches on, stream by hand-built stream, and `k_unshuffle_blocks`
+alone at every size and alignment — is in tests/test_gpu_lz4_streams.py (streams: tests/lz4_streams.py, on the host: tests/test_lz4_streams.py)."""
 import base64
 import json
 import os
