@@ -320,7 +320,7 @@ struct afhip_plan : PlanLayout {             // what the planner made (afhip_pla
     int64_t own_ws_bytes = 0;               // outgrown block is `retired` until the plan is destroyed — no hipFree (a device-wide
     std::vector<void*> retired;             // synchronisation) ever sits on the run path
     double* sums = nullptr;                 // [rows][P][K + 1] of the current run: behind partial + panel in the run's workspace
-    PackArgs unpack{};                      // AFHIP_I16 plans: the unpack rule (afhip_plan_bind_packing)
+    PackArgs unpack{};                      // AFHIP_I16 / AFHIP_U16 plans: the unpack rule (afhip_plan_bind_packing)
     bool unpack_bound = false;
     int last_ws = 0;                        // 1: the last run used a caller-owned workspace, 2: plan-owned (afhip_plan_describe tells)
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -852,40 +852,59 @@ extern "C" int afhip_plan_bind_inter(afhip_plan* plan, int column, const void* i
     return AFHIP_OK;
 }
 
-static int check_packing(const afhip_packing* p, const char* who) {
+// `dtype`: the storage the packing belongs to (AFHIP_I16 / AFHIP_U16) — a fill outside its range could never match a stored value
+static int check_packing(const afhip_packing* p, int dtype, const char* who) {
     static_assert(sizeof(afhip_packing) == sizeof(PackArgs), "afhip_packing is PackArgs");
+    static_assert(offsetof(afhip_packing, pad) == offsetof(PackArgs, is_unsigned), "the public pad is the library's signedness field");
     if (!p) return fail(AFHIP_E_INVALID, "%s: the packing is NULL", who);
     if (p->n_pairs < 0 || p->n_pairs > MAX_PACK_PAIRS) return fail(AFHIP_E_INVALID, "%s: n_pairs must be 0..%d, got %d", who, MAX_PACK_PAIRS, p->n_pairs);
-    if (p->has_fill && (p->fill < INT16_MIN || p->fill > INT16_MAX)) return fail(AFHIP_E_INVALID, "%s: the fill value %d is no int16", who, p->fill);
+    if (dtype == AFHIP_U16) {
+        if (p->has_fill && (p->fill < 0 || p->fill > UINT16_MAX)) return fail(AFHIP_E_INVALID, "%s: the fill value %d is no uint16", who, p->fill);
+    } else if (p->has_fill && (p->fill < INT16_MIN || p->fill > INT16_MAX)) {
+        return fail(AFHIP_E_INVALID, "%s: the fill value %d is no int16", who, p->fill);
+    }
     return AFHIP_OK;
+}
+
+// the caller's packing as the kernels' record: has_fill normalised, the signedness from `dtype` (the caller's pad is not read)
+static PackArgs pack_args_of(const afhip_packing* p, int dtype) {
+    PackArgs pa;
+    memcpy(&pa, p, sizeof pa);
+    pa.has_fill = p->has_fill ? 1 : 0;
+    pa.is_unsigned = dtype == AFHIP_U16 ? 1 : 0;
+    return pa;
 }
 
 extern "C" int afhip_plan_bind_packing(afhip_plan* plan, const afhip_packing* p) {
     if (!plan) return fail(AFHIP_E_INVALID, "plan_bind_packing: plan is NULL");
-    if (plan->desc.dtype != AFHIP_I16) return fail(AFHIP_E_INVALID, "plan_bind_packing: the plan's dtype is not AFHIP_I16");
-    int rc = check_packing(p, "plan_bind_packing");
+    if (!is_packed_dtype(plan->desc.dtype)) return fail(AFHIP_E_INVALID, "plan_bind_packing: the plan's dtype is not AFHIP_I16 or AFHIP_U16");
+    int rc = check_packing(p, plan->desc.dtype, "plan_bind_packing");
     if (rc) return rc;
-    memcpy(&plan->unpack, p, sizeof(PackArgs));
-    plan->unpack.has_fill = p->has_fill ? 1 : 0;
+    plan->unpack = pack_args_of(p, plan->desc.dtype);
     plan->unpack_bound = true;
     return AFHIP_OK;
 }
 
-extern "C" int afhip_unpack_i16(const void* q_dev, int64_t n, const afhip_packing* p, float* out_dev, void* stream) {
-    if (!q_dev || !out_dev || n < 0) return fail(AFHIP_E_INVALID, "unpack_i16: NULL array or negative size");
-    int rc = check_packing(p, "unpack_i16");
+// afhip_unpack_i16 / afhip_unpack_u16: one kernel, the signedness in its record
+static int unpack_16(const void* q_dev, int64_t n, const afhip_packing* p, int dtype, float* out_dev, void* stream, const char* who) {
+    if (!q_dev || !out_dev || n < 0) return fail(AFHIP_E_INVALID, "%s: NULL array or negative size", who);
+    int rc = check_packing(p, dtype, who);
     if (rc) return rc;
     if (n == 0) return AFHIP_OK;
-    if ((uintptr_t)q_dev % 8 != 0 || (uintptr_t)out_dev % 16 != 0) return fail(AFHIP_E_INVALID, "unpack_i16: q_dev must be 8-byte and out_dev 16-byte aligned");
-    PackArgs pa;
-    memcpy(&pa, p, sizeof pa);
-    pa.has_fill = p->has_fill ? 1 : 0;
+    if ((uintptr_t)q_dev % 8 != 0 || (uintptr_t)out_dev % 16 != 0) return fail(AFHIP_E_INVALID, "%s: q_dev must be 8-byte and out_dev 16-byte aligned", who);
+    const PackArgs pa = pack_args_of(p, dtype);
     const int64_t lanes = (n + 3) / 4, blocks = (lanes + WG - 1) / WG;
-    if (blocks > 0x7fffffff) return fail(AFHIP_E_INVALID, "unpack_i16: array too large for one launch");
+    if (blocks > 0x7fffffff) return fail(AFHIP_E_INVALID, "%s: array too large for one launch", who);
     GUARD_DEVICE(pointer_device(out_dev));
     hipLaunchKernelGGL(k_unpack_i16, dim3((unsigned)blocks), dim3(WG), 0, (hipStream_t)stream, (const int16_t*)q_dev, n, pa, out_dev);
     HIP_TRY(hipGetLastError());
     return AFHIP_OK;
+}
+extern "C" int afhip_unpack_i16(const void* q_dev, int64_t n, const afhip_packing* p, float* out_dev, void* stream) {
+    return unpack_16(q_dev, n, p, AFHIP_I16, out_dev, stream, "unpack_i16");
+}
+extern "C" int afhip_unpack_u16(const void* q_dev, int64_t n, const afhip_packing* p, float* out_dev, void* stream) {
+    return unpack_16(q_dev, n, p, AFHIP_U16, out_dev, stream, "unpack_u16");
 }
 
 extern "C" int64_t afhip_plan_workspace_bytes(const afhip_plan* plan) {
@@ -913,7 +932,7 @@ extern "C" int afhip_plan_describe(const afhip_plan* plan, char* buf, int buf_le
     if (plan->last_counts_lanes > 0) snprintf(cg, sizeof cg, " last-run=count-gather/%d-lane", plan->last_counts_lanes);
     int n = snprintf(tmp, sizeof tmp,
                      "variant=%s pipe=%d vec=%d stat=%d slots=%d kmax=%d depth=%d | T=%lld cells=%lld K=%d G1=%lld P=%lld | "
-                     "wg=%d tiles=%lld chunks=%zu (steps %lld..%lld) out_slots=%lld%s%s | workspace=%.1f MiB%s",
+                     "wg=%d tiles=%lld chunks=%zu (steps %lld..%lld) out_slots=%lld%s%s | workspace=%.1f MiB%s%s",
                      plan->variant->name, plan->variant->pipe, plan->variant->vec, plan->variant->stat, plan->variant->nthr,
                      plan->variant->kmax, plan->variant->depth, (long long)plan->desc.T, (long long)plan->desc.n_cells,
                      plan->K, (long long)plan->desc.G1, (long long)plan->desc.P, plan->wg, (long long)plan->tiles, plan->chunks.size(),
@@ -921,7 +940,8 @@ extern "C" int afhip_plan_describe(const afhip_plan* plan, char* buf, int buf_le
                      plan->packed ? (plan->pk.nw == 2 ? " packed-counts16" : " packed-counts32")
                                   : (plan->last_route == 1 ? " last-run=region-fused" : (plan->rf_plan_ok ? " region-fused-capable" : "")),
                      cg, (double)(plan->ws_partial + plan->ws_panel) / (1024.0 * 1024.0),
-                     plan->last_ws == 1 ? " (caller-owned)" : (plan->last_ws == 2 ? " (plan-owned hipMalloc)" : ""));
+                     plan->last_ws == 1 ? " (caller-owned)" : (plan->last_ws == 2 ? " (plan-owned hipMalloc)" : ""),
+                     plan->desc.dtype == AFHIP_U16 ? " storage=uint16" : (plan->desc.dtype == AFHIP_I16 ? " storage=int16" : ""));
     if (buf && buf_len > 0) snprintf(buf, buf_len, "%s", tmp);
     return n + 1;
 }
@@ -943,8 +963,8 @@ static int launch_temporal(afhip_plan* pl, const void* cube, double* partial, hi
     for (int j = 0; j < pl->K; ++j)
         if (pl->cols[(size_t)j].tf == TF_INTER && !pl->cols[(size_t)j].inter)
             return fail(AFHIP_E_INVALID, "column %d multiplies by a second array (AFHIP_TF_INTER) that was never bound: call afhip_plan_bind_inter first", j);
-    if (pl->desc.dtype == AFHIP_I16 && !pl->unpack_bound)
-        return fail(AFHIP_E_INVALID, "the plan reads an int16-packed cube (AFHIP_I16) whose packing was never bound: call afhip_plan_bind_packing first");
+    if (is_packed_dtype(pl->desc.dtype) && !pl->unpack_bound)
+        return fail(AFHIP_E_INVALID, "the plan reads a 16-bit-packed cube (AFHIP_I16 / AFHIP_U16) whose packing was never bound: call afhip_plan_bind_packing first");
     FusedArgs fa{};
     fa.unpack = pl->unpack;
     fa.cube = cube; fa.C = pl->desc.n_cells;

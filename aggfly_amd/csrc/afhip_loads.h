@@ -74,14 +74,18 @@ struct PackedI16 {};
 template <typename TS> struct Storage { typedef TS value_type; typedef TS raw_type; static constexpr bool packed = false; };
 template <> struct Storage<PackedI16> { typedef float value_type; typedef int16_t raw_type; static constexpr bool packed = true; };
 
-// The unpack rule of an int16-packed cube (PackArgs, afhip_plan_types.h), written once: k_fused_temporal applies it where a row is
+// The unpack rule of an int16- or uint16-packed cube (PackArgs, afhip_plan_types.h), written once: k_fused_temporal applies it where a row is
 // consumed, k_unpack_i16 (afhip_panel_kernels.h) to a whole array.  Every operation rounds to float32 on its own — separate
 // statements under -ffp-contract=off, never an fma — which is what torch does to a float32 tensor one operation at a time.  The
-// number of pairs is wave-uniform (a kernel argument): N values share its scalar branches.
+// number of pairs is wave-uniform (a kernel argument): N values share its scalar branches.  So is the signedness of the 16 bits: one
+// mask (a scalar select) widens them — all ones keeps the sign extension, 0xffff leaves the unsigned value, one v_and per element —
+// and the fill is compared on the widened value, so a uint16 fill of 40000 never meets the int16 -25536 of the same bits.
 template <int N>
 __device__ __forceinline__ void unpack_i16(const int16_t (&q)[N], const PackArgs& p, float (&f)[N]) {
+    const int m = p.is_unsigned ? 0xffff : ~0;
+    int w[N];
 #pragma unroll
-    for (int i = 0; i < N; ++i) f[i] = (float)(int)q[i];
+    for (int i = 0; i < N; ++i) { w[i] = (int)q[i] & m; f[i] = (float)w[i]; }
     static_assert(MAX_PACK_PAIRS == 3, "three pairs, written out: every field is read at a constant offset");
     if (p.n_pairs > 0) {
 #pragma unroll
@@ -97,7 +101,7 @@ __device__ __forceinline__ void unpack_i16(const int16_t (&q)[N], const PackArgs
     }
     if (p.has_fill) {
 #pragma unroll
-        for (int i = 0; i < N; ++i) f[i] = ((int)q[i] == p.fill) ? __uint_as_float(0x7fc00000u) : f[i];
+        for (int i = 0; i < N; ++i) f[i] = (w[i] == p.fill) ? __uint_as_float(0x7fc00000u) : f[i];
     }
 }
 

@@ -52,12 +52,14 @@ struct ColOp {
     double o0, o1, obase;      // outer dd/bins thresholds
 };
 
-// How an int16-packed cube (AFHIP_I16) becomes float32 values — the layout of afhip_packing (include/aggfly_hip.h), copied by value into
-// FusedArgs.  f = (float)q, then n_pairs times  f = f * mul[i];  f = f + add[i]  with every operation rounded to float32 (no fma),
-// then NaN where q == fill.  A pair half the chain does not have is sent as its exact identity — mul 1.0f, add -0.0f (x + -0 == x
-// for every x, the sign of zero included) — so the result is bit for bit that of the operations the chain does have.
+// How a 16-bit-packed cube (AFHIP_I16, AFHIP_U16) becomes float32 values — the layout of afhip_packing (include/aggfly_hip.h), copied
+// by value into FusedArgs.  f = (float)q, then n_pairs times  f = f * mul[i];  f = f + add[i]  with every operation rounded to float32
+// (no fma), then NaN where q == fill.  A pair half the chain does not have is sent as its exact identity — mul 1.0f, add -0.0f
+// (x + -0 == x for every x, the sign of zero included) — so the result is bit for bit that of the operations the chain does have.
+// is_unsigned: the 16 stored bits are uint16 (q widens by zero extension, fill is 0..65535).  The public struct calls the field `pad`:
+// the library writes it from the plan's dtype / the entry point's name and never reads the caller's.
 struct PackArgs {
-    int32_t n_pairs, has_fill, fill, pad;
+    int32_t n_pairs, has_fill, fill, is_unsigned;
     float mul[3], add[3];
 };
 constexpr int MAX_PACK_PAIRS = 3;

@@ -151,7 +151,7 @@ static int lower_columns(PlanLayout* pl) {
 
 // (rows of 4 GiB and more: the short-group and arithmetic-edge variants address a row by a 32-bit byte offset per lane)
 // bytes of one stored element
-static int elem_bytes(int dtype) { return dtype == AFHIP_F64 ? 8 : (dtype == AFHIP_I16 ? 2 : 4); }
+static int elem_bytes(int dtype) { return dtype == AFHIP_F64 ? 8 : (is_packed_dtype(dtype) ? 2 : 4); }
 
 static bool rows_fit_32bit(const afhip_plan_desc& d) {
     return (uint64_t)d.n_cells * (uint64_t)elem_bytes(d.dtype) < (1ull << 32);
@@ -378,7 +378,7 @@ static const Variant* twin_of(const Variant* v) {
     return nullptr;
 }
 
-// int16-packed cubes (AFHIP_I16) have a table of their own (packed_variants_table) of general forms on the direct-load path: the
+// int16- and uint16-packed cubes (AFHIP_I16, AFHIP_U16) have a table of their own (packed_variants_table) of general forms on the direct-load path: the
 // widest row piece per lane the rows allow and the menu holds for the plan's shape — four cells (8 bytes, the light shapes only), else
 // two, else one.  (Four against two cells on the light shapes is the float32 rule "8 bytes per lane" carried over; not measured on
 // packed cubes yet: profiles/packed_cube.txt.)
@@ -691,8 +691,8 @@ static int validate_desc(const afhip_plan_desc* d) {
     if (d->T < 0 || d->n_cells <= 0 || d->K <= 0 || d->G1 < 0 || d->P < 0)
         return fail(AFHIP_E_INVALID, "plan_create: bad sizes (T=%lld n_cells=%lld K=%d G1=%lld P=%lld)",
                     (long long)d->T, (long long)d->n_cells, d->K, (long long)d->G1, (long long)d->P);
-    if (d->dtype != AFHIP_F32 && d->dtype != AFHIP_F64 && d->dtype != AFHIP_I16)
-        return fail(AFHIP_E_INVALID, "plan_create: dtype must be AFHIP_F32, AFHIP_F64 or AFHIP_I16");
+    if (d->dtype != AFHIP_F32 && d->dtype != AFHIP_F64 && !is_packed_dtype(d->dtype))
+        return fail(AFHIP_E_INVALID, "plan_create: dtype must be AFHIP_F32, AFHIP_F64, AFHIP_I16 or AFHIP_U16");
     if (!d->inner_bounds || !d->outer_bounds || !d->columns) return fail(AFHIP_E_INVALID, "plan_create: NULL table");
     if (d->inner_bounds[0] != 0 || d->inner_bounds[d->G1] != d->T)
         return fail(AFHIP_E_INVALID, "plan_create: inner_bounds must run from 0 to T");
@@ -718,8 +718,8 @@ int build_plan(const afhip_plan_desc* desc, const DeviceFacts& dev, PlanLayout* 
     pl->desc.inner_bounds = nullptr; pl->desc.outer_bounds = nullptr; pl->desc.columns = nullptr;
     if ((rc = lower_columns(pl))) return rc;
 
-    if (desc->dtype == AFHIP_I16) {
-        // straight to the packed table: no short-group form, no histogram partition, no packed counts, and — the table has no
+    if (is_packed_dtype(desc->dtype)) {
+        // int16 and uint16 storage alike (the kernels take the signedness from the bound packing) straight to the packed table: no short-group form, no histogram partition, no packed counts, and — the table has no
         // region-fused twins — the spatial stage is the slot gather or the table-order sums
         pl->variant = choose_packed_variant(*pl);
         if (!pl->variant)

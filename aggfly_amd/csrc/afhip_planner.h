@@ -19,6 +19,9 @@ namespace afhip {
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 const char* last_error();
 
+// 16-bit integer storage whose values are float32 by a bound afhip_packing: one packed kernel table serves both
+inline bool is_packed_dtype(int dtype) { return dtype == AFHIP_I16 || dtype == AFHIP_U16; }
+
 // What plan building needs to know about the device.
 struct DeviceFacts {
     int cu_count = 0;                                                  // compute units

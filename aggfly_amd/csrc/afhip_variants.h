@@ -37,7 +37,8 @@ struct Variant {
 
 const Variant* variants_table(int* n);   // generated (variants_table.hip)
 const char* variants_menu();             // "full" (the production menu), "arms" (+ the tuning arms) or "dev"
-// The kernels of int16-packed cubes (AFHIP_I16; gen_variants.py: packed_menu), a table of their own (packed_table.hip): general
+// The kernels of int16- and uint16-packed cubes (AFHIP_I16, AFHIP_U16: one set, the signedness is in the unpack record;
+// gen_variants.py: packed_menu), a table of their own (packed_table.hip): general
 // two-level forms on the direct-load path only, so a plan's stat / slots / columns and the cells per lane are all there is to match.
 const Variant* packed_variants_table(int* n);
 

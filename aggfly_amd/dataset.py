@@ -153,7 +153,7 @@ class Dataset:
     # ---- the engine's view ----
     @property
     def is_packed(self) -> bool:
-        """The cube is held as stored int16 (`packed.PackedCube`): the kernels unpack it as they read it."""
+        """The cube is held as stored int16 / uint16 (`packed.PackedCube`): the kernels unpack it as they read it."""
         return is_packed(self.da.data)
 
     def packed_cube(self):

@@ -293,7 +293,7 @@ def aggregate_dataset_sharded(weights, dataset=None, aggregator_dict=None, engin
 
 def _step_bytes(path, var, keep_packed=False):
     """Bytes one time step of ``var`` takes in HBM (full stored grid: a clipped read takes less), or None when
-    the container's shape cannot be told without reading it.  ``keep_packed`` (or AGGFLY_HIP_KEEP_PACKED=1): an int16-packed
+    the container's shape cannot be told without reading it.  ``keep_packed`` (or AGGFLY_HIP_KEEP_PACKED=1): an int16- or uint16-packed
     variable that `io.dataset_from_path` will keep packed counts its 2 stored bytes per cell."""
     import numpy as np
     from . import io as afio

@@ -165,7 +165,7 @@ def lower_spec(key: str, steps):
 # --------------------------------------------------------------------------------------
 def device_cube(dataset: Dataset):
     """The dataset's (time, lat, lon) cube as an HBM tensor (uploaded if still on the host) — of a packed dataset
-    (`Dataset.is_packed`) the `packed.PackedCube` itself: the plans read the stored int16."""
+    (`Dataset.is_packed`) the `packed.PackedCube` itself: the plans read the stored int16 / uint16."""
     import torch
     hip.require_gpu()
     if dataset.is_packed:
@@ -437,7 +437,7 @@ def _run_fused_pass(cube, cols, ib, ob, csr=None, want_cells=True, exact_order=N
     T = int(cube.shape[0])
     n_cells = int(cube[0].numel()) if T else int(np.prod(cube.shape[1:]))
     code = hip._dtype_code(cube)
-    f32_rules = config.match_reference_f32 and code in (hip.F32, hip.I16)      # a packed cube's values are float32
+    f32_rules = config.match_reference_f32 and code in (hip.F32,) + hip.PACKED_CODES      # a packed cube's values are float32
     cdicts = [_column_dict(c, f32_rules) for c in cols]
     try:
         plan = get_plan(T, n_cells, code, ib, ob, cdicts, exact_order, device=cube.device)
@@ -452,8 +452,8 @@ def _run_fused_pass(cube, cols, ib, ob, csr=None, want_cells=True, exact_order=N
     with plan.lock:                     # bind + enqueue as one step: another thread's call on this plan binds its own second cubes
         for j, other in inters.items():
             plan.bind_inter(j, other)
-        if code == hip.I16:             # ... and its own cube's unpack rule
-            plan.bind_packing(cube.packing())
+        if code in hip.PACKED_CODES:    # ... and its own cube's unpack rule (int16 or uint16 storage: the plan's dtype says which)
+            plan.bind_packing(cube)
         if csr is not None:
             out = plan.run(cube, csr, want_cells=want_cells)
             return [PassResult([c.key for c in cols], None, plan, out.get("cells"), out)]

@@ -21,6 +21,8 @@ LIB_PATH = os.environ.get("AGGFLY_HIP_LIB") or os.path.join(_HERE, "libaggfly_hi
 # codes (include/aggfly_hip.h)
 F32, F64 = 0, 1
 I16 = 2                         # AFHIP_I16: int16 storage, float32 values (a `packed.PackedCube`; plans only)
+U16 = 3                         # AFHIP_U16: uint16 storage, likewise (a `packed.PackedCube` with ``unsigned``)
+PACKED_CODES = (I16, U16)       # the dtype codes whose cubes are 2-byte integers unpacked by a bound `Packing`
 MEAN, SUM, MIN, MAX, NANMEAN, DD, BINS, SINE_DD, IDENTITY = range(9)
 TF_NONE, TF_POW, TF_HINGE, TF_INTER = 0, 1, 2, 3
 ROUND_INNER, ROUND_HINGE, ROUND_FINAL = 1, 2, 4
@@ -37,7 +39,7 @@ EXPORTS = (
     "afhip_plan_describe", "afhip_plan_run_temporal", "afhip_plan_run",
     "afhip_plan_profile_begin", "afhip_plan_profile_end", "afhip_plan_bind_inter", "afhip_csr_device", "afhip_plan_device", "afhip_transform", "afhip_panel_divide", "afhip_lz4_decode_streams", "afhip_unshuffle_blocks", "afhip_read_probe",
     "afhip_zstd_scratch_bytes", "afhip_zstd_decode", "afhip_inflate_scratch_bytes", "afhip_inflate_decode", "afhip_bitunshuffle_blocks",
-    "afhip_plan_bind_packing", "afhip_unpack_i16",
+    "afhip_plan_bind_packing", "afhip_unpack_i16", "afhip_unpack_u16",
 )
 
 
@@ -63,7 +65,8 @@ class PlanDesc(C.Structure):
 
 
 class Packing(C.Structure):
-    """``afhip_packing``: how an int16-packed cube becomes float32 values (`packed.PackedCube.packing`)."""
+    """``afhip_packing``: how an int16- or uint16-packed cube becomes float32 values (`packed.PackedCube.packing`).  ``pad`` is
+    ignored: the library takes the signedness of the 16 bits from the plan's dtype (`I16` / `U16`) or from the entry point."""
     _fields_ = [("n_pairs", C.c_int32), ("has_fill", C.c_int32), ("fill", C.c_int32), ("pad", C.c_int32),
                 ("mul", C.c_float * 3), ("add", C.c_float * 3)]
 
@@ -135,6 +138,7 @@ def load():
     lib.afhip_plan_device.argtypes = [vp]
     lib.afhip_plan_bind_packing.argtypes = [vp, C.POINTER(Packing)]
     lib.afhip_unpack_i16.argtypes = [vp, i64, C.POINTER(Packing), vp, vp]
+    lib.afhip_unpack_u16.argtypes = [vp, i64, C.POINTER(Packing), vp, vp]
     _lib = lib
     return lib
 
@@ -156,7 +160,7 @@ def device_count() -> int:
 
 def build_info() -> dict:
     """What the loaded build holds: {"menu": "full" | "arms" | "dev", "variants", "arms", "region_fused_twins", "abi", "packed_variants"}
-    (`afhip_build_info`; the first three counts are of the float32 / float64 kernels, the last of those for int16-packed cubes)."""
+    (`afhip_build_info`; the first three counts are of the float32 / float64 kernels, the last of those for int16- / uint16-packed cubes)."""
     buf = C.create_string_buffer(256)
     load().afhip_build_info(buf, 256)
     out = dict(kv.split("=") for kv in buf.value.decode().split())
@@ -312,7 +316,8 @@ def _ptr(t):
 
 
 def unpack_i16(cube):
-    """`afhip_unpack_i16`: the float32 values of a `packed.PackedCube` as a new HBM tensor of its shape."""
+    """`afhip_unpack_i16` — `afhip_unpack_u16` for a cube of unsigned storage: the float32 values of a `packed.PackedCube` as a
+    new HBM tensor of its shape."""
     torch = _torch()
     require_gpu()
     q = cube.q if cube.q.is_cuda else cube.q.cuda(non_blocking=True)
@@ -321,14 +326,15 @@ def unpack_i16(cube):
         q = q.clone()
     out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
     p = cube.packing()
-    _check(load().afhip_unpack_i16(q.data_ptr(), q.numel(), C.byref(p), out.data_ptr(), _stream_ptr(q)))
+    fn = load().afhip_unpack_u16 if cube.unsigned else load().afhip_unpack_i16
+    _check(fn(q.data_ptr(), q.numel(), C.byref(p), out.data_ptr(), _stream_ptr(q)))
     return out
 
 
 def _dtype_code(t) -> int:
     torch = _torch()
     if _is_packed(t):
-        return I16
+        return U16 if t.unsigned else I16
     if t.dtype == torch.float32:
         return F32
     if t.dtype == torch.float64:
@@ -569,8 +575,14 @@ class FusedPlan:
         _check(load().afhip_plan_bind_inter(self._h, int(column), other.data_ptr(), _dtype_code(other)))
         self._inter[int(column)] = other
 
-    def bind_packing(self, packing: Packing):
-        """Bind the unpack rule of the int16-packed cube the next runs read (``dtype_code`` `I16` plans; `afhip_plan_bind_packing`)."""
+    def bind_packing(self, packing):
+        """Bind the unpack rule of the packed cube the next runs read (``dtype_code`` `I16` / `U16` plans; `afhip_plan_bind_packing`).
+        ``packing``: a `Packing`, or the `packed.PackedCube` itself — then its storage must be the plan's (a uint16 cube's rule on
+        an int16 plan would read every value from 32768 up 65536 too low)."""
+        if _is_packed(packing):
+            if _dtype_code(packing) != self.dtype_code:
+                raise ValueError(f"cube shape/dtype does not match the plan (T={self.T}, cells={self.n_cells}): {packing.storage} storage")
+            packing = packing.packing()
         _check(load().afhip_plan_bind_packing(self._h, C.byref(packing)))
 
     def describe(self) -> str:

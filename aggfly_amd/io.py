@@ -345,9 +345,52 @@ def _torch_dtype(np_dtype):
     table = {"float32": torch.float32, "float64": torch.float64, "int8": torch.int8, "uint8": torch.uint8,
              "int16": torch.int16, "int32": torch.int32, "int64": torch.int64}
     name = np.dtype(np_dtype).name
+    if name in ("uint32", "uint64"):
+        raise ValueError(f"dtype {name} has no device representation on the streaming path: unsigned storage is streamed up to 16 bits "
+                         "(uint8, uint16); wider unsigned integers go through the host route")
     if name not in table:
         raise ValueError(f"dtype {name} has no device representation on the streaming path")
     return table[name]
+
+
+def _attr_unsigned(attrs):
+    """The NetCDF User's Guide attribute ``_Unsigned``: True / False as written ("true" / "false" in any letter case), None: absent."""
+    u = attrs.get("_Unsigned")
+    if u is None:
+        return None
+    if isinstance(u, bytes):
+        u = u.decode("ascii", "replace")
+    if isinstance(u, np.ndarray) and u.size == 1:
+        u = u.reshape(-1)[0]
+    return str(u).strip().lower() == "true"
+
+
+def _stored_unsigned(np_dtype, attrs) -> bool:
+    """Whether the stored integers are unsigned: unsigned storage, or signed storage under ``_Unsigned = "true"`` (the same bits).
+    ``_Unsigned = "false"`` on unsigned storage (signed values in an unsigned container) is refused: no route reads it."""
+    np_dtype, u = np.dtype(np_dtype), _attr_unsigned(attrs)
+    if np_dtype.kind == "u":
+        if u is False:
+            raise ValueError(f'_Unsigned = "false" on {np_dtype.name} storage is not supported')
+        return True
+    return np_dtype.kind == "i" and u is True
+
+
+def _wire_dtype(np_dtype, attrs):
+    """(dtype the stored bits travel and sit in HBM as, modulus).  torch holds no uint16 worth the name (no indexing, no
+    arithmetic), so unsigned 16-bit values travel as the int16 of the same bits and ``modulus`` = 65536.0 puts the float32 values
+    right in HBM (``x.remainder_(modulus)``: -1 -> 65535, exact in float32) — likewise int8 under ``_Unsigned`` (256.0).  None: the
+    values are right as converted.  Wider unsigned storage is refused."""
+    np_dtype = np.dtype(np_dtype)
+    if np_dtype.kind not in "iu" or not _stored_unsigned(np_dtype, attrs):
+        return np_dtype, None
+    if np_dtype.itemsize > 2:
+        raise ValueError(f"unsigned {8 * np_dtype.itemsize}-bit storage ({np_dtype.name}"
+                         + (', _Unsigned = "true"' if np_dtype.kind == "i" else "") + ") has no device representation on the streaming path: "
+                         "unsigned storage is streamed up to 16 bits; wider unsigned integers go through the host route")
+    if np_dtype == np.dtype(np.uint8):
+        return np_dtype, None
+    return np.dtype(f"i{np_dtype.itemsize}"), float(1 << (8 * np_dtype.itemsize))
 
 
 _PINNED_STAGE = {}      # (thread, nbytes rounded up) -> [pinned uint8 tensors]: page-locking is slow, so it is done once per process
@@ -394,17 +437,18 @@ def _pinned_stage(nbytes: int, count: int, device=None):
     return bufs[:count]
 
 
-def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: int, device="cuda", post=None, out_dtype=None):
+def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: int, device="cuda", post=None, out_dtype=None, wire_dtype=None):
     """Fill a (T, *spatial) HBM tensor slab by slab through two cached page-locked staging buffers.
 
     ``read_slab(k0, k1, out)`` fills ``out[:k1-k0]`` with time steps [k0, k1) (a Zarr chunk
     decode on host threads).  The upload of slab i is queued on its own HIP stream while slab
     i+1 is decoded, and the host never holds a second full copy of the cube.  Measured on the
     MI355X box (16 host cores, `profiles/r01_ingest_bench.json`): native Blosc decode 66 GB/s,
-    pageable H2D 56 GB/s."""
+    pageable H2D 56 GB/s.  ``wire_dtype`` (`_wire_dtype`): the dtype of the same size the bits are uploaded as where torch
+    cannot hold ``np_dtype`` (uint16 as int16); ``read_slab`` still fills an array of ``np_dtype``."""
     import torch
     np_dtype = np.dtype(np_dtype)
-    tdt = _torch_dtype(np_dtype)                                    # as stored (packed integers stay packed on the wire)
+    tdt = _torch_dtype(np_dtype if wire_dtype is None else wire_dtype)     # as stored (packed integers stay packed on the wire)
     cube = torch.empty((T,) + tuple(spatial), dtype=_torch_dtype(out_dtype) if out_dtype is not None else tdt, device=device)
     if T == 0:
         return cube
@@ -412,7 +456,7 @@ def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: in
     row = int(np.prod(spatial)) * np_dtype.itemsize
     nstage = 2 if T > slab_steps else 1
     stage_t = [b[:slab_steps * row].view(tdt).reshape((slab_steps,) + tuple(spatial)) for b in _pinned_stage(slab_steps * row, nstage, device)]
-    stage = [t.numpy() for t in stage_t]
+    stage = [t.numpy().view(np_dtype) for t in stage_t]
     copy_stream = torch.cuda.Stream(device=device)
     # the cube (and the staging tensors) come from the caching allocator on the CURRENT stream: a block freed there may
     # still be read by queued kernels (the previous HBM window's fused pass) — order the copies behind them
@@ -449,24 +493,34 @@ def keep_packed_requested(keep_packed=False) -> bool:
 
 
 def packing_of(za):
-    """(scale_factor, add_offset, fill value) under which a streamed array can stay packed in HBM (`packed.PackedCube`), or None:
-    int16 storage only, and a fill value — if any — that is a stored integer."""
-    if np.dtype(za.dtype) != np.dtype(np.int16):
+    """(scale_factor, add_offset, fill value, unsigned) under which a streamed array can stay packed in HBM — the arguments of
+    `packed.PackedCube` —, or None: int16 or uint16 storage only, and a fill value — if any — that is a stored integer.
+    ``unsigned``: uint16 storage, or int16 storage under ``_Unsigned = "true"`` (the same bits: both give the same packing); a
+    fill value written in the signed type is then taken modulo 2^16 (-1 means 65535, as xarray reads it)."""
+    dt = np.dtype(za.dtype)
+    if dt not in (np.dtype(np.int16), np.dtype(np.uint16)):
         return None
+    unsigned = _stored_unsigned(dt, za.attrs)
     fv = _attr_fill(za.attrs)
     if fv is not None and isinstance(fv, float) and np.isnan(fv):
         fv = None
-    if fv is not None and (int(fv) != fv or not -32768 <= int(fv) <= 32767):
-        return None
+    if fv is not None:
+        if int(fv) != fv:
+            return None
+        fv = int(fv)
+        if unsigned and dt.kind == "i" and -32768 <= fv < 0:
+            fv += 65536
+        if not ((0 <= fv <= 65535) if unsigned else (-32768 <= fv <= 32767)):
+            return None
     sf, ao = za.attrs.get("scale_factor"), za.attrs.get("add_offset")
-    return (None if sf is None else float(sf), None if ao is None else float(ao), None if fv is None else int(fv))
+    return (None if sf is None else float(sf), None if ao is None else float(ao), fv, unsigned)
 
 
 def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 << 20, t_range=None, yx_box=None, keep_packed=False):
     """Stream a chunked (time, y, x) array — a `ZarrArray` or an `hdf5.ChunkSource` — straight into HBM: each
     slab is a whole number of time chunks, decoded chunk-parallel by the native codec into page-locked memory
-    and uploaded while the next slab decodes.  Returns (tensor, source).  ``keep_packed`` (int16 storage, `packing_of`): the
-    tensor stays int16 as stored — the CF unpacking in HBM is skipped and left to the kernels that read a `packed.PackedCube`."""
+    and uploaded while the next slab decodes.  Returns (tensor, source).  ``keep_packed`` (int16 / uint16 storage, `packing_of`): the
+    tensor stays int16 as stored (uint16: the int16 of the same bits) — the CF unpacking in HBM is skipped and left to the kernels that read a `packed.PackedCube`."""
     if len(za.shape) != 3:
         raise ValueError("zarr_to_device expects a (time, y, x) array")
     if os.environ.get("AGGFLY_HIP_SLAB_MB"):                       # tuning knob (scripts/e2e_bench.py sweeps it)
@@ -477,7 +531,8 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
         raise ValueError(f"dtype {za.dtype} is not streamed")
     # CF decoding as on the host route (`_cf_mask_scale`): int8/int16 -> float32, wider integers -> float64
     out_np = za.dtype if za.dtype.kind == "f" else np.dtype(np.float64 if za.dtype.itemsize > 2 else np.float32)
-    _torch_dtype(za.dtype)                                          # refuses what torch cannot hold (uint16, ...)
+    wire, modulus = _wire_dtype(za.dtype, za.attrs)                 # uint16 (and int16 / int8 under _Unsigned) travel as signed bits
+    _torch_dtype(wire)                                              # refuses what torch cannot hold (uint32, ...)
     T, ny, nx = za.shape
     tc = za.chunks[0]
     grid_yx = [(iy, ix) for iy in range((ny + za.chunks[1] - 1) // za.chunks[1]) for ix in range((nx + za.chunks[2] - 1) // za.chunks[2])]
@@ -535,10 +590,14 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
 
     fv = _attr_fill(za.attrs)
     has_fv = fv is not None and not (isinstance(fv, float) and np.isnan(fv))
+    if has_fv and modulus is not None and za.dtype.kind == "i" and fv < 0:
+        fv = fv + modulus                                   # a fill written in the signed type, read as the unsigned value (xarray)
 
     def post(dst):
         """CF mask + unpack in HBM, in the order and precision of the host route: the packed integers travel
         over PCIe as stored (half / quarter of the decoded bytes) and are unpacked at HBM speed."""
+        if modulus is not None:
+            dst.remainder_(modulus)                         # unsigned bits that came as signed: -1 -> 65535, in place and exact
         if has_fv:
             dst[dst == fv] = float("nan")                   # exact: the cast from the stored integers is exact
         if sf is not None:
@@ -548,7 +607,7 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
 
     need_post = has_fv or packed
     if keep_packed and packing_of(za) is not None:
-        need_post, out_np = False, za.dtype
+        need_post, out_np = False, wire
     if t_range is not None and tuple(t_range) == (0, T):
         t_range = None
     if yx_box is not None and tuple(yx_box) == (0, ny, 0, nx):
@@ -563,7 +622,7 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
         if (za.native_kind in ("blosc", "zstd") or _deflate_typesize(za.native_kind)) and _gpu_decodable(za, T * ny * nx * za.dtype.itemsize):
             # Blosc-LZ4 / Zstandard / deflate chunks cross PCIe compressed and are decoded in HBM: the scatter route, whatever the chunk grid
             return _stream_chunks_scatter(za, device, threads, slab_bytes, post if need_post else None, out_np), za
-        return stream_to_device(T, (ny, nx), za.dtype, read, slab, device, post if need_post else None, out_np), za
+        return stream_to_device(T, (ny, nx), za.dtype, read, slab, device, post if need_post else None, out_np, wire), za
     finally:
         if pool is not None:
             pool.shutdown()
@@ -712,8 +771,9 @@ class _ScatterJob:
         self.za, self.device = za, device
         T, ny, nx = za.shape
         self.tc, self.yc, self.xc = za.chunks
-        self.tdt = _torch_dtype(za.dtype)
-        self.same_dtype = (out_dtype is None or np.dtype(out_dtype) == za.dtype) and za.dtype.itemsize in (2, 4, 8)
+        self.wire = wire = _wire_dtype(za.dtype, za.attrs)[0]              # the stored bits as torch holds them (uint16: int16)
+        self.tdt = _torch_dtype(wire)
+        self.same_dtype = (out_dtype is None or np.dtype(out_dtype) == wire) and za.dtype.itemsize in (2, 4, 8)
         self.ka, self.kb = (0, T) if t_range is None else (max(0, int(t_range[0])), min(T, int(t_range[1])))   # time window [ka, kb)
         self.ya, self.yb, self.xa, self.xb = (0, ny, 0, nx) if yx_box is None else yx_box                    # spatial box
         self.cube = torch.empty((self.kb - self.ka, self.yb - self.ya, self.xb - self.xa),
@@ -725,6 +785,14 @@ class _ScatterJob:
         # a chunk of whole time steps of the window (full grid, same dtype) is one contiguous run of the cube
         self.whole_steps = self.same_dtype and (self.ya, self.xa) == (0, 0) and (yc, xc) == (self.yb, self.xb) == (ny, nx)
         self.step_bytes = ny * nx * za.dtype.itemsize
+
+    def absent_value(self) -> float:
+        """The array's fill value as the cube holds it: an unsigned one in a cube of the signed bits (a uint16 cube kept packed) is
+        the signed integer of the same bits."""
+        fill = self.za._fill()
+        if not self.cube.dtype.is_floating_point and self.wire != self.za.dtype:
+            return float(np.array(fill).astype(self.za.dtype).view(self.wire))
+        return float(fill)
 
     def inside(self, it) -> bool:
         """All time steps of chunk row ``it`` lie in the window."""
@@ -744,7 +812,7 @@ class _ScatterJob:
             x0, x1 = max(ix * xc, xa), min((ix + 1) * xc, xb)
             dst = cube[t0 - ka:t1 - ka, y0 - ya:y1 - ya, x0 - xa:x1 - xa]
             if r == -100:                           # absent chunk = fill value
-                dst.fill_(float(self.za._fill()))
+                dst.fill_(self.absent_value())
                 continue
             blk = staged[i * cb:(i + 1) * cb].view(self.tdt).view(tc, yc, xc)
             if self.same_dtype:                     # one coalesced pass (torch's strided copy ran at 22 GB/s here)
@@ -1322,6 +1390,12 @@ def _attr_fill(attrs):
 
 def _cf_mask_scale(arr, attrs):
     fv = _attr_fill(attrs)
+    unsigned = arr.dtype.kind in "iu" and _stored_unsigned(arr.dtype, attrs)      # (refuses _Unsigned = "false" on unsigned storage)
+    if unsigned and arr.dtype.kind == "i":
+        # _Unsigned = "true": the same bits read as the unsigned type, and a fill written in the signed type likewise (xarray)
+        arr = arr.view(np.dtype(f"u{arr.dtype.itemsize}"))
+        if fv is not None and not isinstance(fv, str) and not (isinstance(fv, float) and np.isnan(fv)) and int(fv) == fv and fv < 0:
+            fv = int(fv) + (1 << (8 * arr.dtype.itemsize))
     sf, ao = attrs.get("scale_factor"), attrs.get("add_offset")
     if fv is None and sf is None and ao is None:
         return arr
@@ -1569,7 +1643,7 @@ def _open_npz(path, var):
 def _open_hdf5(path, var, xycoords=("longitude", "latitude"), timecoord="time", keep_packed=False):
     """netCDF-4 / HDF5 containers through the built-in reader (`hdf5.py`): variable, CF mask / scale, coordinates
     by dimension name (``DIMENSION_LIST``; for plain HDF5 files without dimension scales, by matching the axis
-    lengths to the 1-D datasets named like the coordinates).  ``keep_packed``: an int16-packed variable (`packing_of`) is
+    lengths to the 1-D datasets named like the coordinates).  ``keep_packed``: an int16- / uint16-packed variable (`packing_of`) is
     left as stored, in a `packed.PackedCube` on the host — for variables the streaming route does not take (contiguous
     layout), whose one upload then moves 2 bytes per value."""
     from . import hdf5
@@ -1756,9 +1830,9 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
     job asks for (`distributed.aggregate_store_sharded`); ``lat_window=(j0, j1)`` (extension) keeps rows ``j0..j1`` of the
     latitude axis AFTER the clip to the regions' extent — the band of a cell-sharded job
     (`distributed.aggregate_store_cells`); on the streaming route only the chunks that touch the band are read.
-    ``keep_packed=True`` (extension; or AGGFLY_HIP_KEEP_PACKED=1): an int16-packed variable (``scale_factor`` / ``add_offset`` /
-    ``_FillValue``) stays packed in HBM as a `packed.PackedCube` — half the memory, half the bytes the temporal kernel reads — and
-    ``preprocess`` folds into its unpack rule.  Honoured on the streaming routes (``device=``) only, for int16 storage, and for several
+    ``keep_packed=True`` (extension; or AGGFLY_HIP_KEEP_PACKED=1): an int16- or uint16-packed variable (``scale_factor`` / ``add_offset`` /
+    ``_FillValue``; int16 under ``_Unsigned = "true"`` counts as uint16) stays packed in HBM as a `packed.PackedCube` — half the memory, half the bytes the temporal kernel reads — and
+    ``preprocess`` folds into its unpack rule.  Honoured on the streaming routes (``device=``) only, for 16-bit integer storage, and for several
     stores only when all share their packing (yearly ERA5 files usually do not: they take the float32 route); ``Dataset.is_packed``
     tells which route was taken."""
     import glob

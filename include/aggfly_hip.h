@@ -41,6 +41,7 @@ extern "C" {
 #define AFHIP_F32 0
 #define AFHIP_F64 1
 #define AFHIP_I16 2      /* afhip_plan_desc.dtype: int16 storage, float32 values by afhip_packing */
+#define AFHIP_U16 3      /* afhip_plan_desc.dtype: uint16 storage, float32 values by afhip_packing */
 
 /* reducer codes: 0..4 are _STAT_CODE of aggfly/aggregate/nb_kernels.py:33 */
 #define AFHIP_MEAN     0
@@ -70,7 +71,7 @@ const char* afhip_last_error(void);
 int afhip_abi_version(void);
 /* What this build of the library holds, as text into buf ("menu=full variants=426 arms=0 region_fused_twins=150 abi=4 packed_variants=69");
  * returns the bytes needed.  menu: full = every kernel the planner can pick; arms = + the tuning arms a `tuning` hint can name (make
- * MENU=arms).  variants / arms / region_fused_twins count the float32 / float64 kernels, packed_variants those of AFHIP_I16 cubes. */
+ * MENU=arms).  variants / arms / region_fused_twins count the float32 / float64 kernels, packed_variants those of AFHIP_I16 / AFHIP_U16 cubes. */
 int afhip_build_info(char* buf, int buf_len);
 /* Number of visible GPUs (hipGetDeviceCount); 0 when there is none. */
 int afhip_device_count(void);
@@ -279,7 +280,7 @@ typedef struct afhip_column {
 typedef struct afhip_plan_desc {
     int64_t T;                     /* time steps in the cube                                */
     int64_t n_cells;               /* NY*NX                                                  */
-    int32_t dtype;                 /* AFHIP_F32 / AFHIP_F64 / AFHIP_I16 (afhip_plan_bind_packing) */
+    int32_t dtype;                 /* AFHIP_F32 / AFHIP_F64 / AFHIP_I16 / AFHIP_U16 (afhip_plan_bind_packing) */
     int32_t K;                     /* number of columns                                      */
     int64_t G1;                    /* inner groups                                           */
     const int64_t* inner_bounds;   /* HOST int64[G1+1] over time steps                       */
@@ -302,20 +303,26 @@ int afhip_plan_device(const afhip_plan* plan);
  * output, whose time axis is the inner groups).  The pointer is read by every later run until it is bound again; the
  * caller keeps the memory alive.  A run with an unbound AFHIP_TF_INTER column fails with AFHIP_E_INVALID. */
 int afhip_plan_bind_inter(afhip_plan* plan, int column, const void* inter_dev, int dtype);
-/* int16-packed cubes (AFHIP_I16).  ERA5-style files store a field as int16 with scale_factor / add_offset / _FillValue; such a cube
+/* 16-bit-packed cubes (AFHIP_I16, AFHIP_U16).  ERA5-style files store a field as int16 with scale_factor / add_offset / _FillValue,
+ * other gridded products as uint16 (or as int16 with the attribute _Unsigned = "true": the same bits); such a cube
  * can stay packed in HBM — 2 bytes per cell and step instead of 4 — and the temporal kernel unpacks each element where it uses it.
  * The value of a stored q is, bit for bit what a float32 array library computes one operation at a time:
  *     f = (float)q;   n_pairs times:  f = f * mul[i];  f = f + add[i]   (each rounded to float32, never fused);   NaN if has_fill && q == fill
  * and everything after it is the float32 path (float64 accumulators, thresholds compared in float32 against the edges rounded down / up).
  * A pair half the chain lacks is sent as its exact identity: mul 1.0f, add -0.0f.  At most three pairs (unpack + a unit conversion or two).
- * afhip_plan_bind_packing: like afhip_plan_bind_inter, copied into the plan and read by every later run; an AFHIP_I16 plan that runs
- * unbound fails with AFHIP_E_INVALID, and binding a plan of another dtype is refused.  AFHIP_I16 plans take the general kernels of the
+ * afhip_plan_bind_packing: like afhip_plan_bind_inter, copied into the plan and read by every later run; an AFHIP_I16 / AFHIP_U16 plan that runs
+ * unbound fails with AFHIP_E_INVALID, and binding a plan of another dtype is refused.  Such plans take the general kernels of the
  * direct-load path (no short-group, single-level, histogram or region-fused form) and the slot-gather / table-order spatial stage.  The
  * afhip_group_* entry points and afhip_transform keep to AFHIP_F32 / AFHIP_F64.
- * afhip_unpack_i16: the same rule on a whole array, q_dev int16[n] -> out_dev float[n] (a plain stream, 8 bytes read per lane). */
+ * AFHIP_U16 differs in one thing: the 16 stored bits are unsigned, f = (float)(unsigned)q (exact for 0..65535), and q == fill compares the
+ * unsigned value.  A fill must lie in the storage's range (-32768..32767 / 0..65535).  Both dtypes run the same kernels: the signedness is a
+ * field of the record the library fills from the plan's dtype at bind time.  `pad` is ignored: whatever the caller writes there is not read.
+ * afhip_unpack_i16: the same rule on a whole array, q_dev int16[n] -> out_dev float[n] (a plain stream, 8 bytes read per lane).
+ * afhip_unpack_u16: the same for uint16 storage, q_dev uint16[n]; same alignment rules (q_dev 8-byte, out_dev 16-byte aligned). */
 typedef struct afhip_packing { int32_t n_pairs, has_fill, fill, pad; float mul[3], add[3]; } afhip_packing;
 int afhip_plan_bind_packing(afhip_plan* plan, const afhip_packing* p);
 int afhip_unpack_i16(const void* q_dev, int64_t n, const afhip_packing* p, float* out_dev, void* stream);
+int afhip_unpack_u16(const void* q_dev, int64_t n, const afhip_packing* p, float* out_dev, void* stream);
 
 /* Bytes of device scratch a run needs.  afhip_plan_workspace_bytes: the temporal stage alone (per-chunk partials; what
  * afhip_plan_run_temporal takes).  afhip_plan_run_workspace_bytes: a whole afhip_plan_run against `csr` (partials + the

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""An int16-packed cube against its float32 unpacking, on the configs[1] shape (T = 8760 x 309,600 cells), in ONE process.
+"""An int16- (or uint16-) packed cube against its float32 unpacking, on the configs[1] shape (T = 8760 x 309,600 cells), in ONE process.
 
 The stored integers are synthesised in HBM (an ERA5-like seasonal + diurnal field in steps of 0.0017 K around 281.3 K, then
 - 273.15 as a second pair); the float32 cube is `PackedCube.materialize()` of them — what the default device route holds for the
@@ -8,7 +8,10 @@ each plan: the temporal kernel's ms on the packed and on the float32 cube (HIP-e
 `afhip_plan_profile_*`; `--launches` back to back after `--warmup`; min / median / max), the bare read of each cube
 (`hip.read_probe`), the kernel variants, and the largest relative difference of the two panels.
 
-    python scripts/packed_bench.py [--out profiles/packed_cube_measured.txt]
+``--storage uint16``: the same field as uint16 storage — every stored integer offset by 32768 into 0...65535 (the sign bit flipped),
+the add_offset lowered by 32768 steps, the fill value 1 — read by the same kernels under an AFHIP_U16 plan.
+
+    python scripts/packed_bench.py [--storage int16|uint16] [--out profiles/packed_cube_measured.txt]
 """
 import argparse
 import os
@@ -62,6 +65,7 @@ def main():
     ap.add_argument("--regions", type=int, default=3100)
     ap.add_argument("--launches", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--storage", choices=("int16", "uint16"), default="int16")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lines = []
@@ -71,9 +75,15 @@ def main():
         lines.append(s)
 
     C = a.ny * a.nx
-    packed = af.PackedCube(stored_cube(a.T, a.ny, a.nx, a.spd), scale_factor=0.0017, add_offset=281.3, fill_value=-32767) - 273.15
+    if a.storage == "uint16":
+        q = stored_cube(a.T, a.ny, a.nx, a.spd)
+        q.bitwise_xor_(-32768)                      # + 32768 modulo 2^16: the int16 tensor now holds the uint16 bits
+        packed = af.PackedCube(q, scale_factor=0.0017, add_offset=281.3 - 32768 * 0.0017, fill_value=1, unsigned=True) - 273.15
+    else:
+        packed = af.PackedCube(stored_cube(a.T, a.ny, a.nx, a.spd), scale_factor=0.0017, add_offset=281.3, fill_value=-32767) - 273.15
+    packed_code = hip._dtype_code(packed)
     plain = packed.materialize()
-    say(f"cube T={a.T} x {a.ny} x {a.nx} = {C} cells: packed {packed.nbytes() / 1e9:.2f} GB (int16, pairs {packed.pairs}), "
+    say(f"cube T={a.T} x {a.ny} x {a.nx} = {C} cells: packed {packed.nbytes() / 1e9:.2f} GB ({a.storage}, pairs {packed.pairs}), "
         f"float32 {plain.numel() * 4 / 1e9:.2f} GB; device {hip.device_info(hip._device_index(plain))['name']}; build {hip.build_info()}")
     for name, cube in (("packed", packed), ("float32", plain)):
         ms = hip.read_probe(cube, launches=a.launches)[a.warmup // 2:]
@@ -88,10 +98,10 @@ def main():
         say()
         say(title)
         med, res = {}, {}
-        for name, cube, code in (("packed", packed, hip.I16), ("float32", plain, hip.F32)):
+        for name, cube, code in (("packed", packed, packed_code), ("float32", plain, hip.F32)):
             p = hip.FusedPlan(a.T, C, code, ib, ob, cols)
-            if code == hip.I16:
-                p.bind_packing(cube.packing())
+            if code == packed_code:
+                p.bind_packing(cube)
             out = p.run(cube, csr)
             for _ in range(a.warmup):
                 p.run(cube, csr, out=out)
@@ -102,7 +112,7 @@ def main():
             torch.cuda.synchronize()
             ms = p.profile_end()
             med[name], res[name] = float(np.median(ms)), out["res"].cpu().numpy()
-            nbytes = a.T * C * (2 if code == hip.I16 else 4)
+            nbytes = a.T * C * (2 if code == packed_code else 4)
             say(f"  {name:8s} {p.describe().split()[0]:40s} {stats(ms)}   {nbytes / med[name] / 1e9:.2f} TB/s of its own bytes at the median")
         with np.errstate(invalid="ignore", divide="ignore"):
             err = np.nanmax(np.abs(res["packed"] - res["float32"]) / np.maximum(np.abs(res["float32"]), 1e-300))
