@@ -320,8 +320,18 @@ struct afhip_plan : PlanLayout {             // what the planner made (afhip_pla
     int64_t own_ws_bytes = 0;               // outgrown block is `retired` until the plan is destroyed — no hipFree (a device-wide
     std::vector<void*> retired;             // synchronisation) ever sits on the run path
     double* sums = nullptr;                 // [rows][P][K + 1] of the current run: behind partial + panel in the run's workspace
-    PackArgs unpack{};                      // AFHIP_I16 / AFHIP_U16 plans: the unpack rule (afhip_plan_bind_packing)
+    PackArgs unpack{};                      // AFHIP_I16 / AFHIP_U16 plans: the unpack rule (afhip_plan_bind_packing; of several rules the first)
     bool unpack_bound = false;
+    // several rules (afhip_plan_bind_packings, n > 1): a bind only writes the host copy below.  The device table — bounds [n + 1], then
+    // rules [n] — is written by the NEXT run, by a copy ordered on that run's stream in front of its kernel, and only when it differs from
+    // what the table holds: a launch that is still running keeps reading the rules it was launched with.  The table grows by a new
+    // hipMalloc, the outgrown block is `retired` like the workspace's.
+    std::vector<PackArgs> rules;            // n > 1: the bound rules; empty: one rule (`unpack`)
+    std::vector<int64_t> rule_bounds;
+    std::vector<unsigned char> rules_dev_image, rules_stage;   // what the device table holds / the bytes of the copy in flight
+    void* d_rules = nullptr;
+    size_t d_rules_bytes = 0;
+    hipEvent_t rules_ev = nullptr;          // recorded behind the table's copy: the next copy waits for it before it rewrites rules_stage
     int last_ws = 0;                        // 1: the last run used a caller-owned workspace, 2: plan-owned (afhip_plan_describe tells)
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     // per-launch profiling ring (afhip_plan_profile_*): event pairs around the temporal kernel
@@ -329,6 +339,8 @@ struct afhip_plan : PlanLayout {             // what the planner made (afhip_pla
     int64_t prof_count = 0;
     ~afhip_plan() {      // run with `device` current (afhip_plan_destroy): the members below free their buffers after this body
         if (own_ws) (void)hipFree(own_ws);
+        if (d_rules) (void)hipFree(d_rules);
+        if (rules_ev) (void)hipEventDestroy(rules_ev);
         for (void* q : retired) (void)hipFree(q);
         for (auto& e : ev) if (e) (void)hipEventDestroy(e);
         for (auto& e : prof_ev) if (e) (void)hipEventDestroy(e);
@@ -875,13 +887,67 @@ static PackArgs pack_args_of(const afhip_packing* p, int dtype) {
     return pa;
 }
 
+// Every check comes before the first write: a refused bind leaves the earlier binding in place.
+extern "C" int afhip_plan_bind_packings(afhip_plan* plan, const afhip_packing* rules, const int64_t* bounds, int32_t n) {
+    const char* who = "plan_bind_packings";
+    if (!plan) return fail(AFHIP_E_INVALID, "%s: plan is NULL", who);
+    if (!is_packed_dtype(plan->desc.dtype)) return fail(AFHIP_E_INVALID, "%s: the plan's dtype is not AFHIP_I16 or AFHIP_U16", who);
+    if (!rules || !bounds) return fail(AFHIP_E_INVALID, "%s: the rules or the bounds are NULL", who);
+    const int64_t T = plan->desc.T;
+    if (n < 1 || (int64_t)n > T) return fail(AFHIP_E_INVALID, "%s: %d rules for %lld time steps (1 .. T)", who, n, (long long)T);
+    if (bounds[0] != 0 || bounds[n] != T)
+        return fail(AFHIP_E_INVALID, "%s: the bounds must run from 0 to T = %lld, got %lld .. %lld", who, (long long)T, (long long)bounds[0], (long long)bounds[n]);
+    for (int32_t i = 0; i < n; ++i) {
+        if (bounds[i + 1] <= bounds[i]) return fail(AFHIP_E_INVALID, "%s: the bounds must strictly increase (rule %d covers no time step)", who, i);
+        int rc = check_packing(&rules[i], plan->desc.dtype, who);
+        if (rc) return rc;
+    }
+    plan->unpack = pack_args_of(&rules[0], plan->desc.dtype);
+    plan->unpack_bound = true;
+    plan->rules.clear();
+    plan->rule_bounds.clear();
+    if (n > 1) {
+        for (int32_t i = 0; i < n; ++i) plan->rules.push_back(pack_args_of(&rules[i], plan->desc.dtype));
+        plan->rule_bounds.assign(bounds, bounds + n + 1);
+    }
+    return AFHIP_OK;
+}
+
 extern "C" int afhip_plan_bind_packing(afhip_plan* plan, const afhip_packing* p) {
     if (!plan) return fail(AFHIP_E_INVALID, "plan_bind_packing: plan is NULL");
     if (!is_packed_dtype(plan->desc.dtype)) return fail(AFHIP_E_INVALID, "plan_bind_packing: the plan's dtype is not AFHIP_I16 or AFHIP_U16");
     int rc = check_packing(p, plan->desc.dtype, "plan_bind_packing");
     if (rc) return rc;
-    plan->unpack = pack_args_of(p, plan->desc.dtype);
-    plan->unpack_bound = true;
+    const int64_t bounds[2] = {0, plan->desc.T};
+    if (plan->desc.T < 1) {                 // (a plan without time steps launches nothing: the one rule is kept as before)
+        plan->unpack = pack_args_of(p, plan->desc.dtype);
+        plan->unpack_bound = true;
+        plan->rules.clear();
+        plan->rule_bounds.clear();
+        return AFHIP_OK;
+    }
+    return afhip_plan_bind_packings(plan, p, bounds, 1);
+}
+
+// The device table of a multi-rule plan, brought up to date in front of a run's kernel on the run's stream `st` (see afhip_plan::rules).
+static int upload_rules(afhip_plan* pl, hipStream_t st) {
+    const size_t n = pl->rules.size(), bb = (n + 1) * sizeof(int64_t), bytes = bb + n * sizeof(PackArgs);
+    std::vector<unsigned char> img(bytes);
+    memcpy(img.data(), pl->rule_bounds.data(), bb);
+    memcpy(img.data() + bb, pl->rules.data(), n * sizeof(PackArgs));
+    if (pl->d_rules && img == pl->rules_dev_image) return AFHIP_OK;
+    if (bytes > pl->d_rules_bytes) {
+        if (pl->d_rules) { pl->retired.push_back(pl->d_rules); pl->d_rules = nullptr; pl->d_rules_bytes = 0; }
+        HIP_TRY(hipMalloc(&pl->d_rules, bytes));
+        pl->d_rules_bytes = bytes;
+    }
+    if (!pl->rules_ev) HIP_TRY(hipEventCreateWithFlags(&pl->rules_ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(pl->rules_ev));        // the earlier copy has read rules_stage
+    pl->rules_stage = img;
+    pl->rules_dev_image.clear();
+    HIP_TRY(hipMemcpyAsync(pl->d_rules, pl->rules_stage.data(), bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(pl->rules_ev, st));
+    pl->rules_dev_image.swap(img);
     return AFHIP_OK;
 }
 
@@ -967,6 +1033,14 @@ static int launch_temporal(afhip_plan* pl, const void* cube, double* partial, hi
         return fail(AFHIP_E_INVALID, "the plan reads a 16-bit-packed cube (AFHIP_I16 / AFHIP_U16) whose packing was never bound: call afhip_plan_bind_packing first");
     FusedArgs fa{};
     fa.unpack = pl->unpack;
+    fa.n_rules = 1;
+    if (is_packed_dtype(pl->desc.dtype) && pl->rules.size() > 1) {
+        int rc = upload_rules(pl, st);
+        if (rc) return rc;
+        fa.n_rules = (int32_t)pl->rules.size();
+        fa.pack_bounds = (const int64_t*)pl->d_rules;
+        fa.pack_rules = (const PackArgs*)((const char*)pl->d_rules + (pl->rules.size() + 1) * sizeof(int64_t));
+    }
     fa.cube = cube; fa.C = pl->desc.n_cells;
     fa.gtab = pl->d_gtab.p; fa.chunks = pl->d_chunks.p;
     fa.partial = partial; fa.K = pl->K; fa.nthr = pl->nthr;

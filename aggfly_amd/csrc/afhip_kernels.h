@@ -52,9 +52,18 @@ struct FusedArgs {
     // int16-packed cubes (the PackedI16 storage) — `unpack`: how a stored integer becomes the float32 value (unpack_i16, afhip_loads.h),
     // read by scalar loads.  It shares the histogram edges' bytes: packed cubes have no histogram form, and the record keeps its size
     // and every field its offset (the general sixteen-column forms index `cols` at run time and hold a copy of the whole record).
+    // A packed cube may carry SEVERAL rules, each for a contiguous range of time steps (one per store of a multi-file record):
+    // n_rules > 1, rule i = pack_rules[i] unpacks steps pack_bounds[i] .. pack_bounds[i + 1] (device tables of the plan; pack_bounds[0] == 0,
+    // pack_bounds[n_rules] == T, strictly increasing).  A row is one time step, so the rule is wave-uniform per row: choosing it is scalar
+    // work.  n_rules <= 1: `unpack` is the one rule and the tables are not read.  The new fields lie in the same shared bytes.
     union {
         double hb_edge[MAX_THR + 1];
-        PackArgs unpack;
+        struct {
+            PackArgs unpack;
+            const PackArgs* pack_rules;    // device [n_rules]
+            const int64_t* pack_bounds;    // device [n_rules + 1]
+            int32_t n_rules, pack_pad;
+        };
     };
     float hb_dn[MAX_THR + 1], hb_up[MAX_THR + 1];
     // arithmetic edges (FEAT_ARITH_EDGES): every edge is EXACTLY hb_lo0 + g * hb_w in the input precision (host-checked with
@@ -106,6 +115,14 @@ struct FusedArgs {
     const uint32_t* rf_lane;       // device [wave tiles * 64][2]
     int32_t rf_lds_off, rf_pad;    // byte offset, in the dynamic LDS, of the waves' parking blocks: RF_LANE_BYTES per lane (weights + lane words)
 };
+
+// The rule table of multi-rule packed cubes was added INSIDE the bytes `unpack` shares with hb_edge: the record keeps its size and every
+// earlier field its offset (the sixteen-column forms hold a copy of the whole record; profiles/packed_cube.txt, section 1).
+static_assert(sizeof(FusedArgs) == 3632, "FusedArgs keeps its size");
+static_assert(offsetof(FusedArgs, hb_edge) == 160 && offsetof(FusedArgs, unpack) == 160 && offsetof(FusedArgs, hb_dn) == 296, "the shared bytes keep their place");
+static_assert(offsetof(FusedArgs, pack_rules) == 200 && offsetof(FusedArgs, pack_bounds) == 208 && offsetof(FusedArgs, n_rules) == 216, "the rule table follows `unpack`");
+static_assert(offsetof(FusedArgs, hb_bin_of_slot) == 96 && offsetof(FusedArgs, hb_up) == 364 && offsetof(FusedArgs, packed) == 432 && offsetof(FusedArgs, hb_w) == 480, "FusedArgs: field offsets");
+static_assert(offsetof(FusedArgs, thr) == 544 && offsetof(FusedArgs, cols) == 1312 && offsetof(FusedArgs, ccode) == 3488 && offsetof(FusedArgs, rf_w) == 3552 && offsetof(FusedArgs, rf_lds_off) == 3624, "FusedArgs: field offsets");
 
 }  // namespace afhip
 
@@ -398,9 +415,12 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
             __hip_atomic_fetch_add(p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);     // the counter is private to this lane: one ds_add_u32
         }
     };
+    // Packed cubes: `pr` is the rule of the row being consumed — scalars: the argument record's rule, or the rule of the plan's table
+    // that holds the row (several rules: rule_at / rule_next in front of the time loop).
+    PackArgs pr;
     auto consume = [&](const RawVec<TRaw, VEC>& rv, bool hb_inline = true) {
         TIn upk[PACKED ? VEC : 1];
-        if constexpr (PACKED) unpack_i16<VEC>(rv.v, a.unpack, upk);      // (uniform fields of the argument record: scalar loads)
+        if constexpr (PACKED) unpack_i16<VEC>(rv.v, pr, upk);
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
             TIn vr_;
@@ -1042,6 +1062,33 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
     int kk = 0;                 // row index relative to the chunk
     int g = g_lo;
 
+    // ---- packed cubes with several unpack rules (FusedArgs::n_rules > 1) ----
+    // pr: the rule that holds the row about to be consumed; rule_at: its index; rule_next: the chunk-relative row at which the next rule
+    // starts (INT32_MAX: not inside this chunk).  All scalars.  The workgroup finds the rule of its first row by a binary search over the
+    // bounds (invariant: bounds[lo] <= k_lo < bounds[hi]; every index read lies in 0 .. n_rules) and from there on reads a rule — ten
+    // scalar words — only at a row where it changes.  One rule: a scalar branch skips all of it, pr is the argument record's rule and
+    // rule_next stays out of reach of the one compare a burst makes.
+    int rule_at = 0, rule_next = INT32_MAX;
+    auto rule_advance = [&]() {                      // the rule changes at the row about to be consumed
+        ++rule_at;
+        const int64_t b = ld_uniform(a.pack_bounds + rule_at + 1);        // (rule_at + 1 <= n_rules: the last bound is T, never a change)
+        rule_next = b < k_hi ? (int)(b - k_lo) : INT32_MAX;
+        pr = ld_pack_rule(a.pack_rules + rule_at);
+    };
+    if constexpr (PACKED) {
+        pr = a.unpack;                             // (uniform fields of the argument record: scalar loads)
+        if (a.n_rules > 1) {
+            KEEP_BRANCH();
+            int lo = 0, hi = a.n_rules;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (ld_uniform(a.pack_bounds + mid) <= k_lo) lo = mid; else hi = mid;
+            }
+            rule_at = lo - 1;
+            rule_advance();
+        }
+    }
+
     if constexpr (PAIR) {
         const TIn* p = cube;
         constexpr int GB = DEPTH / GL;                // groups per block of rows
@@ -1282,6 +1329,17 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
 #pragma unroll
                         for (int i = 0; i < VEC; ++i) hb_count(r[d].v[i], i, hb_b[d][i], hb_e[d][i]);
                     }
+                } else if constexpr (PACKED) {
+                    // A burst wholly inside one rule fails one scalar compare and runs as for one rule; one that straddles a change tests
+                    // each of its rows and reads the next rule where it starts.  One copy of the burst's body serves both: a second,
+                    // test-free copy for the common case was built — 44 of the 69 kernels lost a wave per SIMD or two to it, one gained
+                    // scratch memory (profiles/packed_cube.txt, section 3).
+                    const bool straddles = kk + DEPTH > rule_next;
+#pragma unroll
+                    for (int d = 0; d < DEPTH; ++d) {
+                        if (straddles && kk + d == rule_next) { KEEP_BRANCH(); rule_advance(); }
+                        consume(r[d]);
+                    }
                 } else {
 #pragma unroll
                     for (int d = 0; d < DEPTH; ++d) consume(r[d]);
@@ -1307,9 +1365,16 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
                         if (d < rem) r[d] = ld_stream<TRaw, VEC, AUX>(p + (int64_t)d * C);
                     p += (int64_t)rem * C;
                 }
+                bool straddles = false;
+                if constexpr (PACKED) straddles = gend > rule_next;
 #pragma unroll
                 for (int d = 0; d < DEPTH - 1; ++d)
-                    if (d < rem) consume(r[d]);
+                    if (d < rem) {
+                        if constexpr (PACKED) {
+                            if (straddles && kk + d == rule_next) { KEEP_BRANCH(); rule_advance(); }
+                        }
+                        consume(r[d]);
+                    }
                 kk = gend;
             }
             group_end((w & 1) != 0, gend - gbeg, __longlong_as_double(iv), (int)((uint64_t)w >> 63), g);

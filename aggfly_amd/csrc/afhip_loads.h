@@ -105,6 +105,17 @@ __device__ __forceinline__ void unpack_i16(const int16_t (&q)[N], const PackArgs
     }
 }
 
+// A rule of the plan's rule table (multi-rule packed cubes: FusedArgs::pack_rules), read by scalar loads: `p` is wave-uniform.
+__device__ __forceinline__ PackArgs ld_pack_rule(const PackArgs* p) {
+    static_assert(sizeof(PackArgs) == 40 && MAX_PACK_PAIRS == 3, "ten words");
+    const int32_t* w = (const int32_t*)p;
+    PackArgs r;
+    r.n_pairs = ld_uniform(w); r.has_fill = ld_uniform(w + 1); r.fill = ld_uniform(w + 2); r.is_unsigned = ld_uniform(w + 3);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { r.mul[i] = ld_uniform((const float*)w + 4 + i); r.add[i] = ld_uniform((const float*)w + 7 + i); }
+    return r;
+}
+
 // One lane's VEC cells of a row, read once: non-temporal loads keep the stream from
 // displacing the plan tables and partials in L2 / Infinity Cache.
 template <typename TIn, int VEC, int AUX>

@@ -39,7 +39,7 @@ EXPORTS = (
     "afhip_plan_describe", "afhip_plan_run_temporal", "afhip_plan_run",
     "afhip_plan_profile_begin", "afhip_plan_profile_end", "afhip_plan_bind_inter", "afhip_csr_device", "afhip_plan_device", "afhip_transform", "afhip_panel_divide", "afhip_lz4_decode_streams", "afhip_unshuffle_blocks", "afhip_read_probe",
     "afhip_zstd_scratch_bytes", "afhip_zstd_decode", "afhip_inflate_scratch_bytes", "afhip_inflate_decode", "afhip_bitunshuffle_blocks",
-    "afhip_plan_bind_packing", "afhip_unpack_i16", "afhip_unpack_u16",
+    "afhip_plan_bind_packing", "afhip_unpack_i16", "afhip_unpack_u16", "afhip_plan_bind_packings",
 )
 
 
@@ -137,6 +137,7 @@ def load():
     lib.afhip_csr_device.argtypes = [vp]
     lib.afhip_plan_device.argtypes = [vp]
     lib.afhip_plan_bind_packing.argtypes = [vp, C.POINTER(Packing)]
+    lib.afhip_plan_bind_packings.argtypes = [vp, C.POINTER(Packing), C.POINTER(C.c_int64), C.c_int32]
     lib.afhip_unpack_i16.argtypes = [vp, i64, C.POINTER(Packing), vp, vp]
     lib.afhip_unpack_u16.argtypes = [vp, i64, C.POINTER(Packing), vp, vp]
     _lib = lib
@@ -317,17 +318,31 @@ def _ptr(t):
 
 def unpack_i16(cube):
     """`afhip_unpack_i16` — `afhip_unpack_u16` for a cube of unsigned storage: the float32 values of a `packed.PackedCube` as a
-    new HBM tensor of its shape."""
+    new HBM tensor of its shape.  The entry points take one rule: a multi-rule cube is unpacked rule by rule, each on its range of
+    time steps — straight into the result where the range's rows are contiguous and start on the kernel's alignment (8 bytes of
+    the integers, 16 of the values), else through a copy of the range."""
     torch = _torch()
     require_gpu()
     q = cube.q if cube.q.is_cuda else cube.q.cuda(non_blocking=True)
-    q = q.contiguous()
-    if q.data_ptr() % 8:                  # a view that starts inside an 8-byte piece (the kernel reads 8 bytes per lane)
-        q = q.clone()
-    out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
-    p = cube.packing()
     fn = load().afhip_unpack_u16 if cube.unsigned else load().afhip_unpack_i16
-    _check(fn(q.data_ptr(), q.numel(), C.byref(p), out.data_ptr(), _stream_ptr(q)))
+
+    def run(q1, p, out1=None):
+        q1 = q1.contiguous()
+        if q1.data_ptr() % 8:                 # a view that starts inside an 8-byte piece (the kernel reads 8 bytes per lane)
+            q1 = q1.clone()
+        direct = out1 is not None and out1.is_contiguous() and out1.data_ptr() % 16 == 0
+        dst = out1 if direct else torch.empty(q1.shape, dtype=torch.float32, device=q1.device)
+        _check(fn(q1.data_ptr(), q1.numel(), C.byref(p), dst.data_ptr(), _stream_ptr(q1)))
+        if out1 is not None and not direct:
+            out1.copy_(dst)
+        return dst
+
+    if cube.n_rules == 1:
+        return run(q, cube.packing())
+    out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+    ax = cube._taxis
+    for part, lo, hi in cube.rule_parts():
+        run(q.narrow(ax, lo, hi - lo), part.packing(), out.narrow(ax, lo, hi - lo))
     return out
 
 
@@ -577,13 +592,24 @@ class FusedPlan:
 
     def bind_packing(self, packing):
         """Bind the unpack rule of the packed cube the next runs read (``dtype_code`` `I16` / `U16` plans; `afhip_plan_bind_packing`).
-        ``packing``: a `Packing`, or the `packed.PackedCube` itself — then its storage must be the plan's (a uint16 cube's rule on
+        ``packing``: a `Packing`, or the `packed.PackedCube` itself — all its rules are bound, and its storage must be the plan's (a uint16 cube's rule on
         an int16 plan would read every value from 32768 up 65536 too low)."""
         if _is_packed(packing):
             if _dtype_code(packing) != self.dtype_code:
                 raise ValueError(f"cube shape/dtype does not match the plan (T={self.T}, cells={self.n_cells}): {packing.storage} storage")
+            if packing.n_rules > 1:             # one rule per range of time steps (`afhip_plan_bind_packings`)
+                rules, bounds = packing.packings()
+                _check(load().afhip_plan_bind_packings(self._h, rules, bounds.ctypes.data_as(C.POINTER(C.c_int64)), len(rules)))
+                return
             packing = packing.packing()
         _check(load().afhip_plan_bind_packing(self._h, C.byref(packing)))
+
+    def bind_packings(self, rules, bounds):
+        """`afhip_plan_bind_packings`: ``rules`` (a sequence of `Packing`) along time, rule ``i`` for the steps ``bounds[i] .. bounds[i + 1]``."""
+        rules = list(rules)
+        arr = (Packing * max(len(rules), 1))(*rules)
+        b = _i64(bounds)
+        _check(load().afhip_plan_bind_packings(self._h, arr, b.ctypes.data_as(C.POINTER(C.c_int64)), len(rules)))
 
     def describe(self) -> str:
         buf = C.create_string_buffer(2048)

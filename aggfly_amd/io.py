@@ -516,6 +516,19 @@ def packing_of(za):
     return (None if sf is None else float(sf), None if ao is None else float(ao), fv, unsigned)
 
 
+def packed_rules_of(packings):
+    """Whether a dataset read from several stores stays packed: ``packings`` is what `packing_of` says of each store, in time order.
+    -> the stores' unpack rules [(scale_factor, add_offset, fill value, unsigned)], one per store — equal neighbours are merged later, by
+    `packed.PackedCube.concat`, so stores of ONE packing give one rule — or None: a store that cannot stay packed (float storage,
+    a fill value that is no stored integer), or int16 beside uint16 storage (one plan reads one storage).  Then all take the float32 route."""
+    packings = list(packings)
+    if not packings or any(p is None for p in packings):
+        return None
+    if len({bool(p[3]) for p in packings}) != 1:
+        return None
+    return packings
+
+
 def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 << 20, t_range=None, yx_box=None, keep_packed=False):
     """Stream a chunked (time, y, x) array — a `ZarrArray` or an `hdf5.ChunkSource` — straight into HBM: each
     slab is a whole number of time chunks, decoded chunk-parallel by the native codec into page-locked memory
@@ -1832,8 +1845,10 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
     (`distributed.aggregate_store_cells`); on the streaming route only the chunks that touch the band are read.
     ``keep_packed=True`` (extension; or AGGFLY_HIP_KEEP_PACKED=1): an int16- or uint16-packed variable (``scale_factor`` / ``add_offset`` /
     ``_FillValue``; int16 under ``_Unsigned = "true"`` counts as uint16) stays packed in HBM as a `packed.PackedCube` — half the memory, half the bytes the temporal kernel reads — and
-    ``preprocess`` folds into its unpack rule.  Honoured on the streaming routes (``device=``) only, for 16-bit integer storage, and for several
-    stores only when all share their packing (yearly ERA5 files usually do not: they take the float32 route); ``Dataset.is_packed``
+    ``preprocess`` folds into its unpack rule.  Honoured on the streaming routes (``device=``) only, for 16-bit integer storage.  Several Zarr
+    stores — yearly or monthly ERA5 files, each with its own ``scale_factor`` / ``add_offset`` / ``_FillValue`` — stay packed too: the cube
+    carries one unpack rule per store along time (``PackedCube.rules``; stores of one packing share one rule) and the kernel picks the rule per
+    time step.  They take the float32 route only when a store has no packing or int16 stands beside uint16 storage; ``Dataset.is_packed``
     tells which route was taken."""
     import glob
     keep_packed = keep_packed_requested(keep_packed)
@@ -1845,9 +1860,9 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
     engine = kwargs.pop("engine", None)
     if device is not None and all(engine == "zarr" or (engine is None and _looks_like_zarr(p)) for p in paths):
 
-        # several stores stay packed only under ONE packing: one rule unpacks the whole concatenated cube
-        packings = {packing_of(ZarrArray(os.path.join(p_, var))) for p_ in paths} if keep_packed else {None}
-        stay_packed = len(packings) == 1 and None not in packings
+        # several stores stay packed when each has a packing and all share their signedness: one unpack rule per store, in time order
+        rules = packed_rules_of([packing_of(ZarrArray(os.path.join(p_, var))) for p_ in paths]) if keep_packed else None
+        stay_packed = rules is not None
 
         def part_to_device(path1):
             za = ZarrArray(os.path.join(path1, var))
@@ -1897,15 +1912,20 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
                     time = pd.DatetimeIndex(np.concatenate([np.asarray(g[2][timecoord]) for g in got]))
                 coords = dict(got[0][2])
                 coords[timecoord] = time
-                data, za = torch.cat([g[0] for g in got], dim=0), got[0][1]
+                if stay_packed:                     # (the parts were cut by time_window / time_sel already: the bounds are those of what was read)
+                    from .packed import PackedCube
+                    data = PackedCube.concat([PackedCube(g[0], *r) for g, r in zip(got, rules)])
+                else:
+                    data = torch.cat([g[0] for g in got], dim=0)
+                za = got[0][1]
             else:
                 data, za, coords = got[0]
+                if stay_packed:
+                    from .packed import PackedCube
+                    data = PackedCube(data, *rules[0])
         except ValueError:
             data = None
         if data is not None:
-            if stay_packed:
-                from .packed import PackedCube
-                data = PackedCube(data, *packings.copy().pop())
             da = DataArray(data, za.dims, coords, name=var, attrs=za.attrs)
             # a band was cut out of the already clipped box: the clip is not repeated on the band's own grid
             return Dataset(da, xycoords=xycoords, timecoord=timecoord, time_sel=time_sel, lon_is_360=lon_is_360,

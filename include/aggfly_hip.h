@@ -318,9 +318,23 @@ int afhip_plan_bind_inter(afhip_plan* plan, int column, const void* inter_dev, i
  * unsigned value.  A fill must lie in the storage's range (-32768..32767 / 0..65535).  Both dtypes run the same kernels: the signedness is a
  * field of the record the library fills from the plan's dtype at bind time.  `pad` is ignored: whatever the caller writes there is not read.
  * afhip_unpack_i16: the same rule on a whole array, q_dev int16[n] -> out_dev float[n] (a plain stream, 8 bytes read per lane).
- * afhip_unpack_u16: the same for uint16 storage, q_dev uint16[n]; same alignment rules (q_dev 8-byte, out_dev 16-byte aligned). */
+ * afhip_unpack_u16: the same for uint16 storage, q_dev uint16[n]; same alignment rules (q_dev 8-byte, out_dev 16-byte aligned).
+ * An afhip_packing is ONE rule.  A cube concatenated from several stores (yearly or monthly files, each with its own scale_factor /
+ * add_offset / _FillValue) carries one rule per store:
+ * afhip_plan_bind_packings: rule i unpacks the time steps bounds[i] .. bounds[i + 1]; rules [n], bounds [n + 1] (host arrays, copied),
+ * bounds[0] == 0, bounds[n] == T, strictly increasing, 1 <= n <= T (no other cap on n); every fill in the range of the plan's storage; the
+ * signedness is the plan's dtype for all rules alike.  Anything else returns AFHIP_E_INVALID, binds nothing — the earlier binding still
+ * holds — and launches nothing.  afhip_plan_bind_packing(plan, p) is the case n == 1.  The same kernels serve both: a time step is a row of
+ * the cube, so the rule is uniform per row and chosen by scalar code; with one rule a scalar branch skips the choice.
+ * Binding while a run is in flight: a bind never changes what a launch that was already issued reads.  One rule travels by value in the
+ * launch's argument record.  Several rules live in a table on the device that the plan owns; a bind writes the plan's host copy only, and
+ * the NEXT run brings the table up to date by a copy ordered on that run's stream, in front of its kernel (and only when the rules differ
+ * from the table's).  So runs that share a stream may be re-bound between them freely; as with the plan's workspace, runs of one plan on
+ * DIFFERENT streams must not overlap.  (That copy reads host memory: a run whose rules changed cannot be captured into a graph.)
+ * The afhip_unpack_* entry points take one rule: a multi-rule cube is materialised rule by rule, on its row ranges. */
 typedef struct afhip_packing { int32_t n_pairs, has_fill, fill, pad; float mul[3], add[3]; } afhip_packing;
 int afhip_plan_bind_packing(afhip_plan* plan, const afhip_packing* p);
+int afhip_plan_bind_packings(afhip_plan* plan, const afhip_packing* rules, const int64_t* bounds, int32_t n);
 int afhip_unpack_i16(const void* q_dev, int64_t n, const afhip_packing* p, float* out_dev, void* stream);
 int afhip_unpack_u16(const void* q_dev, int64_t n, const afhip_packing* p, float* out_dev, void* stream);
 

@@ -11,7 +11,12 @@ each plan: the temporal kernel's ms on the packed and on the float32 cube (HIP-e
 ``--storage uint16``: the same field as uint16 storage — every stored integer offset by 32768 into 0...65535 (the sign bit flipped),
 the add_offset lowered by 32768 steps, the fill value 1 — read by the same kernels under an AFHIP_U16 plan.
 
-    python scripts/packed_bench.py [--storage int16|uint16] [--out profiles/packed_cube_measured.txt]
+Beside the single-rule cube each plan also runs with the same cube bound as 1, 40 and 480 equal-length unpack rules (`--rules`;
+`afhip_plan_bind_packings` with the one rule repeated — what a record of that many stores costs the kernel, whatever the stores'
+packings are: the kernel reads a rule from its table at every change and cannot know they are equal).  Each is reported against the
+single-rule row of the same run; the single-rule row carries its run-to-run spread, (max - min) / median.
+
+    python scripts/packed_bench.py [--storage int16|uint16] [--rules 1,40,480] [--out profiles/packed_cube_measured.txt]
 """
 import argparse
 import os
@@ -66,6 +71,7 @@ def main():
     ap.add_argument("--launches", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--storage", choices=("int16", "uint16"), default="int16")
+    ap.add_argument("--rules", default="1,40,480", help="rule counts the packed cube is also bound as (equal-length ranges of time steps)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lines = []
@@ -98,9 +104,13 @@ def main():
         say()
         say(title)
         med, res = {}, {}
-        for name, cube, code in (("packed", packed, packed_code), ("float32", plain, hip.F32)):
+        runs = [("packed", packed, packed_code, 0)] + [(f"{n} rules", packed, packed_code, n) for n in map(int, a.rules.split(",")) if n] + \
+               [("float32", plain, hip.F32, 0)]
+        for name, cube, code, n_rules in runs:
             p = hip.FusedPlan(a.T, C, code, ib, ob, cols)
-            if code == packed_code:
+            if n_rules:
+                p.bind_packings([cube.packing()] * n_rules, [a.T * i // n_rules for i in range(n_rules + 1)])
+            elif code == packed_code:
                 p.bind_packing(cube)
             out = p.run(cube, csr)
             for _ in range(a.warmup):
@@ -113,7 +123,11 @@ def main():
             ms = p.profile_end()
             med[name], res[name] = float(np.median(ms)), out["res"].cpu().numpy()
             nbytes = a.T * C * (2 if code == packed_code else 4)
-            say(f"  {name:8s} {p.describe().split()[0]:40s} {stats(ms)}   {nbytes / med[name] / 1e9:.2f} TB/s of its own bytes at the median")
+            extra = f"   spread (max - min) / median {(max(ms) - min(ms)) / med[name]:.4f}" if name == "packed" else \
+                    (f"   x {med[name] / med['packed']:.4f} of the single-rule median" if n_rules else "")
+            say(f"  {name:9s} {p.describe().split()[0]:40s} {stats(ms)}   {nbytes / med[name] / 1e9:.2f} TB/s of its own bytes at the median{extra}")
+            if n_rules:
+                assert np.array_equal(res[name], res["packed"], equal_nan=True), f"{name}: the panel differs from the single-rule cube's"
         with np.errstate(invalid="ignore", divide="ignore"):
             err = np.nanmax(np.abs(res["packed"] - res["float32"]) / np.maximum(np.abs(res["float32"]), 1e-300))
         say(f"  packed / float32 kernel time (medians): {med['packed'] / med['float32']:.3f};  panels differ by at most {err:.1e} relative")
