@@ -354,13 +354,14 @@ extern "C" const char* afhip_last_error(void) { return last_error(); }
 extern "C" int afhip_abi_version(void) { return AFHIP_ABI_VERSION; }
 
 extern "C" int afhip_build_info(char* buf, int buf_len) {
-    int n = 0, arms = 0, rf = 0, np = 0;
+    int n = 0, arms = 0, rf = 0, np = 0, nh = 0;
     const Variant* tab = variants_table(&n);
     for (int i = 0; i < n; ++i) { arms += tab[i].production ? 0 : 1; rf += tab[i].rf() ? 1 : 0; }
     (void)packed_variants_table(&np);
-    char tmp[200];
-    const int len = snprintf(tmp, sizeof tmp, "menu=%s variants=%d arms=%d region_fused_twins=%d abi=%d packed_variants=%d", variants_menu(), n, arms, rf,
-                             AFHIP_ABI_VERSION, np);
+    (void)packed_hist_variants_table(&nh);
+    char tmp[240];
+    const int len = snprintf(tmp, sizeof tmp, "menu=%s variants=%d arms=%d region_fused_twins=%d abi=%d packed_variants=%d packed_hist_variants=%d", variants_menu(),
+                             n, arms, rf, AFHIP_ABI_VERSION, np, nh);
     if (buf && buf_len > 0) snprintf(buf, buf_len, "%s", tmp);
     return len + 1;
 }
@@ -1085,10 +1086,12 @@ static int launch_temporal(afhip_plan* pl, const void* cube, double* partial, hi
         fa.hb_c1f = (float)pl->hb_c1; fa.hb_c0f = (float)pl->hb_c0;
         fa.hb_shift = pl->wg == 64 ? 6 : (pl->wg == 128 ? 7 : 8);
         for (int i = 0; i < MAX_THR; ++i) fa.hb_bin_of_slot[i] = pl->hb_bin_of_slot[i];
+        // (a packed cube's histogram forms compare in float32 and never read the double edges — whose bytes hold the unpack rule stored above)
+        const bool double_edges = !is_packed_dtype(pl->desc.dtype);
         for (int k = 0; k <= pl->hb_n; ++k) {
             const double t = pl->hb_edge[k];
             const float f = (float)t;
-            fa.hb_edge[k] = t;
+            if (double_edges) fa.hb_edge[k] = t;
             fa.hb_dn[k] = (double)f > t ? std::nextafterf(f, -INFINITY) : f;     // largest float <= t
             fa.hb_up[k] = (double)f < t ? std::nextafterf(f, INFINITY) : f;      // smallest float >= t
         }

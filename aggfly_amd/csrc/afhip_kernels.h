@@ -50,8 +50,9 @@ struct FusedArgs {
     int32_t hb_n, hb_shift;        // hb_shift = log2(blockDim): counters are laid out [bin * VEC + i][blockDim]
     int32_t hb_bin_of_slot[MAX_THR];
     // int16-packed cubes (the PackedI16 storage) — `unpack`: how a stored integer becomes the float32 value (unpack_i16, afhip_loads.h),
-    // read by scalar loads.  It shares the histogram edges' bytes: packed cubes have no histogram form, and the record keeps its size
-    // and every field its offset (the general sixteen-column forms index `cols` at run time and hold a copy of the whole record).
+    // read by scalar loads.  It shares the bytes of the histogram's DOUBLE edges: a packed cube's values are float32, so its histogram forms
+    // read the float constants only (hb_dn / hb_up, hb_c1f, hb_wf ...) and never hb_edge, which the host leaves unwritten for them; the record
+    // keeps its size and every field its offset (the general sixteen-column forms index `cols` at run time and hold a copy of the whole record).
     // A packed cube may carry SEVERAL rules, each for a contiguous range of time steps (one per store of a multi-file record):
     // n_rules > 1, rule i = pack_rules[i] unpacks steps pack_bounds[i] .. pack_bounds[i + 1] (device tables of the plan; pack_bounds[0] == 0,
     // pack_bounds[n_rules] == T, strictly increasing).  A row is one time step, so the rule is wave-uniform per row: choosing it is scalar
@@ -185,8 +186,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
     static_assert(!RF || !(SL || HB), "region-fused period ends: two-level plans only");
     static_assert(!(HB && SINE), "histogram variants carry no sine_dd code");
     static_assert(!RF || VEC <= 2, "region-fused period ends: one or two cells per lane");
-    static_assert(!PACKED || (PIPE == 0 && !feat_has(FEAT, FEAT_SHORT_GROUP | FEAT_INT_BINS | FEAT_SINGLE_LEVEL | FEAT_HIST | FEAT_REGION_FUSED)),
-                  "int16-packed cubes: the general forms of the direct-load path only");
+    static_assert(!PACKED || (PIPE == 0 && !feat_has(FEAT, FEAT_SHORT_GROUP | FEAT_REGION_FUSED) && (HB ? (TKI && STAT <= 1) : !(TKI || SL))),
+                  "int16-packed cubes: the general forms and the LDS-histogram forms of the direct-load path only");
     const int64_t C = a.C;
     const int K = a.K;
     const int lane = threadIdx.x & 63;
@@ -1313,10 +1314,37 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
                 p += (int64_t)DEPTH * C;
             };
             auto use_block = [&](const RawVec<TRaw, VEC> (&r)[DEPTH]) {
-                if constexpr (HA) {
+                if constexpr (HA && !PACKED) {
 #pragma unroll
                     for (int d = 0; d < DEPTH; ++d) consume(r[d]);
-                } else if constexpr (HB) {
+                } else if constexpr (HB && !HA && PACKED) {
+                    // the table form on packed storage: an element is unpacked ONCE, under the rule of its row (the rule logic of the PACKED
+                    // arm below), and guess, count and statistic all take that value; the burst's table reads are issued before the first
+                    // compare needs one, as on float storage
+                    const bool straddles = kk + DEPTH > rule_next;
+                    TIn u[DEPTH][VEC];
+                    int hb_b[DEPTH][VEC];
+                    EdgeT hb_e[DEPTH][VEC];
+#pragma unroll
+                    for (int d = 0; d < DEPTH; ++d) {
+                        if (straddles && kk + d == rule_next) { KEEP_BRANCH(); rule_advance(); }
+                        unpack_i16<VEC>(r[d].v, pr, u[d]);
+#pragma unroll
+                        for (int i = 0; i < VEC; ++i) hb_guess(u[d][i], hb_b[d][i], hb_e[d][i]);
+                    }
+#pragma unroll
+                    for (int d = 0; d < DEPTH; ++d) {
+#pragma unroll
+                        for (int i = 0; i < VEC; ++i) {
+                            const TIn vr = u[d][i];
+                            if constexpr (STAT == 1) {              // (what `consume` does for the histogram forms: STAT <= 1, no threshold slots)
+                                nanmask[i] |= __builtin_amdgcn_ballot_w64(vr != vr);
+                                s[i] += (double)vr;
+                            }
+                            hb_count(vr, i, hb_b[d][i], hb_e[d][i]);
+                        }
+                    }
+                } else if constexpr (HB && !HA) {
                     int hb_b[DEPTH][VEC];
                     EdgeT hb_e[DEPTH][VEC];
 #pragma unroll
@@ -1333,7 +1361,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
                     // A burst wholly inside one rule fails one scalar compare and runs as for one rule; one that straddles a change tests
                     // each of its rows and reads the next rule where it starts.  One copy of the burst's body serves both: a second,
                     // test-free copy for the common case was built — 44 of the 69 kernels lost a wave per SIMD or two to it, one gained
-                    // scratch memory (profiles/packed_cube.txt, section 3).
+                    // scratch memory (profiles/packed_cube.txt, section 3).  (The arithmetic-edge histogram forms take this arm too: `consume`
+                    // unpacks the row and hands each value to ha_update.)
                     const bool straddles = kk + DEPTH > rule_next;
 #pragma unroll
                     for (int d = 0; d < DEPTH; ++d) {

@@ -145,8 +145,11 @@ __device__ __forceinline__ RawVec<TIn, VEC> ld_stream_row(const void* row, uint3
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(row), 0, -1, 0x00020000);
     constexpr int aux = AUX != 0 ? 2 : 0;          // nt
     constexpr int bytes = (int)sizeof(TIn) * VEC;
-    static_assert(bytes == 4 || bytes == 8 || bytes == 16, "one dword, two or four per lane");
-    if constexpr (bytes == 4) {
+    static_assert(bytes == 2 || bytes == 4 || bytes == 8 || bytes == 16, "one dword, two or four per lane — or one 16-bit element (a packed cube at one cell per lane)");
+    if constexpr (bytes == 2) {
+        const uint16_t t = __builtin_amdgcn_raw_buffer_load_b16(rs, voff, 0, aux);
+        __builtin_memcpy(&r, &t, 2);
+    } else if constexpr (bytes == 4) {
         const uint32_t t = __builtin_amdgcn_raw_buffer_load_b32(rs, voff, 0, aux);
         __builtin_memcpy(&r, &t, 4);
     } else if constexpr (bytes == 8) {

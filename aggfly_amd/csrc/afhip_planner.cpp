@@ -49,6 +49,8 @@ PlanKnobs read_knobs() {
     k.no_quad_mode = set("AFHIP_NO_QUAD_MODE");
     k.no_ragged_mode = set("AFHIP_NO_RAGGED_MODE");
     k.no_region_fused = set("AFHIP_NO_REGION_FUSED");
+    k.no_packed_hist = set("AFHIP_NO_PACKED_HIST");
+    if (const char* e = getenv("AFHIP_PACKED_HIST_VEC")) { const int v = atoi(e); if (v == 1 || v == 2) k.packed_hist_vec = v; }
     k.counts_spmm = !set("AFHIP_NO_COUNTS_SPMM");
     if (const char* e = getenv("AFHIP_COUNTS_SPMM_SUB")) k.counts_spmm_sub = atoi(e);
     if (const char* e = getenv("AFHIP_NO_SLOT_SPMM")) k.no_slot_spmm = atoi(e) != 0;
@@ -344,7 +346,8 @@ static HistPartition find_partition(const PlanLayout& pl, bool all_bins) {
     // the in-kernel guess floor(v / w - e0 / w) is computed in the INPUT precision and may be off by
     // one bin at most: the bins must not be narrower than ~2^20 (f32) / 2^48 (f64) ulps of the edges
     const double emax = std::max(std::fabs(e0), std::fabs(e0 + pl.nthr * w));
-    const double eps = desc->dtype == AFHIP_F32 ? 1.2e-7 : 2.3e-16;
+    // (a packed cube's values are float32: its dtype goes the float way here and below)
+    const double eps = desc->dtype != AFHIP_F64 ? 1.2e-7 : 2.3e-16;
     ok = ok && emax * eps * 16.0 < w;
     if (!ok) return h;
     const int n = pl.nthr;
@@ -355,7 +358,7 @@ static HistPartition find_partition(const PlanLayout& pl, bool all_bins) {
     }
     h.hb_edge[n] = pl.thr[(size_t)order[(size_t)n - 1]].t1;
     h.hb_w = w; h.hb_lo0 = e0 - w; h.hb_gl = e0 - 0.5 * w; h.hb_gh = h.hb_edge[n] + 0.5 * w;
-    const bool f32 = desc->dtype == AFHIP_F32;
+    const bool f32 = desc->dtype != AFHIP_F64;
     bool ex = f32 ? edges_exact<float>(h, n, e0) : edges_exact<double>(h, n, e0);
     if (ex) ex = f32 ? biased_guess<float>(h, n, 22, &h.hb_c0b) : biased_guess<double>(h, n, 50, &h.hb_c0b);
     // (these variants address a row by a 32-bit byte offset per lane)
@@ -391,15 +394,42 @@ static const Variant* choose_packed_variant(const PlanLayout& pl) {
     return nullptr;
 }
 
+// one inner group per period and every outer `first`: the plan qualifies for the single-level (`sl`) forms
+static bool is_single_level(const PlanLayout& pl) {
+    const afhip_plan_desc* desc = &pl.desc;
+    bool single_level = desc->P == desc->G1;
+    for (int64_t p = 0; single_level && p <= desc->P; ++p) single_level = pl.ob[(size_t)p] == p;
+    for (const ColOp& c : pl.cols) single_level = single_level && c.outer == OUT_FIRST;
+    return single_level;
+}
+
+// ... and for a plan whose threshold slots are a contiguous equal-width partition (`hist`, found with the float32 rules: the values of a
+// packed cube are float32) the table of LDS-histogram forms (packed_hist_variants_table): the widest cells per lane that divide the row
+// length and that the production menu holds for the plan's stat tier — single-level form for single-level plans, arithmetic edges when
+// the edges are exact, else the edge table.  Which widths the menu holds was measured form by form (gen_variants.py: packed_hist_menu;
+// profiles/packed_cube.txt, section 6): two cells per lane for the single-level edge-table forms only.  Null: no such kernel, the plan
+// takes the general form above.  AFHIP_PACKED_HIST_VEC=1|2 asks for that width where the library holds it, arms included (the A/B knob
+// of that section).
+static const Variant* choose_packed_hist_variant(const PlanLayout& pl, const HistPartition& hist, const PlanKnobs& knobs) {
+    if (hist.hb_n == 0 || knobs.no_packed_hist) return nullptr;
+    const int64_t C = pl.desc.n_cells;
+    const bool sl = is_single_level(pl);
+    if (knobs.packed_hist_vec && C % knobs.packed_hist_vec == 0)
+        if (const Variant* v = find_packed_hist_variant(knobs.packed_hist_vec, pl.stat, pl.nthr, pl.K, sl, hist.hb_arith, true)) return v;
+    for (int vec : {2, 1}) {
+        if (C % vec != 0) continue;
+        if (const Variant* v = find_packed_hist_variant(vec, pl.stat, pl.nthr, pl.K, sl, hist.hb_arith)) return v;
+    }
+    return nullptr;
+}
+
 // `form0` and `path0` are the short-group form and the load path the plan would take by the default rules.  Null: the menu holds
 // no variant that covers the plan.
 static const Variant* choose_variant(const PlanLayout& pl, const GroupForm& form0, const LoadPath& path0, const HistPartition& hist, bool all_bins,
                                      int tuning, const PlanKnobs& knobs, int cu_count) {
     const afhip_plan_desc* desc = &pl.desc;
     // specialisations the lowered plan qualifies for
-    bool single_level = desc->P == desc->G1;
-    for (int64_t p = 0; single_level && p <= desc->P; ++p) single_level = pl.ob[(size_t)p] == p;
-    for (const ColOp& c : pl.cols) single_level = single_level && c.outer == OUT_FIRST;
+    const bool single_level = is_single_level(pl);
     const LoadPath path = (hist.hb_n > 0 && tuning == 0) ? LoadPath{0, 1} : path0;   // the LDS histogram lives on the direct-load path
     const GroupForm form = on_load_path(form0, path.pipe);
     // rows in flight per lane on the direct-load path: f64 four, f32 eight — but four for f32 plans with two cells per lane on
@@ -719,17 +749,26 @@ int build_plan(const afhip_plan_desc* desc, const DeviceFacts& dev, PlanLayout* 
     if ((rc = lower_columns(pl))) return rc;
 
     if (is_packed_dtype(desc->dtype)) {
-        // int16 and uint16 storage alike (the kernels take the signedness from the bound packing) straight to the packed table: no short-group form, no histogram partition, no packed counts, and — the table has no
-        // region-fused twins — the spatial stage is the slot gather or the table-order sums
-        pl->variant = choose_packed_variant(*pl);
+        // int16 and uint16 storage alike (the kernels take the signedness from the bound packing).  A plan of four or more contiguous,
+        // equal-width, strict bins (find_partition, with the float32 rules) takes an LDS-histogram form of the packed histogram table,
+        // chunked like the float histogram plans (single-wave workgroups, many chunks) and, single-level, with packed count records and
+        // the count gather (packed_format); AFHIP_NO_PACKED_HIST sends it on with the rest.  Every other plan goes straight to the packed
+        // table of general forms: no short-group form, no packed counts (packed_format finds no integer-bin form), and — neither table
+        // has region-fused twins — the spatial stage is the slot gather or the table-order sums
+        bool all_bins = pl->nthr > 0;
+        for (const ThrSlot& t : pl->thr) all_bins = all_bins && t.nan_poisons == 0;
+        const HistPartition hist = find_partition(*pl, all_bins);
+        pl->variant = choose_packed_hist_variant(*pl, hist, knobs);
+        if (pl->variant) static_cast<HistPartition&>(*pl) = hist;
+        else pl->variant = choose_packed_variant(*pl);
         if (!pl->variant)
             return fail(AFHIP_E_UNSUPPORTED, "no packed kernel variant for stat=%d slots=%d columns=%d", pl->stat, pl->nthr, pl->K);
         if ((rc = build_chunks(pl, pl->variant->vec, knobs, dev))) return rc;
         pl->variant_rf = nullptr;
         pl->rf_plan_ok = false;
         pl->gtab = group_table(*pl);
-        pl->pk = PackFmt{};
-        pl->packed = false;
+        pl->pk = packed_format(*pl);
+        pl->packed = pl->pk.nw != 0;
         workspace_sizes(pl);
         return AFHIP_OK;
     }

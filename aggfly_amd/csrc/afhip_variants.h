@@ -41,6 +41,9 @@ const char* variants_menu();             // "full" (the production menu), "arms"
 // gen_variants.py: packed_menu), a table of their own (packed_table.hip): general
 // two-level forms on the direct-load path only, so a plan's stat / slots / columns and the cells per lane are all there is to match.
 const Variant* packed_variants_table(int* n);
+// ... and their LDS-histogram forms (gen_variants.py: packed_hist_menu; packed_hist_table.hip): integer-bin forms for plans whose
+// threshold slots are a contiguous equal-width partition, matched on cells per lane, stat tier, single level and arithmetic edges.
+const Variant* packed_hist_variants_table(int* n);
 
 // What a lowered plan asks of the menu (afhip_planner.cpp: choose_variant).  A fallback is the same query with a field changed.
 // tuning: 0 = the default choice below; otherwise an explicit arm
@@ -105,6 +108,25 @@ inline const Variant* find_packed_variant(int vec, int stat, int nthr, int K) {
     for (int i = 0; i < n; ++i) {
         const Variant& v = tab[i];
         if (v.vec != vec || v.stat < stat || v.nthr < nthr || v.kmax < K) continue;
+        const long cost = (long)v.nthr * 1000 + (long)v.kmax * 10 + v.stat;
+        if (!best || cost < best_cost) { best = &v; best_cost = cost; }
+    }
+    return best;
+}
+
+// the packed LDS-histogram kernel with `vec` cells per lane for a partition plan (null: the menu has none at that width).  The form is
+// matched exactly — the single-level form for single-level plans, arithmetic edges when the plan's edges are exact, else the edge table:
+// the menu holds every form at one cell per lane, and a wider kernel of ANOTHER form is no substitute (the widths were measured per form).
+// `arms`: the kernels outside the production menu too (a forced width: AFHIP_PACKED_HIST_VEC)
+inline const Variant* find_packed_hist_variant(int vec, int stat, int nthr, int K, bool single_level, bool arith, bool arms = false) {
+    const Variant* best = nullptr;
+    long best_cost = 0;
+    int n = 0;
+    const Variant* tab = packed_hist_variants_table(&n);
+    for (int i = 0; i < n; ++i) {
+        const Variant& v = tab[i];
+        if (!v.hb() || v.vec != vec || v.stat < stat || v.nthr < nthr || v.kmax < K || (!v.production && !arms)) continue;
+        if (v.sl() != single_level || v.ha() != arith) continue;
         const long cost = (long)v.nthr * 1000 + (long)v.kmax * 10 + v.stat;
         if (!best || cost < best_cost) { best = &v; best_cost = cost; }
     }

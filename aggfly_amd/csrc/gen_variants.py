@@ -6,7 +6,8 @@ Usage: gen_variants.py OUTDIR [--menu full|arms|dev] [--per-file N]      (full: 
 Each generated ``variants_NN.hip`` holds a handful of explicit instantiations so that
 ``make -j`` compiles them in parallel; ``variants_table.hip`` collects the table that
 ``find_variant`` (afhip_variants.h) searches.  The kernels of int16-packed cubes (`packed_menu`) go to ``packed_NN.hip`` and a
-table of their own, ``packed_table.hip`` (``packed_variants_table``): `menu` and its table count the float kernels only.
+table of their own, ``packed_table.hip`` (``packed_variants_table``): `menu` and its table count the float kernels only.  Their
+LDS-histogram forms (`packed_hist_menu`) likewise: ``packed_hist_NN.hip`` and ``packed_hist_table.hip`` (``packed_hist_variants_table``).
 """
 import os
 import sys
@@ -18,6 +19,7 @@ I16 = 2        # AFHIP_I16: int16 storage, float32 values
 # their float32 twins) and one four-cell form (36).  A plan of such a shape takes the next narrower kernel, which has none.
 PACKED_DROPPED = {(2, 3, nthr, 16) for nthr in (0, 1, 4, 16)} | {(4, 3, 1, 6)}
 PACKED_SHALLOW = {(1, 3, 16, 16)}      # ... and the one that keeps eight rows in flight where its width takes sixteen: 36 bytes of scratch at sixteen (and at twelve)
+PACKED_HIST_VECS = (2, 1)              # packed_hist_menu: cells per lane (four: every two-level form holds 528 bytes of scratch, the single-level ones one ... two waves per SIMD)
 
 
 class Feat:
@@ -202,6 +204,29 @@ def packed_menu(kind):
     return [v for v in out if v[2:6] not in PACKED_DROPPED and pickable(v)]
 
 
+def packed_hist_menu(kind):
+    """The LDS-histogram kernels of int16-packed cubes (contiguous equal-width bins; afhip_planner.cpp: choose_packed_hist_variant), same
+    tuples as `menu`: stat 0 / 1, two-level / single-level, edge table / arithmetic edges — the shapes of the float32 histogram menu.  A
+    table and translation units of their own: `packed_menu` keeps its 69.
+    Cells per lane, measured form by form on the configs[1] shape (profiles/packed_cube.txt, section 6): every form at one cell per lane
+    (odd row lengths, and the faster width of six of the eight forms: two cells take 2 ... 39 % longer); two cells only for the
+    single-level edge-table forms, which they carry 27 - 31 % faster.  The planner takes the widest form that divides the rows and that
+    the production menu holds; the six other two-cell kernels are arms (`make MENU=arms`, AFHIP_PACKED_HIST_VEC=2).
+    Rows in flight, from -Rpass-analysis=kernel-resource-usage (section 5): sixteen for the arithmetic-edge forms, which hold a burst as
+    2-byte elements — but eight for the two-cell forms with a mean, which hold 12 bytes of scratch at sixteen — and eight for the table
+    forms, which keep the unpacked value, the guess and two edges of every element of a burst in registers.  No kernel of the menu has
+    scratch memory."""
+    def one(vec, stat, sl, ha):
+        feat = Feat.NT | Feat.INT_BINS | Feat.HIST | (Feat.SINGLE_LEVEL if sl else 0) | (Feat.ARITH_EDGES if ha else 0)
+        depth = 16 if ha and not (vec == 2 and stat == 1) else 8
+        return (I16, 0, vec, stat, 16, 16, depth, feat, 1 if vec == 1 or (sl and not ha) else 0)
+
+    if kind == "dev":
+        return [one(1, 0, 1, 1)]
+    out = [one(vec, stat, sl, ha) for vec in PACKED_HIST_VECS for stat in (0, 1) for sl in (0, 1) for ha in (0, 1)]
+    return out if kind == "arms" else [v for v in out if v[8]]
+
+
 def pickable(v):
     """False for a kernel that no plan can select by the planner's default rules (afhip_planner.cpp: the stage named in each comment), whatever its shape."""
     dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod = v
@@ -296,6 +321,9 @@ def main():
     pvs = packed_menu(kind)
     pfiles, pgroups = write_units(outdir, pvs, per_file, "packed")
     files += pfiles
+    hvs = packed_hist_menu(kind)
+    hfiles, hgroups = write_units(outdir, hvs, per_file, "packed_hist")
+    files += hfiles
     with _KeepIfSame(os.path.join(outdir, "variants_table.hip")) as f:
         f.write("// generated by gen_variants.py — do not edit\n")
         f.write('#include "afhip_variants.h"\n')
@@ -321,7 +349,19 @@ def main():
         for g in range(pgroups):
             f.write(f"        c += register_packed_{g:02d}(g_packed + c);\n")
         f.write("        g_packed_count = c;\n    }\n    *n = g_packed_count;\n    return g_packed;\n}\n}\n")
-    print(" ".join(os.path.basename(x) for x in files + [os.path.join(outdir, 'variants_table.hip'), os.path.join(outdir, 'packed_table.hip')]))
+    with _KeepIfSame(os.path.join(outdir, "packed_hist_table.hip")) as f:
+        f.write("// generated by gen_variants.py — do not edit\n")
+        f.write('#include "afhip_variants.h"\n')
+        f.write("namespace afhip {\n")
+        for g in range(hgroups):
+            f.write(f"int register_packed_hist_{g:02d}(Variant* out);\n")
+        f.write(f"static Variant g_packed_hist[{max(len(hvs), 1)}];\nstatic int g_packed_hist_count = -1;\n")
+        f.write("const Variant* packed_hist_variants_table(int* n) {\n    if (g_packed_hist_count < 0) {\n        int c = 0;\n")
+        for g in range(hgroups):
+            f.write(f"        c += register_packed_hist_{g:02d}(g_packed_hist + c);\n")
+        f.write("        g_packed_hist_count = c;\n    }\n    *n = g_packed_hist_count;\n    return g_packed_hist;\n}\n}\n")
+    tables = ("variants_table.hip", "packed_table.hip", "packed_hist_table.hip")
+    print(" ".join(os.path.basename(x) for x in files + [os.path.join(outdir, t) for t in tables]))
 
 
 if __name__ == "__main__":

@@ -16,6 +16,13 @@ Beside the single-rule cube each plan also runs with the same cube bound as 1, 4
 packings are: the kernel reads a rule from its table at every change and cannot know they are equal).  Each is reported against the
 single-rule row of the same run; the single-rule row carries its run-to-run spread, (max - min) / median.
 
+The bins plan is a partition of equal-width bins: the packed cube takes an LDS-histogram kernel (gen_variants.py: packed_hist_menu).  It
+is also timed on a fresh plan created under AFHIP_NO_PACKED_HIST — the general packed kernel, what the plan took before the menu had
+the histogram forms — and under AFHIP_PACKED_HIST_VEC=2, the two-cell kernel of the form where the library holds it (an arm of most forms:
+`make MENU=arms`; else the row repeats the planner's pick): three figures beside the float32 route's, each with its kernel's name.  ``--hist-forms`` times instead every form of that menu — single-level / two-level (daily groups,
+one yearly period), arithmetic edges / edge table, without / with a mean column — at two cells per lane against one (a `make MENU=arms`
+library holds all sixteen kernels): the pairs behind the widths of the production menu (gen_variants.py: packed_hist_menu).
+
     python scripts/packed_bench.py [--storage int16|uint16] [--rules 1,40,480] [--out profiles/packed_cube_measured.txt]
 """
 import argparse
@@ -41,6 +48,22 @@ def plans_columns():
         "4 degree-day thresholds -> sum": ([dict(inner="dd", inner_args=(float(t), float(t) + 10, 0), outer="sum") for t in (0, 8, 16, 24)], False),
         "13 bins of 5 degC (single level)": ([dict(inner="bins", inner_args=(edges[i], edges[i + 1], 0)) for i in range(13)], True),
     }
+
+
+def hist_forms(T, ib0):
+    """(title, columns, inner bounds, outer bounds) of the eight LDS-histogram forms: thirteen bins of 5 C with integer edges
+    (arithmetic) or of 4.9 C from -19.85 (no float32 holds those: the edge table)."""
+    out = []
+    for single in (True, False):
+        for arith in (True, False):
+            for mean in (False, True):
+                e = np.arange(-20, 50, 5.0) if arith else -19.85 + 4.9 * np.arange(14)
+                outer = {} if single else dict(outer="sum")
+                cols = [dict(inner="bins", inner_args=(e[i], e[i + 1], 0), **outer) for i in range(13)] + ([dict(inner="mean", **outer)] if mean else [])
+                ib, ob = (np.array([0, T]), np.array([0, 1])) if single else (ib0, np.array([0, len(ib0) - 1]))
+                title = f"{'single-level' if single else 'two-level'}, {'arithmetic edges' if arith else 'edge table'}{', + mean' if mean else ''}"
+                out.append((title, cols, ib, ob))
+    return out
 
 
 def stored_cube(T, ny, nx, spd):
@@ -72,6 +95,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--storage", choices=("int16", "uint16"), default="int16")
     ap.add_argument("--rules", default="1,40,480", help="rule counts the packed cube is also bound as (equal-length ranges of time steps)")
+    ap.add_argument("--hist-forms", action="store_true", help="time the LDS-histogram forms at two cells per lane against one, and nothing else")
+    ap.add_argument("--plan", default="", help="run only the plans whose title holds this text")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lines = []
@@ -99,15 +124,43 @@ def main():
     R = int(wdf["index_right"].max()) + 1
     csr = hip.CSR(wdf["index_right"].to_numpy(), wdf["cell_id"].to_numpy(), wdf["weight"].to_numpy(), R, C)
     ib0 = synth.hourly_bounds(a.T, a.spd)
-    for title, (cols, single) in plans_columns().items():
+    for title, cols, ib, ob in (hist_forms(a.T, ib0) if a.hist_forms else []):
+        say()
+        say(title)
+        med = {}
+        for vec in (2, 1):
+            os.environ["AFHIP_PACKED_HIST_VEC"] = str(vec)
+            p = hip.FusedPlan(a.T, C, packed_code, ib, ob, cols)
+            del os.environ["AFHIP_PACKED_HIST_VEC"]
+            p.bind_packing(packed)
+            out = p.run(packed, csr)
+            for _ in range(a.warmup):
+                p.run(packed, csr, out=out)
+            torch.cuda.synchronize()
+            p.profile_begin(a.launches)
+            for _ in range(a.launches):
+                p.run(packed, csr, out=out)
+            torch.cuda.synchronize()
+            ms = p.profile_end()
+            med[vec] = float(np.median(ms))
+            say(f"  {vec} cell{'s' if vec > 1 else ' '}  {p.describe().split()[0]:56s} {stats(ms)}")
+        say(f"  two cells / one cell (medians): {med[2] / med[1]:.3f}")
+    for title, (cols, single) in ({} if a.hist_forms else plans_columns()).items():
+        if a.plan not in title:
+            continue
         ib, ob = (np.array([0, a.T]), np.array([0, 1])) if single else (ib0, np.array([0, len(ib0) - 1]))
         say()
         say(title)
         med, res = {}, {}
-        runs = [("packed", packed, packed_code, 0)] + [(f"{n} rules", packed, packed_code, n) for n in map(int, a.rules.split(",")) if n] + \
-               [("float32", plain, hip.F32, 0)]
-        for name, cube, code, n_rules in runs:
+        runs = [("packed", packed, packed_code, 0, {})] + [(f"{n} rules", packed, packed_code, n, {}) for n in map(int, a.rules.split(",")) if n]
+        if single:      # the knobs are read when a plan is created
+            runs += [("general", packed, packed_code, 0, {"AFHIP_NO_PACKED_HIST": "1"}), ("two cells", packed, packed_code, 0, {"AFHIP_PACKED_HIST_VEC": "2"})]
+        runs += [("float32", plain, hip.F32, 0, {})]
+        for name, cube, code, n_rules, env in runs:
+            os.environ.update(env)
             p = hip.FusedPlan(a.T, C, code, ib, ob, cols)
+            for k in env:
+                del os.environ[k]
             if n_rules:
                 p.bind_packings([cube.packing()] * n_rules, [a.T * i // n_rules for i in range(n_rules + 1)])
             elif code == packed_code:
@@ -124,10 +177,15 @@ def main():
             med[name], res[name] = float(np.median(ms)), out["res"].cpu().numpy()
             nbytes = a.T * C * (2 if code == packed_code else 4)
             extra = f"   spread (max - min) / median {(max(ms) - min(ms)) / med[name]:.4f}" if name == "packed" else \
-                    (f"   x {med[name] / med['packed']:.4f} of the single-rule median" if n_rules else "")
-            say(f"  {name:9s} {p.describe().split()[0]:40s} {stats(ms)}   {nbytes / med[name] / 1e9:.2f} TB/s of its own bytes at the median{extra}")
+                    (f"   x {med[name] / med['packed']:.4f} of the single-rule median" if n_rules else
+                     (f"   x {med[name] / med['packed']:.3f} of the packed plan's median; minimum {min(ms):.4f} ms" if env else ""))
+            say(f"  {name:9s} {p.describe().split()[0]:56s} {stats(ms)}   {nbytes / med[name] / 1e9:.2f} TB/s of its own bytes at the median{extra}")
             if n_rules:
                 assert np.array_equal(res[name], res["packed"], equal_nan=True), f"{name}: the panel differs from the single-rule cube's"
+            if env:     # (the general kernel's plan has no count records: its weighted sums take another spatial route, and another order of adds)
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    d = np.nanmax(np.abs(res[name] - res["packed"]) / np.maximum(np.abs(res["packed"]), 1e-300))
+                say(f"            its panel differs from the packed plan's by at most {d:.1e} relative ({p.describe().split('|')[2].strip()})")
         with np.errstate(invalid="ignore", divide="ignore"):
             err = np.nanmax(np.abs(res["packed"] - res["float32"]) / np.maximum(np.abs(res["float32"]), 1e-300))
         say(f"  packed / float32 kernel time (medians): {med['packed'] / med['float32']:.3f};  panels differ by at most {err:.1e} relative")
