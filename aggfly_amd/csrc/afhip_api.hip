@@ -354,14 +354,15 @@ extern "C" const char* afhip_last_error(void) { return last_error(); }
 extern "C" int afhip_abi_version(void) { return AFHIP_ABI_VERSION; }
 
 extern "C" int afhip_build_info(char* buf, int buf_len) {
-    int n = 0, arms = 0, rf = 0, np = 0, nh = 0;
+    int n = 0, arms = 0, rf = 0, np = 0, nh = 0, ne = 0;
     const Variant* tab = variants_table(&n);
     for (int i = 0; i < n; ++i) { arms += tab[i].production ? 0 : 1; rf += tab[i].rf() ? 1 : 0; }
     (void)packed_variants_table(&np);
     (void)packed_hist_variants_table(&nh);
+    (void)end_bins_variants_table(&ne);
     char tmp[240];
-    const int len = snprintf(tmp, sizeof tmp, "menu=%s variants=%d arms=%d region_fused_twins=%d abi=%d packed_variants=%d packed_hist_variants=%d", variants_menu(),
-                             n, arms, rf, AFHIP_ABI_VERSION, np, nh);
+    const int len = snprintf(tmp, sizeof tmp, "menu=%s variants=%d arms=%d region_fused_twins=%d abi=%d packed_variants=%d packed_hist_variants=%d end_bins_variants=%d",
+                             variants_menu(), n, arms, rf, AFHIP_ABI_VERSION, np, nh, ne);
     if (buf && buf_len > 0) snprintf(buf, buf_len, "%s", tmp);
     return len + 1;
 }
@@ -1098,6 +1099,8 @@ static int launch_temporal(afhip_plan* pl, const void* cube, double* partial, hi
         fa.hb_w = pl->hb_w; fa.hb_lo0 = pl->hb_lo0; fa.hb_gl = pl->hb_gl; fa.hb_gh = pl->hb_gh;
         fa.hb_wf = (float)pl->hb_w; fa.hb_lo0f = (float)pl->hb_lo0; fa.hb_glf = (float)pl->hb_gl; fa.hb_ghf = (float)pl->hb_gh;
         fa.hb_c0b = pl->hb_c0b; fa.hb_c0bf = (float)pl->hb_c0b;
+        // wide end bins (FEAT_END_BINS): the slots whose thr[] entries hold the outer limits L (t0 / t0f) and U (t1 / t1f)
+        fa.hb_ends = feat_has(pl->variant->feat, FEAT_END_BINS) ? (pl->hb_slot_lo | (pl->hb_slot_hi << 8)) : 0;
     }
     HIP_TRY(hipLaunchKernel(fn, grid, dim3((unsigned)pl->wg), args, lds, st));
     return AFHIP_OK;

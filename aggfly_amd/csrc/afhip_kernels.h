@@ -42,7 +42,8 @@ struct FusedArgs {
     int32_t xcd_remap, n_tiles;    // 1: give each XCD a contiguous range of cell tiles (speed only)
     const double* sine_tab;        // device [2][SINE_ROWS][4]: rows of the acos table (sine_theta), or null when no column is sine_dd
     // LDS-histogram bins (FEAT_HIST): the threshold slots form a contiguous partition of equal
-    // width with edges hb_edge[0..hb_n]; hb_bin_of_slot[slot] = position of that slot's bin.
+    // width with edges hb_edge[0..hb_n]; hb_bin_of_slot[slot] = position of that slot's bin (FEAT_END_BINS: -1 / hb_n for the slot
+    // of a wide lower / upper end bin, which reads the guard bin's counter; hb_ends below).
     // guess bin (shifted by one guard bin) = floor(v * hb_c1 + hb_c0); hb_dn / hb_up are the edges
     // rounded down / up to float, so a float v compares exactly:  v > t <=> v > dn,  v < t <=> v < up.
     double hb_c1, hb_c0;
@@ -88,7 +89,10 @@ struct FusedArgs {
     // every value between them (ha_update)
     double hb_c0b;
     float hb_c0bf;
-    int32_t hb_pad;
+    // wide end bins (FEAT_END_BINS): the outer limits L / U of the partition are not stored again — they are t0 / t1 (float cubes: t0f /
+    // t1f, rounded down / up) of the end slots' own thr[] entries, and this word, the record's former padding, names the two slots:
+    // bits 0-7 the slot that holds L, bits 8-15 the slot that holds U.  Other kernels never read it (0).
+    int32_t hb_ends;
     ThrSlot thr[MAX_THR];
     ColOp cols[MAX_COLS];
     // the lean group end's view of a column in ONE word (src | tf << 4 | (tf_iarg & 0xff) << 8): six of them stay in scalar
@@ -169,6 +173,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
     constexpr int AUX = feat_has(FEAT, FEAT_NT) ? 2 : 0;
     constexpr bool TKI = feat_has(FEAT, FEAT_INT_BINS), SL = feat_has(FEAT, FEAT_SINGLE_LEVEL);
     constexpr bool HB = feat_has(FEAT, FEAT_HIST), HA = feat_has(FEAT, FEAT_ARITH_EDGES);
+    constexpr bool EB = feat_has(FEAT, FEAT_END_BINS);
     constexpr bool PAIR = feat_has(FEAT, FEAT_SHORT_GROUP);
     // (the lean group end skips a per-group walk of ~90 scalar instructions per wave and group, as many as the vector ones that do the
     // arithmetic: profiles/r03_kbench_c5_table_arc.txt)
@@ -185,6 +190,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
     static_assert(!LEAN || PAIR, "the lean group end is a short-group form");
     static_assert(!RF || !(SL || HB), "region-fused period ends: two-level plans only");
     static_assert(!(HB && SINE), "histogram variants carry no sine_dd code");
+    static_assert(!EB || HB, "wide end bins: a histogram form");
     static_assert(!RF || VEC <= 2, "region-fused period ends: one or two cells per lane");
     static_assert(!PACKED || (PIPE == 0 && !feat_has(FEAT, FEAT_SHORT_GROUP | FEAT_REGION_FUSED) && (HB ? (TKI && STAT <= 1) : !(TKI || SL))),
                   "int16-packed cubes: the general forms and the LDS-histogram forms of the direct-load path only");
@@ -269,6 +275,13 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
     TIn hb_c1 = 0, hb_c0 = 0, hb_top = 0;
     TIn ha_w = 0, ha_c0b = 0, ha_e0 = 0, ha_gl = 0, ha_gh = 0;
     int hb_sh = 0, hb_lane[VEC] = {0};
+    // wide end bins: a value counts only if  eb_lo < v < eb_hi  (the outer limits, in the input precision; +-inf where a side is open)
+    TIn eb_lo = 0, eb_hi = 0;
+    if constexpr (EB) {
+        const int ql = a.hb_ends & 0xff, qh = (a.hb_ends >> 8) & 0xff;
+        if constexpr (sizeof(TIn) == 4) { eb_lo = a.thr[ql].t0f; eb_hi = a.thr[qh].t1f; }
+        else { eb_lo = a.thr[ql].t0; eb_hi = a.thr[qh].t1; }
+    }
     if constexpr (HB) {
         if (tid < hb_bins) {
             auto edge = [&](int k, bool want_up) -> TIn {        // E[k].up or E[k].dn
@@ -385,6 +398,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
             count = up ? !(vr <= eb.hi) : !(vr >= eb.lo);             // strict bins: an edge value is in none
             b += up ? 1 : -1;
         }
+        // (wide end bins: the guard bins are counted bins, so a value beyond the outer limits — and NaN, which the clamp sent to the
+        // lower guard bin — must not reach them)
+        if constexpr (EB) count = count && (vr > eb_lo) && (vr < eb_hi);
         // the counter is private to this lane: a relaxed LDS atomic is one ds_add_u32 (no return value)
         if (count)
             __hip_atomic_fetch_add((int*)((char*)hcnt + (b << hb_sh) + hb_lane[i]), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -411,7 +427,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
         }
         int b = (int)tf;
         b += (vc > hi) ? 1 : 0;                                     // (a carry-in add)
-        if (vc != hi) {
+        bool count = vc != hi;
+        if constexpr (EB) count = count && (vr > eb_lo) && (vr < eb_hi);       // wide end bins: the outer limits on the unclamped value; NaN fails
+        if (count) {
             int* p = (int*)((char*)hcnt + (b << hb_sh) + hb_lane[i]);
             __hip_atomic_fetch_add(p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);     // the counter is private to this lane: one ds_add_u32
         }
@@ -919,7 +937,15 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
 #pragma unroll
                         for (int q = 0; q < NTHR; ++q)
                             if (q == co.src_idx) {
-                                if constexpr (HB) t = (double)hcnt[((a.hb_bin_of_slot[q] + 1) * VEC + i) * bd + tid];
+                                if constexpr (HB && EB) {
+                                    // (the slot's bin is made opaque here: left visible, the sixteen counter addresses — and a copy of their
+                                    // common term each — were hoisted out of the time loop into 27 VGPRs, a wave per SIMD or two)
+                                    int bin = a.hb_bin_of_slot[q] + 1;
+#if defined(__HIP_DEVICE_COMPILE__)
+                                    asm volatile("" : "+s"(bin));
+#endif
+                                    t = (double)hcnt[(bin * VEC + i) * bd + tid];
+                                } else if constexpr (HB) t = (double)hcnt[((a.hb_bin_of_slot[q] + 1) * VEC + i) * bd + tid];
                                 else t = TKI ? (double)cthr[q][i] : acc[q][i];
                                 poisons = a.thr[q].nan_poisons != 0;
                             }

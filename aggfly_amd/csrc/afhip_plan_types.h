@@ -136,6 +136,12 @@ enum : int {
     // loads and the statistics' tail rows sit under scalar branches on it, the mean is div_by's correctly rounded s / n (n = 2, 4:
     // exact anyway).  Otherwise the four-row form
     FEAT_MIXED = 8192,
+    // histogram (FEAT_HIST only) whose partition has a WIDE END BIN on one side or both — (L, E[0]) and / or (E[n], U) of any positive
+    // width, infinite included, around the equal-width lattice E[0..n].  The guard bins are the end bins: a value is counted only
+    // if it also satisfies  L < v < U  (two compares in the input precision against the end slots' own t0f / t1f; NaN fails both),
+    // and an end slot reads its guard counter (hb_bin_of_slot = -1 / hb_n).  Clamp, guess, repair and "a value on an edge is in no
+    // bin" are the closed form's
+    FEAT_END_BINS = 16384,
 };
 
 // what follows from the bits

@@ -51,6 +51,7 @@ PlanKnobs read_knobs() {
     k.no_region_fused = set("AFHIP_NO_REGION_FUSED");
     k.no_packed_hist = set("AFHIP_NO_PACKED_HIST");
     if (const char* e = getenv("AFHIP_PACKED_HIST_VEC")) { const int v = atoi(e); if (v == 1 || v == 2) k.packed_hist_vec = v; }
+    k.no_end_bins_hist = set("AFHIP_NO_END_BINS_HIST");
     k.counts_spmm = !set("AFHIP_NO_COUNTS_SPMM");
     if (const char* e = getenv("AFHIP_COUNTS_SPMM_SUB")) k.counts_spmm_sub = atoi(e);
     if (const char* e = getenv("AFHIP_NO_SLOT_SPMM")) k.no_slot_spmm = atoi(e) != 0;
@@ -327,36 +328,56 @@ static bool biased_guess(const HistPartition& h, int n, int k_first, double* c0b
     return found;
 }
 
-// contiguous equal-width partition?  (sorted by t0, t1[b] == t0[b+1], constant width)
+// contiguous equal-width partition?  (sorted by t0, t1[b] == t0[b+1], constant width) — closed, or with a WIDE END BIN on one side or
+// both: bin 0 and / or bin m - 1 of any positive width, infinite included (a catch-all below / above the equal-width bins).  The
+// interior bins 1 .. m - 2 (at least two) always belong to the equal-width lattice; an end bin that continues it is an ordinary bin,
+// one that does not is a wide end (its width may be smaller than the lattice's too).  The candidates are tried closed form first, so a
+// partition without a wide end gets exactly the result it always got.  With a wide end hb_n and every constant describe the lattice
+// alone; the end slots sit on the guard bins (HistPartition::hb_wide).
 static HistPartition find_partition(const PlanLayout& pl, bool all_bins) {
     const afhip_plan_desc* desc = &pl.desc;
     HistPartition h;
     if (!(all_bins && pl.nthr >= 4)) return h;
-    std::vector<int> order((size_t)pl.nthr);
-    for (int i = 0; i < pl.nthr; ++i) order[(size_t)i] = i;
+    const int m = pl.nthr;
+    std::vector<int> order((size_t)m);
+    for (int i = 0; i < m; ++i) order[(size_t)i] = i;
     std::sort(order.begin(), order.end(), [&](int x, int y) { return pl.thr[(size_t)x].t0 < pl.thr[(size_t)y].t0; });
-    const double e0 = pl.thr[(size_t)order[0]].t0;
-    const double w = pl.thr[(size_t)order[0]].t1 - e0;
-    bool ok = w > 0 && std::isfinite(e0) && std::isfinite(w);
-    for (int b = 0; ok && b < pl.nthr; ++b) {
-        const ThrSlot& t = pl.thr[(size_t)order[(size_t)b]];
-        ok = std::fabs(t.t0 - (e0 + b * w)) <= 1e-9 * w && std::fabs(t.t1 - (e0 + (b + 1) * w)) <= 1e-9 * w;
-        if (ok && b + 1 < pl.nthr) ok = t.t1 == pl.thr[(size_t)order[(size_t)b + 1]].t0;
+    auto slot = [&](int b) -> const ThrSlot& { return pl.thr[(size_t)order[(size_t)b]]; };
+    bool contiguous = true;
+    for (int b = 0; contiguous && b + 1 < m; ++b) contiguous = slot(b).t1 == slot(b + 1).t0;
+    if (!contiguous) return h;
+    // the lattice: bins first .. first + n - 1 of the sorted slots
+    int first = 0, n = 0;
+    double e0 = 0, w = 0;
+    bool ok = false;
+    for (int cand = 0; !ok && cand < 4; ++cand) {
+        const int lo_wide = cand & 1, hi_wide = cand >> 1;
+        first = lo_wide; n = m - lo_wide - hi_wide;
+        if (n < 2 || (cand && m < 4)) continue;
+        e0 = slot(first).t0;
+        w = slot(first).t1 - e0;
+        ok = w > 0 && std::isfinite(e0) && std::isfinite(w);
+        for (int b = 0; ok && b < n; ++b) {
+            const ThrSlot& t = slot(first + b);
+            ok = std::fabs(t.t0 - (e0 + b * w)) <= 1e-9 * w && std::fabs(t.t1 - (e0 + (b + 1) * w)) <= 1e-9 * w;
+        }
+        // a wide end has a positive width of its own (NaN limits fail)
+        if (ok && lo_wide) ok = slot(0).t1 > slot(0).t0;
+        if (ok && hi_wide) ok = slot(m - 1).t1 > slot(m - 1).t0;
     }
     // the in-kernel guess floor(v / w - e0 / w) is computed in the INPUT precision and may be off by
     // one bin at most: the bins must not be narrower than ~2^20 (f32) / 2^48 (f64) ulps of the edges
-    const double emax = std::max(std::fabs(e0), std::fabs(e0 + pl.nthr * w));
+    const double emax = std::max(std::fabs(e0), std::fabs(e0 + n * w));
     // (a packed cube's values are float32: its dtype goes the float way here and below)
     const double eps = desc->dtype != AFHIP_F64 ? 1.2e-7 : 2.3e-16;
     ok = ok && emax * eps * 16.0 < w;
     if (!ok) return h;
-    const int n = pl.nthr;
     h.hb_n = n; h.hb_c1 = 1.0 / w; h.hb_c0 = 1.0 - e0 / w;      // + 1: bin 0 is the lower guard bin
-    for (int b = 0; b < n; ++b) {
-        h.hb_bin_of_slot[order[(size_t)b]] = b;
-        h.hb_edge[b] = pl.thr[(size_t)order[(size_t)b]].t0;
-    }
-    h.hb_edge[n] = pl.thr[(size_t)order[(size_t)n - 1]].t1;
+    for (int b = 0; b < m; ++b) h.hb_bin_of_slot[order[(size_t)b]] = b - first;      // (a wide lower end: -1, a wide upper end: n)
+    for (int b = 0; b < n; ++b) h.hb_edge[b] = slot(first + b).t0;
+    h.hb_edge[n] = slot(first + n - 1).t1;
+    h.hb_wide = n < m;
+    h.hb_slot_lo = order[0]; h.hb_slot_hi = order[(size_t)m - 1];
     h.hb_w = w; h.hb_lo0 = e0 - w; h.hb_gl = e0 - 0.5 * w; h.hb_gh = h.hb_edge[n] + 0.5 * w;
     const bool f32 = desc->dtype != AFHIP_F64;
     bool ex = f32 ? edges_exact<float>(h, n, e0) : edges_exact<double>(h, n, e0);
@@ -419,6 +440,28 @@ static const Variant* choose_packed_hist_variant(const PlanLayout& pl, const His
     for (int vec : {2, 1}) {
         if (C % vec != 0) continue;
         if (const Variant* v = find_packed_hist_variant(vec, pl.stat, pl.nthr, pl.K, sl, hist.hb_arith)) return v;
+    }
+    return nullptr;
+}
+
+// A partition with a wide end bin (HistPartition::hb_wide) asks the table of end-bin histogram forms (end_bins_variants_table; gen_variants.py:
+// end_bins_menu), on packed and float cubes alike: the storage's production histogram forms with FEAT_END_BINS — one cell per lane, and
+// for packed cubes two where the rows are even and the menu holds the form (the single-level edge-table forms, as in packed_hist_menu).
+// Null: no such kernel (`dev` menu), a tuning arm, or the route is off — the plan then routes as if the partition had not been found.
+// AFHIP_NO_END_BINS_HIST switches the route off (the A/B knob of scripts/end_bins_bench.py); packed cubes follow AFHIP_NO_PACKED_HIST too.
+// The route is the default on every storage, by the rule the packed histogram forms were held to: on the configs[1] shape, thirteen 5-degree bins
+// between two open ends, single level and two-level with a mean, its median lies below the earlier route's minimum in the same process — at
+// x0.11 / x0.12 of it on packed cubes, x0.27 / x0.34 on float32, x0.52 / x0.36 on float64 (profiles/end_bins.txt, section 2: the whole output of
+// scripts/end_bins_bench.py with device, build and min / median / max of the three routes).
+static const Variant* choose_end_bins_variant(const PlanLayout& pl, const HistPartition& hist, int tuning, const PlanKnobs& knobs) {
+    if (hist.hb_n == 0 || !hist.hb_wide || knobs.no_end_bins_hist || tuning != 0) return nullptr;
+    const bool packed = is_packed_dtype(pl.desc.dtype);
+    if (packed && knobs.no_packed_hist) return nullptr;
+    const int dtype = packed ? AFHIP_I16 : pl.desc.dtype;
+    const bool sl = is_single_level(pl);
+    for (int vec : {2, 1}) {
+        if (pl.desc.n_cells % vec != 0) continue;
+        if (const Variant* v = find_end_bins_variant(dtype, vec, pl.stat, pl.nthr, pl.K, sl, hist.hb_arith)) return v;
     }
     return nullptr;
 }
@@ -757,8 +800,9 @@ int build_plan(const afhip_plan_desc* desc, const DeviceFacts& dev, PlanLayout* 
         // has region-fused twins — the spatial stage is the slot gather or the table-order sums
         bool all_bins = pl->nthr > 0;
         for (const ThrSlot& t : pl->thr) all_bins = all_bins && t.nan_poisons == 0;
+        // (a partition with a wide end bin: the end-bin forms or none — no kernel without FEAT_END_BINS ever sees such a partition)
         const HistPartition hist = find_partition(*pl, all_bins);
-        pl->variant = choose_packed_hist_variant(*pl, hist, knobs);
+        pl->variant = hist.hb_wide ? choose_end_bins_variant(*pl, hist, 0, knobs) : choose_packed_hist_variant(*pl, hist, knobs);
         if (pl->variant) static_cast<HistPartition&>(*pl) = hist;
         else pl->variant = choose_packed_variant(*pl);
         if (!pl->variant)
@@ -778,7 +822,13 @@ int build_plan(const afhip_plan_desc* desc, const DeviceFacts& dev, PlanLayout* 
     bool all_bins = pl->nthr > 0;
     for (const ThrSlot& t : pl->thr) all_bins = all_bins && t.nan_poisons == 0;
     static_cast<HistPartition&>(*pl) = find_partition(*pl, all_bins);
-    pl->variant = choose_variant(*pl, form, path, *pl, all_bins, tuning, knobs, dev.cu_count);
+    // a partition with a wide end bin: the end-bin histogram form, or the route of a plan without a partition
+    pl->variant = nullptr;
+    if (pl->hb_wide) {
+        pl->variant = choose_end_bins_variant(*pl, *pl, tuning, knobs);
+        if (!pl->variant) static_cast<HistPartition&>(*pl) = HistPartition{};
+    }
+    if (!pl->variant) pl->variant = choose_variant(*pl, form, path, *pl, all_bins, tuning, knobs, dev.cu_count);
     if (!pl->variant)
         return fail(AFHIP_E_UNSUPPORTED, "no kernel variant for dtype=%d stat=%d slots=%d columns=%d", desc->dtype, pl->stat, pl->nthr, pl->K);
     if ((rc = build_chunks(pl, pl->variant->vec, knobs, dev))) return rc;

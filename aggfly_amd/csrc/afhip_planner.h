@@ -48,6 +48,7 @@ struct PlanKnobs : RunKnobs {
     bool no_region_fused = false;                                            // AFHIP_NO_REGION_FUSED
     bool no_packed_hist = false;   // AFHIP_NO_PACKED_HIST: packed cubes' partition plans take the general packed kernel, not the LDS-histogram forms
     int packed_hist_vec = 0;       // AFHIP_PACKED_HIST_VEC=1|2: the cells per lane such a plan takes where the library holds the kernel, arms included (0: the planner's rule)
+    bool no_end_bins_hist = false; // AFHIP_NO_END_BINS_HIST: partitions with a wide end bin take the route they took without the end-bin histogram forms
 };
 PlanKnobs read_knobs();
 
@@ -57,6 +58,11 @@ struct HistPartition {
     bool hb_arith = false; double hb_w = 0, hb_lo0 = 0, hb_gl = 0, hb_gh = 0, hb_c0b = 0;   // ... with exactly representable edges (+ the biased guess constant)
     int hb_bin_of_slot[MAX_THR] = {0};
     double hb_edge[MAX_THR + 1] = {0};
+    // wide end bins (FEAT_END_BINS): hb_n counts the equal-width bins only and every field above describes that lattice; the slot of a
+    // wide lower end has hb_bin_of_slot = -1, that of a wide upper end hb_n (the guard bins).  hb_slot_lo / hb_slot_hi: the slots
+    // whose t0 / t1 are the outer limits L / U of the whole partition
+    bool hb_wide = false;
+    int hb_slot_lo = 0, hb_slot_hi = 0;
 };
 
 // What the planner produces.  Host data only: afhip_plan (afhip_api.hip) adds the device tables, scratch and run state.

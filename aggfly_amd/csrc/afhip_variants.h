@@ -44,6 +44,9 @@ const Variant* packed_variants_table(int* n);
 // ... and their LDS-histogram forms (gen_variants.py: packed_hist_menu; packed_hist_table.hip): integer-bin forms for plans whose
 // threshold slots are a contiguous equal-width partition, matched on cells per lane, stat tier, single level and arithmetic edges.
 const Variant* packed_hist_variants_table(int* n);
+// ... and the LDS-histogram forms with FEAT_END_BINS, for partitions with a wide end bin on one side or both — float32, float64 and
+// packed storage in one table (gen_variants.py: end_bins_menu; end_bins_table.hip), matched like the packed histogram forms plus the dtype.
+const Variant* end_bins_variants_table(int* n);
 
 // What a lowered plan asks of the menu (afhip_planner.cpp: choose_variant).  A fallback is the same query with a field changed.
 // tuning: 0 = the default choice below; otherwise an explicit arm
@@ -126,6 +129,23 @@ inline const Variant* find_packed_hist_variant(int vec, int stat, int nthr, int 
     for (int i = 0; i < n; ++i) {
         const Variant& v = tab[i];
         if (!v.hb() || v.vec != vec || v.stat < stat || v.nthr < nthr || v.kmax < K || (!v.production && !arms)) continue;
+        if (v.sl() != single_level || v.ha() != arith) continue;
+        const long cost = (long)v.nthr * 1000 + (long)v.kmax * 10 + v.stat;
+        if (!best || cost < best_cost) { best = &v; best_cost = cost; }
+    }
+    return best;
+}
+
+// the end-bin histogram kernel of storage `dtype` (AFHIP_I16 for either packed dtype) with `vec` cells per lane; the form is matched exactly,
+// as in find_packed_hist_variant (null: the menu has none)
+inline const Variant* find_end_bins_variant(int dtype, int vec, int stat, int nthr, int K, bool single_level, bool arith) {
+    const Variant* best = nullptr;
+    long best_cost = 0;
+    int n = 0;
+    const Variant* tab = end_bins_variants_table(&n);
+    for (int i = 0; i < n; ++i) {
+        const Variant& v = tab[i];
+        if (!v.hb() || !feat_has(v.feat, FEAT_END_BINS) || v.dtype != dtype || v.vec != vec || v.stat < stat || v.nthr < nthr || v.kmax < K || !v.production) continue;
         if (v.sl() != single_level || v.ha() != arith) continue;
         const long cost = (long)v.nthr * 1000 + (long)v.kmax * 10 + v.stat;
         if (!best || cost < best_cost) { best = &v; best_cost = cost; }

@@ -8,6 +8,8 @@ Each generated ``variants_NN.hip`` holds a handful of explicit instantiations so
 ``find_variant`` (afhip_variants.h) searches.  The kernels of int16-packed cubes (`packed_menu`) go to ``packed_NN.hip`` and a
 table of their own, ``packed_table.hip`` (``packed_variants_table``): `menu` and its table count the float kernels only.  Their
 LDS-histogram forms (`packed_hist_menu`) likewise: ``packed_hist_NN.hip`` and ``packed_hist_table.hip`` (``packed_hist_variants_table``).
+The histogram forms for partitions with a wide end bin (`end_bins_menu`: Feat.END_BINS, float32, float64 and packed storage together) go to
+``end_bins_NN.hip`` (float32 / float64), ``end_bins_packed_NN.hip`` and ``end_bins_table.hip`` (``end_bins_variants_table``): the three menus above keep their counts and their contents.
 """
 import os
 import sys
@@ -39,12 +41,13 @@ class Feat:
     REGION_FUSED = 2048
     THREE_ROW = 4096
     MIXED = 8192
+    END_BINS = 16384
 
 
 FEAT_NAMES = [n for n in vars(Feat) if n.isupper()]
 GROUP_LENGTH = Feat.FOUR_ROW | Feat.THREE_ROW | Feat.MIXED      # the short-group forms of other than two rows
 # name suffixes, in name order (`_ss` instead of `_lean` for the sine-only lean form)
-SUFFIXES = ((Feat.NT, "_nt"), (Feat.INT_BINS, "_ibins"), (Feat.SINGLE_LEVEL, "_sl"), (Feat.HIST, "_hist"), (Feat.ARITH_EDGES, "_arith"),
+SUFFIXES = ((Feat.NT, "_nt"), (Feat.INT_BINS, "_ibins"), (Feat.SINGLE_LEVEL, "_sl"), (Feat.HIST, "_hist"), (Feat.ARITH_EDGES, "_arith"), (Feat.END_BINS, "_ends"),
             (Feat.SHORT_GROUP, "_pair"), (Feat.LEAN, "_lean"), (Feat.FOUR_ROW, "_quad"), (Feat.THREE_ROW, "_tri"), (Feat.MIXED, "_rag"),
             (Feat.REGION_FUSED, "_rf"))
 
@@ -227,6 +230,25 @@ def packed_hist_menu(kind):
     return out if kind == "arms" else [v for v in out if v[8]]
 
 
+def end_bins_menu(kind):
+    """The LDS-histogram kernels for partitions with a wide end bin on one side or both (Feat.END_BINS; afhip_planner.cpp:
+    choose_end_bins_variant), same tuples as `menu`: the production histogram forms of each storage with the bit set, all of them sixteen
+    slots x sixteen columns, nt loads, integer bins.  float32 (eight rows in flight) and float64 (four) at one cell per lane: stat 0 / 1 x
+    two-level / single-level x edge table / arithmetic edges.  Packed storage: the ten shapes of the production `packed_hist_menu`, at
+    its cells per lane and rows in flight.  No tuning arms; the `dev` menu has none of them (such a plan then routes without them)."""
+    if kind == "dev":
+        return []
+    out = []
+    for dtype, depth in ((0, 8), (1, 4)):
+        for stat in (0, 1):
+            for sl in (0, 1):
+                for ha in (0, 1):
+                    feat = Feat.NT | Feat.INT_BINS | Feat.HIST | Feat.END_BINS | (Feat.SINGLE_LEVEL if sl else 0) | (Feat.ARITH_EDGES if ha else 0)
+                    out.append((dtype, 0, 1, stat, 16, 16, depth, feat, 1))
+    out += [v[:7] + (v[7] | Feat.END_BINS, 1) for v in packed_hist_menu("full")]
+    return out
+
+
 def pickable(v):
     """False for a kernel that no plan can select by the planner's default rules (afhip_planner.cpp: the stage named in each comment), whatever its shape."""
     dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod = v
@@ -324,6 +346,11 @@ def main():
     hvs = packed_hist_menu(kind)
     hfiles, hgroups = write_units(outdir, hvs, per_file, "packed_hist")
     files += hfiles
+    # (float and packed kernels in units of their own: the packed ones are compiled with the Makefile's PACKED_FLAGS, the float ones as every float kernel)
+    evs = end_bins_menu(kind)
+    efiles, egroups = write_units(outdir, [v for v in evs if v[0] != I16], per_file, "end_bins")
+    epfiles, epgroups = write_units(outdir, [v for v in evs if v[0] == I16], per_file, "end_bins_packed")
+    files += efiles + epfiles
     with _KeepIfSame(os.path.join(outdir, "variants_table.hip")) as f:
         f.write("// generated by gen_variants.py — do not edit\n")
         f.write('#include "afhip_variants.h"\n')
@@ -360,7 +387,19 @@ def main():
         for g in range(hgroups):
             f.write(f"        c += register_packed_hist_{g:02d}(g_packed_hist + c);\n")
         f.write("        g_packed_hist_count = c;\n    }\n    *n = g_packed_hist_count;\n    return g_packed_hist;\n}\n}\n")
-    tables = ("variants_table.hip", "packed_table.hip", "packed_hist_table.hip")
+    with _KeepIfSame(os.path.join(outdir, "end_bins_table.hip")) as f:
+        f.write("// generated by gen_variants.py — do not edit\n")
+        f.write('#include "afhip_variants.h"\n')
+        f.write("namespace afhip {\n")
+        estems = [f"end_bins_{g:02d}" for g in range(egroups)] + [f"end_bins_packed_{g:02d}" for g in range(epgroups)]
+        for stem in estems:
+            f.write(f"int register_{stem}(Variant* out);\n")
+        f.write(f"static Variant g_end_bins[{max(len(evs), 1)}];\nstatic int g_end_bins_count = -1;\n")
+        f.write("const Variant* end_bins_variants_table(int* n) {\n    if (g_end_bins_count < 0) {\n        int c = 0;\n")
+        for stem in estems:
+            f.write(f"        c += register_{stem}(g_end_bins + c);\n")
+        f.write("        g_end_bins_count = c;\n    }\n    *n = g_end_bins_count;\n    return g_end_bins;\n}\n}\n")
+    tables = ("variants_table.hip", "packed_table.hip", "packed_hist_table.hip", "end_bins_table.hip")
     print(" ".join(os.path.basename(x) for x in files + [os.path.join(outdir, t) for t in tables]))
 
 

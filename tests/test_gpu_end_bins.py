@@ -1,0 +1,418 @@
+"""Bins plans with a wide or open-ended end bin on the LDS-histogram kernels with FEAT_END_BINS (gen_variants.py: end_bins_menu;
+afhip_planner.cpp: find_partition, choose_end_bins_variant): every kernel of the menu against the oracle, the partition shapes, the
+plans that must not move, the A/B knob, multi-rule and uint16 packed cubes, and the whole pass up to the public route.
+
+Bin counts are integers and the compares are the contract's (L < v < U strictly, a value on an edge, NaN and a value on
+or beyond an outer limit in no bin), so every count column is held with ZERO tolerance to the oracle (`block_bins` of the C port, on
+the host-unpacked values for packed cubes).  Zero tolerance is the rule of the per-cell count columns; the public route's frame — weighted
+means of those counts over regions — is held bit for bit between the packed and the float32 route, and to the oracle's frame at the
+suite's bar for frames (1e-10 relative: the order of the weighted adds differs).
+"""
+import json
+import os
+import zlib
+
+import numpy as np
+import pandas as pd
+import pytest
+
+import aggfly_amd as af
+from aggfly_amd import synth
+
+import end_bins_recipes as eb
+import packed_hist_recipes as ph
+import packed_recipes as pr
+import variant_recipes as vr
+import test_gpu_packed_hist as hist_mod
+import test_gpu_unsigned as uns
+from test_gpu_packed import _run_recipe
+from test_gpu_variant_menu import _assert_cells, _csr_table, _oracle_two_level
+
+pytestmark = pytest.mark.gpu
+INF = float("inf")
+
+
+def _menu_kind():
+    try:
+        from aggfly_amd import hip
+        return hip.build_info()["menu"]
+    except Exception:          # no library at collection time: the cases fail on their own
+        return "full"
+
+
+LOADED = eb.end_bins_menu(_menu_kind())
+MENU = [vr.variant(t) for t in LOADED]
+BY_NAME = {v.name: v for v in MENU}
+ANY = vr.Variant("bins plan", pr.I16, 0, 1, 1, 16, 16, 8, 0)          # what _assert_cells reads of a variant: its name, not lean
+STORAGES = {"f32": vr.F32, "f64": vr.F64, "i16": pr.I16}
+
+
+@pytest.fixture(autouse=True)
+def _no_knob(monkeypatch):
+    monkeypatch.delenv("AFHIP_NO_END_BINS_HIST", raising=False)
+
+
+def _name(plan):
+    return plan.describe().split()[0][len("variant="):]
+
+
+def _run(torch_cuda, r, seed=0, data=None):
+    """(plan, got[K, P, cells], want, values in the cube's precision, stored integers or None) of recipe `r` on its own planted cube."""
+    from aggfly_amd import hip
+    if eb.is_packed(r.dtype):
+        q = eb.stored_cube(r, seed) if data is None else data
+        plan, got, want, values = _run_recipe(torch_cuda, r, q)
+        return plan, got, want, values, q
+    cube = eb.cube_for(r, seed) if data is None else data
+    plan = hip.FusedPlan(r.T, r.n_cells, r.dtype, r.inner_bounds, r.outer_bounds, r.columns, exact_order=r.exact_order)
+    got = plan.run_temporal(torch_cuda.from_numpy(cube).cuda()).cpu().numpy()
+    want = _oracle_two_level(cube.astype(np.float64).reshape(r.T, 1, r.n_cells), r.inner_bounds, r.outer_bounds, r.columns)
+    return plan, got, want, cube, None
+
+
+def _assert_counts(r, got, want, values, what=""):
+    """Every count column equal to the oracle's, and per cell and period the counts add up to the period's steps strictly inside (L, U)
+    and on no edge (a period with an empty group is NaN in every column, as in the reference: it has no counts to add up)."""
+    nb = 0
+    for k, c in enumerate(r.columns):
+        if c["inner"] == "bins":
+            np.testing.assert_array_equal(got[k], want[k], err_msg=f"{what} column {k}: {c}")
+            nb += 1
+    inside = eb.in_some_bin(r, values)
+    ib, ob = r.inner_bounds, r.outer_bounds
+    expect = np.stack([inside[ib[ob[p]]:ib[ob[p + 1]]].sum(axis=0) for p in range(len(ob) - 1)]).astype(np.float64)      # [P, cells]
+    total = got[:nb].sum(axis=0)
+    counted = ~np.isnan(total)
+    print(f"{what}: {int(total[counted].sum())} counted in {int(counted.sum())} (period, cell) pairs, {int(expect[counted].sum())} strictly "
+          f"inside and off every edge there, of {values.size} values")
+    assert counted.sum() > 0.3 * counted.size
+    np.testing.assert_array_equal(total[counted], expect[counted], err_msg=f"{what}: the bins of a cell do not add up")
+
+
+# ---- 1. every kernel of the table ----
+@pytest.mark.parametrize("name", [v.name for v in MENU])
+def test_end_bins_variant_against_the_oracle(torch_cuda, name):
+    v = BY_NAME[name]
+    r = eb.recipe(v)
+    plan, got, want, values, q = _run(torch_cuda, r, seed=zlib.crc32(name.encode()))
+    assert _name(plan) == name, plan.describe()
+    if v.has(vr.SL):
+        assert "packed-counts" in plan.describe() if v.stat == 0 else "packed-counts" not in plan.describe(), plan.describe()
+    have = eb.planted(r, values, q)
+    assert all(have.values()), {k: ok for k, ok in have.items() if not ok}
+    _assert_cells(v, r.columns, got, want)
+    _assert_counts(r, got, want, values, name)
+    # (two-level recipes: three of their six periods hold an empty group and are NaN in every column)
+    assert np.nansum(got[:16 - v.stat]) > (0.5 if v.has(vr.SL) else 0.25) * np.isfinite(values).sum()
+
+
+def test_the_cases_cover_the_loaded_builds_end_bins_menu(torch_cuda):
+    from aggfly_amd import hip
+    assert hip.build_info()["end_bins_variants"] == len(LOADED) == len(BY_NAME)
+    assert {(v.dtype, v.vec) for v in MENU} == {(vr.F32, 1), (vr.F64, 1), (pr.I16, 1), (pr.I16, 2)}
+
+
+# ---- 2. partition shapes ----
+def _shape_bins(shape, dtype):
+    """The bins of partition shape `shape` on storage `dtype`, and whether its lattice edges are exact (the `_arith` form)."""
+    lo, hi = eb.ends_for("finite", dtype)
+    lat = lambda n, arith=True: eb.lattice(dtype, n, arith)      # noqa: E731
+    if shape == "both_open":
+        return eb.with_ends(lat(13), -INF, INF), True
+    if shape == "both_finite":
+        return eb.with_ends(lat(13), lo, hi), True
+    if shape == "lower_only":
+        return eb.with_ends(lat(13), lo, None), True
+    if shape == "lower_open_only":
+        return eb.with_ends(lat(13), -INF, None), True
+    if shape == "upper_only":
+        return eb.with_ends(lat(13), None, hi), True
+    if shape == "upper_open_only":
+        return eb.with_ends(lat(13), None, INF), True
+    if shape == "ends_narrower_than_the_bins":
+        e = lat(13)
+        if eb.is_packed(dtype):                                  # the end limits on stored values too: E[0] - 2 C, E[13] + 1.5 C
+            return eb.with_ends(e, pr._snap(e[0] - 2.0), pr._snap(e[-1] + 1.5)), True
+        return eb.with_ends(e, e[0] - 2.0, e[-1] + 1.5), True
+    if shape == "two_interior_bins":
+        return eb.with_ends(lat(2), lo, INF), True
+    if shape == "fourteen_interior_bins":
+        return eb.with_ends(lat(14), -INF, hi), True
+    if shape == "width_0.1":
+        return eb.with_ends(0.05 + 0.1 * np.arange(15), -INF, INF), False
+    raise KeyError(shape)
+
+
+SHAPES = ["both_open", "both_finite", "lower_only", "lower_open_only", "upper_only", "upper_open_only", "ends_narrower_than_the_bins",
+          "two_interior_bins", "fourteen_interior_bins", "width_0.1"]
+
+
+@pytest.mark.parametrize("storage", list(STORAGES))
+@pytest.mark.parametrize("shape", SHAPES)
+def test_partition_shapes(torch_cuda, shape, storage):
+    dtype = STORAGES[storage]
+    bins, arith = _shape_bins(shape, dtype)
+    sl = SHAPES.index(shape) % 2 == 0
+    odd = SHAPES.index(shape) % 3 == 0
+    n_cells = (1101 if odd else 1102) if eb.is_packed(dtype) else (60 if odd else 64)
+    seed = zlib.crc32(f"{shape} {storage}".encode())
+    r = eb.make_recipe("", dtype, n_cells, bins, sl, False, seed=seed)          # (columns in an order shuffled per case)
+    assert [c["inner_args"][:2] for c in r.columns] != sorted(c["inner_args"][:2] for c in r.columns)
+    plan, got, want, values, q = _run(torch_cuda, r, seed)
+    name = _name(plan)
+    vec = 2 if (eb.is_packed(dtype) and n_cells % 2 == 0 and sl and not arith) else 1
+    assert name.startswith(f"{storage}_p0_v{vec}_s0_t16_k16_") and name.endswith("_ends") and "_hist" in name, plan.describe()
+    assert ("_arith" in name) == arith and ("_sl_" in name) == sl, plan.describe()
+    have = eb.planted(r, values, q)
+    assert all(have.values()), {k: ok for k, ok in have.items() if not ok}
+    for t0, t1 in bins:                                                            # every bin, the end bins included, is met
+        assert ((values > t0) & (values < t1)).sum() > 5, (t0, t1)
+    _assert_counts(r, got, want, values, f"{shape} {storage}")
+
+
+# ---- 3. what must not move ----
+@pytest.mark.parametrize("storage", list(STORAGES))
+def test_closed_partition_keeps_its_kernel(torch_cuda, storage):
+    dtype = STORAGES[storage]
+    bins = eb.with_ends(eb.lattice(dtype, 13))
+    r = eb.make_recipe("", dtype, 1101 if eb.is_packed(dtype) else 60, bins, True, False)
+    plan, got, want, values, _ = _run(torch_cuda, r, 3)
+    depth = {"f32": 8, "f64": 4, "i16": 16}[storage]
+    assert _name(plan) == f"{storage}_p0_v1_s0_t16_k16_d{depth}_nt_ibins_sl_hist_arith", plan.describe()
+    _assert_counts(r, got, want, values, f"closed {storage}")
+
+
+def _off_route_cases(dtype):
+    a = [float(x) for x in eb.lattice(dtype, 13)]
+    open_bins = eb.with_ends(a, -INF, INF)
+    cols = lambda bins: [dict(inner="bins", inner_args=(t0, t1, 0.0), outer="sum") for t0, t1 in bins]      # noqa: E731
+    w = 2.0 ** -14
+    narrow = 300.0 + 2.0 ** -15 + w * np.arange(7)             # bins of two float32 ulps at 300: too narrow for the guess
+    return {
+        "unequal_interior_widths": cols([(-20.0, 0.0), (0.0, 7.5), (7.5, 10.0), (10.0, 30.0), (30.0, 99.0)]),
+        "a_gap": cols([b for i, b in enumerate(open_bins) if i != 4]),
+        "three_bins": cols([(-INF, 0.0), (0.0, 5.0), (5.0, INF)]),
+        "a_degree_day_slot_beside_the_bins": cols(open_bins[:14]) + [dict(inner="dd", inner_args=(a[0], a[0] + 30.0, 0.0), outer="sum")],
+        "too_narrow_for_the_guess": cols(eb.with_ends(narrow, -INF, INF)),
+    }
+
+
+@pytest.mark.parametrize("storage", ["f32", "i16"])
+@pytest.mark.parametrize("case", list(_off_route_cases(vr.F32)))
+def test_other_plans_stay_off_the_histogram_route(torch_cuda, case, storage):
+    dtype = STORAGES[storage]
+    cols = _off_route_cases(dtype)[case]
+    ib, ob = ph.groups(False)
+    es = sorted({float(x) for c in cols for x in c["inner_args"][:2] if np.isfinite(x)})
+    seed = zlib.crc32(case.encode())
+    if eb.is_packed(dtype) and case == "too_narrow_for_the_guess":
+        # values 300 + q / 16384, exact in float32: one stored integer per narrow bin (as in test_gpu_packed_hist)
+        r = vr.Recipe("", dtype, int(ib[-1]), 1102, ib, ob, cols, True, 0, edges=[12.0])
+        q = ph.stored_cube(r, seed)
+        q[::5, ::9] = np.random.default_rng(1).integers(-2, 9, q[::5, ::9].shape).astype(np.int16)
+        plan, got, want, values = _run_recipe(torch_cuda, r, q, pairs=[(2.0 ** -14, 300.0)])
+    else:
+        r = vr.Recipe("", dtype, int(ib[-1]), 1102 if eb.is_packed(dtype) else 64, ib, ob, cols, True, 0, edges=es)
+        plan, got, want, values, _ = _run(torch_cuda, r, seed)
+    name = _name(plan)
+    assert "_hist" not in name and "_ends" not in name, plan.describe()
+    if storage == "i16":
+        assert name.startswith("i16_p0_v2_") and name.endswith("_nt") and "_ibins" not in name, plan.describe()
+    elif case != "a_degree_day_slot_beside_the_bins":
+        assert "_ibins" in name, plan.describe()
+    for k in range(len(cols)):
+        np.testing.assert_array_equal(got[k], want[k], err_msg=f"{case} column {k}")
+
+
+@pytest.mark.parametrize("storage", list(STORAGES))
+@pytest.mark.parametrize("single_level,mean", [(True, False), (False, True)], ids=["sl", "two_level_mean"])
+def test_knob_sends_the_plan_down_the_earlier_route_with_the_same_counts(torch_cuda, monkeypatch, single_level, mean, storage):
+    dtype = STORAGES[storage]
+    r = eb.make_recipe("", dtype, 1102 if eb.is_packed(dtype) else 64, eb.with_ends(eb.lattice(dtype, 13), -INF, INF), single_level, mean)
+    data = eb.stored_cube(r, 9) if eb.is_packed(dtype) else eb.cube_for(r, 9)
+    plan, got, want, values, _ = _run(torch_cuda, r, data=data)
+    assert "_hist_arith_ends" in _name(plan) and ("_sl_" in _name(plan)) == single_level, plan.describe()
+    monkeypatch.setenv("AFHIP_NO_END_BINS_HIST", "1")
+    earlier, got_e, _, _, _ = _run(torch_cuda, r, data=data)
+    monkeypatch.delenv("AFHIP_NO_END_BINS_HIST")
+    name = _name(earlier)
+    assert "_hist" not in name and "_ends" not in name, earlier.describe()
+    if storage == "i16":
+        assert name == f"i16_p0_v2_s{int(mean)}_t16_k16_d16_nt" and "packed-counts" not in earlier.describe(), earlier.describe()
+    else:
+        assert name.startswith(f"{storage}_p0_") and f"_s{int(mean)}_t16_k16_" in name and "_ibins" in name and ("_sl" in name) == single_level, earlier.describe()
+    np.testing.assert_array_equal(got[:15], got_e[:15])               # the counts, bit for bit (NaN where the other has NaN)
+    _assert_cells(ANY, r.columns, got_e, want)
+    _assert_counts(r, got, want, values, f"knob {storage}")
+
+
+# ---- 4. packed specifics ----
+OPEN5 = eb.with_ends(hist_mod.EDGES5, -INF, INF)              # thirteen bins of 5 C between two open ends: arithmetic edges
+TABLE5 = eb.with_ends(hist_mod.TABLE5, -INF, 60.0)
+
+
+@pytest.mark.parametrize("single_level", [False, True], ids=["two_level", "sl"])
+@pytest.mark.parametrize("form", ["arith", "table"])
+@pytest.mark.parametrize("n_cells", [1102, 1101])
+def test_rule_changes_wherever_they_can_fall(torch_cuda, n_cells, form, single_level):
+    from aggfly_amd import hip
+    cube, values64, bits = hist_mod._case5(n_cells)
+    T5, IB5 = hist_mod.T5, hist_mod.IB5
+    assert cube.n_rules == len(hist_mod.BOUNDS5) - 1 >= 3
+    ob = np.arange(len(IB5), dtype=np.int64) if single_level else np.arange(0, 41, 8, dtype=np.int64)
+    bins = OPEN5 if form == "arith" else TABLE5
+    cols = eb.bin_columns(bins, "identity" if single_level else "sum", mean=not single_level)
+    plan = hip.FusedPlan(T5, n_cells, hip.I16, IB5, ob, cols, exact_order=True)
+    plan.bind_packing(cube)
+    d = plan.describe()
+    vec = 2 if (n_cells % 2 == 0 and single_level and form == "table") else 1
+    name = _name(plan)
+    assert name.startswith(f"i16_p0_v{vec}_s{0 if single_level else 1}_t16_k16_") and name.endswith("_ends"), d
+    assert ("_arith" in name) == (form == "arith") and ("_sl_" in name) == single_level, d
+    got = plan.run_temporal(cube).cpu().numpy()
+    want = _oracle_two_level(values64, IB5, ob, cols)
+    _assert_cells(ANY, cols, got, want)
+    r = vr.Recipe("", pr.I16, T5, n_cells, IB5, ob, cols, True, 0)
+    _assert_counts(r, got, want, values64, f"rules {form}")
+    for t0, t1 in (bins[0], bins[-1]):                                 # both end bins are met, under several rules
+        assert ((values64 > t0) & (values64 < t1)).sum() > 1000
+
+
+@pytest.mark.parametrize("form", ["arith", "table"])
+def test_uint16_storage_takes_the_same_kernels(torch_cuda, form):
+    from aggfly_amd import hip
+    pairs, fill = uns.PAIRS, 65535                        # value(q) = q * 0.001 + 252.4 - 273.15: -20.75 ... 44.79 C
+    near = lambda x: uns.stored_near(x, pairs)            # noqa: E731
+    val = lambda x: float(uns.np_unpack([near(x)], pairs, None)[0])      # noqa: E731
+    if form == "arith":
+        edges = val(-15.0) + 4.0 * np.arange(14)
+    else:
+        edges = -14.85 + 3.7 * np.arange(14)
+    bins = eb.with_ends(edges, val(-19.0), val(43.0))     # finite outer limits on stored values, inside the storage's range
+    ib, ob = ph.groups(True)
+    cols = eb.bin_columns(bins, "identity")
+    T, C = int(ib[-1]), 1102
+    rng = np.random.default_rng(6)
+    q = rng.integers(0, 65536, (T, C)).astype(np.uint16)
+    every = sorted({x for b in bins for x in b})
+    plant = [0, 1, 32767, 32768, 65534] + [s + d for x in every for s in [near(x)] for d in (-3, -2, -1, 0, 1, 2, 3)]
+    q.reshape(-1)[rng.choice(q.size, 20 * len(plant), replace=False)] = np.array(plant * 20, dtype=np.uint16)
+    ne = np.flatnonzero(np.diff(ib) > 0)
+    q[ib[ne[::5]], 40:60] = fill                                   # the fill in first rows of groups
+    for g in ne[2::7]:
+        q[ib[g]:ib[g + 1], 100:104] = fill                        # in whole groups
+    q[:, [3, C - 1]] = fill                                        # in whole cells, the last one included
+    cube = uns._cuda_cube(torch_cuda, q.reshape(T, 1, C), scale_factor=pairs[0][0], add_offset=pairs[0][1], fill_value=fill) - 273.15
+    plans = {}
+    for code, c in ((hip.U16, cube), (hip.I16, af.PackedCube(cube.q, fill_value=-1, unsigned=False, _pairs=cube.pairs))):
+        plan = hip.FusedPlan(T, C, code, ib, ob, cols, exact_order=True)
+        plan.bind_packing(c)
+        plans[code] = plan
+    pu = plans[hip.U16]
+    assert _name(pu) == _name(plans[hip.I16]) and _name(pu).startswith("i16_") and _name(pu).endswith("_ends"), pu.describe()
+    assert "_sl_hist" in _name(pu) and ("_arith" in _name(pu)) == (form == "arith"), pu.describe()
+    assert "storage=uint16" in pu.describe() and "storage=int16" in plans[hip.I16].describe()
+    values = uns.np_unpack(q, pairs, fill)
+    assert (q > 32767).mean() > 0.4 and np.isnan(values).sum() == (q == fill).sum() > 2 * T
+    assert (values == np.float32(bins[0][0])).any() and (values < np.float32(bins[0][0])).any() and (values > np.float32(bins[-1][1])).any()
+    got = pu.run_temporal(cube).cpu().numpy()
+    want = _oracle_two_level(values.astype(np.float64).reshape(T, 1, C), ib, ob, cols)
+    r = vr.Recipe("", pr.I16, T, C, ib, ob, cols, True, 0)
+    _assert_counts(r, got, want, values, f"uint16 {form}")
+
+
+# ---- 5. the whole pass ----
+@pytest.mark.parametrize("storage", list(STORAGES))
+def test_whole_pass_direct_gather_and_cell_major_panel_agree(torch_cuda, storage):
+    from aggfly_amd import hip
+    dtype = STORAGES[storage]
+    r = eb.make_recipe("", dtype, 1102 if eb.is_packed(dtype) else 64, eb.with_ends(eb.lattice(dtype, 13), -INF, INF), True, False)
+    if eb.is_packed(dtype):
+        q = eb.stored_cube(r, 4)
+        values = pr.np_unpack(q)
+        d = af.PackedCube(torch_cuda.from_numpy(q.reshape(r.T, 1, r.n_cells)).cuda(), scale_factor=pr.PAIRS[0][0], add_offset=pr.PAIRS[0][1],
+                          fill_value=pr.FILL) + pr.PAIRS[1][1]
+    else:
+        values = eb.cube_for(r, 4)
+        d = torch_cuda.from_numpy(values).cuda()
+    plan = hip.FusedPlan(r.T, r.n_cells, hip.I16 if eb.is_packed(dtype) else dtype, r.inner_bounds, r.outer_bounds, r.columns, exact_order=True)
+    if eb.is_packed(dtype):
+        plan.bind_packing(d)
+    assert _name(plan).endswith("_sl_hist_arith_ends") and "packed-counts" in plan.describe(), plan.describe()
+    tab = _csr_table(r.n_cells, seed=5)
+    csr = hip.CSR(tab["index_right"].to_numpy(), tab["cell_id"].to_numpy(), tab["weight"].to_numpy(), int(tab["index_right"].max()) + 1, r.n_cells)
+    direct = plan.run(d, csr, want_cells=False)
+    via_panel = plan.run(d, csr, want_cells=True)
+    for key in ("num", "den", "res"):
+        np.testing.assert_array_equal(direct[key].cpu().numpy(), via_panel[key].cpu().numpy(), err_msg=key)
+    want = _oracle_two_level(values.astype(np.float64).reshape(r.T, 1, r.n_cells), r.inner_bounds, r.outer_bounds, r.columns)
+    np.testing.assert_array_equal(via_panel["cells"].cpu().numpy(), want)
+    # the weighted sums in table order on the oracle's cells (spatial.py:181-186): where(valid, x, 0), valid = no NaN among the columns
+    valid = ~np.isnan(want).any(axis=0)                                          # [P, cells]
+    n_regions = int(tab["index_right"].max()) + 1
+    den = np.zeros((n_regions, want.shape[1]))
+    num = np.zeros((want.shape[0], n_regions, want.shape[1]))
+    for r_, c_, w_ in zip(tab["index_right"].to_numpy(), tab["cell_id"].to_numpy(), tab["weight"].to_numpy()):
+        den[r_] += w_ * valid[:, c_]
+        num[:, r_] += w_ * np.where(valid[:, c_], want[:, :, c_], 0.0)
+    np.testing.assert_array_equal(direct["den"].cpu().numpy(), den)
+    np.testing.assert_array_equal(direct["num"].cpu().numpy(), num)
+
+
+def test_open_ended_bins_spec_through_the_public_api(torch_cuda, tmp_path):
+    from aggfly_amd import engine as eng
+    from aggfly_amd import io as afio
+    from oracle import ref_aggregate as ra
+    T, ny, nx = 24 * 20, 25, 44                                        # 1,100 cells, twenty days over a new year: two yearly periods
+    rng = np.random.default_rng(12)
+    per_deg = 1.0 / 0.0017
+    stored = np.clip(np.rint(pr.stored_near(12.0) + rng.normal(0.0, 14.0, (T, ny, nx)) * per_deg), -32766, 32766).astype(np.int16)
+    stored[rng.random((T, ny, nx)) < 0.01] = -32767
+    stored[:, 2, 3] = -32767                                            # an ocean cell
+    edges = [float(x) for x in -20.0 + 5.0 * np.arange(14)]
+    for x in edges:                                                     # the stored integers around every edge
+        s = pr.stored_near(x)
+        stored.reshape(-1)[rng.choice(stored.size, 30, replace=False)] = np.array([s - 1, s, s + 1] * 10, dtype=np.int16)
+    attrs = {"scale_factor": 0.0017, "add_offset": 281.3, "_FillValue": -32767}
+    time = pd.date_range("2003-12-22", periods=T, freq="h")
+    lat, lon = 35 + 0.25 * np.arange(ny), 250 + 0.25 * np.arange(nx)
+    tv, tattrs = afio._encode_time(time)
+    store = str(tmp_path / "bins.zarr")
+    os.makedirs(store)
+    json.dump({"zarr_format": 2}, open(os.path.join(store, ".zgroup"), "w"))
+    afio._write_array(store, "t2m", stored, ("time", "latitude", "longitude"), (48, ny, nx), attrs, None)
+    afio._write_array(store, "time", np.asarray(tv, dtype=np.float64), ("time",), (T,), tattrs, None)
+    afio._write_array(store, "latitude", lat, ("latitude",), (ny,), {}, None)
+    afio._write_array(store, "longitude", lon, ("longitude",), (nx,), {}, None)
+    celsius = lambda x: x - 273.15                                      # noqa: E731
+    packed = af.dataset_from_path(store, "t2m", device="cuda", keep_packed=True, preprocess=celsius)
+    plain = af.dataset_from_path(store, "t2m", device="cuda", preprocess=celsius)
+    assert packed.is_packed and not plain.is_packed
+    tab = synth.weights_table(ny, nx, 20, seed=3, secondary=True)
+    regions = pd.DataFrame({"geoid": [f"r{i}" for i in range(int(tab.index_right.max()) + 1)]})
+    gr = af.GeoRegions(regions, regionid="geoid")
+    ddargs = [[-INF, edges[0], 0]] + [[a, b, 0] for a, b in zip(edges[:-1], edges[1:])] + [[edges[-1], INF, 0]]
+    spec = dict(bins=[("aggregate", {"calc": "bins", "groupby": "year", "ddargs": ddargs})])
+    frames, descs = {}, {}
+    for key, ds in (("packed", packed), ("plain", plain)):
+        eng._PLAN_CACHE.clear()
+        frames[key] = af.aggregate_dataset(dataset=ds, weights=af.weights_from_objects(ds, gr, table=tab), **spec)
+        plans = list(eng._PLAN_CACHE.values())
+        assert len(plans) == 1
+        descs[key] = plans[0].describe()
+    dp, df = descs["packed"], descs["plain"]
+    assert "variant=i16_p0_v1_s0_t16_k16_" in dp and "_sl_hist_arith_ends" in dp and "packed-counts" in dp and "last-run=count-gather" in dp and "storage=int16" in dp, dp
+    assert "variant=f32_" in df and "_sl_hist_arith_ends" in df and "packed-counts" in df, df
+    last = lambda d: [w for w in d.split() if w.startswith("last-run=")]      # noqa: E731
+    assert last(dp) == last(df) and last(dp), (dp, df)                  # the same spatial route: the frames must agree in every bit
+    cols = [c for c in frames["packed"].columns if c not in ("geoid", "time")]
+    assert len(cols) == 15 and frames["packed"]["time"].nunique() == 2
+    pd.testing.assert_frame_equal(frames["packed"], frames["plain"], check_exact=True)
+    # ... and the oracle's frame, on the host-unpacked float32 values
+    values = pr.np_unpack(stored.reshape(T, -1)).reshape(T, ny, nx)
+    ow = ra.OWeights(tab, np.arange(ny * nx), regions["geoid"], "geoid", "nan")
+    want = ra.aggregate_dataset(ow, ra.ODataset(values.astype(np.float64), time, lat, lon, True), engine="numba", **spec)
+    assert list(frames["plain"].columns) == list(want.columns) and len(want) == len(frames["plain"])
+    np.testing.assert_allclose(frames["plain"][cols].values, want[cols].values, rtol=1e-10, atol=0, equal_nan=True)      # the suite's bar for a frame against the oracle's
+    totals = frames["plain"][cols].values.sum(axis=1)
+    assert np.isfinite(totals).any() and (frames["plain"][[cols[0], cols[-1]]].values > 0).any()      # the open bins hold values
