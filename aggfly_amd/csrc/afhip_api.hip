@@ -354,15 +354,14 @@ extern "C" const char* afhip_last_error(void) { return last_error(); }
 extern "C" int afhip_abi_version(void) { return AFHIP_ABI_VERSION; }
 
 extern "C" int afhip_build_info(char* buf, int buf_len) {
-    int n = 0, arms = 0, rf = 0, np = 0, nh = 0, ne = 0;
-    const Variant* tab = variants_table(&n);
+    int count[MENU_COUNT], arms = 0, rf = 0;
+    for (int m = 0; m < MENU_COUNT; ++m) (void)menu_table((Menu)m, &count[m]);
+    int n = 0;
+    const Variant* tab = menu_table(MENU_FLOAT, &n);
     for (int i = 0; i < n; ++i) { arms += tab[i].production ? 0 : 1; rf += tab[i].rf() ? 1 : 0; }
-    (void)packed_variants_table(&np);
-    (void)packed_hist_variants_table(&nh);
-    (void)end_bins_variants_table(&ne);
     char tmp[240];
     const int len = snprintf(tmp, sizeof tmp, "menu=%s variants=%d arms=%d region_fused_twins=%d abi=%d packed_variants=%d packed_hist_variants=%d end_bins_variants=%d",
-                             variants_menu(), n, arms, rf, AFHIP_ABI_VERSION, np, nh, ne);
+                             variants_menu(), n, arms, rf, AFHIP_ABI_VERSION, count[MENU_PACKED], count[MENU_PACKED_HIST], count[MENU_END_BINS]);
     if (buf && buf_len > 0) snprintf(buf, buf_len, "%s", tmp);
     return len + 1;
 }

@@ -392,7 +392,7 @@ static HistPartition find_partition(const PlanLayout& pl, bool all_bins) {
 // the variant with the region-fused period ends compiled in and every other field equal (null: the menu has none)
 static const Variant* twin_of(const Variant* v) {
     int n = 0;
-    const Variant* tab = variants_table(&n);
+    const Variant* tab = menu_table(MENU_FLOAT, &n);
     for (int i = 0; i < n; ++i) {
         const Variant& t = tab[i];
         if (t.feat == (v->feat | FEAT_REGION_FUSED) && t.dtype == v->dtype && t.pipe == v->pipe && t.vec == v->vec && t.stat == v->stat && t.nthr == v->nthr &&
@@ -402,7 +402,7 @@ static const Variant* twin_of(const Variant* v) {
     return nullptr;
 }
 
-// int16- and uint16-packed cubes (AFHIP_I16, AFHIP_U16) have a table of their own (packed_variants_table) of general forms on the direct-load path: the
+// int16- and uint16-packed cubes (AFHIP_I16, AFHIP_U16) have a menu of their own (MENU_PACKED) of general forms on the direct-load path: the
 // widest row piece per lane the rows allow and the menu holds for the plan's shape — four cells (8 bytes, the light shapes only), else
 // two, else one.  (Four against two cells on the light shapes is the float32 rule "8 bytes per lane" carried over; not measured on
 // packed cubes yet: profiles/packed_cube.txt.)
@@ -410,7 +410,7 @@ static const Variant* choose_packed_variant(const PlanLayout& pl) {
     const int64_t C = pl.desc.n_cells;
     for (int vec : {4, 2, 1}) {
         if (C % vec != 0) continue;
-        if (const Variant* v = find_packed_variant(vec, pl.stat, pl.nthr, pl.K)) return v;
+        if (const Variant* v = find_exact_form(MENU_PACKED, AFHIP_I16, vec, pl.stat, pl.nthr, pl.K, false, false)) return v;
     }
     return nullptr;
 }
@@ -424,45 +424,39 @@ static bool is_single_level(const PlanLayout& pl) {
     return single_level;
 }
 
-// ... and for a plan whose threshold slots are a contiguous equal-width partition (`hist`, found with the float32 rules: the values of a
-// packed cube are float32) the table of LDS-histogram forms (packed_hist_variants_table): the widest cells per lane that divide the row
-// length and that the production menu holds for the plan's stat tier — single-level form for single-level plans, arithmetic edges when
-// the edges are exact, else the edge table.  Which widths the menu holds was measured form by form (gen_variants.py: packed_hist_menu;
-// profiles/packed_cube.txt, section 6): two cells per lane for the single-level edge-table forms only.  Null: no such kernel, the plan
-// takes the general form above.  AFHIP_PACKED_HIST_VEC=1|2 asks for that width where the library holds it, arms included (the A/B knob
-// of that section).
-static const Variant* choose_packed_hist_variant(const PlanLayout& pl, const HistPartition& hist, const PlanKnobs& knobs) {
-    if (hist.hb_n == 0 || knobs.no_packed_hist) return nullptr;
-    const int64_t C = pl.desc.n_cells;
-    const bool sl = is_single_level(pl);
-    if (knobs.packed_hist_vec && C % knobs.packed_hist_vec == 0)
-        if (const Variant* v = find_packed_hist_variant(knobs.packed_hist_vec, pl.stat, pl.nthr, pl.K, sl, hist.hb_arith, true)) return v;
-    for (int vec : {2, 1}) {
-        if (C % vec != 0) continue;
-        if (const Variant* v = find_packed_hist_variant(vec, pl.stat, pl.nthr, pl.K, sl, hist.hb_arith)) return v;
-    }
-    return nullptr;
-}
-
-// A partition with a wide end bin (HistPartition::hb_wide) asks the table of end-bin histogram forms (end_bins_variants_table; gen_variants.py:
-// end_bins_menu), on packed and float cubes alike: the storage's production histogram forms with FEAT_END_BINS — one cell per lane, and
-// for packed cubes two where the rows are even and the menu holds the form (the single-level edge-table forms, as in packed_hist_menu).
-// Null: no such kernel (`dev` menu), a tuning arm, or the route is off — the plan then routes as if the partition had not been found.
-// AFHIP_NO_END_BINS_HIST switches the route off (the A/B knob of scripts/end_bins_bench.py); packed cubes follow AFHIP_NO_PACKED_HIST too.
-// The route is the default on every storage, by the rule the packed histogram forms were held to: on the configs[1] shape, thirteen 5-degree bins
-// between two open ends, single level and two-level with a mean, its median lies below the earlier route's minimum in the same process — at
-// x0.11 / x0.12 of it on packed cubes, x0.27 / x0.34 on float32, x0.52 / x0.36 on float64 (profiles/end_bins.txt, section 2: the whole output of
-// scripts/end_bins_bench.py with device, build and min / median / max of the three routes).
-static const Variant* choose_end_bins_variant(const PlanLayout& pl, const HistPartition& hist, int tuning, const PlanKnobs& knobs) {
-    if (hist.hb_n == 0 || !hist.hb_wide || knobs.no_end_bins_hist || tuning != 0) return nullptr;
+// The LDS-histogram forms that are matched exactly (find_exact_form): those of packed cubes (MENU_PACKED_HIST) for a closed partition
+// `hist` — found with the float32 rules: the values of a packed cube are float32 — and the end-bin forms (MENU_END_BINS) for a partition
+// with a wide end bin (HistPartition::hb_wide), on packed and float cubes alike.  A closed partition on a float cube never comes here: it
+// goes through choose_variant.  Either way the widest of two and one cells per lane that divides the row length and that the production
+// menu holds for the plan's stat tier and storage — single-level form for single-level plans, arithmetic edges when the edges are exact,
+// else the edge table.  Null: no such kernel, or the route is off.
+//   Closed, packed: which widths the menu holds was measured form by form (gen_variants.py: packed_hist_menu; profiles/packed_cube.txt,
+// section 6): two cells per lane for the single-level edge-table forms only.  Null sends the plan to the general form above, and so does
+// AFHIP_NO_PACKED_HIST.  AFHIP_PACKED_HIST_VEC=1|2 asks for that width where the library holds it, arms included (the A/B knob of that
+// section).
+//   Wide: the storage's production histogram forms with FEAT_END_BINS (gen_variants.py: end_bins_menu) — one cell per lane, and for packed
+// cubes two where the rows are even and the menu holds the form (the single-level edge-table forms, as in packed_hist_menu).  Null — no
+// such kernel (`dev` menu), a tuning arm, or the route is off — routes the plan as if the partition had not been found.
+// AFHIP_NO_END_BINS_HIST switches the route off (the A/B knob of scripts/end_bins_bench.py); packed cubes follow AFHIP_NO_PACKED_HIST too,
+// but not AFHIP_PACKED_HIST_VEC.  The route is the default on every storage, by the rule the packed histogram forms were held to: on the
+// configs[1] shape, thirteen 5-degree bins between two open ends, single level and two-level with a mean, its median lies below the
+// earlier route's minimum in the same process — at x0.11 / x0.12 of it on packed cubes, x0.27 / x0.34 on float32, x0.52 / x0.36 on
+// float64 (profiles/end_bins.txt, section 2: the whole output of scripts/end_bins_bench.py with device, build and min / median / max of
+// the three routes).
+static const Variant* choose_hist_variant(const PlanLayout& pl, const HistPartition& hist, int tuning, const PlanKnobs& knobs) {
     const bool packed = is_packed_dtype(pl.desc.dtype);
-    if (packed && knobs.no_packed_hist) return nullptr;
+    if (hist.hb_n == 0 || (packed && knobs.no_packed_hist)) return nullptr;
+    if (hist.hb_wide ? (knobs.no_end_bins_hist || tuning != 0) : !packed) return nullptr;
+    const Menu menu = hist.hb_wide ? MENU_END_BINS : MENU_PACKED_HIST;
     const int dtype = packed ? AFHIP_I16 : pl.desc.dtype;
     const bool sl = is_single_level(pl);
-    for (int vec : {2, 1}) {
-        if (pl.desc.n_cells % vec != 0) continue;
-        if (const Variant* v = find_end_bins_variant(dtype, vec, pl.stat, pl.nthr, pl.K, sl, hist.hb_arith)) return v;
-    }
+    auto find = [&](int vec, bool arms) {
+        return pl.desc.n_cells % vec == 0 ? find_exact_form(menu, dtype, vec, pl.stat, pl.nthr, pl.K, sl, hist.hb_arith, arms) : nullptr;
+    };
+    if (!hist.hb_wide && knobs.packed_hist_vec)
+        if (const Variant* v = find(knobs.packed_hist_vec, true)) return v;
+    for (int vec : {2, 1})
+        if (const Variant* v = find(vec, false)) return v;
     return nullptr;
 }
 
@@ -791,48 +785,39 @@ int build_plan(const afhip_plan_desc* desc, const DeviceFacts& dev, PlanLayout* 
     pl->desc.inner_bounds = nullptr; pl->desc.outer_bounds = nullptr; pl->desc.columns = nullptr;
     if ((rc = lower_columns(pl))) return rc;
 
-    if (is_packed_dtype(desc->dtype)) {
-        // int16 and uint16 storage alike (the kernels take the signedness from the bound packing).  A plan of four or more contiguous,
-        // equal-width, strict bins (find_partition, with the float32 rules) takes an LDS-histogram form of the packed histogram table,
-        // chunked like the float histogram plans (single-wave workgroups, many chunks) and, single-level, with packed count records and
-        // the count gather (packed_format); AFHIP_NO_PACKED_HIST sends it on with the rest.  Every other plan goes straight to the packed
-        // table of general forms: no short-group form, no packed counts (packed_format finds no integer-bin form), and — neither table
-        // has region-fused twins — the spatial stage is the slot gather or the table-order sums
-        bool all_bins = pl->nthr > 0;
-        for (const ThrSlot& t : pl->thr) all_bins = all_bins && t.nan_poisons == 0;
-        // (a partition with a wide end bin: the end-bin forms or none — no kernel without FEAT_END_BINS ever sees such a partition)
-        const HistPartition hist = find_partition(*pl, all_bins);
-        pl->variant = hist.hb_wide ? choose_end_bins_variant(*pl, hist, 0, knobs) : choose_packed_hist_variant(*pl, hist, knobs);
-        if (pl->variant) static_cast<HistPartition&>(*pl) = hist;
-        else pl->variant = choose_packed_variant(*pl);
-        if (!pl->variant)
-            return fail(AFHIP_E_UNSUPPORTED, "no packed kernel variant for stat=%d slots=%d columns=%d", pl->stat, pl->nthr, pl->K);
-        if ((rc = build_chunks(pl, pl->variant->vec, knobs, dev))) return rc;
-        pl->variant_rf = nullptr;
-        pl->rf_plan_ok = false;
-        pl->gtab = group_table(*pl);
-        pl->pk = packed_format(*pl);
-        pl->packed = pl->pk.nw != 0;
-        workspace_sizes(pl);
-        return AFHIP_OK;
-    }
-    const GroupForm form = short_group_form(*pl, knobs);
-    const LoadPath path = load_path(*pl, form.pairs);
-    const int tuning = usable_tuning(pl->desc);
+    // int16 and uint16 storage alike (the kernels take the signedness from the bound packing).  Their menus hold no tuning arm that
+    // `tuning` names, no short-group form and no region-fused twin.
+    const bool packed = is_packed_dtype(desc->dtype);
+    const int tuning = packed ? 0 : usable_tuning(pl->desc);
     bool all_bins = pl->nthr > 0;
     for (const ThrSlot& t : pl->thr) all_bins = all_bins && t.nan_poisons == 0;
-    static_cast<HistPartition&>(*pl) = find_partition(*pl, all_bins);
-    // a partition with a wide end bin: the end-bin histogram form, or the route of a plan without a partition
+    // A plan of four or more contiguous, equal-width, strict bins (on packed storage by the float32 rules) takes an LDS-histogram form,
+    // chunked with single-wave workgroups and many chunks and, single-level, with packed count records and the count gather
+    // (packed_format).  A float cube's closed partition finds its form in choose_variant, which may also leave the partition unused;
+    // packed cubes and partitions with a wide end bin have menus of exact forms: that form or none — no kernel without FEAT_END_BINS ever
+    // sees a partition with a wide end, and the general packed kernels see none at all — so without one the plan routes as if the
+    // partition had not been found.
+    HistPartition hist = find_partition(*pl, all_bins);
     pl->variant = nullptr;
-    if (pl->hb_wide) {
-        pl->variant = choose_end_bins_variant(*pl, *pl, tuning, knobs);
-        if (!pl->variant) static_cast<HistPartition&>(*pl) = HistPartition{};
+    if (packed || hist.hb_wide) {
+        pl->variant = choose_hist_variant(*pl, hist, tuning, knobs);
+        if (!pl->variant) hist = HistPartition{};
     }
-    if (!pl->variant) pl->variant = choose_variant(*pl, form, path, *pl, all_bins, tuning, knobs, dev.cu_count);
+    static_cast<HistPartition&>(*pl) = hist;
+    if (!pl->variant && packed) {
+        // the packed menu of general forms: no packed counts (packed_format finds no integer-bin form); the spatial stage is the slot
+        // gather or the table-order sums
+        pl->variant = choose_packed_variant(*pl);
+    } else if (!pl->variant) {
+        const GroupForm form = short_group_form(*pl, knobs);
+        const LoadPath path = load_path(*pl, form.pairs);
+        pl->variant = choose_variant(*pl, form, path, hist, all_bins, tuning, knobs, dev.cu_count);
+    }
     if (!pl->variant)
-        return fail(AFHIP_E_UNSUPPORTED, "no kernel variant for dtype=%d stat=%d slots=%d columns=%d", desc->dtype, pl->stat, pl->nthr, pl->K);
+        return packed ? fail(AFHIP_E_UNSUPPORTED, "no packed kernel variant for stat=%d slots=%d columns=%d", pl->stat, pl->nthr, pl->K)
+                      : fail(AFHIP_E_UNSUPPORTED, "no kernel variant for dtype=%d stat=%d slots=%d columns=%d", desc->dtype, pl->stat, pl->nthr, pl->K);
     if ((rc = build_chunks(pl, pl->variant->vec, knobs, dev))) return rc;
-    pl->variant_rf = twin_of(pl->variant);
+    pl->variant_rf = twin_of(pl->variant);      // (the float menu alone holds twins: null on packed storage, and rf_plan_ok false)
     pl->rf_plan_ok = rf_plan_ok(*pl, knobs);
     pl->gtab = group_table(*pl);
     pl->pk = packed_format(*pl);

@@ -1,9 +1,11 @@
-// afhip_variants.h — the menu of compiled k_fused_temporal specialisations.
+// afhip_variants.h — the menus of compiled k_fused_temporal specialisations.
 //
 // The hot per-element loop must be straight-line code with every accumulator in a
 // register, so the accumulator counts are template parameters.  gen_variants.py writes
-// one translation unit per group of instantiations (compiled in parallel) plus the table
-// below; find_variant() picks the cheapest instantiation that covers a lowered plan.
+// one translation unit per group of instantiations (compiled in parallel) plus ONE table
+// (variants_table.hip) with a slice per menu: menu_table() hands out a slice, find_variant()
+// picks the cheapest float instantiation that covers a lowered plan, find_exact_form() the
+// kernel of one of the other menus.
 #pragma once
 #include <stdint.h>
 #include "afhip_plan_types.h"
@@ -11,7 +13,7 @@
 namespace afhip {
 
 struct Variant {
-    int dtype;    // AFHIP_F32 / AFHIP_F64; AFHIP_I16 in the packed table
+    int dtype;    // AFHIP_F32 / AFHIP_F64; AFHIP_I16 for packed storage
     int pipe;     // 0 direct loads, 1 LDS-DMA ring
     int vec;      // cells per lane
     int stat;     // 0 none, 1 sum, 2 sum+min+max, 3 NaN-skipping sum+count+min+max
@@ -35,18 +37,18 @@ struct Variant {
     bool sine_p2() const { return feat_sine_p2(feat); }                   // sine_dd plans: the P2 table instead of the acos table
 };
 
-const Variant* variants_table(int* n);   // generated (variants_table.hip)
-const char* variants_menu();             // "full" (the production menu), "arms" (+ the tuning arms) or "dev"
-// The kernels of int16- and uint16-packed cubes (AFHIP_I16, AFHIP_U16: one set, the signedness is in the unpack record;
-// gen_variants.py: packed_menu), a table of their own (packed_table.hip): general
-// two-level forms on the direct-load path only, so a plan's stat / slots / columns and the cells per lane are all there is to match.
-const Variant* packed_variants_table(int* n);
-// ... and their LDS-histogram forms (gen_variants.py: packed_hist_menu; packed_hist_table.hip): integer-bin forms for plans whose
-// threshold slots are a contiguous equal-width partition, matched on cells per lane, stat tier, single level and arithmetic edges.
-const Variant* packed_hist_variants_table(int* n);
-// ... and the LDS-histogram forms with FEAT_END_BINS, for partitions with a wide end bin on one side or both — float32, float64 and
-// packed storage in one table (gen_variants.py: end_bins_menu; end_bins_table.hip), matched like the packed histogram forms plus the dtype.
-const Variant* end_bins_variants_table(int* n);
+// The kernel menus (gen_variants.py: MENUS, same names and order; the generated table asserts it).
+//   MENU_FLOAT        float32 / float64 cubes: every form (gen_variants.py: menu), searched by find_variant
+//   MENU_PACKED       int16- and uint16-packed cubes (AFHIP_I16, AFHIP_U16: one set of AFHIP_I16 kernels, the signedness is in the unpack
+//                     record; packed_menu): general two-level forms on the direct-load path only, all production
+//   MENU_PACKED_HIST  ... and their LDS-histogram forms (packed_hist_menu): integer-bin forms for plans whose threshold slots are a
+//                     contiguous equal-width partition; the kernels outside production are tuning arms
+//   MENU_END_BINS     the LDS-histogram forms with FEAT_END_BINS, for partitions with a wide end bin on one side or both — float32,
+//                     float64 and packed storage together (end_bins_menu), all production
+// The last three are searched by find_exact_form.
+enum Menu { MENU_FLOAT, MENU_PACKED, MENU_PACKED_HIST, MENU_END_BINS, MENU_COUNT };
+const Variant* menu_table(Menu menu, int* n);   // generated (variants_table.hip): the menu's kernels, in gen_variants.py's order
+const char* variants_menu();                    // "full" (the production menu), "arms" (+ the tuning arms) or "dev"
 
 // What a lowered plan asks of the menu (afhip_planner.cpp: choose_variant).  A fallback is the same query with a field changed.
 // tuning: 0 = the default choice below; otherwise an explicit arm
@@ -76,7 +78,7 @@ inline const Variant* find_variant(const VariantQuery& q) {
     const Variant* best = nullptr;
     long best_cost = 0;
     int n = 0;
-    const Variant* tab = variants_table(&n);
+    const Variant* tab = menu_table(MENU_FLOAT, &n);
     int want_nt = 1, want_pipe = pipe, want_vec = -1, want_depth = -1;
     if (tuning > 0) {
         int t = tuning;
@@ -102,50 +104,21 @@ inline const Variant* find_variant(const VariantQuery& q) {
     return best;
 }
 
-// the cheapest packed kernel with `vec` cells per lane that covers the plan (null: the menu has none at that width)
-inline const Variant* find_packed_variant(int vec, int stat, int nthr, int K) {
+// The cheapest kernel of `menu` of storage `dtype` (AFHIP_I16 for either packed dtype) with `vec` cells per lane that covers the plan's
+// stat / slots / columns (null: the menu has none at that width).  The form — single level, arithmetic edges — is matched exactly: the
+// single-level form for single-level plans only, arithmetic edges when the plan's edges are exact, else the edge table.  The histogram
+// menus hold every form at one cell per lane, and a wider kernel of ANOTHER form is no substitute (the widths were measured per form);
+// MENU_PACKED holds the form (false, false) only.  What else a kernel has compiled in (LDS histogram, end bins) follows from the menu it
+// stands in.  `arms`: the kernels outside the production menu too (a forced width: AFHIP_PACKED_HIST_VEC).  Among equally cheap
+// kernels the first in table order.
+inline const Variant* find_exact_form(Menu menu, int dtype, int vec, int stat, int nthr, int K, bool single_level, bool arith, bool arms = false) {
     const Variant* best = nullptr;
     long best_cost = 0;
     int n = 0;
-    const Variant* tab = packed_variants_table(&n);
+    const Variant* tab = menu_table(menu, &n);
     for (int i = 0; i < n; ++i) {
         const Variant& v = tab[i];
-        if (v.vec != vec || v.stat < stat || v.nthr < nthr || v.kmax < K) continue;
-        const long cost = (long)v.nthr * 1000 + (long)v.kmax * 10 + v.stat;
-        if (!best || cost < best_cost) { best = &v; best_cost = cost; }
-    }
-    return best;
-}
-
-// the packed LDS-histogram kernel with `vec` cells per lane for a partition plan (null: the menu has none at that width).  The form is
-// matched exactly — the single-level form for single-level plans, arithmetic edges when the plan's edges are exact, else the edge table:
-// the menu holds every form at one cell per lane, and a wider kernel of ANOTHER form is no substitute (the widths were measured per form).
-// `arms`: the kernels outside the production menu too (a forced width: AFHIP_PACKED_HIST_VEC)
-inline const Variant* find_packed_hist_variant(int vec, int stat, int nthr, int K, bool single_level, bool arith, bool arms = false) {
-    const Variant* best = nullptr;
-    long best_cost = 0;
-    int n = 0;
-    const Variant* tab = packed_hist_variants_table(&n);
-    for (int i = 0; i < n; ++i) {
-        const Variant& v = tab[i];
-        if (!v.hb() || v.vec != vec || v.stat < stat || v.nthr < nthr || v.kmax < K || (!v.production && !arms)) continue;
-        if (v.sl() != single_level || v.ha() != arith) continue;
-        const long cost = (long)v.nthr * 1000 + (long)v.kmax * 10 + v.stat;
-        if (!best || cost < best_cost) { best = &v; best_cost = cost; }
-    }
-    return best;
-}
-
-// the end-bin histogram kernel of storage `dtype` (AFHIP_I16 for either packed dtype) with `vec` cells per lane; the form is matched exactly,
-// as in find_packed_hist_variant (null: the menu has none)
-inline const Variant* find_end_bins_variant(int dtype, int vec, int stat, int nthr, int K, bool single_level, bool arith) {
-    const Variant* best = nullptr;
-    long best_cost = 0;
-    int n = 0;
-    const Variant* tab = end_bins_variants_table(&n);
-    for (int i = 0; i < n; ++i) {
-        const Variant& v = tab[i];
-        if (!v.hb() || !feat_has(v.feat, FEAT_END_BINS) || v.dtype != dtype || v.vec != vec || v.stat < stat || v.nthr < nthr || v.kmax < K || !v.production) continue;
+        if (v.dtype != dtype || v.vec != vec || v.stat < stat || v.nthr < nthr || v.kmax < K || (!v.production && !arms)) continue;
         if (v.sl() != single_level || v.ha() != arith) continue;
         const long cost = (long)v.nthr * 1000 + (long)v.kmax * 10 + v.stat;
         if (!best || cost < best_cost) { best = &v; best_cost = cost; }

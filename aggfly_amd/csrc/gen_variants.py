@@ -3,13 +3,15 @@
 
 Usage: gen_variants.py OUTDIR [--menu full|arms|dev] [--per-file N]      (full: the production menu; arms: + the tuning arms)
 
-Each generated ``variants_NN.hip`` holds a handful of explicit instantiations so that
-``make -j`` compiles them in parallel; ``variants_table.hip`` collects the table that
-``find_variant`` (afhip_variants.h) searches.  The kernels of int16-packed cubes (`packed_menu`) go to ``packed_NN.hip`` and a
-table of their own, ``packed_table.hip`` (``packed_variants_table``): `menu` and its table count the float kernels only.  Their
-LDS-histogram forms (`packed_hist_menu`) likewise: ``packed_hist_NN.hip`` and ``packed_hist_table.hip`` (``packed_hist_variants_table``).
-The histogram forms for partitions with a wide end bin (`end_bins_menu`: Feat.END_BINS, float32, float64 and packed storage together) go to
-``end_bins_NN.hip`` (float32 / float64), ``end_bins_packed_NN.hip`` and ``end_bins_table.hip`` (``end_bins_variants_table``): the three menus above keep their counts and their contents.
+Each generated unit holds a handful of explicit instantiations so that ``make -j`` compiles them in parallel.  `MENUS` lists the
+kernel menus and the stems of their units: the float kernels (`menu`) go to ``variants_NN.hip``, the kernels of int16-packed cubes
+(`packed_menu`) to ``packed_NN.hip``, their LDS-histogram forms (`packed_hist_menu`) to ``packed_hist_NN.hip``, and the histogram forms
+for partitions with a wide end bin (`end_bins_menu`: Feat.END_BINS, float32, float64 and packed storage together) to ``end_bins_NN.hip``
+(float32 / float64) and ``end_bins_packed_NN.hip``.  ``variants_table.hip`` collects ONE table, a slice per menu in `MENUS` order, behind
+``menu_table`` (afhip_variants.h), which ``find_variant`` and ``find_exact_form`` search; every menu keeps its own count and contents.
+
+Adding a menu: a menu function and an entry of `MENUS` here, the enumerator of the same name in afhip_variants.h's `Menu` (the table asserts
+that the two agree), and a recipe module under tests/ beside `variant_recipes` ("Adding a kernel menu").
 """
 import os
 import sys
@@ -208,9 +210,9 @@ def packed_menu(kind):
 
 
 def packed_hist_menu(kind):
-    """The LDS-histogram kernels of int16-packed cubes (contiguous equal-width bins; afhip_planner.cpp: choose_packed_hist_variant), same
+    """The LDS-histogram kernels of int16-packed cubes (contiguous equal-width bins; afhip_planner.cpp: choose_hist_variant), same
     tuples as `menu`: stat 0 / 1, two-level / single-level, edge table / arithmetic edges — the shapes of the float32 histogram menu.  A
-    table and translation units of their own: `packed_menu` keeps its 69.
+    menu and translation units of their own: `packed_menu` keeps its 69.
     Cells per lane, measured form by form on the configs[1] shape (profiles/packed_cube.txt, section 6): every form at one cell per lane
     (odd row lengths, and the faster width of six of the eight forms: two cells take 2 ... 39 % longer); two cells only for the
     single-level edge-table forms, which they carry 27 - 31 % faster.  The planner takes the widest form that divides the rows and that
@@ -232,7 +234,7 @@ def packed_hist_menu(kind):
 
 def end_bins_menu(kind):
     """The LDS-histogram kernels for partitions with a wide end bin on one side or both (Feat.END_BINS; afhip_planner.cpp:
-    choose_end_bins_variant), same tuples as `menu`: the production histogram forms of each storage with the bit set, all of them sixteen
+    choose_hist_variant), same tuples as `menu`: the production histogram forms of each storage with the bit set, all of them sixteen
     slots x sixteen columns, nt loads, integer bins.  float32 (eight rows in flight) and float64 (four) at one cell per lane: stat 0 / 1 x
     two-level / single-level x edge table / arithmetic edges.  Packed storage: the ten shapes of the production `packed_hist_menu`, at
     its cells per lane and rows in flight.  No tuning arms; the `dev` menu has none of them (such a plan then routes without them)."""
@@ -326,6 +328,43 @@ def write_units(outdir, vs, per_file, stem):
     return files, ngroups
 
 
+# The kernel menus, in table order: (key, menu function, ((unit stem, storage dtypes), ...)).  The key is the Menu enumerator of
+# afhip_variants.h without its MENU_ prefix, in lower case; a menu's kernels stand in one slice of the table, stem by stem.  A stem's
+# units hold the menu's kernels of the dtypes it names: float and packed kernels go to units of their own, because the packed ones are
+# compiled with the Makefile's PACKED_FLAGS and the float ones as every float kernel.
+MENUS = (
+    ("float", menu, (("variants", (0, 1)),)),
+    ("packed", packed_menu, (("packed", (I16,)),)),
+    ("packed_hist", packed_hist_menu, (("packed_hist", (I16,)),)),
+    ("end_bins", end_bins_menu, (("end_bins", (0, 1)), ("end_bins_packed", (I16,)))),
+)
+
+
+def write_table(outdir, kind, slices, units):
+    """variants_table.hip: the table of every menu.  `slices`: the kernel count per menu, in MENUS order; `units`: every unit's name."""
+    fn = os.path.join(outdir, "variants_table.hip")
+    starts = [sum(slices[:i]) for i in range(len(slices) + 1)]
+    with _KeepIfSame(fn) as f:
+        f.write("// generated by gen_variants.py — do not edit\n")
+        f.write('#include "afhip_variants.h"\n')
+        f.write("namespace afhip {\n")
+        for name in FEAT_NAMES:
+            f.write(f'static_assert(FEAT_{name} == {getattr(Feat, name)}, "gen_variants.py and afhip_plan_types.h disagree on a FEAT bit");\n')
+        f.write(f'static_assert(MENU_COUNT == {len(MENUS)}, "gen_variants.py and afhip_variants.h disagree on the menus");\n')
+        for i, (key, _, _) in enumerate(MENUS):
+            f.write(f'static_assert(MENU_{key.upper()} == {i}, "gen_variants.py and afhip_variants.h disagree on the menus");\n')
+        for u in units:
+            f.write(f"int register_{u}(Variant* out);\n")
+        f.write(f"static Variant g_table[{max(starts[-1], 1)}];\nstatic int g_count = -1;\n")
+        f.write(f"static const int g_start[MENU_COUNT + 1] = {{{', '.join(map(str, starts))}}};      // each menu's slice of g_table\n")
+        f.write(f'const char* variants_menu() {{ return "{kind}"; }}\n')
+        f.write("const Variant* menu_table(Menu m, int* n) {\n    if (g_count < 0) {\n        int c = 0;\n")
+        for u in units:
+            f.write(f"        c += register_{u}(g_table + c);\n")
+        f.write("        g_count = c;\n    }\n    *n = g_start[m + 1] - g_start[m];\n    return g_table + g_start[m];\n}\n}\n")
+    return fn
+
+
 def main():
     outdir = sys.argv[1]
     kind = "full"
@@ -338,69 +377,16 @@ def main():
         elif a == "--per-file":
             per_file = int(args.pop(0))
     os.makedirs(outdir, exist_ok=True)
-    vs = menu(kind)
-    files, ngroups = write_units(outdir, vs, per_file, "variants")
-    pvs = packed_menu(kind)
-    pfiles, pgroups = write_units(outdir, pvs, per_file, "packed")
-    files += pfiles
-    hvs = packed_hist_menu(kind)
-    hfiles, hgroups = write_units(outdir, hvs, per_file, "packed_hist")
-    files += hfiles
-    # (float and packed kernels in units of their own: the packed ones are compiled with the Makefile's PACKED_FLAGS, the float ones as every float kernel)
-    evs = end_bins_menu(kind)
-    efiles, egroups = write_units(outdir, [v for v in evs if v[0] != I16], per_file, "end_bins")
-    epfiles, epgroups = write_units(outdir, [v for v in evs if v[0] == I16], per_file, "end_bins_packed")
-    files += efiles + epfiles
-    with _KeepIfSame(os.path.join(outdir, "variants_table.hip")) as f:
-        f.write("// generated by gen_variants.py — do not edit\n")
-        f.write('#include "afhip_variants.h"\n')
-        f.write("namespace afhip {\n")
-        for name in FEAT_NAMES:
-            f.write(f'static_assert(FEAT_{name} == {getattr(Feat, name)}, "gen_variants.py and afhip_plan_types.h disagree on a FEAT bit");\n')
-        for g in range(ngroups):
-            f.write(f"int register_variants_{g:02d}(Variant* out);\n")
-        f.write(f"static Variant g_table[{len(vs)}];\nstatic int g_count = -1;\n")
-        f.write(f'const char* variants_menu() {{ return "{kind}"; }}\n')
-        f.write("const Variant* variants_table(int* n) {\n    if (g_count < 0) {\n        int c = 0;\n")
-        for g in range(ngroups):
-            f.write(f"        c += register_variants_{g:02d}(g_table + c);\n")
-        f.write("        g_count = c;\n    }\n    *n = g_count;\n    return g_table;\n}\n}\n")
-    with _KeepIfSame(os.path.join(outdir, "packed_table.hip")) as f:
-        f.write("// generated by gen_variants.py — do not edit\n")
-        f.write('#include "afhip_variants.h"\n')
-        f.write("namespace afhip {\n")
-        for g in range(pgroups):
-            f.write(f"int register_packed_{g:02d}(Variant* out);\n")
-        f.write(f"static Variant g_packed[{max(len(pvs), 1)}];\nstatic int g_packed_count = -1;\n")
-        f.write("const Variant* packed_variants_table(int* n) {\n    if (g_packed_count < 0) {\n        int c = 0;\n")
-        for g in range(pgroups):
-            f.write(f"        c += register_packed_{g:02d}(g_packed + c);\n")
-        f.write("        g_packed_count = c;\n    }\n    *n = g_packed_count;\n    return g_packed;\n}\n}\n")
-    with _KeepIfSame(os.path.join(outdir, "packed_hist_table.hip")) as f:
-        f.write("// generated by gen_variants.py — do not edit\n")
-        f.write('#include "afhip_variants.h"\n')
-        f.write("namespace afhip {\n")
-        for g in range(hgroups):
-            f.write(f"int register_packed_hist_{g:02d}(Variant* out);\n")
-        f.write(f"static Variant g_packed_hist[{max(len(hvs), 1)}];\nstatic int g_packed_hist_count = -1;\n")
-        f.write("const Variant* packed_hist_variants_table(int* n) {\n    if (g_packed_hist_count < 0) {\n        int c = 0;\n")
-        for g in range(hgroups):
-            f.write(f"        c += register_packed_hist_{g:02d}(g_packed_hist + c);\n")
-        f.write("        g_packed_hist_count = c;\n    }\n    *n = g_packed_hist_count;\n    return g_packed_hist;\n}\n}\n")
-    with _KeepIfSame(os.path.join(outdir, "end_bins_table.hip")) as f:
-        f.write("// generated by gen_variants.py — do not edit\n")
-        f.write('#include "afhip_variants.h"\n')
-        f.write("namespace afhip {\n")
-        estems = [f"end_bins_{g:02d}" for g in range(egroups)] + [f"end_bins_packed_{g:02d}" for g in range(epgroups)]
-        for stem in estems:
-            f.write(f"int register_{stem}(Variant* out);\n")
-        f.write(f"static Variant g_end_bins[{max(len(evs), 1)}];\nstatic int g_end_bins_count = -1;\n")
-        f.write("const Variant* end_bins_variants_table(int* n) {\n    if (g_end_bins_count < 0) {\n        int c = 0;\n")
-        for stem in estems:
-            f.write(f"        c += register_{stem}(g_end_bins + c);\n")
-        f.write("        g_end_bins_count = c;\n    }\n    *n = g_end_bins_count;\n    return g_end_bins;\n}\n}\n")
-    tables = ("variants_table.hip", "packed_table.hip", "packed_hist_table.hip", "end_bins_table.hip")
-    print(" ".join(os.path.basename(x) for x in files + [os.path.join(outdir, t) for t in tables]))
+    files, slices = [], []
+    for key, fn, stems in MENUS:
+        vs = fn(kind)
+        assert all(sum(v[0] in dtypes for _, dtypes in stems) == 1 for v in vs), key      # every kernel in one stem's units
+        slices.append(len(vs))
+        for stem, dtypes in stems:
+            files += write_units(outdir, [v for v in vs if v[0] in dtypes], per_file, stem)[0]
+    units = [os.path.basename(x)[:-len(".hip")] for x in files]
+    files.append(write_table(outdir, kind, slices, units))
+    print(" ".join(os.path.basename(x) for x in files))
 
 
 if __name__ == "__main__":

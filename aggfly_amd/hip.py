@@ -161,7 +161,7 @@ def device_count() -> int:
 
 def build_info() -> dict:
     """What the loaded build holds: {"menu": "full" | "arms" | "dev", "variants", "arms", "region_fused_twins", "abi", "packed_variants",
-    "packed_hist_variants", "end_bins_variants"} (`afhip_build_info`; the first three counts are of the float32 / float64 kernels, `packed_variants` of the general
+    "packed_hist_variants", "end_bins_variants"} (`afhip_build_info`: one count per kernel menu; the first three counts are of the float32 / float64 kernels, `packed_variants` of the general
     kernels for int16- / uint16-packed cubes, `packed_hist_variants` of their LDS-histogram kernels for equal-width bin plans,
     `end_bins_variants` of the histogram kernels, of every storage, for such plans with a wide or open-ended end bin)."""
     buf = C.create_string_buffer(256)

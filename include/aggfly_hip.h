@@ -71,7 +71,7 @@ const char* afhip_last_error(void);
 int afhip_abi_version(void);
 /* What this build of the library holds, as text into buf ("menu=full variants=426 arms=0 region_fused_twins=150 abi=4 packed_variants=69 packed_hist_variants=10 end_bins_variants=26");
  * returns the bytes needed.  menu: full = every kernel the planner can pick; arms = + the tuning arms a `tuning` hint can name (make
- * MENU=arms).  variants / arms / region_fused_twins count the float32 / float64 kernels, packed_variants the general kernels of AFHIP_I16 / AFHIP_U16 cubes,
+ * MENU=arms).  One count per kernel menu ("Kernel menus"): variants / arms / region_fused_twins count the float32 / float64 kernels, packed_variants the general kernels of AFHIP_I16 / AFHIP_U16 cubes,
  * packed_hist_variants their LDS-histogram kernels (plans of four or more contiguous equal-width strict bins), end_bins_variants the
  * LDS-histogram kernels of float32, float64 and packed cubes for such plans whose first and / or last bin is wider, or open-ended. */
 int afhip_build_info(char* buf, int buf_len);

@@ -2,7 +2,7 @@
 `variant_recipes`, `packed_recipes` and `packed_hist_recipes`: a run of equal-width strict bins between two end bins of another width —
 finite (the -99 / 99 of the reference's own documents) or open (-inf / inf) — as float32, float64 and int16-packed plans.
 
-Pure Python and numpy.  How a recipe selects its variant (afhip_planner.cpp: find_partition, choose_end_bins_variant): the storage by
+Pure Python and numpy.  How a recipe selects its variant (afhip_planner.cpp: find_partition, choose_hist_variant): the storage by
 the dtype; cells per lane by the row length (packed: even rows take two where the menu holds the form); stat tier by a mean column;
 `sl` by identity outers with one period per inner group; `arith` by lattice edges the edge fma reproduces exactly in the input
 precision (E0 + 5 k), the edge table by edges no float32 holds (-19.85 + 3.1 k); the `_ends` forms by the end bins, whose widths differ
@@ -26,10 +26,6 @@ INF = float("inf")
 # the outer limits of the packed recipes: values of stored integers inside the storage's range (-47.5 ... 63.8 C), so that the cube
 # holds values on them and beyond them
 P_LO, P_HI = pr._snap(-40.0), pr._snap(58.0)
-
-
-def end_bins_menu(kind="full"):
-    return list(vr.gen_variants().end_bins_menu(kind))
 
 
 def is_packed(dtype):

@@ -2,7 +2,7 @@
 `packed_recipes`: a partition of thirteen to sixteen contiguous equal-width strict bins, a mean column for the stat-1 kernels, an
 int16 cube around 12 C and the rule that unpacks it.
 
-Pure Python and numpy.  How a recipe selects its variant (afhip_planner.cpp: choose_packed_hist_variant): cells per lane by the row
+Pure Python and numpy.  How a recipe selects its variant (afhip_planner.cpp: choose_hist_variant): cells per lane by the row
 length (even: two, odd: one); stat tier by the mean column; `sl` by identity outers with one period per inner group; `arith` by
 edges the float32 edge fma reproduces exactly — E0 + 5 k, with E0 the VALUE of the stored integer nearest -20 C, so that at least
 that edge is met exactly by a stored integer — and the edge table by edges no float32 holds (-19.85 + 3.1 k).
@@ -20,10 +20,6 @@ import packed_recipes as pr
 import variant_recipes as vr
 
 N_BINS = {(0, 0): 13, (0, 1): 16, (1, 0): 14, (1, 1): 15}      # (stat, single level) -> bins; stat 1 adds a mean column (K <= 16)
-
-
-def packed_hist_menu(kind="full"):
-    return list(vr.gen_variants().packed_hist_menu(kind))
 
 
 def arith_edges(n, width=5.0, near=-20.0, pairs=pr.PAIRS):

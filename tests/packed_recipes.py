@@ -23,10 +23,6 @@ FILL = -32767
 PAIRS = [(0.0017, 281.3), (None, -273.15)]   # (multiply, add) in float32; None: that half is left out
 
 
-def packed_menu(kind="full"):
-    return list(vr.gen_variants().packed_menu(kind))
-
-
 def np_unpack(q, pairs=PAIRS, fill=FILL):
     """The unpack rule in numpy float32, one rounded operation at a time; NaN at the fill."""
     q = np.asarray(q, dtype=np.int16)

@@ -7,11 +7,10 @@ import numpy as np
 import pytest
 
 import end_bins_recipes as eb
-import packed_hist_recipes as ph
 import packed_recipes as pr
 import variant_recipes as vr
 
-FULL = eb.end_bins_menu("full")
+FULL = vr.menu_of("end_bins", "full")
 VARIANTS = [vr.variant(t) for t in FULL]
 
 
@@ -33,11 +32,11 @@ def test_menu_shape_and_names():
         assert all((v.vec, v.depth) == (1, depth) for v in VARIANTS if v.dtype == dtype)
     # packed: the production packed_hist_menu with the bit set, entry by entry
     packed = [t for t in FULL if t[0] == pr.I16]
-    assert [t[:7] + (t[7] & ~eb.EB,) for t in packed] == [t[:8] for t in ph.packed_hist_menu("full") if t[8]]
+    assert [t[:7] + (t[7] & ~eb.EB,) for t in packed] == [t[:8] for t in vr.menu_of("packed_hist", "full") if t[8]]
     assert sorted(v.vec for v in VARIANTS if v.dtype == pr.I16) == [1] * 8 + [2] * 2
     assert all(v.has(vr.SL) and not v.has(vr.HA) for v in VARIANTS if v.vec == 2)
     # no tuning arms; the dev menu has none of them
-    assert eb.end_bins_menu("arms") == FULL and eb.end_bins_menu("dev") == []
+    assert vr.menu_of("end_bins", "arms") == FULL and vr.menu_of("end_bins", "dev") == []
 
 
 def test_the_older_menus_keep_their_counts():
@@ -52,7 +51,7 @@ def test_build_info_counts_the_new_table():
     info = hip.build_info()
     kind = info["menu"]
     assert list(info)[-1] == "end_bins_variants"                        # appended at the end of the string
-    assert info["end_bins_variants"] == len(eb.end_bins_menu(kind))
+    assert info["end_bins_variants"] == len(vr.menu_of("end_bins", kind))
     assert info["variants"] == len(gv.menu(kind)) and info["packed_variants"] == len(gv.packed_menu(kind))
     assert info["packed_hist_variants"] == len(gv.packed_hist_menu(kind))
     if kind == "full":

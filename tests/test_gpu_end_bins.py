@@ -1,5 +1,5 @@
 """Bins plans with a wide or open-ended end bin on the LDS-histogram kernels with FEAT_END_BINS (gen_variants.py: end_bins_menu;
-afhip_planner.cpp: find_partition, choose_end_bins_variant): every kernel of the menu against the oracle, the partition shapes, the
+afhip_planner.cpp: find_partition, choose_hist_variant): every kernel of the menu against the oracle, the partition shapes, the
 plans that must not move, the A/B knob, multi-rule and uint16 packed cubes, and the whole pass up to the public route.
 
 Bin counts are integers and the compares are the contract's (L < v < U strictly, a value on an edge, NaN and a value on
@@ -32,15 +32,7 @@ pytestmark = pytest.mark.gpu
 INF = float("inf")
 
 
-def _menu_kind():
-    try:
-        from aggfly_amd import hip
-        return hip.build_info()["menu"]
-    except Exception:          # no library at collection time: the cases fail on their own
-        return "full"
-
-
-LOADED = eb.end_bins_menu(_menu_kind())
+LOADED = vr.menu_of("end_bins", vr.loaded_menu_kind())
 MENU = [vr.variant(t) for t in LOADED]
 BY_NAME = {v.name: v for v in MENU}
 ANY = vr.Variant("bins plan", pr.I16, 0, 1, 1, 16, 16, 8, 0)          # what _assert_cells reads of a variant: its name, not lean
@@ -50,10 +42,6 @@ STORAGES = {"f32": vr.F32, "f64": vr.F64, "i16": pr.I16}
 @pytest.fixture(autouse=True)
 def _no_knob(monkeypatch):
     monkeypatch.delenv("AFHIP_NO_END_BINS_HIST", raising=False)
-
-
-def _name(plan):
-    return plan.describe().split()[0][len("variant="):]
 
 
 def _run(torch_cuda, r, seed=0, data=None):
@@ -95,7 +83,7 @@ def test_end_bins_variant_against_the_oracle(torch_cuda, name):
     v = BY_NAME[name]
     r = eb.recipe(v)
     plan, got, want, values, q = _run(torch_cuda, r, seed=zlib.crc32(name.encode()))
-    assert _name(plan) == name, plan.describe()
+    assert vr.plan_name(plan) == name, plan.describe()
     if v.has(vr.SL):
         assert "packed-counts" in plan.describe() if v.stat == 0 else "packed-counts" not in plan.describe(), plan.describe()
     have = eb.planted(r, values, q)
@@ -159,7 +147,7 @@ def test_partition_shapes(torch_cuda, shape, storage):
     r = eb.make_recipe("", dtype, n_cells, bins, sl, False, seed=seed)          # (columns in an order shuffled per case)
     assert [c["inner_args"][:2] for c in r.columns] != sorted(c["inner_args"][:2] for c in r.columns)
     plan, got, want, values, q = _run(torch_cuda, r, seed)
-    name = _name(plan)
+    name = vr.plan_name(plan)
     vec = 2 if (eb.is_packed(dtype) and n_cells % 2 == 0 and sl and not arith) else 1
     assert name.startswith(f"{storage}_p0_v{vec}_s0_t16_k16_") and name.endswith("_ends") and "_hist" in name, plan.describe()
     assert ("_arith" in name) == arith and ("_sl_" in name) == sl, plan.describe()
@@ -178,7 +166,7 @@ def test_closed_partition_keeps_its_kernel(torch_cuda, storage):
     r = eb.make_recipe("", dtype, 1101 if eb.is_packed(dtype) else 60, bins, True, False)
     plan, got, want, values, _ = _run(torch_cuda, r, 3)
     depth = {"f32": 8, "f64": 4, "i16": 16}[storage]
-    assert _name(plan) == f"{storage}_p0_v1_s0_t16_k16_d{depth}_nt_ibins_sl_hist_arith", plan.describe()
+    assert vr.plan_name(plan) == f"{storage}_p0_v1_s0_t16_k16_d{depth}_nt_ibins_sl_hist_arith", plan.describe()
     _assert_counts(r, got, want, values, f"closed {storage}")
 
 
@@ -214,7 +202,7 @@ def test_other_plans_stay_off_the_histogram_route(torch_cuda, case, storage):
     else:
         r = vr.Recipe("", dtype, int(ib[-1]), 1102 if eb.is_packed(dtype) else 64, ib, ob, cols, True, 0, edges=es)
         plan, got, want, values, _ = _run(torch_cuda, r, seed)
-    name = _name(plan)
+    name = vr.plan_name(plan)
     assert "_hist" not in name and "_ends" not in name, plan.describe()
     if storage == "i16":
         assert name.startswith("i16_p0_v2_") and name.endswith("_nt") and "_ibins" not in name, plan.describe()
@@ -231,11 +219,11 @@ def test_knob_sends_the_plan_down_the_earlier_route_with_the_same_counts(torch_c
     r = eb.make_recipe("", dtype, 1102 if eb.is_packed(dtype) else 64, eb.with_ends(eb.lattice(dtype, 13), -INF, INF), single_level, mean)
     data = eb.stored_cube(r, 9) if eb.is_packed(dtype) else eb.cube_for(r, 9)
     plan, got, want, values, _ = _run(torch_cuda, r, data=data)
-    assert "_hist_arith_ends" in _name(plan) and ("_sl_" in _name(plan)) == single_level, plan.describe()
+    assert "_hist_arith_ends" in vr.plan_name(plan) and ("_sl_" in vr.plan_name(plan)) == single_level, plan.describe()
     monkeypatch.setenv("AFHIP_NO_END_BINS_HIST", "1")
     earlier, got_e, _, _, _ = _run(torch_cuda, r, data=data)
     monkeypatch.delenv("AFHIP_NO_END_BINS_HIST")
-    name = _name(earlier)
+    name = vr.plan_name(earlier)
     assert "_hist" not in name and "_ends" not in name, earlier.describe()
     if storage == "i16":
         assert name == f"i16_p0_v2_s{int(mean)}_t16_k16_d16_nt" and "packed-counts" not in earlier.describe(), earlier.describe()
@@ -266,7 +254,7 @@ def test_rule_changes_wherever_they_can_fall(torch_cuda, n_cells, form, single_l
     plan.bind_packing(cube)
     d = plan.describe()
     vec = 2 if (n_cells % 2 == 0 and single_level and form == "table") else 1
-    name = _name(plan)
+    name = vr.plan_name(plan)
     assert name.startswith(f"i16_p0_v{vec}_s{0 if single_level else 1}_t16_k16_") and name.endswith("_ends"), d
     assert ("_arith" in name) == (form == "arith") and ("_sl_" in name) == single_level, d
     got = plan.run_temporal(cube).cpu().numpy()
@@ -309,8 +297,9 @@ def test_uint16_storage_takes_the_same_kernels(torch_cuda, form):
         plan.bind_packing(c)
         plans[code] = plan
     pu = plans[hip.U16]
-    assert _name(pu) == _name(plans[hip.I16]) and _name(pu).startswith("i16_") and _name(pu).endswith("_ends"), pu.describe()
-    assert "_sl_hist" in _name(pu) and ("_arith" in _name(pu)) == (form == "arith"), pu.describe()
+    name = vr.plan_name(pu)
+    assert name == vr.plan_name(plans[hip.I16]) and name.startswith("i16_") and name.endswith("_ends"), pu.describe()
+    assert "_sl_hist" in name and ("_arith" in name) == (form == "arith"), pu.describe()
     assert "storage=uint16" in pu.describe() and "storage=int16" in plans[hip.I16].describe()
     values = uns.np_unpack(q, pairs, fill)
     assert (q > 32767).mean() > 0.4 and np.isnan(values).sum() == (q == fill).sum() > 2 * T
@@ -338,7 +327,7 @@ def test_whole_pass_direct_gather_and_cell_major_panel_agree(torch_cuda, storage
     plan = hip.FusedPlan(r.T, r.n_cells, hip.I16 if eb.is_packed(dtype) else dtype, r.inner_bounds, r.outer_bounds, r.columns, exact_order=True)
     if eb.is_packed(dtype):
         plan.bind_packing(d)
-    assert _name(plan).endswith("_sl_hist_arith_ends") and "packed-counts" in plan.describe(), plan.describe()
+    assert vr.plan_name(plan).endswith("_sl_hist_arith_ends") and "packed-counts" in plan.describe(), plan.describe()
     tab = _csr_table(r.n_cells, seed=5)
     csr = hip.CSR(tab["index_right"].to_numpy(), tab["cell_id"].to_numpy(), tab["weight"].to_numpy(), int(tab["index_right"].max()) + 1, r.n_cells)
     direct = plan.run(d, csr, want_cells=False)

@@ -27,15 +27,7 @@ pytestmark = pytest.mark.gpu
 FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hdf5")
 
 
-def _menu_kind():
-    try:
-        from aggfly_amd import hip
-        return hip.build_info()["menu"]
-    except Exception:          # no library at collection time: the cases fail on their own
-        return "full"
-
-
-MENU = [vr.variant(v) for v in pr.packed_menu(_menu_kind())]
+MENU = [vr.variant(v) for v in vr.menu_of("packed", vr.loaded_menu_kind())]
 BY_NAME = {v.name: v for v in MENU}
 
 

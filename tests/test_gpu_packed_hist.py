@@ -1,5 +1,5 @@
 """Packed cubes' bins plans on the LDS-histogram kernels (gen_variants.py: packed_hist_menu; afhip_planner.cpp:
-choose_packed_hist_variant): every kernel of the menu against the oracle, the edge-table form, the plans that must stay on the general
+choose_hist_variant): every kernel of the menu against the oracle, the edge-table form, the plans that must stay on the general
 packed kernels, the A/B knob, rule changes wherever they can fall, uint16 storage, and the public route.
 
 Bin counts are integers far below 2^53 and the compares are the contract's (a float32 value against the float32
@@ -31,22 +31,10 @@ from test_gpu_variant_menu import _assert_cells, _oracle_two_level
 pytestmark = pytest.mark.gpu
 
 
-def _menu_kind():
-    try:
-        from aggfly_amd import hip
-        return hip.build_info()["menu"]
-    except Exception:          # no library at collection time: the cases fail on their own
-        return "full"
-
-
-LOADED = ph.packed_hist_menu(_menu_kind())
+LOADED = vr.menu_of("packed_hist", vr.loaded_menu_kind())
 MENU = [vr.variant(t) for t in LOADED if t[8]]          # the production kernels: what the planner picks by its own rule
 BY_NAME = {v.name: v for v in MENU}
 ANY = vr.Variant("packed bins plan", pr.I16, 0, 1, 1, 16, 16, 8, 0)          # what _assert_cells reads of a variant: its name, not lean
-
-
-def _name(plan):
-    return plan.describe().split()[0][len("variant="):]
 
 
 def _vec(n_cells, single_level, arith):
@@ -61,7 +49,7 @@ def test_packed_hist_variant_against_the_oracle(torch_cuda, name):
     r = ph.recipe(v)
     q = ph.stored_cube(r, seed=zlib.crc32(name.encode()))
     plan, got, want, values = _run_recipe(torch_cuda, r, q)
-    assert _name(plan) == name and "storage=int16" in plan.describe(), plan.describe()
+    assert vr.plan_name(plan) == name and "storage=int16" in plan.describe(), plan.describe()
     if v.has(vr.SL):
         assert "packed-counts" in plan.describe() if v.stat == 0 else "packed-counts" not in plan.describe(), plan.describe()
     # the data: stored integers on an edge (arithmetic plans), next to every edge, in both guard bins, the extremes, whole groups of fills
@@ -101,7 +89,7 @@ def test_inexact_edges_take_the_table_form(torch_cuda, n_cells, single_level):
     lo, hi = pr.stored_near(-0.1), pr.stored_near(1.6)       # a tenth of the cube inside and around the fourteen bins
     q[::3, 7::11] = np.random.default_rng(n_cells).integers(lo, hi, q[::3, 7::11].shape).astype(np.int16)
     plan, got, want, values = _run_recipe(torch_cuda, r, q)
-    name = _name(plan)
+    name = vr.plan_name(plan)
     assert name.startswith(f"i16_p0_v{vec}_s0_") and "_hist" in name and "_arith" not in name and ("_sl_" in name) == single_level, plan.describe()
     assert all(((values > np.float32(a)) & (values < np.float32(b))).sum() > 50 for a, b in zip(edges[:-1], edges[1:]))   # every bin is met
     for k in range(len(r.columns)):
@@ -139,7 +127,7 @@ def test_other_plans_stay_on_the_general_kernels(torch_cuda, case):
         pairs = [(2.0 ** -14, 300.0)]                      # values 300 + q / 16384, exact in float32: one stored integer per bin
         q[::5, ::9] = np.random.default_rng(1).integers(-2, 9, q[::5, ::9].shape).astype(np.int16)
     plan, got, want, values = _run_recipe(torch_cuda, r, q, pairs=pairs)
-    name = _name(plan)
+    name = vr.plan_name(plan)
     assert name.startswith("i16_p0_v2_") and name.endswith("_nt") and "_hist" not in name and "_ibins" not in name, plan.describe()
     if case == "too_narrow_for_the_guess":
         assert sum(np.nansum(want[k]) for k in range(len(cols))) > 100
@@ -153,18 +141,18 @@ def test_knob_sends_the_plan_to_the_general_kernel_with_the_same_bits(torch_cuda
     from aggfly_amd import hip
     r, q = _plan_case(1102, ph.arith_edges(13), single_level, mean)
     plan, got, want, _ = _run_recipe(torch_cuda, r, q)
-    assert "_hist_arith" in _name(plan) and ("_sl_" in _name(plan)) == single_level, plan.describe()
+    assert "_hist_arith" in vr.plan_name(plan) and ("_sl_" in vr.plan_name(plan)) == single_level, plan.describe()
     monkeypatch.setenv("AFHIP_NO_PACKED_HIST", "1")
     general, got_g, _, _ = _run_recipe(torch_cuda, r, q)
     monkeypatch.delenv("AFHIP_NO_PACKED_HIST")
     tier = f"i16_p0_v2_s{int(mean)}_t16_k16_d16_nt"
-    assert _name(general) == tier and "packed-counts" not in general.describe(), general.describe()
+    assert vr.plan_name(general) == tier and "packed-counts" not in general.describe(), general.describe()
     assert got.dtype == got_g.dtype == np.float64
     np.testing.assert_array_equal(got, got_g)              # bit for bit (counts and means; NaN where the other has NaN)
     _assert_cells(ANY, r.columns, got, want)
     # ... and so does the float32 route on the unpacked values (the single-level LDS-histogram kernel of the float menu)
     f32 = hip.FusedPlan(r.T, r.n_cells, hip.F32, r.inner_bounds, r.outer_bounds, r.columns, exact_order=True)
-    assert "_hist" in _name(f32), f32.describe()
+    assert "_hist" in vr.plan_name(f32), f32.describe()
     vals = torch_cuda.from_numpy(pr.np_unpack(q).reshape(r.T, 1, r.n_cells)).cuda()
     np.testing.assert_array_equal(f32.run_temporal(vals).cpu().numpy(), got)
 
@@ -215,7 +203,7 @@ def test_rule_changes_wherever_they_can_fall(torch_cuda, n_cells, form, single_l
     plan.bind_packing(cube)
     d = plan.describe()
     want_name = f"i16_p0_v{_vec(n_cells, single_level, form == 'arith')}_s{0 if single_level else 1}_t16_k16_"
-    assert _name(plan).startswith(want_name) and "_hist" in d and ("_arith" in d) == (form == "arith") and ("_sl_" in d) == single_level, d
+    assert vr.plan_name(plan).startswith(want_name) and "_hist" in d and ("_arith" in d) == (form == "arith") and ("_sl_" in d) == single_level, d
     # three chunks and more, all of one length that divides 192 and 240: rules change at chunk starts, and chunks start inside rules
     n_chunks, lo, hi = (int(x) for x in re.search(r"chunks=(\d+) \(steps (\d+)\.\.(\d+)\)", d).groups())
     assert n_chunks >= 3 and lo == hi == T5 // n_chunks and 192 % lo == 0 and (240 % lo == 0 or not single_level), d
@@ -255,7 +243,8 @@ def test_uint16_storage_takes_the_same_kernels(torch_cuda, form):
         plan.bind_packing(c)
         plans[code] = plan
     pu = plans[hip.U16]
-    assert _name(pu) == _name(plans[hip.I16]) and "_sl_hist" in _name(pu) and ("_arith" in _name(pu)) == (form == "arith"), pu.describe()
+    name = vr.plan_name(pu)
+    assert name == vr.plan_name(plans[hip.I16]) and "_sl_hist" in name and ("_arith" in name) == (form == "arith"), pu.describe()
     assert "storage=uint16" in pu.describe() and "storage=int16" in plans[hip.I16].describe()
     values = uns.np_unpack(q, pairs, fill)
     assert (q > 32767).mean() > 0.4 and np.isnan(values).sum() == (q == fill).sum() > 2 * T

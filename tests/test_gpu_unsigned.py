@@ -201,7 +201,7 @@ def _heavy_vec(n_cells):
     """Cells per lane of the stat-3, sixteen-slot, sixteen-column kernel the loaded menu holds for a row length (the widest that
     divides it: the packed menu leaves the two-cell form of this shape out, so even rows take one cell per lane too)."""
     from aggfly_amd import hip
-    menu = [vr.variant(v) for v in pr.packed_menu(hip.build_info()["menu"])]
+    menu = [vr.variant(v) for v in vr.menu_of("packed", hip.build_info()["menu"])]
     return max(v.vec for v in menu if (v.stat, v.nthr, v.kmax) == (3, 16, 16) and n_cells % v.vec == 0)
 
 

@@ -25,15 +25,7 @@ from oracle import cport
 pytestmark = pytest.mark.gpu
 
 
-def _menu_kind():
-    try:
-        from aggfly_amd import hip
-        return hip.build_info()["menu"]
-    except Exception:          # no library at collection time: the cases fail on their own, in torch_cuda / FusedPlan
-        return "full"
-
-
-MENU = [vr.variant(v) for v in vr.production_menu(_menu_kind())]
+MENU = [vr.variant(v) for v in vr.production_menu(vr.loaded_menu_kind())]
 BY_NAME = {v.name: v for v in MENU}
 
 

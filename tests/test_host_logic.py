@@ -491,8 +491,8 @@ def test_kernel_menu_shape():
     """The production menu (`make`) holds no tuning arm, every region-fused twin has its plain variant beside it (same fields, FEAT bit
     11 apart), twins exist only for direct-load two-level forms of at most six columns and four slots, the three-row (8-hourly) forms are
     lean short-group forms with depth 6; `MENU=arms` adds the arms and nothing else; the loaded library reports the menu it was built from."""
-    sys.path.insert(0, os.path.join(ROOT, "aggfly_amd", "csrc"))
-    import gen_variants as gv
+    import variant_recipes as vr
+    gv = vr.gen_variants()
     full, arms = gv.menu("full"), gv.menu("arms")
     assert all(v[8] for v in full) and sum(1 for v in arms if not v[8]) == len(arms) - len(full) > 0
     assert set(full) <= set(arms)

@@ -33,7 +33,7 @@ def test_packed_hist_menu_shape_and_build_info():
 
 
 def test_recipes_are_partitions_with_the_data_on_their_edges():
-    for t in ph.packed_hist_menu("full"):
+    for t in vr.menu_of("packed_hist", "full"):
         v = vr.variant(t)
         r = ph.recipe(v)
         bins = [c for c in r.columns if c["inner"] == "bins"]

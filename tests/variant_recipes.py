@@ -48,9 +48,29 @@ NT, TKI, SL, HB, HA, PAIR, LEAN, SS2 = _F.NT, _F.INT_BINS, _F.SINGLE_LEVEL, _F.H
 QUAD, RF, TRI, RAG = _F.FOUR_ROW, _F.REGION_FUSED, _F.THREE_ROW, _F.MIXED
 
 
+def menu_of(key, kind="full"):
+    """The tuples of the kernel menu `key` (gen_variants.py: MENUS — "float", "packed", "packed_hist", "end_bins") of the build `kind`
+    ("full" / "arms" / "dev"), in table order."""
+    return list({k: fn for k, fn, _ in gen_variants().MENUS}[key](kind))
+
+
 def production_menu(kind="full"):
-    """The production entries of the menu `kind` ("full" / "arms" / "dev"), in table order."""
-    return [v for v in gen_variants().menu(kind) if v[8]]
+    """The production entries of the float menu of `kind`, in table order."""
+    return [v for v in menu_of("float", kind) if v[8]]
+
+
+def loaded_menu_kind():
+    """The menu kind of the library the tests load (collection time: the parametrised cases are one per kernel of that build)."""
+    try:
+        from aggfly_amd import hip
+        return hip.build_info()["menu"]
+    except Exception:          # no library at collection time: the cases fail on their own, in torch_cuda / FusedPlan
+        return "full"
+
+
+def plan_name(plan):
+    """The name of the kernel variant a FusedPlan landed on."""
+    return plan.describe().split()[0][len("variant="):]
 
 
 @dataclass
