@@ -455,6 +455,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
                 s[i] += v;
                 mn[i] = __builtin_fmin(mn[i], v);   // minNum/maxNum skip a NaN like the reference's
                 mx[i] = __builtin_fmax(mx[i], v);   // "v < mn" / "v > mx" updates: one VALU op each
+                // (zeros of both signs: v_min / v_max order -0 < +0 where the reference keeps the first seen — the one rule of its
+                // own, DESIGN.md §5, pinned by tests/test_gpu_special_values.py)
             } else if (STAT == 3) {
                 s[i] += isn ? 0.0 : v;
                 cnt[i] += isn ? 0 : 1;
@@ -763,7 +765,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
                 } else {
                     const double rng = mx[i] - mn[i], alpha = rng * 0.5;
                     double inv_rng = 0.0;
-                    if (in0 || in1) inv_rng = rcp_newton1(rng);
+                    if (in0 || in1) inv_rng = rcp_range(rng);
                     if (co.skind == 0) {
                         KEEP_BRANCH();
                         xv = sine_cool(co.s0, co.s0x2, in0, mn[i], mx[i], tavg, alpha, inv_rng, sine_tab)
@@ -854,7 +856,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
                                     }
                                 }
 #pragma unroll
-                                for (int i = 0; i < VEC; ++i) os[j][i] += hi[i] + lo[i];
+                                for (int i = 0; i < VEC; ++i) os[j][i] += powi_finish(hi[i], lo[i]);      // (an overflowed power adds +-inf, not NaN)
                                 asm volatile("; leaf: x^n, n >= 3");          // (distinct tails: the leaves are not merged back)
                             } else {
 #pragma unroll

@@ -15,6 +15,23 @@ __device__ __forceinline__ double inf64() { return __longlong_as_double(0x7ff000
 // A volatile empty asm cannot be speculated, so a block that starts with it stays behind its branch.
 #define KEEP_BRANCH() asm volatile("")
 
+// min(max(x, -2^1023), 2^1023) IN PLACE: NaN and +-inf become finite (v_max returns its other operand for a NaN), every |x| <= 2^1023
+// stays as it is.  The bound is built in VCC inside the block — a constant kept in a scalar register pair across the time loop cost
+// the kernels two SGPRs and thirteen of them 34 more scalar spills — so: no new VGPR, no new SGPR, two SALU + two VALU.
+__device__ __forceinline__ double clamp_finite(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("s_mov_b32 vcc_lo, 0\n\ts_mov_b32 vcc_hi, 0x7fe00000\n\tv_max_f64 %0, %0, -vcc\n\tv_min_f64 %0, %0, vcc" : "+v"(x) : : "vcc");
+    return x;
+#else
+    return x != x ? -0x1p1023 : (x > 0x1p1023 ? 0x1p1023 : (x < -0x1p1023 ? -0x1p1023 : x));
+#endif
+}
+// The last step of powi_dd_vec's chain (below), hi + lo — but once the product has overflowed, the error term is no error of anything: hi = +-inf comes with
+// lo = fma(inf, x, -inf) = NaN or an infinity of the other sign, and hi + lo would be NaN where np.power gives +-inf.  The term is
+// made finite in place (inf + finite = inf).  (A v_cmp_class on hi and a select — between hi and hi + lo, or on lo — kept two more
+// VGPRs alive in 343 / 441 of the 529 kernels and cost 18 / 36 of them a wave per SIMD; profiles/special_values.txt.)
+__device__ __forceinline__ double powi_finish(double hi, double lo) { return hi + clamp_finite(lo); }
+
 // x**e for a small integer e, evaluated as a double-double product chain so that the
 // result is the correctly rounded power in all but ~1e-14 of cases — what libm's pow()
 // behind np.power (dataset.py:543) returns.  Plain repeated multiplication differs from
@@ -25,7 +42,10 @@ __device__ __forceinline__ double inf64() { return __longlong_as_double(0x7ff000
 // (one fma) and the small term rounded once (a second fma) — |lo| stays within a few ulps of hi for every exponent lowered to this
 // form (|e| <= 64), so its rounding errors are of order 2^-106 and only the final hi + lo rounds at 2^-53.  Three instructions per
 // step, two for the first (lo = 0), instead of the six of a renormalising step: x^3 6 instructions, x^4 9 (were 13 and 19).
-template <int N, bool NEG = true>
+// ZERO_SIGN (k_transform, held to np.power's signed zeros): a power that underflows is the +-0 of its product chain — hi — where
+// hi + lo may be -0 + +0 = +0; the fused kernels leave it (their power columns are held by value: an outer sum starts at +0.0 and
+// loses the sign anyway).
+template <int N, bool NEG = true, bool ZERO_SIGN = false>
 __device__ __forceinline__ void powi_dd_vec(double (&x)[N], int e) {
     if (e == 0) {
 #pragma unroll
@@ -57,7 +77,11 @@ __device__ __forceinline__ void powi_dd_vec(double (&x)[N], int e) {
             for (int it = 4; it < n; ++it) step();
         }
 #pragma unroll
-        for (int i = 0; i < N; ++i) x[i] = hi[i] + lo[i];
+        for (int i = 0; i < N; ++i) x[i] = powi_finish(hi[i], lo[i]);
+        if constexpr (ZERO_SIGN) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) x[i] = (x[i] == 0.0) ? hi[i] : x[i];
+        }
     }
     if constexpr (NEG) {                // (the lean short-group forms take non-negative exponents only: no division code in them)
         if (e < 0) {
@@ -81,6 +105,20 @@ __device__ __forceinline__ double rcp_newton1(double x) {
     const double y = __builtin_amdgcn_rcp(x);
     const double e = __fma_rn(-x, y, 1.0);
     return __fma_rn(y, e, y);
+}
+// rcp_newton1 for a window's range: a SUBNORMAL range (a window of +- the smallest subnormals: below 2^-1022) has no finite
+// reciprocal seed — v_rcp_f64 gives inf, the Newton step NaN, and sine_dd was NaN where the reference's division gives a value
+// of the order of the range.  min(., 2^1022) leaves the reciprocal of every normal range as it is (<= 2^1022; doubled for the
+// heating form it stays finite) and takes inf / NaN to 2^1022: the quotient z then keeps its sign and |z| <= 1, so the arc is
+// finite and, like the exact one, below four times the range (< 9e-308) in size.  One v_min_f64, the bound built in VCC (clamp_finite).
+__device__ __forceinline__ double rcp_range(double x) {
+    double y = rcp_newton1(x);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("s_mov_b32 vcc_lo, 0\n\ts_mov_b32 vcc_hi, 0x7fd00000\n\tv_min_f64 %0, %0, vcc" : "+v"(y) : : "vcc");
+#else
+    y = (y < 0x1p1022) ? y : 0x1p1022;
+#endif
+    return y;
 }
 // a / b given y ~ 1/b (Markstein): q0 = a*y, r = a - b*q0 exactly (fma), q = q0 + r*y.  With y the
 // CORRECTLY rounded reciprocal (the host's 1.0/n for a group length n) q is the correctly rounded

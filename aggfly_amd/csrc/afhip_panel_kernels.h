@@ -751,7 +751,7 @@ __global__ __launch_bounds__(WG) void k_transform(const TransformArgs a) {
     }
     const bool all_f32 = a.x_f32 && a.out_f32;
     if (a.tf == TF_POWI) {
-        powi_dd_vec<TRANSFORM_PER_THREAD>(v, a.iarg);
+        powi_dd_vec<TRANSFORM_PER_THREAD, true, true>(v, a.iarg);       // signed zeros as np.power's
     } else if (a.tf == TF_POW) {
 #pragma unroll
         for (int u = 0; u < TRANSFORM_PER_THREAD; ++u) v[u] = pow(v[u], a.arg);

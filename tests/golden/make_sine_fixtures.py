@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/sine_dd_fixtures.json: known answers for sine-interpolated degree days at 50 digits.
+"""Generates tests/golden/sine_dd_fixtures.json and sine_dd_fixtures_degenerate.json: known answers for sine-interpolated degree days at 50 digits.
 
     python tests/golden/make_sine_fixtures.py          (build container: needs mpmath, which the GPU box need not have)
 
@@ -19,6 +19,9 @@ bound it achieves.  Cases:
   * windows of 2 rows ((tmin, tmax) pairs: BASELINE configs[4]), 4 rows (6-hourly) and 6 rows (generic group end);
   * thresholds far outside, at the edges, and inside the window; thresholds within 1e-3 ... 1e-9 of the window's range
     from either edge (where acos / sqrt(1 - r^2) lose digits: the cases that decide which side carries an error);
+  * degenerate windows, in sine_dd_fixtures_degenerate.json: flat windows of 1-5 rows at, above and below each threshold, windows whose extremes
+    are attained twice, zeros of both signs around the [0, 5] row, and windows of 3 and 5 rows (the three-row and mixed-length
+    forms, the generic group end) with the threshold at tmin, tmax, the mean and strictly inside;
   * `f32_ok` cases have float32-representable windows and run on float32 cubes too.
 """
 import json
@@ -126,12 +129,57 @@ def main():
                         inner = rng.uniform(tmin, tmax, L - 2)
                         w = np.concatenate([[tmin], inner, [tmax]])
                         add(w[rng.permutation(L)] if L > 2 else w, row, False, f"threshold {delta:.1e} * rng inside {'tmin' if side == 0 else 'tmax'}")
-    out = {"about": "sine_dd known answers at 50 digits; generated by tests/golden/make_sine_fixtures.py (mpmath), closed forms of "
-                    "aggfly/aggregate/nb_kernels.py:202-251 on the exact values of the inputs; value = null: the reference gives NaN (|r| > 1)",
-           "ddargs": DDARGS, "cases": cases}
+    n_main = len(cases)
+    # 4. degenerate windows, kept in a file of their own, one case per line (no random draws: the stream of sections 1-3 is left as it was, and their cases stay the first ones):
+    #    flat windows at, above and below each threshold (1-5 rows; a one-row window is always flat), windows whose minimum and
+    #    maximum are attained twice, zeros of both signs around the [0, 5] row, and windows of 3 and 5 rows — the three-row and
+    #    mixed-length forms, the generic group end — with the threshold at tmin, at tmax, at the mean and strictly inside
+    is32 = lambda w: all(float(np.float32(x)) == float(x) for x in w)
+    add_plain = add
+
+    def add(w, row, f32_ok, tag):
+        """A threshold that lies within 1e-2 of the range inside an edge (the 18.3 / 18.3000001 row on a window that starts at 18.3)
+        makes the case one of section 3's kind: tagged like them, so that the tests read it against the near-edge figures."""
+        lo, hi = min(w), max(w)
+        for thr in DDARGS[row][:2]:
+            if lo < thr < hi and min(thr - lo, hi - thr) < 1e-2 * (hi - lo):
+                side = "tmin" if thr - lo < hi - thr else "tmax"
+                tag += f"; threshold {min(thr - lo, hi - thr) / (hi - lo):.1e} * rng inside {side}"
+                break
+        add_plain(w, row, f32_ok, tag)
+
+    for row, (t0, t1, _k) in enumerate(DDARGS):
+        for thr in (t0, t1):
+            for L in (1, 2, 3, 4, 5):
+                for off in (0.0, 2.5, -2.5):
+                    w = [thr + off] * L
+                    add(w, row, is32(w), f"flat L={L}")
+            for lo, hi, what in ((thr, thr + 7.0, "threshold == tmin"), (thr - 7.0, thr, "threshold == tmax"), (thr - 3.0, thr + 4.0, "threshold inside")):
+                mid = lo + 2.25
+                for w in ([lo, hi, hi], [hi, lo, lo], [lo, hi, hi, lo], [hi, lo, mid, lo, hi], [lo, hi, mid, mid + 1.5, hi, lo]):
+                    add(w, row, is32(w), f"extremes twice, {what}, L={len(w)}")
+            for w, what in (([thr, thr + 2.0, thr + 7.0], "threshold == tmin"), ([thr - 7.0, thr, thr - 1.5], "threshold == tmax"),
+                            ([thr - 3.0, thr + 4.0, thr - 1.0], "threshold == mean"), ([thr + 5.5, thr - 2.0, thr + 0.75], "threshold inside"),
+                            ([thr + 2.0, thr, thr + 7.0, thr + 3.25, thr + 1.0], "threshold == tmin"),
+                            ([thr - 1.0, thr - 7.0, thr - 3.25, thr, thr - 2.0], "threshold == tmax"),
+                            ([thr - 3.0, thr + 4.0, thr - 1.0, thr + 1.5, thr - 1.5], "threshold == mean"),
+                            ([thr + 5.5, thr - 2.0, thr + 0.75, thr - 0.5, thr + 3.0], "threshold inside")):
+                add(w, row, is32(w), f"{what}, L={len(w)}")
+    zrow = DDARGS.index([0.0, 5.0, 0.0])
+    for w in ([0.0, -0.0], [-0.0, 0.0], [-0.0], [0.0, -0.0, 0.0], [-0.0, 0.0, -0.0, 0.0], [-0.0, -0.0, -0.0, -0.0, -0.0],
+              [-0.0, 5.0], [5.0, -0.0], [0.0, 5.0], [-0.0, 2.0], [-2.0, -0.0], [2.0, -0.0, 0.0], [-0.0, 7.0, 0.0, 3.0]):
+        add(w, zrow, True, f"zeros of both signs, L={len(w)}")
+    about = ("sine_dd known answers at 50 digits; generated by tests/golden/make_sine_fixtures.py (mpmath), closed forms of "
+             "aggfly/aggregate/nb_kernels.py:202-251 on the exact values of the inputs; value = null: the reference gives NaN (|r| > 1)")
     path = os.path.join(HERE, "sine_dd_fixtures.json")
     with open(path, "w") as f:
-        json.dump(out, f, separators=(",", ":"))
+        json.dump({"about": about, "ddargs": DDARGS, "cases": cases[:n_main]}, f, separators=(",", ":"))
+    extra = os.path.join(HERE, "sine_dd_fixtures_degenerate.json")          # same ddargs rows; a case per line, so that a change shows as lines
+    with open(extra, "w") as f:
+        f.write('{"about":' + json.dumps(about + "; section 4: degenerate windows") + ',"ddargs":' + json.dumps(DDARGS, separators=(",", ":")) + ',"cases":[\n')
+        f.write(",\n".join(json.dumps(c, separators=(",", ":")) for c in cases[n_main:]))
+        f.write("\n]}\n")
+    print(f"{len(cases) - n_main} degenerate cases -> {extra} ({os.path.getsize(extra) >> 10} KiB)")
     tags = {}
     for c in cases:
         k = c["tag"].split(" * ")[-1] if c["tag"].startswith("threshold ") and "*" in c["tag"] else c["tag"]
