@@ -315,6 +315,7 @@ struct afhip_plan : PlanLayout {             // what the planner made (afhip_pla
     DevBuf<int64_t> d_gtab;
     DevBuf<ChunkDesc> d_chunks;
     DevBuf<int32_t> d_slot_ptr;
+    DevBuf<uint8_t> d_cmap;                 // the cell map of a FEAT_CELL_MAP plan (256 bytes; FusedArgs::hb_cmap)
     // workspace
     void* own_ws = nullptr;                 // plan-owned scratch (callers that hand no workspace): grown by a new hipMalloc, the
     int64_t own_ws_bytes = 0;               // outgrown block is `retired` until the plan is destroyed — no hipFree (a device-wide
@@ -364,6 +365,17 @@ extern "C" int afhip_build_info(char* buf, int buf_len) {
                              variants_menu(), n, arms, rf, AFHIP_ABI_VERSION, count[MENU_PACKED], count[MENU_PACKED_HIST], count[MENU_END_BINS]);
     if (buf && buf_len > 0) snprintf(buf, buf_len, "%s", tmp);
     return len + 1;
+}
+
+// the menus by their keys in gen_variants.py's MENUS
+extern "C" int afhip_menu_size(const char* key) {
+    for (int m = 0; key && m < MENU_COUNT; ++m) {
+        if (strcmp(key, menu_key((Menu)m)) != 0) continue;
+        int n = 0;
+        (void)menu_table((Menu)m, &n);
+        return n;
+    }
+    return -1;
 }
 
 extern "C" int afhip_device_count(void) {
@@ -826,7 +838,8 @@ extern "C" int afhip_plan_create(const afhip_plan_desc* desc, afhip_plan** out) 
     dev.resident_wgs = resident_wgs_per_cu;
     int rc;
     if ((rc = build_plan(desc, dev, pl)) || (rc = pl->d_ob.upload(pl->ob)) || (rc = pl->d_gtab.upload(pl->gtab)) ||
-        (rc = pl->d_chunks.upload(pl->chunks)) || (rc = pl->d_slot_ptr.upload(pl->slot_ptr))) {
+        (rc = pl->d_chunks.upload(pl->chunks)) || (rc = pl->d_slot_ptr.upload(pl->slot_ptr)) ||
+        (pl->hb_cells > 0 && (rc = pl->d_cmap.upload(std::vector<uint8_t>(pl->hb_cmap, pl->hb_cmap + sizeof pl->hb_cmap))))) {
         delete pl;
         return rc;
     }
@@ -995,13 +1008,14 @@ extern "C" int afhip_plan_describe(const afhip_plan* plan, char* buf, int buf_le
     if (!plan) return 0;
     int64_t min_len = INT64_MAX, max_len = 0;
     for (auto& c : plan->chunks) { min_len = std::min(min_len, c.k_hi - c.k_lo); max_len = std::max(max_len, c.k_hi - c.k_lo); }
-    char tmp[1024], cg[48] = "";
+    char tmp[1024], cg[48] = "", cm[24] = "";
+    if (feat_has(plan->variant->feat, FEAT_CELL_MAP)) snprintf(cm, sizeof cm, " cells=%d", plan->hb_cells);
     if (plan->last_counts_lanes > 0) snprintf(cg, sizeof cg, " last-run=count-gather/%d-lane", plan->last_counts_lanes);
     int n = snprintf(tmp, sizeof tmp,
-                     "variant=%s pipe=%d vec=%d stat=%d slots=%d kmax=%d depth=%d | T=%lld cells=%lld K=%d G1=%lld P=%lld | "
+                     "variant=%s pipe=%d vec=%d stat=%d slots=%d kmax=%d depth=%d%s | T=%lld cells=%lld K=%d G1=%lld P=%lld | "
                      "wg=%d tiles=%lld chunks=%zu (steps %lld..%lld) out_slots=%lld%s%s | workspace=%.1f MiB%s%s",
                      plan->variant->name, plan->variant->pipe, plan->variant->vec, plan->variant->stat, plan->variant->nthr,
-                     plan->variant->kmax, plan->variant->depth, (long long)plan->desc.T, (long long)plan->desc.n_cells,
+                     plan->variant->kmax, plan->variant->depth, cm, (long long)plan->desc.T, (long long)plan->desc.n_cells,
                      plan->K, (long long)plan->desc.G1, (long long)plan->desc.P, plan->wg, (long long)plan->tiles, plan->chunks.size(),
                      (long long)(plan->chunks.empty() ? 0 : min_len), (long long)max_len, (long long)plan->n_slots,
                      plan->packed ? (plan->pk.nw == 2 ? " packed-counts16" : " packed-counts32")
@@ -1095,7 +1109,8 @@ static int launch_temporal(afhip_plan* pl, const void* cube, double* partial, hi
             fa.hb_dn[k] = (double)f > t ? std::nextafterf(f, -INFINITY) : f;     // largest float <= t
             fa.hb_up[k] = (double)f < t ? std::nextafterf(f, INFINITY) : f;      // smallest float >= t
         }
-        fa.hb_w = pl->hb_w; fa.hb_lo0 = pl->hb_lo0; fa.hb_gl = pl->hb_gl; fa.hb_gh = pl->hb_gh;
+        if (feat_has(pl->variant->feat, FEAT_CELL_MAP)) { fa.hb_cmap = pl->d_cmap.p; fa.hb_cells = pl->hb_cells; }      // (shares the bytes of the next four)
+        else { fa.hb_w = pl->hb_w; fa.hb_lo0 = pl->hb_lo0; fa.hb_gl = pl->hb_gl; fa.hb_gh = pl->hb_gh; }
         fa.hb_wf = (float)pl->hb_w; fa.hb_lo0f = (float)pl->hb_lo0; fa.hb_glf = (float)pl->hb_gl; fa.hb_ghf = (float)pl->hb_gh;
         fa.hb_c0b = pl->hb_c0b; fa.hb_c0bf = (float)pl->hb_c0b;
         // wide end bins (FEAT_END_BINS): the slots whose thr[] entries hold the outer limits L (t0 / t0f) and U (t1 / t1f)

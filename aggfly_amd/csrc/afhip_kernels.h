@@ -81,7 +81,17 @@ struct FusedArgs {
     int32_t pk_nw;
     uint32_t pk_mask;
     uint8_t pk_word[MAX_COLS], pk_shift[MAX_COLS];
-    double hb_w, hb_lo0, hb_gl, hb_gh;
+    // The cell map (FEAT_CELL_MAP: interior bins of unequal widths) shares the bytes of the arithmetic-edge constants, which its kernels
+    // — edge-table forms all — never read: hb_cmap is the plan's device table of 256 bytes, hb_cmap[g] = guarded bin of cell g for
+    // g = 0 .. hb_cells + 1 (cell 0 and cell hb_cells + 1 are the guard cells), zero behind.  hb_c1 / hb_c0 (and their float copies) then
+    // guess the cell, not the bin (afhip_cell_map.h).
+    union {
+        struct { double hb_w, hb_lo0, hb_gl, hb_gh; };
+        struct {
+            const uint8_t* hb_cmap;
+            int32_t hb_cells, hb_cmap_pad;
+        };
+    };
     float hb_wf, hb_lo0f, hb_glf, hb_ghf;
     // ... and the guess constant biased DOWN (hb_c0 - delta, host-chosen): floor(v * hb_c1 + hb_c0b) is then never above the
     // value's bin and at most one below it, and an edge value E[k] always guesses k - 1 — checked by the host on every edge
@@ -127,6 +137,8 @@ static_assert(sizeof(FusedArgs) == 3632, "FusedArgs keeps its size");
 static_assert(offsetof(FusedArgs, hb_edge) == 160 && offsetof(FusedArgs, unpack) == 160 && offsetof(FusedArgs, hb_dn) == 296, "the shared bytes keep their place");
 static_assert(offsetof(FusedArgs, pack_rules) == 200 && offsetof(FusedArgs, pack_bounds) == 208 && offsetof(FusedArgs, n_rules) == 216, "the rule table follows `unpack`");
 static_assert(offsetof(FusedArgs, hb_bin_of_slot) == 96 && offsetof(FusedArgs, hb_up) == 364 && offsetof(FusedArgs, packed) == 432 && offsetof(FusedArgs, hb_w) == 480, "FusedArgs: field offsets");
+static_assert(offsetof(FusedArgs, hb_cmap) == 480 && offsetof(FusedArgs, hb_cells) == 488 && offsetof(FusedArgs, hb_lo0) == 488 && offsetof(FusedArgs, hb_gh) == 504 &&
+              offsetof(FusedArgs, hb_wf) == 512, "the cell map lies inside the arithmetic-edge constants");
 static_assert(offsetof(FusedArgs, thr) == 544 && offsetof(FusedArgs, cols) == 1312 && offsetof(FusedArgs, ccode) == 3488 && offsetof(FusedArgs, rf_w) == 3552 && offsetof(FusedArgs, rf_lds_off) == 3624, "FusedArgs: field offsets");
 
 }  // namespace afhip
@@ -174,6 +186,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
     constexpr bool TKI = feat_has(FEAT, FEAT_INT_BINS), SL = feat_has(FEAT, FEAT_SINGLE_LEVEL);
     constexpr bool HB = feat_has(FEAT, FEAT_HIST), HA = feat_has(FEAT, FEAT_ARITH_EDGES);
     constexpr bool EB = feat_has(FEAT, FEAT_END_BINS);
+    constexpr bool CM = feat_has(FEAT, FEAT_CELL_MAP);
     constexpr bool PAIR = feat_has(FEAT, FEAT_SHORT_GROUP);
     // (the lean group end skips a per-group walk of ~90 scalar instructions per wave and group, as many as the vector ones that do the
     // arithmetic: profiles/r03_kbench_c5_table_arc.txt)
@@ -191,6 +204,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
     static_assert(!RF || !(SL || HB), "region-fused period ends: two-level plans only");
     static_assert(!(HB && SINE), "histogram variants carry no sine_dd code");
     static_assert(!EB || HB, "wide end bins: a histogram form");
+    static_assert(!CM || (EB && !HA), "the cell map: an end-bin histogram form with the edge table");
     static_assert(!RF || VEC <= 2, "region-fused period ends: one or two cells per lane");
     static_assert(!PACKED || (PIPE == 0 && !feat_has(FEAT, FEAT_SHORT_GROUP | FEAT_REGION_FUSED) && (HB ? (TKI && STAT <= 1) : !(TKI || SL))),
                   "int16-packed cubes: the general forms and the LDS-histogram forms of the direct-load path only");
@@ -250,6 +264,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
     EdgeT* etab_b = (EdgeT*)(dynlds + HB_TABLE_BYTES / 2);
     int* hcnt = (int*)(dynlds + HB_TABLE_BYTES);
     const int bd = blockDim.x, tid = threadIdx.x;
+    // FEAT_CELL_MAP: the cell -> bin map, 256 bytes behind the counters (hb_bins is at most sixteen: inside the launch's LDS for every VEC and bd)
+    const unsigned char* cmap = nullptr;
     // sine_dd plans: every workgroup copies the acos table (sine_theta) into LDS, behind the LDS-DMA ring if there is one
     // (feat_sine_p2 variants — two-row groups: the P2 table of sine_pair_g; the others: the acos table of sine_theta — the host
     // hands over the one the variant reads)
@@ -295,10 +311,16 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
             etab_a[tid] = ea; etab_b[tid] = eb;
         }
         for (int b = 0; b < hb_bins * VEC; ++b) hcnt[b * bd + tid] = 0;
+        if constexpr (CM) {
+            // the plan's map as 64 words (a workgroup has 64 threads at least; the table is 256 bytes whatever hb_cells)
+            uint32_t* cw = (uint32_t*)(hcnt + hb_bins * VEC * bd);
+            if (tid < 64) cw[tid] = ((const uint32_t*)a.hb_cmap)[tid];
+            cmap = (const unsigned char*)cw;
+        }
         __syncthreads();
         if constexpr (sizeof(TIn) == 4) { hb_c1 = a.hb_c1f; hb_c0 = a.hb_c0f; }
         else { hb_c1 = a.hb_c1; hb_c0 = a.hb_c0; }
-        hb_top = (TIn)(a.hb_n + 1);
+        hb_top = (TIn)((CM ? a.hb_cells : a.hb_n) + 1);          // the last cell / bin of the guarded range
         if constexpr (HA) {
             if constexpr (sizeof(TIn) == 4) { ha_w = a.hb_wf; ha_e0 = a.hb_lo0f + a.hb_wf; ha_gl = a.hb_glf; ha_gh = a.hb_ghf; ha_c0b = a.hb_c0bf; }
             else { ha_w = a.hb_w; ha_e0 = a.hb_lo0 + a.hb_w; ha_gl = a.hb_gl; ha_gh = a.hb_gh; ha_c0b = a.hb_c0b; }   // (lo0 + w: exact, host-checked)
@@ -388,6 +410,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
         if constexpr (sizeof(TIn) == 4) t = __builtin_amdgcn_fmed3f(__fmaf_rn(vr, hb_c1, hb_c0), 0.0f, hb_top);
         else t = fmin(fmax(__fma_rn((double)vr, hb_c1, hb_c0), 0.0), hb_top);
         b = (int)t;
+        if constexpr (CM) b = cmap[b];                // the cell's bin: one byte from LDS
         ea = etab_a[b];
     };
     auto hb_count = [&](TIn vr, int i, int b, const EdgeT& ea) {

@@ -142,6 +142,12 @@ enum : int {
     // and an end slot reads its guard counter (hb_bin_of_slot = -1 / hb_n).  Clamp, guess, repair and "a value on an edge is in no
     // bin" are the closed form's
     FEAT_END_BINS = 16384,
+    // histogram with end bins (FEAT_HIST | FEAT_END_BINS, never FEAT_ARITH_EDGES) whose INTERIOR bins have unequal widths: the fma
+    // guesses a CELL of a lattice of half the smallest interior width, and one byte read from a cell -> bin map in LDS (FusedArgs::
+    // hb_cmap, copied behind the counters at kernel start) turns it into the guessed bin.  Everything after the guess — edge table,
+    // repair by +-1, "a value on an edge is in no bin", the outer limits, the counters — is the end-bin form's (afhip_cell_map.h has
+    // the construction and the host check that the guess is one bin off at most)
+    FEAT_CELL_MAP = 32768,
 };
 
 // what follows from the bits
@@ -161,6 +167,7 @@ constexpr int feat_sine_bytes(int feat) { return feat_sine_p2(feat) ? SINE_P2_BY
 // instead; the parking blocks of a region-fused launch come last (FusedArgs::rf_lds_off).
 constexpr size_t lds_ring_bytes_per_wave(int depth) { return (size_t)depth * 1024; }
 constexpr size_t lds_sine_offset(int pipe, int waves, int depth) { return pipe == 1 ? (size_t)waves * lds_ring_bytes_per_wave(depth) : (size_t)0; }
+// (FEAT_CELL_MAP: + the 256-byte cell map, behind the counters — plan_lds_bytes)
 constexpr size_t lds_hist_bytes(int bins, int vec, int wg) { return (size_t)HB_TABLE_BYTES + (size_t)bins * vec * wg * 4; }    // counters [bins * vec][wg]; bins = hb_n + 2 with the guards
 constexpr int rf_lane_bytes(int vec) { return vec * 16 + 16; }     // a lane's parking block: its cells' weight pairs + its two lane words (a multiple of 16: read and written in 16-byte pieces)
 

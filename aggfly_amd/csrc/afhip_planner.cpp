@@ -10,6 +10,7 @@
 // One function per decision, in the order build_plan calls them; each takes what it reads as parameters and returns its
 // result as a small value.
 #include "afhip_planner.h"
+#include "afhip_cell_map.h"
 
 #include <algorithm>
 #include <cmath>
@@ -52,6 +53,7 @@ PlanKnobs read_knobs() {
     k.no_packed_hist = set("AFHIP_NO_PACKED_HIST");
     if (const char* e = getenv("AFHIP_PACKED_HIST_VEC")) { const int v = atoi(e); if (v == 1 || v == 2) k.packed_hist_vec = v; }
     k.no_end_bins_hist = set("AFHIP_NO_END_BINS_HIST");
+    k.no_cell_map_hist = set("AFHIP_NO_CELL_MAP_HIST");
     k.counts_spmm = !set("AFHIP_NO_COUNTS_SPMM");
     if (const char* e = getenv("AFHIP_COUNTS_SPMM_SUB")) k.counts_spmm_sub = atoi(e);
     if (const char* e = getenv("AFHIP_NO_SLOT_SPMM")) k.no_slot_spmm = atoi(e) != 0;
@@ -328,12 +330,43 @@ static bool biased_guess(const HistPartition& h, int n, int k_first, double* c0b
     return found;
 }
 
+// Bins of UNEQUAL interior widths (afhip_cell_map.h): `m` contiguous sorted bins, six at least, all of positive width.  Bin 0 and bin
+// m - 1 are END bins exactly as FEAT_END_BINS has them — any positive width, infinite included, counted on the guard bins under the
+// test  L < v < U  — and the m - 2 interior bins are described by the hb_* fields as ever; only the guess differs: hb_c1 / hb_c0 guess a
+// cell of hb_cells cells of half the smallest interior width, and hb_cmap sends the cell to its bin.  Found only if the map fits a byte
+// index (254 cells: range over smallest width up to 127), the cells are wide enough for a guess in the input precision, and the host
+// check with the kernel's own fma passes.  (Five bins stay on the per-slot kernels, which do about as much work per value there.)
+template <typename Slot>
+static HistPartition find_cell_map(const PlanLayout& pl, int m, const std::vector<int>& order, Slot slot) {
+    HistPartition h;
+    if (m < 6 || !rows_fit_32bit(pl.desc)) return h;
+    for (int b = 0; b < m; ++b)
+        if (!(slot(b).t1 > slot(b).t0)) return h;             // (NaN limits fail)
+    const int n = m - 2;
+    double E[MAX_THR + 1];
+    for (int k = 0; k < n; ++k) E[k] = slot(1 + k).t0;
+    E[n] = slot(n).t1;
+    CellMap cm;
+    // (a packed cube's values are float32)
+    const bool found = pl.desc.dtype != AFHIP_F64 ? cell_map_find<float>(E, n, &cm) : cell_map_find<double>(E, n, &cm);
+    if (!found) return h;
+    h.hb_n = n; h.hb_c1 = cm.c1; h.hb_c0 = cm.c0;
+    for (int b = 0; b < m; ++b) h.hb_bin_of_slot[order[(size_t)b]] = b - 1;      // (the lower end: -1, the upper end: n)
+    for (int k = 0; k <= n; ++k) h.hb_edge[k] = E[k];
+    h.hb_wide = true;
+    h.hb_slot_lo = order[0]; h.hb_slot_hi = order[(size_t)m - 1];
+    h.hb_cells = cm.cells;
+    memcpy(h.hb_cmap, cm.map, sizeof h.hb_cmap);
+    return h;
+}
+
 // contiguous equal-width partition?  (sorted by t0, t1[b] == t0[b+1], constant width) — closed, or with a WIDE END BIN on one side or
 // both: bin 0 and / or bin m - 1 of any positive width, infinite included (a catch-all below / above the equal-width bins).  The
 // interior bins 1 .. m - 2 (at least two) always belong to the equal-width lattice; an end bin that continues it is an ordinary bin,
 // one that does not is a wide end (its width may be smaller than the lattice's too).  The candidates are tried closed form first, so a
 // partition without a wide end gets exactly the result it always got.  With a wide end hb_n and every constant describe the lattice
-// alone; the end slots sit on the guard bins (HistPartition::hb_wide).
+// alone; the end slots sit on the guard bins (HistPartition::hb_wide).  A contiguous partition that none of the four candidates fits —
+// interior widths that differ — is handed to find_cell_map last, so no partition found here is ever found there.
 static HistPartition find_partition(const PlanLayout& pl, bool all_bins) {
     const afhip_plan_desc* desc = &pl.desc;
     HistPartition h;
@@ -371,7 +404,7 @@ static HistPartition find_partition(const PlanLayout& pl, bool all_bins) {
     // (a packed cube's values are float32: its dtype goes the float way here and below)
     const double eps = desc->dtype != AFHIP_F64 ? 1.2e-7 : 2.3e-16;
     ok = ok && emax * eps * 16.0 < w;
-    if (!ok) return h;
+    if (!ok) return find_cell_map(pl, m, order, slot);
     h.hb_n = n; h.hb_c1 = 1.0 / w; h.hb_c0 = 1.0 - e0 / w;      // + 1: bin 0 is the lower guard bin
     for (int b = 0; b < m; ++b) h.hb_bin_of_slot[order[(size_t)b]] = b - first;      // (a wide lower end: -1, a wide upper end: n)
     for (int b = 0; b < n; ++b) h.hb_edge[b] = slot(first + b).t0;
@@ -425,8 +458,9 @@ static bool is_single_level(const PlanLayout& pl) {
 }
 
 // The LDS-histogram forms that are matched exactly (find_exact_form): those of packed cubes (MENU_PACKED_HIST) for a closed partition
-// `hist` — found with the float32 rules: the values of a packed cube are float32 — and the end-bin forms (MENU_END_BINS) for a partition
-// with a wide end bin (HistPartition::hb_wide), on packed and float cubes alike.  A closed partition on a float cube never comes here: it
+// `hist` — found with the float32 rules: the values of a packed cube are float32 — the end-bin forms (MENU_END_BINS) for a partition
+// with a wide end bin (HistPartition::hb_wide) and the cell-map forms (MENU_CELL_MAP) for one whose interior widths differ, on packed and
+// float cubes alike.  A closed partition on a float cube never comes here: it
 // goes through choose_variant.  Either way the widest of two and one cells per lane that divides the row length and that the production
 // menu holds for the plan's stat tier and storage — single-level form for single-level plans, arithmetic edges when the edges are exact,
 // else the edge table.  Null: no such kernel, or the route is off.
@@ -443,11 +477,19 @@ static bool is_single_level(const PlanLayout& pl) {
 // earlier route's minimum in the same process — at x0.11 / x0.12 of it on packed cubes, x0.27 / x0.34 on float32, x0.52 / x0.36 on
 // float64 (profiles/end_bins.txt, section 2: the whole output of scripts/end_bins_bench.py with device, build and min / median / max of
 // the three routes).
+//   Cell map (HistPartition::hb_cells: interior bins of unequal widths, found by find_cell_map): the edge-table end-bin forms with
+// FEAT_CELL_MAP (gen_variants.py: cell_map_menu, MENU_CELL_MAP), the widest of two and one cells per lane as for the end-bin menu; never an
+// arithmetic-edge form.  Null under the same conditions as the end-bin route, with AFHIP_NO_CELL_MAP_HIST as its A/B knob
+// (scripts/cell_map_bench.py).  The default on every storage by the same rule — on the configs[1] shape, the eight-bin spec
+// (-inf,-10] ... (35,inf) and a fourteen-bin spec of three interior widths, single level / two-level with a mean, its median lies below the
+// earlier route's minimum in the same process, the two alternating: at x0.14 / x0.14 and x0.14 / x0.15 of it on packed cubes, x0.30 / x0.46 and
+// x0.30 / x0.47 on float32, x0.51 / x0.45 and x0.51 / x0.42 on float64 — and six closed bins win as well (x0.14 / x0.13, x0.30 / x0.45,
+// x0.51 / x0.46), so the floor of six bins (find_cell_map) holds on all three (profiles/cell_map_bins.txt, section 2: the script's whole output).
 static const Variant* choose_hist_variant(const PlanLayout& pl, const HistPartition& hist, int tuning, const PlanKnobs& knobs) {
     const bool packed = is_packed_dtype(pl.desc.dtype);
     if (hist.hb_n == 0 || (packed && knobs.no_packed_hist)) return nullptr;
-    if (hist.hb_wide ? (knobs.no_end_bins_hist || tuning != 0) : !packed) return nullptr;
-    const Menu menu = hist.hb_wide ? MENU_END_BINS : MENU_PACKED_HIST;
+    if (hist.hb_cells ? (knobs.no_cell_map_hist || tuning != 0) : (hist.hb_wide ? (knobs.no_end_bins_hist || tuning != 0) : !packed)) return nullptr;
+    const Menu menu = hist.hb_cells ? MENU_CELL_MAP : (hist.hb_wide ? MENU_END_BINS : MENU_PACKED_HIST);
     const int dtype = packed ? AFHIP_I16 : pl.desc.dtype;
     const bool sl = is_single_level(pl);
     auto find = [&](int vec, bool arms) {
@@ -512,7 +554,7 @@ static const Variant* choose_variant(const PlanLayout& pl, const GroupForm& form
 // ---- 6. chunking ----
 size_t plan_lds_bytes(const PlanLayout* pl) {
     const Variant& v = *pl->variant;
-    if (v.hb()) return lds_hist_bytes(pl->hb_n + 2, v.vec, pl->wg);
+    if (v.hb()) return lds_hist_bytes(pl->hb_n + 2, v.vec, pl->wg) + (feat_has(v.feat, FEAT_CELL_MAP) ? (size_t)CELL_MAP_BYTES : 0);      // (the cell map, behind the counters)
     return lds_sine_offset(v.pipe, pl->wg / 64, v.depth) + (pl->has_sine ? (size_t)feat_sine_bytes(v.feat) : 0);      // the variant's sine table, behind the ring
 }
 
@@ -791,7 +833,8 @@ int build_plan(const afhip_plan_desc* desc, const DeviceFacts& dev, PlanLayout* 
     const int tuning = packed ? 0 : usable_tuning(pl->desc);
     bool all_bins = pl->nthr > 0;
     for (const ThrSlot& t : pl->thr) all_bins = all_bins && t.nan_poisons == 0;
-    // A plan of four or more contiguous, equal-width, strict bins (on packed storage by the float32 rules) takes an LDS-histogram form,
+    // A plan of four or more contiguous, equal-width, strict bins (on packed storage by the float32 rules) — or of six or more whose interior
+    // widths differ (find_cell_map: hb_wide with a cell map) — takes an LDS-histogram form,
     // chunked with single-wave workgroups and many chunks and, single-level, with packed count records and the count gather
     // (packed_format).  A float cube's closed partition finds its form in choose_variant, which may also leave the partition unused;
     // packed cubes and partitions with a wide end bin have menus of exact forms: that form or none — no kernel without FEAT_END_BINS ever

@@ -48,6 +48,7 @@ struct PlanKnobs : RunKnobs {
     bool no_region_fused = false;                                            // AFHIP_NO_REGION_FUSED
     bool no_packed_hist = false;   // AFHIP_NO_PACKED_HIST: packed cubes' partition plans take the general packed kernel, not the LDS-histogram forms
     int packed_hist_vec = 0;       // AFHIP_PACKED_HIST_VEC=1|2: the cells per lane such a plan takes where the library holds the kernel, arms included (0: the planner's rule)
+    bool no_cell_map_hist = false; // AFHIP_NO_CELL_MAP_HIST: partitions of unequal interior widths take the route they took without the cell-map histogram forms
     bool no_end_bins_hist = false; // AFHIP_NO_END_BINS_HIST: partitions with a wide end bin take the route they took without the end-bin histogram forms
 };
 PlanKnobs read_knobs();
@@ -63,6 +64,10 @@ struct HistPartition {
     // whose t0 / t1 are the outer limits L / U of the whole partition
     bool hb_wide = false;
     int hb_slot_lo = 0, hb_slot_hi = 0;
+    // interior bins of unequal widths (FEAT_CELL_MAP; afhip_cell_map.h): hb_wide is set, hb_c1 / hb_c0 guess one of hb_cells cells (0: none)
+    // between two guard cells, and hb_cmap[cell] is the cell's guarded bin; no arithmetic edges
+    int hb_cells = 0;
+    uint8_t hb_cmap[256] = {0};
 };
 
 // What the planner produces.  Host data only: afhip_plan (afhip_api.hip) adds the device tables, scratch and run state.

@@ -45,9 +45,12 @@ struct Variant {
 //                     contiguous equal-width partition; the kernels outside production are tuning arms
 //   MENU_END_BINS     the LDS-histogram forms with FEAT_END_BINS, for partitions with a wide end bin on one side or both — float32,
 //                     float64 and packed storage together (end_bins_menu), all production
-// The last three are searched by find_exact_form.
-enum Menu { MENU_FLOAT, MENU_PACKED, MENU_PACKED_HIST, MENU_END_BINS, MENU_COUNT };
+//   MENU_CELL_MAP     the edge-table forms of MENU_END_BINS with FEAT_CELL_MAP, for partitions whose interior widths differ
+//                     (cell_map_menu), all production
+// The last four are searched by find_exact_form.
+enum Menu { MENU_FLOAT, MENU_PACKED, MENU_PACKED_HIST, MENU_END_BINS, MENU_CELL_MAP, MENU_COUNT };
 const Variant* menu_table(Menu menu, int* n);   // generated (variants_table.hip): the menu's kernels, in gen_variants.py's order
+const char* menu_key(Menu menu);                // generated: the menu's key in gen_variants.py's MENUS ("float", "packed", ... "cell_map")
 const char* variants_menu();                    // "full" (the production menu), "arms" (+ the tuning arms) or "dev"
 
 // What a lowered plan asks of the menu (afhip_planner.cpp: choose_variant).  A fallback is the same query with a field changed.

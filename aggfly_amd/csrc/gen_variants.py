@@ -7,7 +7,8 @@ Each generated unit holds a handful of explicit instantiations so that ``make -j
 kernel menus and the stems of their units: the float kernels (`menu`) go to ``variants_NN.hip``, the kernels of int16-packed cubes
 (`packed_menu`) to ``packed_NN.hip``, their LDS-histogram forms (`packed_hist_menu`) to ``packed_hist_NN.hip``, and the histogram forms
 for partitions with a wide end bin (`end_bins_menu`: Feat.END_BINS, float32, float64 and packed storage together) to ``end_bins_NN.hip``
-(float32 / float64) and ``end_bins_packed_NN.hip``.  ``variants_table.hip`` collects ONE table, a slice per menu in `MENUS` order, behind
+(float32 / float64) and ``end_bins_packed_NN.hip``, and their twins for interior bins of unequal widths (`cell_map_menu`: Feat.CELL_MAP) to
+``cell_map_NN.hip`` and ``cell_map_packed_NN.hip``.  ``variants_table.hip`` collects ONE table, a slice per menu in `MENUS` order, behind
 ``menu_table`` (afhip_variants.h), which ``find_variant`` and ``find_exact_form`` search; every menu keeps its own count and contents.
 
 Adding a menu: a menu function and an entry of `MENUS` here, the enumerator of the same name in afhip_variants.h's `Menu` (the table asserts
@@ -44,12 +45,13 @@ class Feat:
     THREE_ROW = 4096
     MIXED = 8192
     END_BINS = 16384
+    CELL_MAP = 32768
 
 
 FEAT_NAMES = [n for n in vars(Feat) if n.isupper()]
 GROUP_LENGTH = Feat.FOUR_ROW | Feat.THREE_ROW | Feat.MIXED      # the short-group forms of other than two rows
 # name suffixes, in name order (`_ss` instead of `_lean` for the sine-only lean form)
-SUFFIXES = ((Feat.NT, "_nt"), (Feat.INT_BINS, "_ibins"), (Feat.SINGLE_LEVEL, "_sl"), (Feat.HIST, "_hist"), (Feat.ARITH_EDGES, "_arith"), (Feat.END_BINS, "_ends"),
+SUFFIXES = ((Feat.NT, "_nt"), (Feat.INT_BINS, "_ibins"), (Feat.SINGLE_LEVEL, "_sl"), (Feat.HIST, "_hist"), (Feat.ARITH_EDGES, "_arith"), (Feat.END_BINS, "_ends"), (Feat.CELL_MAP, "_cmap"),
             (Feat.SHORT_GROUP, "_pair"), (Feat.LEAN, "_lean"), (Feat.FOUR_ROW, "_quad"), (Feat.THREE_ROW, "_tri"), (Feat.MIXED, "_rag"),
             (Feat.REGION_FUSED, "_rf"))
 
@@ -251,6 +253,15 @@ def end_bins_menu(kind):
     return out
 
 
+def cell_map_menu(kind):
+    """The LDS-histogram kernels for partitions whose interior widths differ (Feat.CELL_MAP; afhip_planner.cpp: find_cell_map), same
+    tuples as `menu`: the edge-table entries of `end_bins_menu` with the bit set, entry by entry — float32 and float64 at one cell per lane,
+    stat 0 / 1 x two-level / single-level; packed storage the same four at one cell per lane and the two single-level forms at two.  No
+    arithmetic-edge form (the edges of such a partition are no lattice), no tuning arms; the `dev` menu has none of them.  Rows in flight
+    are the end-bin twin's: no kernel of the menu has scratch memory (-Rpass-analysis=kernel-resource-usage; profiles/cell_map_bins.txt)."""
+    return [v[:7] + (v[7] | Feat.CELL_MAP, 1) for v in end_bins_menu(kind) if not v[7] & Feat.ARITH_EDGES]
+
+
 def pickable(v):
     """False for a kernel that no plan can select by the planner's default rules (afhip_planner.cpp: the stage named in each comment), whatever its shape."""
     dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod = v
@@ -337,6 +348,7 @@ MENUS = (
     ("packed", packed_menu, (("packed", (I16,)),)),
     ("packed_hist", packed_hist_menu, (("packed_hist", (I16,)),)),
     ("end_bins", end_bins_menu, (("end_bins", (0, 1)), ("end_bins_packed", (I16,)))),
+    ("cell_map", cell_map_menu, (("cell_map", (0, 1)), ("cell_map_packed", (I16,)))),
 )
 
 
@@ -358,6 +370,8 @@ def write_table(outdir, kind, slices, units):
         f.write(f"static Variant g_table[{max(starts[-1], 1)}];\nstatic int g_count = -1;\n")
         f.write(f"static const int g_start[MENU_COUNT + 1] = {{{', '.join(map(str, starts))}}};      // each menu's slice of g_table\n")
         f.write(f'const char* variants_menu() {{ return "{kind}"; }}\n')
+        keys = ", ".join(f'"{key}"' for key, _, _ in MENUS)
+        f.write(f"const char* menu_key(Menu m) {{\n    static const char* const keys[MENU_COUNT] = {{{keys}}};\n    return keys[m];\n}}\n")
         f.write("const Variant* menu_table(Menu m, int* n) {\n    if (g_count < 0) {\n        int c = 0;\n")
         for u in units:
             f.write(f"        c += register_{u}(g_table + c);\n")

@@ -32,7 +32,7 @@ E_INVALID, E_HIP, E_UNSUPPORTED, E_NOMEM = -1, -2, -3, -4
 ABI_VERSION = 4                 # AFHIP_ABI_VERSION of include/aggfly_hip.h this binding was written against
 
 EXPORTS = (
-    "afhip_last_error", "afhip_abi_version", "afhip_build_info", "afhip_device_count", "afhip_device_info",
+    "afhip_last_error", "afhip_abi_version", "afhip_build_info", "afhip_menu_size", "afhip_device_count", "afhip_device_info",
     "afhip_group_stat", "afhip_group_dd", "afhip_group_bins", "afhip_group_sine_dd",
     "afhip_csr_create", "afhip_csr_destroy", "afhip_scatter_block", "afhip_spatial_wavg", "afhip_place_box",
     "afhip_plan_create", "afhip_plan_destroy", "afhip_plan_workspace_bytes", "afhip_plan_run_workspace_bytes",
@@ -103,6 +103,8 @@ def load():
     lib.afhip_csr_destroy.restype = None
     lib.afhip_plan_destroy.restype = None
     lib.afhip_build_info.argtypes = [C.c_char_p, i32]
+    lib.afhip_menu_size.argtypes = [C.c_char_p]
+    lib.afhip_menu_size.restype = i32
     lib.afhip_read_probe.argtypes = [vp, i64, i64, i32, C.POINTER(C.c_float), vp]
     lib.afhip_device_info.argtypes = [i32, C.c_char_p, i32, C.c_char_p, i32, C.POINTER(i32), C.POINTER(i64)]
     lib.afhip_group_stat.argtypes = [vp, i32, i64, i64, vp, i64, i32, vp, vp]
@@ -157,6 +159,12 @@ def _check(rc: int):
 
 def device_count() -> int:
     return int(load().afhip_device_count())
+
+
+def menu_size(key: str) -> int:
+    """Kernels of the menu `key` in the loaded build ("float", "packed", "packed_hist", "end_bins", "cell_map": the keys of
+    gen_variants.py's MENUS); -1 for a key that names no menu (`afhip_menu_size`)."""
+    return int(load().afhip_menu_size(key.encode()))
 
 
 def build_info() -> dict:
