@@ -507,7 +507,9 @@ AFZ_FN void afz_pass_sequences(const afz_ctx* c, int64_t b) {
         const uint32_t llc = tab[0] ? (tab[0][st[0]] & 0xff) : rle[0];
         const uint32_t ofc = tab[1] ? (tab[1][st[1]] & 0xff) : rle[1];
         const uint32_t mlc = tab[2] ? (tab[2][st[2]] & 0xff) : rle[2];
-        if (llc > 35 || ofc > 31 || mlc > 52) { afz_mark_bad(c, k->frame); return; }
+        /* offset code 31 means an offset of 2^31 - 3 or more, past any frame the planner takes; as an int32 it would turn
+         * negative and read as a symbolic entry below */
+        if (llc > 35 || ofc > 30 || mlc > 52) { afz_mark_bad(c, k->frame); return; }
         const uint32_t ofv = (1u << ofc) + afz_read(&br, (int)ofc);
         const uint32_t ml = afz_ml_base[mlc] + afz_read(&br, afz_ml_bits[mlc]);
         const uint32_t ll = afz_ll_base[llc] + afz_read(&br, afz_ll_bits[llc]);
