@@ -282,7 +282,7 @@ AFZ_FN int afi_match(afi_emit* e, int32_t len, int32_t dist) {
     afz_seq* q = &e->seq[e->nseq++];               /* (a match is >= 3 bytes: at most dsize / 3 of them) */
     q->ll = (uint32_t)e->pend; q->ml = (uint32_t)len; q->off = dist;
     e->pend = 0; e->cur += len; e->outn += len;
-    return 0;
+    return e->cur == AFZ_BLOCK_MAX ? afi_close(e, 0) : 0;      /* (as a literal that ends on the limit: literals after it open the next block) */
 }
 
 AFZ_FN int afi_front(const afi_ctx* c, const afi_stream* st, afi_emit* e, uint8_t* slot, uint32_t* want) {
