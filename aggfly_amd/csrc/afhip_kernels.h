@@ -206,8 +206,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
     static_assert(!EB || HB, "wide end bins: a histogram form");
     static_assert(!CM || (EB && !HA), "the cell map: an end-bin histogram form with the edge table");
     static_assert(!RF || VEC <= 2, "region-fused period ends: one or two cells per lane");
-    static_assert(!PACKED || (PIPE == 0 && !feat_has(FEAT, FEAT_SHORT_GROUP | FEAT_REGION_FUSED) && (HB ? (TKI && STAT <= 1) : !(TKI || SL))),
-                  "int16-packed cubes: the general forms and the LDS-histogram forms of the direct-load path only");
+    static_assert(!PACKED || (PIPE == 0 && !RF && (!PAIR || LEAN) && (HB ? (TKI && STAT <= 1) : !(TKI || SL))),
+                  "int16-packed cubes: the general forms, the lean short-group forms and the LDS-histogram forms of the direct-load path only");
     const int64_t C = a.C;
     const int K = a.K;
     const int lane = threadIdx.x & 63;
@@ -1142,7 +1142,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
     }
 
     if constexpr (PAIR) {
-        const TIn* p = cube;
+        const TRaw* p = cube;
         constexpr int GB = DEPTH / GL;                // groups per block of rows
         // the group's statistics: min / max in the input precision (exact), the sum in time order — for a pair min + max, the same
         // two addends the reference adds; a NaN in any row marks the lane (the group is NaN, nb_kernels.py:145-147)
@@ -1222,9 +1222,26 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
         // Addresses: ONE scalar row pointer that advances by a row per load, in a buffer descriptor, + the lane's 32-bit byte
         // offset — no vector address arithmetic (a global_load needs a v_lshl_add_u64 per row) and two scalar adds per row; the host
         // keeps plans whose rows reach 4 GiB off this path.
-        const char* nx = (const char*)a.cube + (size_t)(k_lo * C) * sizeof(TIn);       // the next row to load (uniform)
-        const uint32_t voff = (uint32_t)((uint64_t)c_ld * sizeof(TIn));
-        const size_t rowb = (size_t)C * sizeof(TIn);
+        const char* nx = (const char*)a.cube + (size_t)(k_lo * C) * sizeof(TRaw);      // the next row to load (uniform)
+        const uint32_t voff = (uint32_t)((uint64_t)c_ld * sizeof(TRaw));
+        const size_t rowb = (size_t)C * sizeof(TRaw);
+        // Packed cubes: the rows wait in their registers as 2-byte elements (TRaw) and a group's rows are unpacked to float32 right in
+        // front of its statistics, in time order — `n` rows from chunk-relative row `row0`.  Several rules: the scheme of the general
+        // path (`pr`, rule_next, rule_advance), `straddles` being the caller's one scalar compare for the rows it is about to consume;
+        // only then is each row tested, and the next rule read at the row where it starts.  From here on the code is the float32 form's.
+        auto unpack_rows = [&](const RawVec<TRaw, VEC>* rr, int n, int row0, bool straddles, RawVec<TIn, VEC>* u) {
+            if constexpr (PACKED) {
+#pragma unroll
+                for (int d = 0; d < GL; ++d) {
+                    if (d == 0 || d < n) {
+                        if (straddles && row0 + d == rule_next) { KEEP_BRANCH(); rule_advance(); }
+                        unpack_i16<VEC>(rr[d].v, pr, u[d].v);
+                    } else {
+                        u[d] = u[0];                   // (never read: the statistics stop at the group's length)
+                    }
+                }
+            }
+        };
         if constexpr (RAG) {
             // groups of one to four rows: slot q of the block holds group g + q in its four row registers, as many of them filled
             // as the group is long.  Rows are requested in time order through the one scalar row pointer, a group's successor in
@@ -1263,7 +1280,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
                     for (int i = 0; i < VEC; ++i) { plo[i] = lo[i]; phi[i] = hi[i]; mn[i] = (double)lo[i]; mx[i] = (double)hi[i]; }
                 }
             };
-            RawVec<TIn, VEC> r[DEPTH];
+            RawVec<TRaw, VEC> r[DEPTH];
             int lens[GB];
             int k_next = (int)k_lo;                     // the next row to request (the cube's row index)
 #pragma unroll
@@ -1276,7 +1293,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
                 }
 #pragma unroll
                 for (int d = 0; d < GL; ++d) {
-                    if (d < lens[q]) { r[GL * q + d] = ld_stream_row<TIn, VEC, AUX>(nx, voff); nx += rowb; }
+                    if (d < lens[q]) { r[GL * q + d] = ld_stream_row<TRaw, VEC, AUX>(nx, voff); nx += rowb; }
                     else r[GL * q + d] = r[0];         // (never read: the statistics stop at the group's length)
                 }
             }
@@ -1287,7 +1304,14 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
                     if (q < ng) {
                         const int64_t w = ld_uniform(&a.gtab[2 * (g + q)]);
                         const int len = lens[q];
-                        rag_stats(&r[GL * q], len);
+                        if constexpr (PACKED) {
+                            const int gend = ((int)(w >> 1) & 0x7fffffff) - (int)k_lo;        // the group's end, chunk-relative
+                            RawVec<TIn, VEC> u[GL];
+                            unpack_rows(&r[GL * q], len, gend - len, gend > rule_next, u);
+                            rag_stats(u, len);
+                        } else {
+                            rag_stats(&r[GL * q], len);
+                        }
                         if (g + GB + q < g_hi) {
                             const int e = (int)(ld_uniform(&a.gtab[2 * (g + GB + q)]) >> 1) & 0x7fffffff;
                             const int ln = e - k_next;
@@ -1295,7 +1319,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
                             lens[q] = ln;
 #pragma unroll
                             for (int d = 0; d < GL; ++d) {
-                                if (d < ln) { r[GL * q + d] = ld_stream_row<TIn, VEC, AUX>(nx, voff); nx += rowb; }
+                                if (d < ln) { r[GL * q + d] = ld_stream_row<TRaw, VEC, AUX>(nx, voff); nx += rowb; }
                             }
                         }
                         const double inv = len == 3 ? 1.0 / 3.0 : (len == 2 ? 0.5 : (len == 4 ? 0.25 : 1.0));
@@ -1305,24 +1329,32 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
                 g += ng;
             }
         } else {
-        RawVec<TIn, VEC> r[DEPTH];
+        RawVec<TRaw, VEC> r[DEPTH];
 #pragma unroll
         for (int d = 0; d < DEPTH; ++d) {
-            if (d < rows) { r[d] = ld_stream_row<TIn, VEC, AUX>(nx, voff); nx += rowb; }
+            if (d < rows) { r[d] = ld_stream_row<TRaw, VEC, AUX>(nx, voff); nx += rowb; }
             else r[d] = r[0];                      // (a chunk shorter than a block: these rows' groups are not evaluated)
         }
         while (g < g_hi) {
             const int ng = (g_hi - g) < GB ? (g_hi - g) : GB;
+            bool straddles = false;                    // packed cubes: a rule starts inside this block of rows
+            if constexpr (PACKED) straddles = kk + DEPTH > rule_next;
             // one copy of the group end per group of the block: since the arcs come from a table the copies fit the instruction
             // cache, and the rows need not be shifted down GL registers per group (round 2's rolled loop: 4 VALU per cell-day)
 #pragma unroll
             for (int q = 0; q < GB; ++q) {
                 if (q < ng) {
                     const int64_t w = ld_uniform(&a.gtab[2 * (g + q)]);
-                    short_stats(&r[GL * q]);
+                    if constexpr (PACKED) {
+                        RawVec<TIn, VEC> u[GL];
+                        unpack_rows(&r[GL * q], GL, kk + GL * q, straddles, u);
+                        short_stats(u);
+                    } else {
+                        short_stats(&r[GL * q]);
+                    }
                     if (kk + DEPTH + GL * (q + 1) <= rows) {       // (groups are whole: all of the next block's group q, or none)
 #pragma unroll
-                        for (int d = 0; d < GL; ++d) { r[GL * q + d] = ld_stream_row<TIn, VEC, AUX>(nx, voff); nx += rowb; }
+                        for (int d = 0; d < GL; ++d) { r[GL * q + d] = ld_stream_row<TRaw, VEC, AUX>(nx, voff); nx += rowb; }
                     }
                     group_end((w & 1) != 0, GL, 1.0 / GL, (int)((uint64_t)w >> 63), g + q);
                 }

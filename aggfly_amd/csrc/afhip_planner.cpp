@@ -52,6 +52,8 @@ PlanKnobs read_knobs() {
     k.no_region_fused = set("AFHIP_NO_REGION_FUSED");
     k.no_packed_hist = set("AFHIP_NO_PACKED_HIST");
     if (const char* e = getenv("AFHIP_PACKED_HIST_VEC")) { const int v = atoi(e); if (v == 1 || v == 2) k.packed_hist_vec = v; }
+    k.no_packed_short = set("AFHIP_NO_PACKED_SHORT");
+    if (const char* e = getenv("AFHIP_PACKED_SHORT_VEC")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) k.packed_short_vec = v; }
     k.no_end_bins_hist = set("AFHIP_NO_END_BINS_HIST");
     k.no_cell_map_hist = set("AFHIP_NO_CELL_MAP_HIST");
     k.counts_spmm = !set("AFHIP_NO_COUNTS_SPMM");
@@ -220,10 +222,12 @@ static GroupForm short_group_form(const PlanLayout& pl, const PlanKnobs& knobs) 
     }
     f.lean_sine = f.lean_sine && f.lean;
     // four-row groups exist in the lean form only, for as many columns as its variants hold
+    // (packed storage: the form is asked of its own menu afterwards, and which light plans take it is that menu's rule — choose_packed_short_variant)
+    const bool packed = is_packed_dtype(desc->dtype);
     if (f.quad_len()) {
         VariantQuery q;
         q.dtype = desc->dtype; q.stat = pl.stat; q.K = pl.K; q.lean = 1; q.quads = f.glcode();
-        if (!(f.lean && find_variant(q))) f.pairs = f.lean = false;
+        if (!(f.lean && (packed || find_variant(q)))) f.pairs = f.lean = false;
     }
     // mean / sum columns alone (no min, max or sine): the pair path exists in the lean form only, and a light plan (one or two
     // columns) streams faster through the LDS-DMA ring, whose prefetch runs across the two-row groups (5.99 vs 5.44 TB/s on
@@ -234,7 +238,7 @@ static GroupForm short_group_form(const PlanLayout& pl, const PlanKnobs& knobs) 
         // 1801 x 3600; from three columns on, and on float64 at every count, the lean form is ahead: profiles/r04_three_row_groups.txt)
         // (mixed lengths likewise: 6.25 / 6.39 against 6.89 / 6.83 ms, float64 level; profiles/r04_mixed_short_groups.txt)
         const int min_k = f.quad_len() ? (((f.glen == 3 || f.glen == 5) && desc->dtype == AFHIP_F32) ? 3 : 1) : 3;
-        if (!f.lean || pl.K < min_k) f.pairs = f.lean = f.lean_sine = false;
+        if (!f.lean || (!packed && pl.K < min_k)) f.pairs = f.lean = f.lean_sine = false;
     }
     return f;
 }
@@ -445,6 +449,37 @@ static const Variant* choose_packed_variant(const PlanLayout& pl) {
         if (C % vec != 0) continue;
         if (const Variant* v = find_exact_form(MENU_PACKED, AFHIP_I16, vec, pl.stat, pl.nthr, pl.K, false, false)) return v;
     }
+    return nullptr;
+}
+
+// ... and a menu of lean short-group forms (MENU_PACKED_SHORT) for plans whose inner groups are all two, three or four rows or mixed one to
+// four: short_group_form's rules — no threshold slot, stat 1 or 2, rows under 4 GiB at two bytes an element, every column lean
+// (mean | sum | min | max | sine_dd -> integer power -> sum | mean) — and the exact form of the plan's group length, sine-only where
+// every column is a plain sine_dd; the widest of four, two and one cells per lane that divides the rows and that the production menu holds
+// (the stat-2 six-column forms exist at two and one only).  Null — not such a plan, no such kernel (`dev` menu), or AFHIP_NO_PACKED_SHORT (the
+// A/B knob of scripts/packed_short_bench.py) — leaves the plan to the general packed kernel.  AFHIP_PACKED_SHORT_VEC=1|2|4 asks for that
+// width where the library holds it (the width arms of the same script).
+//   Which plans take the form by default was measured, by the rule the histogram routes were held to: on the configs[1] shape held as int16, a
+// class of plans (group length x one mean column / the K = 5 polynomial / min and max / four stat-2 columns / two sine_dd columns) takes it only
+// if the median of its widest production width lies below the general packed kernel's minimum in the same process, the routes alternating.
+// Every class does (profiles/packed_short_groups.txt, section 2: the script's whole output): two-row groups x0.42 / x0.34 / x0.41 / x0.43 and
+// x0.46 for sine_dd, three-row x0.61 / x0.45 / x0.51 / x0.49, four-row x0.61 / x0.41 / x0.53 / x0.53, mixed x0.70 / x0.48 / x0.63 / x0.62 — so
+// LIGHT plans take it too: packed storage has no LDS-DMA ring, and the float rule that sends light stat-1 plans there (short_group_form: min_k)
+// has no packed counterpart.  The same holds on rows that take two cells per lane on both routes (x0.38 ... x0.69) and one (x0.35 ... x0.76:
+// section 3).  Widths by the same rule, form by form: four cells against two x0.63 ... x0.96, two against one x0.53 ... x0.82 — all production.
+static const Variant* choose_packed_short_variant(const PlanLayout& pl, const PlanKnobs& knobs) {
+    if (knobs.no_packed_short) return nullptr;
+    const GroupForm f = short_group_form(pl, knobs);
+    if (!f.pairs || !f.lean) return nullptr;
+    auto find = [&](int vec, bool arms) {
+        return pl.desc.n_cells % vec == 0
+                   ? find_exact_form(MENU_PACKED_SHORT, AFHIP_I16, vec, pl.stat, pl.nthr, pl.K, false, false, arms, f.glcode(), f.lean_sine ? 2 : 1)
+                   : nullptr;
+    };
+    if (knobs.packed_short_vec)
+        if (const Variant* v = find(knobs.packed_short_vec, true)) return v;
+    for (int vec : {4, 2, 1})
+        if (const Variant* v = find(vec, false)) return v;
     return nullptr;
 }
 
@@ -828,7 +863,7 @@ int build_plan(const afhip_plan_desc* desc, const DeviceFacts& dev, PlanLayout* 
     if ((rc = lower_columns(pl))) return rc;
 
     // int16 and uint16 storage alike (the kernels take the signedness from the bound packing).  Their menus hold no tuning arm that
-    // `tuning` names, no short-group form and no region-fused twin.
+    // `tuning` names and no region-fused twin; of the short-group forms the lean ones.
     const bool packed = is_packed_dtype(desc->dtype);
     const int tuning = packed ? 0 : usable_tuning(pl->desc);
     bool all_bins = pl->nthr > 0;
@@ -848,9 +883,10 @@ int build_plan(const afhip_plan_desc* desc, const DeviceFacts& dev, PlanLayout* 
     }
     static_cast<HistPartition&>(*pl) = hist;
     if (!pl->variant && packed) {
-        // the packed menu of general forms: no packed counts (packed_format finds no integer-bin form); the spatial stage is the slot
-        // gather or the table-order sums
-        pl->variant = choose_packed_variant(*pl);
+        // the lean short-group forms, else the packed menu of general forms: no packed counts (packed_format finds no integer-bin
+        // form); the spatial stage is the slot gather or the table-order sums
+        pl->variant = choose_packed_short_variant(*pl, knobs);
+        if (!pl->variant) pl->variant = choose_packed_variant(*pl);
     } else if (!pl->variant) {
         const GroupForm form = short_group_form(*pl, knobs);
         const LoadPath path = load_path(*pl, form.pairs);

@@ -48,6 +48,8 @@ struct PlanKnobs : RunKnobs {
     bool no_region_fused = false;                                            // AFHIP_NO_REGION_FUSED
     bool no_packed_hist = false;   // AFHIP_NO_PACKED_HIST: packed cubes' partition plans take the general packed kernel, not the LDS-histogram forms
     int packed_hist_vec = 0;       // AFHIP_PACKED_HIST_VEC=1|2: the cells per lane such a plan takes where the library holds the kernel, arms included (0: the planner's rule)
+    bool no_packed_short = false;  // AFHIP_NO_PACKED_SHORT: packed cubes' short-group plans take the general packed kernel, not the lean short-group forms
+    int packed_short_vec = 0;      // AFHIP_PACKED_SHORT_VEC=1|2|4: the cells per lane such a plan takes where the rows allow it and the library holds the kernel, arms included (0: the planner's rule)
     bool no_cell_map_hist = false; // AFHIP_NO_CELL_MAP_HIST: partitions of unequal interior widths take the route they took without the cell-map histogram forms
     bool no_end_bins_hist = false; // AFHIP_NO_END_BINS_HIST: partitions with a wide end bin take the route they took without the end-bin histogram forms
 };

@@ -47,10 +47,12 @@ struct Variant {
 //                     float64 and packed storage together (end_bins_menu), all production
 //   MENU_CELL_MAP     the edge-table forms of MENU_END_BINS with FEAT_CELL_MAP, for partitions whose interior widths differ
 //                     (cell_map_menu), all production
-// The last four are searched by find_exact_form.
-enum Menu { MENU_FLOAT, MENU_PACKED, MENU_PACKED_HIST, MENU_END_BINS, MENU_CELL_MAP, MENU_COUNT };
+//   MENU_PACKED_SHORT the lean short-group forms of packed cubes (gen_variants.py: MORE_MENUS, packed_short_menu): two-, three-, four-row
+//                     and mixed inner groups, the float32 lean menu's shapes at two cells and at one cell per lane, most of them at four as well, all production
+// All but the first are searched by find_exact_form.
+enum Menu { MENU_FLOAT, MENU_PACKED, MENU_PACKED_HIST, MENU_END_BINS, MENU_CELL_MAP, MENU_PACKED_SHORT, MENU_COUNT };
 const Variant* menu_table(Menu menu, int* n);   // generated (variants_table.hip): the menu's kernels, in gen_variants.py's order
-const char* menu_key(Menu menu);                // generated: the menu's key in gen_variants.py's MENUS ("float", "packed", ... "cell_map")
+const char* menu_key(Menu menu);                // generated: the menu's key in gen_variants.py's MENUS ("float", "packed", ... "packed_short")
 const char* variants_menu();                    // "full" (the production menu), "arms" (+ the tuning arms) or "dev"
 
 // What a lowered plan asks of the menu (afhip_planner.cpp: choose_variant).  A fallback is the same query with a field changed.
@@ -114,7 +116,11 @@ inline const Variant* find_variant(const VariantQuery& q) {
 // MENU_PACKED holds the form (false, false) only.  What else a kernel has compiled in (LDS histogram, end bins) follows from the menu it
 // stands in.  `arms`: the kernels outside the production menu too (a forced width: AFHIP_PACKED_HIST_VEC).  Among equally cheap
 // kernels the first in table order.
-inline const Variant* find_exact_form(Menu menu, int dtype, int vec, int stat, int nthr, int K, bool single_level, bool arith, bool arms = false) {
+//   `group_form` >= 0 asks for a short-group form (MENU_PACKED_SHORT) of that Variant::group_form — 0: two-row groups — and is matched
+// exactly too; `lean` is the lean group end the plan qualifies for (VariantQuery::lean): a kernel may ask for less, and the leanest that
+// fits is the cheapest.  -1: no short-group form, which is all the other menus hold.
+inline const Variant* find_exact_form(Menu menu, int dtype, int vec, int stat, int nthr, int K, bool single_level, bool arith, bool arms = false,
+                                      int group_form = -1, int lean = 0) {
     const Variant* best = nullptr;
     long best_cost = 0;
     int n = 0;
@@ -123,7 +129,8 @@ inline const Variant* find_exact_form(Menu menu, int dtype, int vec, int stat, i
         const Variant& v = tab[i];
         if (v.dtype != dtype || v.vec != vec || v.stat < stat || v.nthr < nthr || v.kmax < K || (!v.production && !arms)) continue;
         if (v.sl() != single_level || v.ha() != arith) continue;
-        const long cost = (long)v.nthr * 1000 + (long)v.kmax * 10 + v.stat;
+        if (group_form < 0 ? v.pair() : (!v.pair() || v.group_form() != group_form || v.lean() > lean)) continue;
+        const long cost = (long)v.nthr * 1000 + (long)v.kmax * 10 + v.stat - 3 * v.lean();
         if (!best || cost < best_cost) { best = &v; best_cost = cost; }
     }
     return best;

@@ -10,8 +10,10 @@ for partitions with a wide end bin (`end_bins_menu`: Feat.END_BINS, float32, flo
 (float32 / float64) and ``end_bins_packed_NN.hip``, and their twins for interior bins of unequal widths (`cell_map_menu`: Feat.CELL_MAP) to
 ``cell_map_NN.hip`` and ``cell_map_packed_NN.hip``.  ``variants_table.hip`` collects ONE table, a slice per menu in `MENUS` order, behind
 ``menu_table`` (afhip_variants.h), which ``find_variant`` and ``find_exact_form`` search; every menu keeps its own count and contents.
+`MORE_MENUS` continues the list — the lean short-group kernels of packed cubes (`packed_short_menu`) in ``packed_short_NN.hip`` — and
+`ALL_MENUS` is the two together, which the table follows.
 
-Adding a menu: a menu function and an entry of `MENUS` here, the enumerator of the same name in afhip_variants.h's `Menu` (the table asserts
+Adding a menu: a menu function and an entry of `MORE_MENUS` here, the enumerator of the same name in afhip_variants.h's `Menu` (the table asserts
 that the two agree), and a recipe module under tests/ beside `variant_recipes` ("Adding a kernel menu").
 """
 import os
@@ -24,6 +26,7 @@ I16 = 2        # AFHIP_I16: int16 storage, float32 values
 # their float32 twins) and one four-cell form (36).  A plan of such a shape takes the next narrower kernel, which has none.
 PACKED_DROPPED = {(2, 3, nthr, 16) for nthr in (0, 1, 4, 16)} | {(4, 3, 1, 6)}
 PACKED_SHALLOW = {(1, 3, 16, 16)}      # ... and the one that keeps eight rows in flight where its width takes sixteen: 36 bytes of scratch at sixteen (and at twelve)
+PACKED_SHORT_DROPPED = {(4, 2, 6)}      # packed_short_menu: the (cells per lane, stat, columns) it leaves out, whatever the group length (scratch memory: see there)
 PACKED_HIST_VECS = (2, 1)              # packed_hist_menu: cells per lane (four: every two-level form holds 528 bytes of scratch, the single-level ones one ... two waves per SIMD)
 
 
@@ -262,6 +265,36 @@ def cell_map_menu(kind):
     return [v[:7] + (v[7] | Feat.CELL_MAP, 1) for v in end_bins_menu(kind) if not v[7] & Feat.ARITH_EDGES]
 
 
+def packed_short_menu(kind):
+    """The lean short-group kernels of int16-packed cubes (afhip_planner.cpp: choose_packed_short_variant), same tuples as `menu`: the
+    float32 lean menu's seventeen shapes with nt loads — two-row groups: the sine-only form (K <= 2), stat 2 and stat 1 at two and six
+    columns; four-row, three-row and mixed (one to four rows) groups: stat 1 / 2 at two and six columns — each at two cells and at one
+    cell per lane (4 / 2 bytes per lane and row), and thirteen of them at four (8 bytes, what a float32 lane reads at two cells): 47
+    kernels in units of their own.  The rows wait in their registers as 2-byte elements and are unpacked where a group's statistics
+    consume them; from there on a kernel is its float32 twin.
+    Rows in flight are the float32 twin's — eight, and six for three-row groups: a multiple of the group length, and with one copy of the
+    group end per group of a block a deeper block is that much more code.  No kernel of the menu has scratch memory
+    (-Rpass-analysis=kernel-resource-usage; profiles/packed_short_groups.txt has the register table).  PACKED_SHORT_DROPPED: the stat-2
+    six-column forms at four cells per lane, every group length — 64 to 80 bytes of scratch at these depths, none at half of them but then
+    168 to 171 VGPRs and two or three waves per SIMD; such a plan takes two cells per lane.
+    All production, by the measurement of scripts/packed_short_bench.py on the configs[1] shape (profiles/packed_short_groups.txt, section
+    2): every wider kernel's median lies below the next narrower one's minimum (four cells against two: x0.63 ... x0.96; two against one:
+    x0.53 ... x0.82), and every class of plans beats the general packed kernel.  The `dev` menu has none of them."""
+    def one(vec, stat, kmax, depth, form=0, ss=1):
+        feat = (Feat.SINE if stat == 2 else 0) | Feat.NT | Feat.SHORT_GROUP | Feat.LEAN | (Feat.LEAN_SINE if ss == 2 else 0) | form
+        return (I16, 0, vec, stat, 0, kmax, depth, feat, 1)
+
+    if kind == "dev":
+        return []
+    out = []
+    for vec in (2, 1, 4):
+        out.append(one(vec, 2, 2, 8, ss=2))
+        out += [one(vec, stat, kmax, 8) for stat in (2, 1) for kmax in (2, 6)]
+        for form, depth in ((Feat.FOUR_ROW, 8), (Feat.THREE_ROW, 6), (Feat.MIXED, 8)):
+            out += [one(vec, stat, kmax, depth, form) for stat in (1, 2) for kmax in (2, 6)]
+    return [v for v in out if v[2:4] + v[5:6] not in PACKED_SHORT_DROPPED]
+
+
 def pickable(v):
     """False for a kernel that no plan can select by the planner's default rules (afhip_planner.cpp: the stage named in each comment), whatever its shape."""
     dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod = v
@@ -350,10 +383,16 @@ MENUS = (
     ("end_bins", end_bins_menu, (("end_bins", (0, 1)), ("end_bins_packed", (I16,)))),
     ("cell_map", cell_map_menu, (("cell_map", (0, 1)), ("cell_map_packed", (I16,)))),
 )
+# ... continued: the menus that came after those five, same entries, behind them in the table.  (A tuple of its own: the length and
+# keys of `MENUS` are what the older menus' recipe modules and tests know.)
+MORE_MENUS = (
+    ("packed_short", packed_short_menu, (("packed_short", (I16,)),)),
+)
+ALL_MENUS = MENUS + MORE_MENUS
 
 
 def write_table(outdir, kind, slices, units):
-    """variants_table.hip: the table of every menu.  `slices`: the kernel count per menu, in MENUS order; `units`: every unit's name."""
+    """variants_table.hip: the table of every menu.  `slices`: the kernel count per menu, in ALL_MENUS order; `units`: every unit's name."""
     fn = os.path.join(outdir, "variants_table.hip")
     starts = [sum(slices[:i]) for i in range(len(slices) + 1)]
     with _KeepIfSame(fn) as f:
@@ -362,15 +401,15 @@ def write_table(outdir, kind, slices, units):
         f.write("namespace afhip {\n")
         for name in FEAT_NAMES:
             f.write(f'static_assert(FEAT_{name} == {getattr(Feat, name)}, "gen_variants.py and afhip_plan_types.h disagree on a FEAT bit");\n')
-        f.write(f'static_assert(MENU_COUNT == {len(MENUS)}, "gen_variants.py and afhip_variants.h disagree on the menus");\n')
-        for i, (key, _, _) in enumerate(MENUS):
+        f.write(f'static_assert(MENU_COUNT == {len(ALL_MENUS)}, "gen_variants.py and afhip_variants.h disagree on the menus");\n')
+        for i, (key, _, _) in enumerate(ALL_MENUS):
             f.write(f'static_assert(MENU_{key.upper()} == {i}, "gen_variants.py and afhip_variants.h disagree on the menus");\n')
         for u in units:
             f.write(f"int register_{u}(Variant* out);\n")
         f.write(f"static Variant g_table[{max(starts[-1], 1)}];\nstatic int g_count = -1;\n")
         f.write(f"static const int g_start[MENU_COUNT + 1] = {{{', '.join(map(str, starts))}}};      // each menu's slice of g_table\n")
         f.write(f'const char* variants_menu() {{ return "{kind}"; }}\n')
-        keys = ", ".join(f'"{key}"' for key, _, _ in MENUS)
+        keys = ", ".join(f'"{key}"' for key, _, _ in ALL_MENUS)
         f.write(f"const char* menu_key(Menu m) {{\n    static const char* const keys[MENU_COUNT] = {{{keys}}};\n    return keys[m];\n}}\n")
         f.write("const Variant* menu_table(Menu m, int* n) {\n    if (g_count < 0) {\n        int c = 0;\n")
         for u in units:
@@ -392,7 +431,7 @@ def main():
             per_file = int(args.pop(0))
     os.makedirs(outdir, exist_ok=True)
     files, slices = [], []
-    for key, fn, stems in MENUS:
+    for key, fn, stems in ALL_MENUS:
         vs = fn(kind)
         assert all(sum(v[0] in dtypes for _, dtypes in stems) == 1 for v in vs), key      # every kernel in one stem's units
         slices.append(len(vs))

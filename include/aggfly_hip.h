@@ -75,8 +75,9 @@ int afhip_abi_version(void);
  * packed_hist_variants their LDS-histogram kernels (plans of four or more contiguous equal-width strict bins), end_bins_variants the
  * LDS-histogram kernels of float32, float64 and packed cubes for such plans whose first and / or last bin is wider, or open-ended. */
 int afhip_build_info(char* buf, int buf_len);
-/* Kernels of one menu in the loaded build, by the menu's key: "float", "packed", "packed_hist", "end_bins" or "cell_map" (the
- * LDS-histogram kernels, of every storage, for bins plans whose interior widths differ).  -1: no menu of that name. */
+/* Kernels of one menu in the loaded build, by the menu's key: "float", "packed", "packed_hist", "end_bins", "cell_map" (the
+ * LDS-histogram kernels, of every storage, for bins plans whose interior widths differ) or "packed_short" (the lean short-group kernels
+ * of AFHIP_I16 / AFHIP_U16 cubes: inner groups of two to four rows).  -1: no menu of that name. */
 int afhip_menu_size(const char* key);
 /* Number of visible GPUs (hipGetDeviceCount); 0 when there is none. */
 int afhip_device_count(void);
