@@ -206,8 +206,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1))) void k_
     static_assert(!EB || HB, "wide end bins: a histogram form");
     static_assert(!CM || (EB && !HA), "the cell map: an end-bin histogram form with the edge table");
     static_assert(!RF || VEC <= 2, "region-fused period ends: one or two cells per lane");
-    static_assert(!PACKED || (PIPE == 0 && !RF && (!PAIR || LEAN) && (HB ? (TKI && STAT <= 1) : !(TKI || SL))),
-                  "int16-packed cubes: the general forms, the lean short-group forms and the LDS-histogram forms of the direct-load path only");
+    static_assert(!PACKED || (PIPE == 0 && (!PAIR || LEAN) && (HB ? (TKI && STAT <= 1) : !(TKI || SL))),
+                  "int16-packed cubes: the general forms, the lean short-group forms (both with region-fused twins) and the LDS-histogram forms of the direct-load path only");
     const int64_t C = a.C;
     const int K = a.K;
     const int lane = threadIdx.x & 63;

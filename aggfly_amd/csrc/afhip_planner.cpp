@@ -50,6 +50,7 @@ PlanKnobs read_knobs() {
     k.no_quad_mode = set("AFHIP_NO_QUAD_MODE");
     k.no_ragged_mode = set("AFHIP_NO_RAGGED_MODE");
     k.no_region_fused = set("AFHIP_NO_REGION_FUSED");
+    k.no_packed_rf = set("AFHIP_NO_PACKED_RF");
     k.no_packed_hist = set("AFHIP_NO_PACKED_HIST");
     if (const char* e = getenv("AFHIP_PACKED_HIST_VEC")) { const int v = atoi(e); if (v == 1 || v == 2) k.packed_hist_vec = v; }
     k.no_packed_short = set("AFHIP_NO_PACKED_SHORT");
@@ -426,25 +427,77 @@ static HistPartition find_partition(const PlanLayout& pl, bool all_bins) {
 }
 
 // ---- 5. variant choice ----
-// the variant with the region-fused period ends compiled in and every other field equal (null: the menu has none)
+// the variant with the region-fused period ends compiled in and every other field equal (null: the menu has none).  Float kernels have
+// their twins in their own menu, at their own rows in flight; packed kernels (MENU_PACKED, MENU_PACKED_SHORT) in MENU_PACKED_RF, where a
+// twin may keep FEWER rows in flight than its plain kernel (gen_variants.py: PACKED_RF_SHALLOW) — every field but `depth` is matched.
+// Nothing the planner or the launch derives from the plain variant depends on that field on the direct-load path, the only one packed
+// cubes have: the LDS layout (lds_sine_offset) reads the depth of the LDS-DMA ring only, and the chunk table is laid in whole inner groups,
+// not in bursts.  (The round fill of build_chunks asks the PLAIN kernel how many workgroups a CU holds, on every storage.)
 static const Variant* twin_of(const Variant* v) {
+    const bool packed = v->dtype == AFHIP_I16;
     int n = 0;
-    const Variant* tab = menu_table(MENU_FLOAT, &n);
+    const Variant* tab = menu_table(packed ? MENU_PACKED_RF : MENU_FLOAT, &n);
     for (int i = 0; i < n; ++i) {
         const Variant& t = tab[i];
         if (t.feat == (v->feat | FEAT_REGION_FUSED) && t.dtype == v->dtype && t.pipe == v->pipe && t.vec == v->vec && t.stat == v->stat && t.nthr == v->nthr &&
-            t.kmax == v->kmax && t.depth == v->depth)
+            t.kmax == v->kmax && (packed || t.depth == v->depth))
             return &t;
     }
     return nullptr;
+}
+
+// Region-fused period ends: per-cell period values that would be a noticeable share of the traffic — P K 8 bytes per cell against T elem —
+// by the thresholds of rf_plan_ok (section 7, which says where they come from), for a plan that runs variant `v`.
+static double rf_share(const PlanLayout& pl) {
+    return (double)pl.desc.P * pl.K * 8.0 / std::max(1.0, (double)pl.desc.T * (double)elem_bytes(pl.desc.dtype));
+}
+static bool rf_share_ok(const PlanLayout& pl, const Variant* v) {
+    const bool two_row_light = v->pair() && !v->group_form() && !(v->lean() == 1 && v->kmax == 6);
+    if (!two_row_light) return rf_share(pl) >= 0.002;
+    return rf_share(pl) >= (is_packed_dtype(pl.desc.dtype) ? 0.10 : 0.05);
+}
+
+// Packed cubes: what can be known BEFORE chunking of whether a plan that would run `v` takes the region-fused route — everything
+// rf_plan_ok asks but the one-slot-per-period test: a twin in the library, several periods, no table-order promise, no float32 rounding of
+// the final value, the share of the period values, and neither AFHIP_NO_REGION_FUSED nor AFHIP_NO_PACKED_RF.  (Up to six columns and four
+// threshold slots: MENU_PACKED_RF holds no other twin.)
+//   `gives_up_four`: the rows are a multiple of four and the library holds the plan's kernel at four cells per lane, which has no twin — taking
+// `v` costs the plan that kernel.  The four-cell kernel is ahead over the whole stream (x0.63 ... x0.96 on the short-group forms,
+// profiles/packed_short_groups.txt) and the twin saves at the period ends alone, so such a plan is a candidate
+//   - from PACKED_RF_NARROW_MIN_P periods on (below eight build_chunks lays no chunk per period either; the float32 twins gain 3 - 6 % at twelve),
+//   - and a short-group plan only with period values of a quarter of the cube's bytes and more: on the configs[1] shape (rows a multiple of
+//     four: the two-cell twin against the four-cell kernel on the per-cell route, profiles/packed_region_fused.txt, section 2) the 6-hourly
+//     monthly polynomial (share 0.13) is BEHIND at x1.01 — and ahead at x0.94 / x0.95 where both routes run two cells or one —, weekly sine_dd
+//     from pairs (0.29) ahead at x0.94, daily 8-hourly and mixed-length panels (5.3) at x0.37.  The general forms are ahead at every share
+//     measured (monthly polynomial, 0.024: x0.91 ... x0.94; weekly x0.88 ... x0.90; daily degree days x0.90 ... x0.92; the daily K = 5 panel x0.77).
+constexpr int64_t PACKED_RF_NARROW_MIN_P = 8;
+static bool packed_rf_candidate(const PlanLayout& pl, const PlanKnobs& knobs, const Variant* v, bool gives_up_four) {
+    if (!v || knobs.no_region_fused || knobs.no_packed_rf || pl.desc.exact_order || pl.desc.P < 2 || pl.K > 6 || pl.nthr > 4) return false;
+    for (const ColOp& c : pl.cols)
+        if (c.rounding & AFHIP_ROUND_FINAL) return false;
+    if (gives_up_four && (pl.desc.P < PACKED_RF_NARROW_MIN_P || (v->pair() && rf_share(pl) < 0.25))) return false;
+    return twin_of(v) != nullptr && rf_share_ok(pl, v);
 }
 
 // int16- and uint16-packed cubes (AFHIP_I16, AFHIP_U16) have a menu of their own (MENU_PACKED) of general forms on the direct-load path: the
 // widest row piece per lane the rows allow and the menu holds for the plan's shape — four cells (8 bytes, the light shapes only), else
 // two, else one.  (Four against two cells on the light shapes is the float32 rule "8 bytes per lane" carried over; not measured on
 // packed cubes yet: profiles/packed_cube.txt.)
-static const Variant* choose_packed_variant(const PlanLayout& pl) {
+//   The four-cell forms have no region-fused twin (the period end's scan is written for one and two cells per lane).  A plan that is a
+// candidate for that route (packed_rf_candidate) therefore takes the widest of two cells and one that divides the rows, where that
+// kernel has a twin; where it has none (gen_variants.py: PACKED_RF_DROPPED) the choice is the one above.  The cost: a run of such a plan that
+// wants the per-cell values (`want_cells`), or whose table has no runs that fit, goes through the two-cell plain kernel instead of the
+// four-cell one.  AFHIP_NO_PACKED_RF restores the choice above, widths included.
+// A plan whose rows allow four cells is a candidate under the further conditions of packed_rf_candidate (`gives_up_four`).
+static const Variant* choose_packed_variant(const PlanLayout& pl, const PlanKnobs& knobs) {
     const int64_t C = pl.desc.n_cells;
+    const bool gives_up_four = C % 4 == 0 && find_exact_form(MENU_PACKED, AFHIP_I16, 4, pl.stat, pl.nthr, pl.K, false, false) != nullptr;
+    for (int vec : {2, 1}) {
+        if (C % vec != 0) continue;
+        const Variant* v = find_exact_form(MENU_PACKED, AFHIP_I16, vec, pl.stat, pl.nthr, pl.K, false, false);
+        if (v && packed_rf_candidate(pl, knobs, v, gives_up_four)) return v;
+        if (v) break;          // (the widest of the two the rows allow and the menu holds: no narrower kernel for the sake of a twin)
+    }
     for (int vec : {4, 2, 1}) {
         if (C % vec != 0) continue;
         if (const Variant* v = find_exact_form(MENU_PACKED, AFHIP_I16, vec, pl.stat, pl.nthr, pl.K, false, false)) return v;
@@ -478,6 +531,14 @@ static const Variant* choose_packed_short_variant(const PlanLayout& pl, const Pl
     };
     if (knobs.packed_short_vec)
         if (const Variant* v = find(knobs.packed_short_vec, true)) return v;
+    // (a candidate for the region-fused route: two cells or one, as in choose_packed_variant and at the same cost — four cells against two
+    // measured x0.63 ... x0.96 on the per-cell route, profiles/packed_short_groups.txt)
+    const bool gives_up_four = find(4, false) != nullptr;
+    for (int vec : {2, 1})
+        if (const Variant* v = find(vec, false)) {
+            if (packed_rf_candidate(pl, knobs, v, gives_up_four)) return v;
+            break;
+        }
     for (int vec : {4, 2, 1})
         if (const Variant* v = find(vec, false)) return v;
     return nullptr;
@@ -761,13 +822,12 @@ static bool rf_plan_ok(const PlanLayout& pl, const PlanKnobs& knobs) {
     const afhip_plan_desc* desc = &pl.desc;
     const Variant* v = pl.variant;
     bool ok = pl.variant_rf != nullptr && !desc->exact_order && desc->P >= 2 && !knobs.no_region_fused;
+    if (is_packed_dtype(desc->dtype) && knobs.no_packed_rf) ok = false;      // (the A/B knob of scripts/packed_rf_bench.py)
     for (const ColOp& c : pl.cols) ok = ok && !(c.rounding & AFHIP_ROUND_FINAL);      // (identity outers too: a daily panel of daily means)
     for (int64_t p = 0; ok && p < desc->P; ++p) ok = pl.slot_ptr[(size_t)p + 1] - pl.slot_ptr[(size_t)p] <= 1;
     // ... and per-cell period values that would be a noticeable share of the traffic: P K 8 bytes per cell against T elem.  Below
     // ~0.2 % there is nothing to win and the emit still costs: configs[2]'s shape (40 annual values of 2 columns from 350,640
     // hourly steps: 0.05 %) measured 0.25 % behind, the one-period headline (0.06 %) 0.6 %; the shapes that gain sit at 0.5 % and up.
-    const double share = (double)desc->P * pl.K * 8.0 / std::max(1.0, (double)desc->T * (double)elem_bytes(desc->dtype));
-    if (ok) ok = share >= 0.002;
     // Which forms gain was measured, not derived (profiles/r03_region_fused.txt: an occupancy rule could not tell them apart): float64
     // forms and float32 forms without threshold slots gain 3 - 50 % from two periods on; the lean four-row forms and the six-column
     // lean pair form likewise (6-hourly monthly polynomial: step 0.97 against 1.13 - 1.33 ms).
@@ -777,8 +837,14 @@ static bool rf_plan_ok(const PlanLayout& pl, const PlanKnobs& knobs) {
     // two-row forms other than the six-column lean one (sine_dd from (tmin, tmax) pairs: a period end every few rows) pay only where
     // the per-cell route's own traffic decides: monthly 4.44 against 3.77 ms (behind), weekly 5.80 against 6.20, daily 17.7 against
     // 21.5 — from period values of 5 % of the cube.
-    const bool two_row_light = v->pair() && !v->group_form() && !(v->lean() == 1 && v->kmax == 6);
-    if (ok && two_row_light) ok = share >= 0.05;
+    //   Packed cubes (profiles/packed_region_fused.txt, sections 2 and 3: scripts/packed_rf_bench.py on the configs[1] shape held as int16, the
+    // twin's median against the per-cell route's minimum in one process, on rows that take two cells per lane on both routes / one): the
+    // same rule holds at 0.2 % — monthly polynomial (share 0.024) x0.95 ... x0.99, weekly x0.89 ... x0.94, daily degree days x0.83 / x0.86, the
+    // daily K = 5 panel x0.75 / x0.63, 6-hourly monthly polynomial x0.94 / x0.95, daily 8-hourly and mixed-length panels x0.37 ... x0.43.  The
+    // light two-row forms: the same jobs are twice the share at two bytes an element, and the threshold doubles with them — sine_dd from pairs
+    // monthly (0.067) is BEHIND at x1.05 / x1.04, weekly (0.29) ahead at x0.80 / x0.83, daily (2.0) at x0.48 / x0.50: from period values of 10 %
+    // of the cube.
+    if (ok) ok = rf_share_ok(pl, v);
     return ok;
 }
 
@@ -863,7 +929,7 @@ int build_plan(const afhip_plan_desc* desc, const DeviceFacts& dev, PlanLayout* 
     if ((rc = lower_columns(pl))) return rc;
 
     // int16 and uint16 storage alike (the kernels take the signedness from the bound packing).  Their menus hold no tuning arm that
-    // `tuning` names and no region-fused twin; of the short-group forms the lean ones.
+    // `tuning` names; of the short-group forms the lean ones; region-fused twins at two cells and at one cell per lane (MENU_PACKED_RF).
     const bool packed = is_packed_dtype(desc->dtype);
     const int tuning = packed ? 0 : usable_tuning(pl->desc);
     bool all_bins = pl->nthr > 0;
@@ -886,7 +952,7 @@ int build_plan(const afhip_plan_desc* desc, const DeviceFacts& dev, PlanLayout* 
         // the lean short-group forms, else the packed menu of general forms: no packed counts (packed_format finds no integer-bin
         // form); the spatial stage is the slot gather or the table-order sums
         pl->variant = choose_packed_short_variant(*pl, knobs);
-        if (!pl->variant) pl->variant = choose_packed_variant(*pl);
+        if (!pl->variant) pl->variant = choose_packed_variant(*pl, knobs);
     } else if (!pl->variant) {
         const GroupForm form = short_group_form(*pl, knobs);
         const LoadPath path = load_path(*pl, form.pairs);
@@ -896,7 +962,7 @@ int build_plan(const afhip_plan_desc* desc, const DeviceFacts& dev, PlanLayout* 
         return packed ? fail(AFHIP_E_UNSUPPORTED, "no packed kernel variant for stat=%d slots=%d columns=%d", pl->stat, pl->nthr, pl->K)
                       : fail(AFHIP_E_UNSUPPORTED, "no kernel variant for dtype=%d stat=%d slots=%d columns=%d", desc->dtype, pl->stat, pl->nthr, pl->K);
     if ((rc = build_chunks(pl, pl->variant->vec, knobs, dev))) return rc;
-    pl->variant_rf = twin_of(pl->variant);      // (the float menu alone holds twins: null on packed storage, and rf_plan_ok false)
+    pl->variant_rf = twin_of(pl->variant);      // (null: the storage's menu of twins holds none for this kernel, and rf_plan_ok is false)
     pl->rf_plan_ok = rf_plan_ok(*pl, knobs);
     pl->gtab = group_table(*pl);
     pl->pk = packed_format(*pl);

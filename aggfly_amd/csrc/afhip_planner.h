@@ -46,6 +46,7 @@ struct PlanKnobs : RunKnobs {
     bool no_period_chunks = false, no_round_fill = false;                    // AFHIP_NO_PERIOD_CHUNKS, AFHIP_NO_ROUND_FILL
     bool no_pair_mode = false, no_quad_mode = false, no_ragged_mode = false;  // AFHIP_NO_PAIR_MODE, AFHIP_NO_QUAD_MODE, AFHIP_NO_RAGGED_MODE
     bool no_region_fused = false;                                            // AFHIP_NO_REGION_FUSED
+    bool no_packed_rf = false;     // AFHIP_NO_PACKED_RF: packed cubes' plans choose their kernels and routes as they did without the region-fused twins of MENU_PACKED_RF
     bool no_packed_hist = false;   // AFHIP_NO_PACKED_HIST: packed cubes' partition plans take the general packed kernel, not the LDS-histogram forms
     int packed_hist_vec = 0;       // AFHIP_PACKED_HIST_VEC=1|2: the cells per lane such a plan takes where the library holds the kernel, arms included (0: the planner's rule)
     bool no_packed_short = false;  // AFHIP_NO_PACKED_SHORT: packed cubes' short-group plans take the general packed kernel, not the lean short-group forms

@@ -37,7 +37,7 @@ struct Variant {
     bool sine_p2() const { return feat_sine_p2(feat); }                   // sine_dd plans: the P2 table instead of the acos table
 };
 
-// The kernel menus (gen_variants.py: MENUS, same names and order; the generated table asserts it).
+// The kernel menus (gen_variants.py: TABLE_MENUS, same names and order; the generated table asserts it).
 //   MENU_FLOAT        float32 / float64 cubes: every form (gen_variants.py: menu), searched by find_variant
 //   MENU_PACKED       int16- and uint16-packed cubes (AFHIP_I16, AFHIP_U16: one set of AFHIP_I16 kernels, the signedness is in the unpack
 //                     record; packed_menu): general two-level forms on the direct-load path only, all production
@@ -49,10 +49,12 @@ struct Variant {
 //                     (cell_map_menu), all production
 //   MENU_PACKED_SHORT the lean short-group forms of packed cubes (gen_variants.py: MORE_MENUS, packed_short_menu): two-, three-, four-row
 //                     and mixed inner groups, the float32 lean menu's shapes at two cells and at one cell per lane, most of them at four as well, all production
-// All but the first are searched by find_exact_form.
-enum Menu { MENU_FLOAT, MENU_PACKED, MENU_PACKED_HIST, MENU_END_BINS, MENU_CELL_MAP, MENU_PACKED_SHORT, MENU_COUNT };
+//   MENU_PACKED_RF    the region-fused twins (FEAT_REGION_FUSED) of MENU_PACKED's and MENU_PACKED_SHORT's kernels at two cells and at one cell
+//                     per lane (gen_variants.py: LATER_MENUS, packed_rf_menu), all production; searched by twin_of (afhip_planner.cpp)
+// MENU_PACKED ... MENU_PACKED_SHORT are searched by find_exact_form.
+enum Menu { MENU_FLOAT, MENU_PACKED, MENU_PACKED_HIST, MENU_END_BINS, MENU_CELL_MAP, MENU_PACKED_SHORT, MENU_PACKED_RF, MENU_COUNT };
 const Variant* menu_table(Menu menu, int* n);   // generated (variants_table.hip): the menu's kernels, in gen_variants.py's order
-const char* menu_key(Menu menu);                // generated: the menu's key in gen_variants.py's MENUS ("float", "packed", ... "packed_short")
+const char* menu_key(Menu menu);                // generated: the menu's key in gen_variants.py's TABLE_MENUS ("float", "packed", ... "packed_rf")
 const char* variants_menu();                    // "full" (the production menu), "arms" (+ the tuning arms) or "dev"
 
 // What a lowered plan asks of the menu (afhip_planner.cpp: choose_variant).  A fallback is the same query with a field changed.

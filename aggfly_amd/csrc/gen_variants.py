@@ -11,9 +11,10 @@ for partitions with a wide end bin (`end_bins_menu`: Feat.END_BINS, float32, flo
 ``cell_map_NN.hip`` and ``cell_map_packed_NN.hip``.  ``variants_table.hip`` collects ONE table, a slice per menu in `MENUS` order, behind
 ``menu_table`` (afhip_variants.h), which ``find_variant`` and ``find_exact_form`` search; every menu keeps its own count and contents.
 `MORE_MENUS` continues the list — the lean short-group kernels of packed cubes (`packed_short_menu`) in ``packed_short_NN.hip`` — and
-`ALL_MENUS` is the two together, which the table follows.
+`ALL_MENUS` is the two together; `LATER_MENUS` goes on behind them — the region-fused twins of packed cubes' general and short-group kernels
+(`packed_rf_menu`) in ``packed_rf_NN.hip`` — and `TABLE_MENUS` is all of them, which the table follows.
 
-Adding a menu: a menu function and an entry of `MORE_MENUS` here, the enumerator of the same name in afhip_variants.h's `Menu` (the table asserts
+Adding a menu: a menu function and an entry of `LATER_MENUS` here, the enumerator of the same name in afhip_variants.h's `Menu` (the table asserts
 that the two agree), and a recipe module under tests/ beside `variant_recipes` ("Adding a kernel menu").
 """
 import os
@@ -58,6 +59,14 @@ SUFFIXES = ((Feat.NT, "_nt"), (Feat.INT_BINS, "_ibins"), (Feat.SINGLE_LEVEL, "_s
             (Feat.SHORT_GROUP, "_pair"), (Feat.LEAN, "_lean"), (Feat.FOUR_ROW, "_quad"), (Feat.THREE_ROW, "_tri"), (Feat.MIXED, "_rag"),
             (Feat.REGION_FUSED, "_rf"))
 
+# packed_rf_menu: the twins that hold scratch memory at their plain kernel's rows in flight — keys (cells per lane, stat, slots, columns,
+# short-group feature bits or 0).  PACKED_RF_SHALLOW: those that hold none at HALF the depth, and that depth (sixteen -> eight, the
+# stat-2 six-column pair form eight -> four: the depths the packed menus use).  PACKED_RF_DROPPED: those that hold the same 36 bytes per
+# lane at every depth probed (1, 2, 4, 6 ... 16; some of them at 52 VGPRs: not a register spill) — no twin, such a plan keeps the per-cell route.
+PACKED_RF_SHALLOW = {**{(1, stat, nthr, kmax, 0): 8 for stat, nthr, kmax in ((0, 4, 2), (1, 1, 6))},
+                     **{(2, stat, 0, kmax, 0): 8 for stat in (1, 2) for kmax in (2, 6)},
+                     **{(vec, 2, 0, 6, Feat.SHORT_GROUP | Feat.LEAN): 4 for vec in (2, 1)}}
+PACKED_RF_DROPPED = {(1, 0, 4, 6, 0), (1, 1, 4, 6, 0), (1, 3, 1, 6, 0), (1, 3, 4, 2, 0), (1, 3, 4, 6, 0), (2, 3, 0, 2, 0), (2, 3, 0, 6, 0)}
 
 def menu(kind):
     """(dtype, pipe, vec, stat, nthr, kmax, depth, feat, production)"""
@@ -195,7 +204,8 @@ def menu(kind):
 
 def packed_menu(kind):
     """The kernels of int16-packed cubes (storage tag PackedI16), same tuples as `menu`: the general two-level forms on the direct-load
-    path with nt loads — no short-group, lean, single-level, integer-bin, histogram or region-fused form.  Every shape at two cells and
+    path with nt loads — no short-group, lean, single-level, integer-bin or histogram form (the short-group forms and the region-fused twins
+    have menus of their own: `packed_short_menu`, `packed_rf_menu`).  Every shape at two cells and
     at one cell per lane (4 / 2 bytes per lane and row); the light shapes also at four (8 bytes, what a float32 lane reads at two cells).
     Rows in flight: eight at four cells per lane — 64 bytes per lane, the float32 production forms' — and sixteen at two and one,
     whose rows are half and a quarter of that (PACKED_SHALLOW: one exception).  Chosen from -Rpass-analysis=kernel-resource-usage, not from a measurement: no kernel of the menu has scratch memory
@@ -279,7 +289,8 @@ def packed_short_menu(kind):
     168 to 171 VGPRs and two or three waves per SIMD; such a plan takes two cells per lane.
     All production, by the measurement of scripts/packed_short_bench.py on the configs[1] shape (profiles/packed_short_groups.txt, section
     2): every wider kernel's median lies below the next narrower one's minimum (four cells against two: x0.63 ... x0.96; two against one:
-    x0.53 ... x0.82), and every class of plans beats the general packed kernel.  The `dev` menu has none of them."""
+    x0.53 ... x0.82), and every class of plans beats the general packed kernel.  The `dev` menu has none of them.  Their region-fused
+    twins, at two cells and at one, are in `packed_rf_menu`."""
     def one(vec, stat, kmax, depth, form=0, ss=1):
         feat = (Feat.SINE if stat == 2 else 0) | Feat.NT | Feat.SHORT_GROUP | Feat.LEAN | (Feat.LEAN_SINE if ss == 2 else 0) | form
         return (I16, 0, vec, stat, 0, kmax, depth, feat, 1)
@@ -293,6 +304,32 @@ def packed_short_menu(kind):
         for form, depth in ((Feat.FOUR_ROW, 8), (Feat.THREE_ROW, 6), (Feat.MIXED, 8)):
             out += [one(vec, stat, kmax, depth, form) for stat in (1, 2) for kmax in (2, 6)]
     return [v for v in out if v[2:4] + v[5:6] not in PACKED_SHORT_DROPPED]
+
+
+def packed_rf_menu(kind):
+    """The region-fused twins (Feat.REGION_FUSED, names `i16_..._rf`) of int16-packed cubes' kernels (afhip_planner.cpp: twin_of), same
+    tuples as `menu`: of every production kernel of `packed_menu` at two cells and at one cell per lane with up to six columns and four
+    threshold slots — the float rule of `menu` — and of every production kernel of `packed_short_menu` at two cells and at one.  No
+    four-cell twin (the period end's scan is written for one and two cells per lane), none for the histogram menus.  Units of their own
+    (``packed_rf_NN.hip``, compiled with the Makefile's PACKED_FLAGS): the older menus keep their counts and contents.
+    Rows in flight are the plain kernel's, unless the twin then holds scratch memory (-Rpass-analysis=kernel-resource-usage;
+    profiles/packed_region_fused.txt has the register table and every depth probed): PACKED_RF_SHALLOW names those and their depth — half
+    the plain kernel's, a multiple of the group length and one of the depths the packed menus use; a twin with scratch at every depth is
+    left out (PACKED_RF_DROPPED: such a plan keeps the per-cell route).  No kernel of the menu has scratch memory: 61 kernels.
+    All production, by the measurement of scripts/packed_rf_bench.py (profiles/packed_region_fused.txt, sections 2 and 3; afhip_planner.cpp:
+    rf_plan_ok and packed_rf_candidate hold the thresholds it set): every twin can be selected by some plan.  The `dev` menu has none of them."""
+    if kind == "dev":
+        return []
+    out = []
+    plain = [v for v in packed_menu("full") if v[2] <= 2 and v[5] <= 6 and v[4] <= 4] + [v for v in packed_short_menu("full") if v[2] <= 2]
+    for dtype, pipe, vec, stat, nthr, kmax, depth, feat, prod in plain:
+        if not prod:
+            continue
+        key = (vec, stat, nthr, kmax, feat & (Feat.SHORT_GROUP | Feat.LEAN | Feat.LEAN_SINE | GROUP_LENGTH))
+        if key in PACKED_RF_DROPPED:
+            continue
+        out.append((dtype, pipe, vec, stat, nthr, kmax, PACKED_RF_SHALLOW.get(key, depth), feat | Feat.REGION_FUSED, 1))
+    return out
 
 
 def pickable(v):
@@ -389,10 +426,16 @@ MORE_MENUS = (
     ("packed_short", packed_short_menu, (("packed_short", (I16,)),)),
 )
 ALL_MENUS = MENUS + MORE_MENUS
+# ... and on: the menus behind those six (a further tuple for the same reason: `MORE_MENUS` holds one menu and `ALL_MENUS` is the two above,
+# by the packed short-group menu's tests).  `TABLE_MENUS` is every menu, in table order.
+LATER_MENUS = (
+    ("packed_rf", packed_rf_menu, (("packed_rf", (I16,)),)),
+)
+TABLE_MENUS = ALL_MENUS + LATER_MENUS
 
 
 def write_table(outdir, kind, slices, units):
-    """variants_table.hip: the table of every menu.  `slices`: the kernel count per menu, in ALL_MENUS order; `units`: every unit's name."""
+    """variants_table.hip: the table of every menu.  `slices`: the kernel count per menu, in TABLE_MENUS order; `units`: every unit's name."""
     fn = os.path.join(outdir, "variants_table.hip")
     starts = [sum(slices[:i]) for i in range(len(slices) + 1)]
     with _KeepIfSame(fn) as f:
@@ -401,15 +444,15 @@ def write_table(outdir, kind, slices, units):
         f.write("namespace afhip {\n")
         for name in FEAT_NAMES:
             f.write(f'static_assert(FEAT_{name} == {getattr(Feat, name)}, "gen_variants.py and afhip_plan_types.h disagree on a FEAT bit");\n')
-        f.write(f'static_assert(MENU_COUNT == {len(ALL_MENUS)}, "gen_variants.py and afhip_variants.h disagree on the menus");\n')
-        for i, (key, _, _) in enumerate(ALL_MENUS):
+        f.write(f'static_assert(MENU_COUNT == {len(TABLE_MENUS)}, "gen_variants.py and afhip_variants.h disagree on the menus");\n')
+        for i, (key, _, _) in enumerate(TABLE_MENUS):
             f.write(f'static_assert(MENU_{key.upper()} == {i}, "gen_variants.py and afhip_variants.h disagree on the menus");\n')
         for u in units:
             f.write(f"int register_{u}(Variant* out);\n")
         f.write(f"static Variant g_table[{max(starts[-1], 1)}];\nstatic int g_count = -1;\n")
         f.write(f"static const int g_start[MENU_COUNT + 1] = {{{', '.join(map(str, starts))}}};      // each menu's slice of g_table\n")
         f.write(f'const char* variants_menu() {{ return "{kind}"; }}\n')
-        keys = ", ".join(f'"{key}"' for key, _, _ in ALL_MENUS)
+        keys = ", ".join(f'"{key}"' for key, _, _ in TABLE_MENUS)
         f.write(f"const char* menu_key(Menu m) {{\n    static const char* const keys[MENU_COUNT] = {{{keys}}};\n    return keys[m];\n}}\n")
         f.write("const Variant* menu_table(Menu m, int* n) {\n    if (g_count < 0) {\n        int c = 0;\n")
         for u in units:
@@ -431,7 +474,7 @@ def main():
             per_file = int(args.pop(0))
     os.makedirs(outdir, exist_ok=True)
     files, slices = [], []
-    for key, fn, stems in ALL_MENUS:
+    for key, fn, stems in TABLE_MENUS:
         vs = fn(kind)
         assert all(sum(v[0] in dtypes for _, dtypes in stems) == 1 for v in vs), key      # every kernel in one stem's units
         slices.append(len(vs))

@@ -162,8 +162,8 @@ def device_count() -> int:
 
 
 def menu_size(key: str) -> int:
-    """Kernels of the menu `key` in the loaded build ("float", "packed", "packed_hist", "end_bins", "cell_map", "packed_short": the
-    keys of gen_variants.py's ALL_MENUS); -1 for a key that names no menu (`afhip_menu_size`)."""
+    """Kernels of the menu `key` in the loaded build ("float", "packed", "packed_hist", "end_bins", "cell_map", "packed_short", "packed_rf":
+    the keys of gen_variants.py's TABLE_MENUS); -1 for a key that names no menu (`afhip_menu_size`)."""
     return int(load().afhip_menu_size(key.encode()))
 
 

@@ -321,7 +321,9 @@ int afhip_plan_bind_inter(afhip_plan* plan, int column, const void* inter_dev, i
  * A pair half the chain lacks is sent as its exact identity: mul 1.0f, add -0.0f.  At most three pairs (unpack + a unit conversion or two).
  * afhip_plan_bind_packing: like afhip_plan_bind_inter, copied into the plan and read by every later run; an AFHIP_I16 / AFHIP_U16 plan that runs
  * unbound fails with AFHIP_E_INVALID, and binding a plan of another dtype is refused.  Such plans take the general kernels of the
- * direct-load path (no short-group, single-level, histogram or region-fused form) and the slot-gather / table-order spatial stage.  The
+ * direct-load path (no single-level form) and the slot-gather / table-order spatial stage; a plan of several output periods, without
+ * exact_order, takes the region-fused period ends as a float plan does where the library holds the twin of its kernel (general and lean
+ * short-group kernels at one and two cells per lane: afhip_menu_size("packed_rf"); afhip_plan_describe then says so).  The
  * afhip_group_* entry points and afhip_transform keep to AFHIP_F32 / AFHIP_F64.
  * AFHIP_U16 differs in one thing: the 16 stored bits are unsigned, f = (float)(unsigned)q (exact for 0..65535), and q == fill compares the
  * unsigned value.  A fill must lie in the storage's range (-32768..32767 / 0..65535).  Both dtypes run the same kernels: the signedness is a
