@@ -1,15 +1,27 @@
 """``aggfly`` command (`aggfly/cli/main.py:18-255`): info | regions | validate | weights | run."""
 from __future__ import annotations
 
+import os
 import sys
 
 import click
 
 from . import config as cfg
+from . import launch as launcher
 from . import pipeline
 
+_ARGV = "aggfly_amd.cli.argv"
 
-@click.group()
+
+class _Cli(click.Group):
+    """Keeps the command line as it was typed: `run` hands it on, unchanged, to the ranks it starts."""
+
+    def parse_args(self, ctx, args):
+        ctx.meta[_ARGV] = list(args)
+        return super().parse_args(ctx, args)
+
+
+@click.group(cls=_Cli)
 def cli():
     """Aggregate gridded climate data onto regions on AMD MI355X GPUs."""
 
@@ -133,6 +145,18 @@ def weights(config, project_dir, verbose):
         click.echo(f"Cached under: {c.project_dir}")
 
 
+def _gpus_option(ctx, param, value):
+    try:
+        return launcher.parse_gpus(value)
+    except ValueError as e:
+        raise click.BadParameter(str(e))
+
+
+def _visible_gpus() -> int:
+    import torch          # counting devices does not initialise the GPU
+    return torch.cuda.device_count()
+
+
 @cli.command()
 @click.argument("config")
 @click.option("-o", "--output", default=None, help="Override output.path from the config.")
@@ -141,12 +165,23 @@ def weights(config, project_dir, verbose):
 @click.option("--years", default=None, help="Override years for a {year}-templated dataset path (e.g. 1980:1990).")
 @click.option("--project-dir", default=None, help="Override weights.project_dir (weight cache).")
 @click.option("--backend", type=click.Choice(sorted(cfg.ALLOWED_BACKEND)), default=None,
-              help="Override execution.backend (accepted; there is no dask cluster here, ranks come from torch.distributed.run).")
-@click.option("--n-workers", type=int, default=None, help="Override execution.n_workers (accepted, unused).")
+              help="Override execution.backend (accepted for the reference's configs; there is no dask cluster here: "
+                   "workers are ranks, one process per GPU, see --n-workers and --gpus).")
+@click.option("--n-workers", type=int, default=None,
+              help="Override execution.n_workers: the ranks to start, one GPU each; at most the visible GPUs and, for a "
+                   "{year}-templated path, the years.  1 (the default) runs in this process.")
+@click.option("--gpus", default=None, callback=_gpus_option, metavar="N|all",
+              help="Start exactly N ranks, one GPU each (all = every visible GPU); refused when fewer GPUs are visible.  "
+                   "Wins over --n-workers.")
 @click.option("-v", "--verbose", is_flag=True, help="Print per-step progress.")
 @click.option("--quiet", is_flag=True, hidden=True)
-def run(config, output, engine, years, project_dir, backend, n_workers, verbose, quiet):
-    """Run the full aggregation pipeline from a config file and write the region-by-period panel."""
+@click.pass_context
+def run(ctx, config, output, engine, years, project_dir, backend, n_workers, gpus, verbose, quiet):
+    """Run the full aggregation pipeline from a config file and write the region-by-period panel.
+
+    With --gpus or execution.n_workers above 1 the command starts one rank per GPU (a child `python -m
+    torch.distributed.run` with this same command line) and waits for it; the ranks share the years of a
+    {year}-templated path, or the output periods of a single store, and rank 0 writes the panel."""
     c = _load_or_exit(config)
     if output is not None:
         c.output_path = output
@@ -165,6 +200,16 @@ def run(config, output, engine, years, project_dir, backend, n_workers, verbose,
         c.years = cfg._parse_years(years, errs)
         if errs:
             raise click.ClickException("; ".join(errs))
+    # one rank per GPU: decided and started before anything below touches torch's GPU side or the HIP library
+    n_visible = _visible_gpus() if launcher.needs_gpu_count(c, gpus, os.environ) else 0
+    try:
+        n_ranks, why = launcher.plan_ranks(c, gpus, os.environ, n_visible, len(c.resolved_paths()))
+    except launcher.LaunchRefused as e:
+        raise click.ClickException(str(e))
+    if n_ranks > 1:
+        if verbose:
+            click.echo(f"Starting {n_ranks} ranks ({why})", err=True)
+        sys.exit(launcher.launch(n_ranks, ctx.meta.get(_ARGV, sys.argv[1:]), c))
     _resolve_preprocess(c)
     _maybe_init_distributed()
     log = click.echo if verbose else (lambda m: None)
@@ -182,7 +227,6 @@ def run(config, output, engine, years, project_dir, backend, n_workers, verbose,
 
 
 def _maybe_init_distributed():
-    import os
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch.distributed as dist
         if not dist.is_initialized():

@@ -2,9 +2,11 @@
 ``aggregate_dataset`` per resolved ``{year}`` path -> concatenated panel -> writer.
 
 The reference loops the years sequentially in one process.  Here the loop is the multi-GPU
-time-shard scheduler: launched under ``torch.distributed.run`` each rank takes every
+time-shard scheduler: launched under ``torch.distributed.run`` (by hand, or by ``run --gpus N`` /
+``execution.n_workers``: `launch.py`) each rank takes every
 ``world``-th path (a year is an outer-period-aligned time shard), reduces it on its own GPU,
-and the per-year region x period panels are all-gathered (RCCL over xGMI) to rank 0.
+and the per-year region x period panels are all-gathered (RCCL over xGMI) to rank 0.  The sample
+year the weights are laid on is loaded by its owner only; the other ranks open it for its grid.
 A config with ONE un-templated store is cut along time inside the store instead (`run_store`):
 ranks take runs of output periods and stream only their own chunks; a share beyond the HBM
 budget (``AGGFLY_HIP_WINDOW_BYTES``, default 60 % of the free HBM) goes through in windows.
@@ -150,12 +152,31 @@ def find_weights_table(config) -> str:
         "aggfly's calculate_weights() (weights are computed on the CPU by aggfly.weights, not by this engine)")
 
 
-def compute_weights(config, log=lambda m: None):
+def _streams_from_store(path) -> bool:
+    """Is `path` a file the streaming route takes (one Zarr store or netCDF-4 file, a GPU to stream to)?  Only there does
+    ``time_window`` cut the read itself; everywhere else `dataset_from_path` reads the file whole and cuts on the host."""
+    from .. import hip, io as afio
+    if hip.device_count() == 0 or not isinstance(path, str) or any(ch in path for ch in "*?[") or "://" in path:
+        return False
+    return afio._looks_like_zarr(path) or (os.path.isfile(path) and afio._is_hdf5(path))
+
+
+def load_grid(config, path, georegions):
+    """`path` opened for its grid and coordinates only (no time step is read), the way `distributed.aggregate_store_cells`
+    opens its ``head``; today's full load where the streaming route does not take the file."""
+    if not _streams_from_store(path):
+        return load_dataset(config, path, georegions)
+    return af.dataset_from_path(path, var=config.var, device="cuda", time_window=(0, 0), **_open_kwargs(config, georegions))
+
+
+def compute_weights(config, log=lambda m: None, sample_data=True):
+    """-> (weights, georegions, sample).  ``sample_data=False``: the caller only wants the weights laid on the sample
+    year's grid (a rank that does not own that year), so the sample comes back without its time steps."""
     log(f"Loading regions: {config.regions_path}")
     georegions = build_regions(config)
     path0 = config.resolved_paths()[0]
-    log(f"Loading sample layer: {path0}")
-    sample = load_dataset(config, path0, georegions)
+    log(f"Loading sample layer: {path0}" + ("" if sample_data else " (grid only)"))
+    sample = load_dataset(config, path0, georegions) if sample_data else load_grid(config, path0, georegions)
     tpath = find_weights_table(config)
     log(f"Loading weights table: {tpath}")
     weights = af.weights_from_objects(sample, georegions, table=_read_table(tpath),
@@ -171,10 +192,12 @@ def run_pipeline(config, log=lambda m: None):
         df = run_store(config, paths[0], log)
         if df is not None:
             return df
-    weights, georegions, sample = compute_weights(config, log)
-    aggregator_dict = config.to_aggregator_dict()
     rank, world = D.world()
     mine = list(range(len(paths)))[rank::world]
+    # the sample year is read once per job: only its owner loads it (and reuses it as its first dataset), the other
+    # ranks open it for the grid the weights are laid on
+    weights, georegions, sample = compute_weights(config, log, sample_data=0 in mine)
+    aggregator_dict = config.to_aggregator_dict()
     frames = {}
     for i in mine:
         log(f"Aggregating [{i + 1}/{len(paths)}] on rank {rank}: {paths[i]}")
