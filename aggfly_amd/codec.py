@@ -80,6 +80,10 @@ def load():
         lib.afcodec_inflate_scratch_bytes.argtypes = [C.c_int64] * 6
         lib.afcodec_inflate_emulate.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int64] * 6 + [
             C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        lib.afcodec_lz4_encode_emulate.restype = C.c_int64
+        lib.afcodec_lz4_encode_emulate.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+        lib.afcodec_blosc_encode_plan.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
+                                                  C.POINTER(C.c_int64), C.c_void_p]
         lib.afcodec_read_packed.argtypes = [C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
                                             C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
         _lib = lib
@@ -91,7 +95,7 @@ EXPORTS = ("afcodec_last_error", "afcodec_have", "afcodec_blosc_info", "afcodec_
            "afcodec_blosc_bound", "afcodec_blosc_encode_lz4", "afcodec_zstd_decode", "afcodec_zstd_bound", "afcodec_zstd_encode", "afcodec_lz4_decode", "afcodec_blosc_lz4_plan", "afcodec_read_packed",
            "afcodec_zstd_plan", "afcodec_zstd_scratch_bytes", "afcodec_zstd_emulate",
            "afcodec_inflate_plan", "afcodec_inflate_scratch_bytes", "afcodec_inflate_emulate",
-           "afcodec_blosc_plan", "afcodec_blosc_encode")
+           "afcodec_blosc_plan", "afcodec_blosc_encode", "afcodec_lz4_encode_emulate", "afcodec_blosc_encode_plan")
 
 
 def _err(lib, what):
@@ -314,6 +318,92 @@ def blosc_lz4_plan(base: np.ndarray, comp_off, comp_size, out_off, out_size, str
             raise PlanCapacityError(f"blosc_lz4_plan: {msg}")
         raise CodecError(f"blosc_lz4_plan: chunks {bad[:8]} are malformed: {msg}")
     return int(ns.value), int(nb.value), int(tmp.value), int(maxd.value), res
+
+
+# ---- the write side in HBM: `hip.shuffle_blocks`, `hip.lz4_encode_streams`, `hip.copy_ranges` (io.dataset_to_zarr, encode="gpu") ----
+COPY_RANGE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("n", "<i8")])       # == afhip_copy_range
+
+
+def lz4_encode_emulate(data) -> bytes:
+    """`afcodec_lz4_encode_emulate`: the LZ4 block encoder of `lz4_encode_pass.h` as `hip.lz4_encode_streams` runs it, on the host.
+    -> the stream; as long as the input = stored (the raw bytes)."""
+    lib = load()
+    arr = np.ascontiguousarray(data).view(np.uint8).reshape(-1) if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), dtype=np.uint8)
+    dst = np.empty(max(arr.nbytes, 1), dtype=np.uint8)
+    r = lib.afcodec_lz4_encode_emulate(arr.ctypes.data, arr.nbytes, dst.ctypes.data, arr.nbytes)
+    if r < 0:
+        raise _err(lib, "lz4_encode_emulate")
+    return dst[:r].tobytes()
+
+
+def _put_u32(buf: np.ndarray, offs, vals):
+    """Little-endian uint32 ``vals`` at the (unaligned) byte offsets ``offs`` of the uint8 array ``buf``."""
+    offs = np.asarray(offs, dtype=np.int64).reshape(-1)
+    buf[offs[:, None] + np.arange(4)] = np.asarray(vals).astype("<u4").reshape(-1).view(np.uint8).reshape(-1, 4)
+
+
+class BloscEncodePlan:
+    """`afcodec_blosc_encode_plan` for ``n`` chunks of ``nbytes`` bytes each (LZ4 + byte shuffle, automatic block size), and what the
+    host does around the kernels: ``streams`` (`LZ4_STREAM`) / ``blocks`` (`SHUFFLE_BLOCK`) for `hip.lz4_encode_streams` /
+    `hip.shuffle_blocks`; once the stream sizes are known, `place` lays the containers out in one packed buffer (-> `COPY_RANGE`
+    records for `hip.copy_ranges`) and `finish` writes their headers, block tables and stream lengths into it."""
+
+    def __init__(self, n: int, nbytes: int, typesize: int):
+        lib = load()
+        ns, nb = C.c_int64(0), C.c_int64(0)
+        layout = np.zeros(5, dtype=np.int64)
+        if lib.afcodec_blosc_encode_plan(int(n), int(nbytes), int(typesize), None, 0, C.byref(ns), None, 0, C.byref(nb), layout.ctypes.data):
+            raise _err(lib, "blosc_encode_plan")
+        self.n, self.nbytes, self.typesize = int(n), int(nbytes), int(typesize)
+        self.streams = np.zeros(ns.value, dtype=LZ4_STREAM)
+        self.blocks = np.zeros(nb.value, dtype=SHUFFLE_BLOCK)
+        if lib.afcodec_blosc_encode_plan(int(n), int(nbytes), int(typesize), self.streams.ctypes.data, len(self.streams), C.byref(ns),
+                                         self.blocks.ctypes.data, len(self.blocks), C.byref(nb), layout.ctypes.data):
+            raise _err(lib, "blosc_encode_plan")
+        self.blocksize, self.n_bstarts, self.per_chunk, self.flags, self.len_bytes = (int(v) for v in layout)
+        self.header_bytes = 16 + 4 * self.n_bstarts
+        self.max_bsize = int(self.blocks["bsize"].max()) if len(self.blocks) else 0
+        # the first stream of every block of a chunk (the records' `pad` is the stream's block)
+        self.block_first = np.searchsorted(self.streams["pad"][:self.per_chunk], np.arange(self.n_bstarts))
+
+    def place(self, csizes):
+        """``csizes[n * per_chunk]`` -> (ranges, chunk_off[n], chunk_size[n]): chunk i's container is ``chunk_size[i]`` bytes at
+        ``chunk_off[i]`` of the packed buffer; ``ranges`` move every stream from its slot behind its length field."""
+        cs = np.asarray(csizes, dtype=np.int64).reshape(self.n, self.per_chunk)
+        step = cs + self.len_bytes
+        self._rel = self.header_bytes + np.cumsum(step, axis=1) - step          # each stream's length field, from the chunk's start
+        size = self.header_bytes + step.sum(axis=1)
+        off = np.cumsum(size) - size
+        ranges = np.zeros(self.n * self.per_chunk, dtype=COPY_RANGE)
+        ranges["src_off"] = self.streams["dst_off"]
+        ranges["dst_off"] = (off[:, None] + self._rel + self.len_bytes).reshape(-1)
+        ranges["n"] = cs.reshape(-1)
+        self._cs, self._off, self._size = cs, off, size
+        return ranges, off, size
+
+    def finish(self, buf: np.ndarray):
+        """The 16-byte headers, the bstarts tables and the stream lengths of the containers `place` laid out, into ``buf`` (uint8)."""
+        off, size = self._off, self._size
+        head = np.zeros((self.n, 16), dtype=np.uint8)
+        head[:, 0], head[:, 1], head[:, 2], head[:, 3] = 2, 1, self.flags, self.typesize
+        head[:, 4:8] = np.frombuffer(np.uint32(self.nbytes).astype("<u4").tobytes(), dtype=np.uint8)
+        head[:, 8:12] = np.frombuffer(np.uint32(self.blocksize).astype("<u4").tobytes(), dtype=np.uint8)
+        head[:, 12:16] = size.astype("<u4").view(np.uint8).reshape(-1, 4)
+        buf[off[:, None] + np.arange(16)] = head
+        if self.n_bstarts:
+            at = off[:, None] + 16 + 4 * np.arange(self.n_bstarts)
+            _put_u32(buf, at, self._rel[:, self.block_first])
+        if self.len_bytes:
+            _put_u32(buf, off[:, None] + self._rel, self._cs)
+
+    def assemble_host(self, slots: np.ndarray, csizes):
+        """`place` + the range copies + `finish` on the host -> the n containers (the CPU tests' stand-in for `hip.copy_ranges`)."""
+        ranges, off, size = self.place(csizes)
+        buf = np.zeros(int(size.sum()), dtype=np.uint8)
+        for r in ranges:
+            buf[r["dst_off"]:r["dst_off"] + r["n"]] = slots[r["src_off"]:r["src_off"] + r["n"]]
+        self.finish(buf)
+        return [buf[o:o + z].tobytes() for o, z in zip(off, size)]
 
 
 # record layouts shared with libaggfly_hip (include/aggfly_hip.h: afhip_zstd_frame, afhip_zstd_block; zstd_passes.h)

@@ -17,6 +17,7 @@
 #include "afhip_kernels.h"
 #include "afhip_panel_kernels.h"
 #include "afhip_lz4_kernels.h"
+#include "afhip_lz4_encode_kernels.h"
 #include "afhip_zstd_kernels.h"
 #include "afhip_inflate_kernels.h"
 #include "afhip_planner.h"
@@ -704,6 +705,64 @@ extern "C" int afhip_bitunshuffle_blocks(const void* tmp_dev, void* out_dev, con
     const unsigned tiles = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)max_bsize / 32 + 255) / 256));
     hipLaunchKernelGGL(k_bitunshuffle_blocks, dim3(tiles, (unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)tmp_dev,
                        (uint8_t*)out_dev, (const ShufBlock*)blocks_dev);
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
+extern "C" int afhip_take_box(const void* cube_dev, void* chunk_dev, int elem_size, int64_t NY, int64_t NX,
+                              int64_t t0, int64_t y0, int64_t x0, int64_t nt, int64_t ny, int64_t nx,
+                              int64_t ct, int64_t cy, int64_t cx, uint64_t fill, void* stream) {
+    if (!cube_dev || !chunk_dev || NY <= 0 || NX <= 0 || ct <= 0 || cy <= 0 || cx <= 0 || nt < 0 || ny < 0 || nx < 0 ||
+        t0 < 0 || y0 < 0 || x0 < 0 || nt > ct || ny > cy || nx > cx || y0 + ny > NY || x0 + nx > NX)
+        return fail(AFHIP_E_INVALID, "take_box: box outside the chunk or the cube");
+    const int64_t n = ct * cy * cx;
+    GUARD_DEVICE(pointer_device(cube_dev));
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, 1 << 20)), block(256);     // (grid-stride beyond 2^28 elements)
+    switch (elem_size) {
+        case 1: hipLaunchKernelGGL(k_take_box<uint8_t>, grid, block, 0, s, (const uint8_t*)cube_dev, (uint8_t*)chunk_dev, NY, NX, t0, y0, x0, nt, ny, nx, ct, cy, cx, (uint8_t)fill); break;
+        case 2: hipLaunchKernelGGL(k_take_box<uint16_t>, grid, block, 0, s, (const uint16_t*)cube_dev, (uint16_t*)chunk_dev, NY, NX, t0, y0, x0, nt, ny, nx, ct, cy, cx, (uint16_t)fill); break;
+        case 4: hipLaunchKernelGGL(k_take_box<uint32_t>, grid, block, 0, s, (const uint32_t*)cube_dev, (uint32_t*)chunk_dev, NY, NX, t0, y0, x0, nt, ny, nx, ct, cy, cx, (uint32_t)fill); break;
+        case 8: hipLaunchKernelGGL(k_take_box<uint64_t>, grid, block, 0, s, (const uint64_t*)cube_dev, (uint64_t*)chunk_dev, NY, NX, t0, y0, x0, nt, ny, nx, ct, cy, cx, (uint64_t)fill); break;
+        default: return fail(AFHIP_E_INVALID, "take_box: elem_size must be 1, 2, 4 or 8");
+    }
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
+extern "C" int afhip_shuffle_blocks(const void* out_dev, void* tmp_dev, const afhip_shuffle_block* blocks_dev, int64_t n_blocks,
+                                    int32_t max_bsize, void* stream) {
+    if (!tmp_dev || !out_dev || !blocks_dev || n_blocks < 0 || max_bsize < 0) return fail(AFHIP_E_INVALID, "shuffle_blocks: bad arguments");
+    if (n_blocks == 0) return AFHIP_OK;
+    if (n_blocks > 65535) return fail(AFHIP_E_INVALID, "shuffle_blocks: more than 65535 blocks in one call");
+    GUARD_DEVICE(pointer_device(tmp_dev));
+    const unsigned tiles = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)max_bsize / 2 + 255) / 256));
+    hipLaunchKernelGGL(k_shuffle_blocks, dim3(tiles, (unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)out_dev,
+                       (uint8_t*)tmp_dev, (const ShufBlock*)blocks_dev);
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
+extern "C" int afhip_lz4_encode_streams(const void* in_dev, const afhip_lz4_stream* streams_dev, int64_t n_streams, void* slots_dev,
+                                        int32_t* csize_dev, void* stream) {
+    if (!in_dev || !streams_dev || !slots_dev || !csize_dev || n_streams < 0) return fail(AFHIP_E_INVALID, "lz4_encode_streams: bad arguments");
+    if (n_streams == 0) return AFHIP_OK;
+    if (n_streams > 0x7fffffff) return fail(AFHIP_E_INVALID, "lz4_encode_streams: too many streams for one launch");
+    GUARD_DEVICE(pointer_device(slots_dev));
+    hipLaunchKernelGGL(k_lz4_encode_streams, dim3((unsigned)n_streams), dim3(64), 0, (hipStream_t)stream, (const uint8_t*)in_dev,
+                       (const Lz4Stream*)streams_dev, (uint8_t*)slots_dev, csize_dev);
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
+extern "C" int afhip_copy_ranges(const void* src_dev, void* dst_dev, const afhip_copy_range* ranges_dev, int64_t n_ranges, void* stream) {
+    static_assert(sizeof(afhip_copy_range) == sizeof(CopyRange), "record layouts");
+    if (!src_dev || !dst_dev || !ranges_dev || n_ranges < 0) return fail(AFHIP_E_INVALID, "copy_ranges: bad arguments");
+    if (n_ranges == 0) return AFHIP_OK;
+    if (n_ranges > 0x7fffffff) return fail(AFHIP_E_INVALID, "copy_ranges: too many ranges for one launch");
+    GUARD_DEVICE(pointer_device(dst_dev));
+    hipLaunchKernelGGL(k_copy_ranges, dim3((unsigned)n_ranges), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src_dev,
+                       (uint8_t*)dst_dev, (const CopyRange*)ranges_dev);
     HIP_TRY(hipGetLastError());
     return AFHIP_OK;
 }

@@ -936,6 +936,26 @@ static int64_t blosc_need(int64_t nbytes, int64_t blocksize) {           /* exac
     const int64_t nblocks = (nbytes + blocksize - 1) / blocksize;
     return 16 + nblocks * (4 + 4 * 16) + nbytes + nbytes / 255 + 64;
 }
+/* The block size the writer uses: the geometry afcodec_blosc_encode and afcodec_blosc_encode_plan share. */
+static int64_t blosc_encode_blocksize(int cname, int typesize, int64_t blocksize, int64_t nbytes) {
+    if (blocksize <= 0) {
+        /* LZ4, like c-blosc at level 5: 64 KiB per byte plane (blocks of 64 KiB x typesize, split into one stream per plane) */
+        if (cname == 1) { blocksize = (int64_t)65536 * (typesize <= 16 ? typesize : 1); if (blocksize > (1 << 20)) blocksize = 1 << 20; }
+        else blocksize = 256 << 10;
+    }
+    blocksize -= blocksize % typesize;
+    if (blocksize < typesize) blocksize = typesize;
+    if (blocksize > nbytes && nbytes > 0) blocksize = nbytes;
+    /* the clamp may have left a block that is not a whole number of elements: round down again (c-blosc's compute_blocksize
+     * does), so that a split block divides evenly into its byte planes and the remainder becomes the short, unsplit last
+     * block — a 1001-byte buffer of 4-byte elements used to lose its last byte */
+    if (blocksize > typesize) blocksize -= blocksize % typesize;
+    return blocksize;
+}
+/* streams of a block of an LZ4 chunk: one per byte plane of a full block under a shuffle, else one (the reader's rule in blosc_block) */
+static int blosc_encode_nsplits(int split, int typesize, int64_t blocksize, int last_short) {
+    return (split && typesize <= 16 && blocksize / typesize >= 128 && !last_short) ? typesize : 1;
+}
 /* Blosc-1 writer: inner codec LZ4 (cname 1) or Zstandard (cname 4, through the system's libzstd at `level`), shuffle 0 none / 1 byte /
  * 2 bit.  LZ4 chunks are laid out as before (and as c-blosc lays out shuffled ones): split blocks of 64 KiB per byte plane, one
  * stream per plane — also under the bit shuffle, c-blosc's flags 0x24.  Zstandard chunks are what c-blosc 1.21 writes: unsplit
@@ -950,18 +970,7 @@ int64_t afcodec_blosc_encode(const void* srcv, int64_t nbytes, int typesize, int
     if (rc) return rc;
     if (cname == 4 && !p_zstd_enc) return fail(AFCODEC_E_UNSUPPORTED, "libzstd has no ZSTD_compress");
     if (nbytes < 0 || nbytes > 0x7fffffffLL - 64 || typesize < 1 || typesize > 255) return fail(AFCODEC_E_SIZE, "bad nbytes / typesize");
-    if (blocksize <= 0) {
-        /* LZ4, like c-blosc at level 5: 64 KiB per byte plane (blocks of 64 KiB x typesize, split into one stream per plane) */
-        if (cname == 1) { blocksize = (int64_t)65536 * (typesize <= 16 ? typesize : 1); if (blocksize > (1 << 20)) blocksize = 1 << 20; }
-        else blocksize = 256 << 10;
-    }
-    blocksize -= blocksize % typesize;
-    if (blocksize < typesize) blocksize = typesize;
-    if (blocksize > nbytes && nbytes > 0) blocksize = nbytes;
-    /* the clamp may have left a block that is not a whole number of elements: round down again (c-blosc's compute_blocksize
-     * does), so that a split block divides evenly into its byte planes and the remainder becomes the short, unsplit last
-     * block — a 1001-byte buffer of 4-byte elements used to lose its last byte */
-    if (blocksize > typesize) blocksize -= blocksize % typesize;
+    blocksize = blosc_encode_blocksize(cname, typesize, blocksize, nbytes);
     if (cap < blosc_need(nbytes, blocksize)) return fail(AFCODEC_E_SIZE, "destination smaller than afcodec_blosc_bound()");
     const int do_shuf = shuffle == 1 && typesize > 1, do_bits = shuffle == 2;
     const int filter = do_shuf ? 0x01 : (do_bits ? 0x04 : 0);
@@ -991,8 +1000,7 @@ int64_t afcodec_blosc_encode(const void* srcv, int64_t nbytes, int typesize, int
         if (do_shuf) { shuffle_bytes(typesize, bsize, in, tmp); in = tmp; }
         else if (do_bits && bsize >= typesize) { shuffle_bits(typesize, bsize, in, tmp); in = tmp; }
         put32(dst + 16 + 4 * b, (uint32_t)pos);
-        int nsplits = 1;
-        if (split && typesize <= 16 && blocksize / typesize >= 128 && !last_short) nsplits = typesize;
+        const int nsplits = blosc_encode_nsplits(split, typesize, blocksize, last_short);
         const int64_t ne = bsize / nsplits;
         for (int j = 0; j < nsplits; ++j) {
             int64_t csz = 0;                                    /* stays 0 if the stream does not shrink */
@@ -1013,6 +1021,68 @@ int64_t afcodec_blosc_encode(const void* srcv, int64_t nbytes, int typesize, int
 
 int64_t afcodec_blosc_encode_lz4(const void* src, int64_t nbytes, int typesize, int shuffle, int64_t blocksize, void* dst, int64_t cap) {
     return afcodec_blosc_encode(src, nbytes, typesize, shuffle ? 1 : 0, 1, 0, blocksize, dst, cap);
+}
+
+/* ---- the write side in HBM (libaggfly_hip: afhip_shuffle_blocks, afhip_lz4_encode_streams, afhip_copy_ranges) ---- */
+#include "lz4_encode_pass.h"
+
+/* The encoder of lz4_encode_pass.h as the kernel runs it, on the host: src[0 .. n) -> dst (cap >= n) -> csize; n = stored. */
+int64_t afcodec_lz4_encode_emulate(const void* src, int64_t n, void* dst, int64_t cap) {
+    if (n < 0 || n > 0x7fffffffLL || (n && (!src || !dst))) return fail(AFCODEC_E_SIZE, "lz4_encode_emulate: bad arguments");
+    if (cap < n) return fail(AFCODEC_E_SIZE, "lz4_encode_emulate: the slot holds fewer than n bytes");
+    uint32_t* table = (uint32_t*)malloc(sizeof(uint32_t) * AFL_TABLE_ENTRIES);
+    if (!table) return fail(AFCODEC_E_SIZE, "out of memory");
+    const int32_t c = afl_encode_wave((const uint8_t*)src, (int32_t)n, (uint8_t*)dst, table, 0, 0);
+    free(table);
+    return c;
+}
+
+/* Geometry of n chunks of nbytes bytes each, chunk i at offset i * nbytes of the chunk buffer, written as afcodec_blosc_encode writes
+ * LZ4 chunks under the byte shuffle with the automatic block size. */
+int afcodec_blosc_encode_plan(int64_t n, int64_t nbytes, int typesize, void* streams_v, int64_t cap_streams, int64_t* n_streams,
+                              void* blocks_v, int64_t cap_blocks, int64_t* n_blocks, int64_t* layout) {
+    typedef struct { int64_t src_off, dst_off; int32_t csize, dsize, to_out, pad; } stream_rec;   /* == afhip_lz4_stream */
+    typedef struct { int64_t tmp_off, out_off; int32_t bsize, typesize; } shuf_rec;               /* == afhip_shuffle_block */
+    stream_rec* st = (stream_rec*)streams_v;
+    shuf_rec* bl = (shuf_rec*)blocks_v;
+    if (n < 0 || nbytes <= 0 || nbytes > 0x7fffffffLL - 64 || typesize < 1 || typesize > 255 || !n_streams || !n_blocks || !layout)
+        return fail(AFCODEC_E_SIZE, "blosc_encode_plan: bad n / nbytes / typesize");
+    const int cname = 1, filter = typesize > 1 ? 0x01 : 0, split = filter != 0;
+    const int stored = nbytes < 128;                         /* tiny buffers are stored */
+    const int64_t blocksize = stored ? nbytes : blosc_encode_blocksize(cname, typesize, 0, nbytes);
+    const int64_t nblocks = stored ? 1 : (nbytes + blocksize - 1) / blocksize, leftover = stored ? 0 : nbytes % blocksize;
+    int64_t per_chunk = 0;
+    for (int64_t b = 0; b < nblocks; ++b) per_chunk += blosc_encode_nsplits(split && !stored, typesize, blocksize, b == nblocks - 1 && leftover > 0);
+    layout[0] = stored ? nbytes : blocksize;                 /* header field */
+    layout[1] = stored ? 0 : nblocks;                        /* entries of the bstarts table */
+    layout[2] = per_chunk;                                   /* streams per chunk */
+    layout[3] = stored ? (0x02 | filter | (cname << 5) | 0x10) : (filter | (split ? 0 : 0x10) | (cname << 5));
+    layout[4] = stored ? 0 : 4;                              /* bytes of the length field in front of every stream */
+    *n_streams = n * per_chunk;
+    *n_blocks = n * nblocks;
+    if (!st && !bl) return AFCODEC_OK;                       /* the counts and the layout alone */
+    if (!st || !bl || *n_streams > cap_streams || *n_blocks > cap_blocks) return fail(AFCODEC_E_SIZE, "blosc_encode_plan: record list too small");
+    int64_t si = 0, bi = 0;
+    for (int64_t c = 0; c < n; ++c) {
+        for (int64_t b = 0; b < nblocks; ++b) {
+            const int last_short = b == nblocks - 1 && leftover > 0;
+            const int64_t bsize = last_short ? leftover : blocksize, off = c * nbytes + b * blocksize;
+            bl[bi].tmp_off = bl[bi].out_off = off;
+            bl[bi].bsize = (int32_t)bsize;
+            bl[bi].typesize = (filter && !stored) ? typesize : 1;        /* (a stored chunk holds the raw bytes: a copy) */
+            ++bi;
+            const int nsplits = blosc_encode_nsplits(split && !stored, typesize, blocksize, last_short);
+            const int64_t ne = bsize / nsplits;
+            for (int j = 0; j < nsplits; ++j, ++si) {
+                st[si].src_off = st[si].dst_off = off + j * ne;
+                st[si].csize = 0;
+                st[si].dsize = (int32_t)ne;
+                st[si].to_out = stored;
+                st[si].pad = (int32_t)b;
+            }
+        }
+    }
+    return AFCODEC_OK;
 }
 
 /* Plain Zstandard frames (Zarr compressor id "zstd"). */

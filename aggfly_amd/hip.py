@@ -40,6 +40,7 @@ EXPORTS = (
     "afhip_plan_profile_begin", "afhip_plan_profile_end", "afhip_plan_bind_inter", "afhip_csr_device", "afhip_plan_device", "afhip_transform", "afhip_panel_divide", "afhip_lz4_decode_streams", "afhip_unshuffle_blocks", "afhip_read_probe",
     "afhip_zstd_scratch_bytes", "afhip_zstd_decode", "afhip_inflate_scratch_bytes", "afhip_inflate_decode", "afhip_bitunshuffle_blocks",
     "afhip_plan_bind_packing", "afhip_unpack_i16", "afhip_unpack_u16", "afhip_plan_bind_packings",
+    "afhip_take_box", "afhip_shuffle_blocks", "afhip_lz4_encode_streams", "afhip_copy_ranges",
 )
 
 
@@ -127,6 +128,10 @@ def load():
     lib.afhip_lz4_decode_streams.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
     lib.afhip_unshuffle_blocks.argtypes = [vp, vp, vp, i64, i32, vp]
     lib.afhip_bitunshuffle_blocks.argtypes = [vp, vp, vp, i64, i32, vp]
+    lib.afhip_take_box.argtypes = [vp, vp, i32] + [i64] * 11 + [C.c_uint64, vp]
+    lib.afhip_shuffle_blocks.argtypes = [vp, vp, vp, i64, i32, vp]
+    lib.afhip_lz4_encode_streams.argtypes = [vp, vp, i64, vp, vp, vp]
+    lib.afhip_copy_ranges.argtypes = [vp, vp, vp, i64, vp]
     lib.afhip_zstd_scratch_bytes.restype = i64
     lib.afhip_zstd_scratch_bytes.argtypes = [i64] * 5
     lib.afhip_zstd_decode.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, i64, vp, i64, vp, vp, vp, vp]
@@ -259,6 +264,33 @@ def bitunshuffle_blocks(tmp, out, blocks, n_blocks: int, max_bsize: int):
     """`afhip_bitunshuffle_blocks`: Blosc's bit shuffle undone per block (records in the uint8 HBM tensor ``blocks``, the second
     unshuffle list of `codec.blosc_plan`)."""
     _check(load().afhip_bitunshuffle_blocks(tmp.data_ptr(), out.data_ptr(), blocks.data_ptr(), int(n_blocks), int(max_bsize), _stream_ptr(out)))
+
+
+def take_box(cube, chunk, at, box, fill_bits: int = 0):
+    """chunk[:nt, :ny, :nx] = cube[t0:t0+nt, y0:y0+ny, x0:x0+nx], the rest of ``chunk`` ([ct, cy, cx]) = the element whose bits are
+    ``fill_bits``, on the current stream: `afhip_take_box`, the inverse of `place_box`.  Both tensors contiguous, elements of the same
+    size (1 / 2 / 4 / 8 bytes)."""
+    (t0, y0, x0), (nt, ny, nx) = at, box
+    _check(load().afhip_take_box(cube.data_ptr(), chunk.data_ptr(), cube.element_size(), cube.shape[1], cube.shape[2], t0, y0, x0,
+                                 nt, ny, nx, chunk.shape[0], chunk.shape[1], chunk.shape[2], int(fill_bits), _stream_ptr(cube)))
+
+
+def shuffle_blocks(out, tmp, blocks, n_blocks: int, max_bsize: int):
+    """`afhip_shuffle_blocks`: Blosc's byte shuffle per block, ``out`` (the chunk buffer) -> ``tmp`` (records in the uint8 HBM tensor
+    ``blocks``, as `unshuffle_blocks` takes them)."""
+    _check(load().afhip_shuffle_blocks(out.data_ptr(), tmp.data_ptr(), blocks.data_ptr(), int(n_blocks), int(max_bsize), _stream_ptr(tmp)))
+
+
+def lz4_encode_streams(inp, streams, n_streams: int, slots, csize):
+    """`afhip_lz4_encode_streams`: one wave per record of ``streams`` (uint8 HBM tensor of `codec.LZ4_STREAM` records) encodes
+    ``inp[src_off : src_off + dsize]`` into ``slots[dst_off : dst_off + dsize]``; the sizes go to the int32 HBM tensor ``csize``."""
+    _check(load().afhip_lz4_encode_streams(inp.data_ptr(), streams.data_ptr(), int(n_streams), slots.data_ptr(), csize.data_ptr(),
+                                           _stream_ptr(slots)))
+
+
+def copy_ranges(src, dst, ranges, n_ranges: int):
+    """`afhip_copy_ranges`: ``dst[dst_off : dst_off + n] = src[src_off : src_off + n]`` per `codec.COPY_RANGE` record of ``ranges``."""
+    _check(load().afhip_copy_ranges(src.data_ptr(), dst.data_ptr(), ranges.data_ptr(), int(n_ranges), _stream_ptr(dst)))
 
 
 def require_gpu():

@@ -1456,10 +1456,22 @@ def _crc32c(data: bytes) -> int:
     return c ^ 0xFFFFFFFF
 
 
+class _DeviceCube:
+    """Stands for the array in `_write_array` when the chunks are cut and encoded in HBM (`_write_chunks_gpu`): the shape and the numpy
+    dtype the metadata is written from, and the HBM tensor."""
+
+    def __init__(self, tensor):
+        self.tensor = tensor
+        self.shape = tuple(int(n) for n in tensor.shape)
+        self.dtype = np.dtype(str(tensor.dtype).replace("torch.", ""))
+        self.nbytes = int(tensor.numel()) * int(tensor.element_size())
+
+
 def _write_array(path, name, data, dims, chunks, attrs, compressor, zarr_format: int = 2, shards=None):
     d = os.path.join(path, name)
     os.makedirs(d, exist_ok=True)
-    data = np.ascontiguousarray(data)
+    if not isinstance(data, _DeviceCube):
+        data = np.ascontiguousarray(data)
     chunks = tuple(int(min(c, s)) if s else 1 for c, s in zip(chunks, data.shape))
     cid = compressor["id"] if compressor else None
     if zarr_format == 2:
@@ -1501,6 +1513,8 @@ def _write_array(path, name, data, dims, chunks, attrs, compressor, zarr_format:
 
     if shards is not None and zarr_format != 3:
         raise ValueError("shards need zarr_format=3")
+    if isinstance(data, _DeviceCube):
+        return _write_chunks_gpu(d, data, chunks, zarr_format, shards)
 
     def encode_chunk(idx):
         sl = tuple(slice(i * c, min((i + 1) * c, s)) for i, c, s in zip(idx, chunks, data.shape))
@@ -1564,6 +1578,177 @@ def _write_array(path, name, data, dims, chunks, attrs, compressor, zarr_format:
             write_chunk(idx)
 
 
+# The write side in HBM.  `dataset_to_zarr(..., encode="gpu")`: the decode-in-HBM route (`_Lz4Route`) in reverse — the cube stays in HBM,
+# chunks are cut out of it, byte-shuffled and LZ4-encoded there, and cross PCIe compressed; the host fills the Blosc-1 headers and tables
+# and writes the files.  encode="auto" takes it for device-resident cubes of GPU_ENCODE_AUTO_BYTES and more, or when
+# AGGFLY_HIP_GPU_ENCODE=1 asks for it (=0: never).
+# Set by the rule of GPU_DECODE_AUTO_BYTES_DEFLATE: the smallest size from which, on every layout of scripts/encode_bench.py ((1, ny, nx),
+# (24, ny, nx), whole-series tiles of the configs[0] cube, 64 MiB ... 860 MB), the GPU route's median is <= 0.9 x the host route's minimum
+# AND the store it writes is at most 1.10 x the host-written one.  Measured (profiles/lz4_encode.txt): 0.68 / 0.61 / 0.46 / 0.45 x at
+# 128 / 256 / 512 / 860 MB on the worst layout, 1.07 x at 64 MiB; stores 1.005-1.007 x.  None would mean: never without the environment.
+GPU_ENCODE_AUTO_BYTES = 128 << 20
+GPU_ENCODE_BATCH_BYTES = 256 << 20                # decoded bytes of a batch of chunks (one chunk at least)
+_GPU_ENCODE_DTYPES = ("f4", "f8", "i1", "u1", "i2", "u2", "i4", "u4", "i8", "u8")
+
+
+def _gpu_encode_refusal(compress, np_dtype, ctuple) -> Optional[str]:
+    """None, or why `dataset_to_zarr` cannot take the GPU route for this call."""
+    if compress not in (True, "blosc"):
+        return f"compress={compress!r}: the GPU route writes Blosc-1 chunks of LZ4 streams under the byte shuffle (compress=True or 'blosc') only"
+    if np.dtype(np_dtype).str[1:] not in _GPU_ENCODE_DTYPES:
+        return f"dtype {np.dtype(np_dtype)}: the GPU route takes float32, float64 and integers of 1, 2, 4 or 8 bytes"
+    if int(np.prod(ctuple)) * np.dtype(np_dtype).itemsize > 0x7fffffff - 64:
+        return "a chunk of 2 GiB or more does not fit a Blosc-1 container"
+    return None
+
+
+def _write_chunks_gpu(d, data: "_DeviceCube", chunks, zarr_format, shards):
+    """The chunk files (or shard files) of one array, encoded in HBM.  Per batch of chunks of up to GPU_ENCODE_BATCH_BYTES:
+    `hip.take_box` per chunk (edge chunks padded with the fill value) -> `hip.shuffle_blocks` -> `hip.lz4_encode_streams` into one
+    slot per stream -> the sizes to the host (a small D2H) -> `hip.copy_ranges` packs the streams into their containers -> one D2H
+    into a page-locked buffer -> `codec.BloscEncodePlan.finish` fills headers, block tables and stream lengths -> files, from a small
+    thread pool.  Two packed buffers on each side: batch i's D2H and file writes overlap batch i + 1's kernels.  Shard bodies and the
+    shard index with its crc32c are host work over the compressed chunks."""
+    import torch
+    from . import codec, hip
+    hip.require_gpu()
+    cube = data.tensor.contiguous()
+    dev = cube.device
+    shape, item = data.shape, data.dtype.itemsize
+    cb = int(np.prod(chunks)) * item
+    fill_bits = int(np.array([np.nan], dtype=data.dtype).view(f"u{item}")[0]) if data.dtype.kind == "f" else 0
+    grid = [(s + c - 1) // c for s, c in zip(shape, chunks)]
+    if shards is None:
+        order = [(idx, None) for idx in np.ndindex(*grid)]
+    else:                                                   # shard by shard, the inner chunks in the order of the shard's index
+        per_shard = [s_ // c_ for s_, c_ in zip(shards, chunks)]
+        nshard = [-(-n // s_) for n, s_ in zip(shape, shards)]
+        order = []
+        for sidx in np.ndindex(*nshard):
+            for k, inner in enumerate(np.ndindex(*per_shard)):
+                idx = tuple(si * p_ + ii for si, p_, ii in zip(sidx, per_shard, inner))
+                if all(i * c < n for i, c, n in zip(idx, chunks, shape)):      # (an inner chunk wholly outside the array stays empty)
+                    order.append((idx, (sidx, k)))
+        n_inner = int(np.prod(per_shard))
+    if not order:
+        return
+    per = max(1, min(len(order), GPU_ENCODE_BATCH_BYTES // cb))
+    plans = {}
+
+    def plan_of(n):                                         # (two at most: the full batch and the last one)
+        if n not in plans:
+            pl = codec.BloscEncodePlan(n, cb, item)
+            rec = np.concatenate([pl.streams.view(np.uint8), pl.blocks.view(np.uint8)])
+            plans[n] = (pl, torch.from_numpy(rec).to(dev), pl.streams.nbytes)
+        return plans[n]
+
+    pl0 = plan_of(per)[0]
+    packed_cap = per * (cb + pl0.header_bytes + 4 * pl0.per_chunk)
+    chunk_dev, tmp_dev, slots_dev = (torch.empty(per * cb, dtype=torch.uint8, device=dev) for _ in range(3))
+    csize_dev = torch.empty(per * pl0.per_chunk, dtype=torch.int32, device=dev)
+    packed_dev = [torch.empty(packed_cap, dtype=torch.uint8, device=dev) for _ in range(2)]
+    pinned = _pinned_stage(packed_cap, 2, dev)
+    work, copy = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+    cview = chunk_dev.view(cube.dtype)
+    shard_body = {}                                          # sidx -> {k: bytes}, until the shard's last chunk has arrived
+
+    def chunk_file(idx):
+        fn = os.path.join(d, ".".join(str(i) for i in idx)) if zarr_format == 2 else os.path.join(d, "c", *[str(i) for i in idx])
+        os.makedirs(os.path.dirname(fn), exist_ok=True)
+        return fn
+
+    def write_file(fn, buf):
+        with open(fn, "wb") as f:
+            f.write(buf)
+
+    def write_files(items):                                  # (one task per group of files: a task per file costs more than a small file)
+        for idx, buf in items:
+            write_file(chunk_file(idx), buf)
+
+    def write_shard(sidx, parts):
+        index = np.full((n_inner, 2), 0xFFFFFFFFFFFFFFFF, dtype="<u8")
+        pos, body = 0, []
+        for k in sorted(parts):
+            index[k] = (pos, len(parts[k]))
+            body.append(parts[k])
+            pos += len(parts[k])
+        tail = index.tobytes()
+        write_file(chunk_file(sidx), b"".join(body) + tail + _crc32c(tail).to_bytes(4, "little"))
+
+    def kernels(batch):
+        """take, shuffle, encode: everything up to the stream sizes."""
+        pl, rec_dev, blocks_at = plan_of(len(batch))
+        j = 0
+        while j < len(batch):
+            # chunks that follow one another in time over the same cells are one box of m * chunks[0] steps: one launch (a store of
+            # whole-grid chunks, (1, ny, nx) or (24, ny, nx), is one launch per batch, not thousands)
+            idx, m = batch[j][0], 1
+            while j + m < len(batch) and batch[j + m][0] == (idx[0] + m,) + tuple(idx[1:]):
+                m += 1
+            at = tuple(i * c for i, c in zip(idx, chunks))
+            run = (m * chunks[0],) + tuple(chunks[1:])
+            box = tuple(min(c, n - a) for c, n, a in zip(run, shape, at))
+            hip.take_box(cube, cview[j * (cb // item):(j + m) * (cb // item)].view(run), at, box, fill_bits)
+            j += m
+        nb = len(pl.blocks)
+        for b0 in range(0, nb, 65535):
+            hip.shuffle_blocks(chunk_dev, tmp_dev, rec_dev[blocks_at + b0 * codec.SHUFFLE_BLOCK.itemsize:], min(65535, nb - b0), pl.max_bsize)
+        hip.lz4_encode_streams(tmp_dev, rec_dev, len(pl.streams), slots_dev, csize_dev)
+        return pl
+
+    def pack(k, pl):
+        """The sizes to the host, the streams into their containers, the containers on their way to the host."""
+        csizes = csize_dev[:len(pl.streams)].cpu().numpy()   # (waits for the batch's kernels)
+        ranges, off, size = pl.place(csizes)
+        total = int(size.sum())
+        hip.copy_ranges(slots_dev, packed_dev[k % 2], torch.from_numpy(ranges.view(np.uint8)).to(dev), len(ranges))
+        done = torch.cuda.Event()
+        done.record(work)
+        with torch.cuda.stream(copy):
+            copy.wait_event(done)
+            pinned[k % 2][:total].copy_(packed_dev[k % 2][:total], non_blocking=True)
+            arrived = torch.cuda.Event()
+            arrived.record(copy)
+        return arrived, off, size, total
+
+    def finish(k, batch, pl, arrived, off, size, total, pool):
+        arrived.synchronize()
+        host = pinned[k % 2][:total].numpy()
+        pl.finish(host)
+        futures, plain = [], []
+        for (idx, shard), o, z in zip(batch, off, size):
+            if shard is None:
+                plain.append((idx, host[o:o + z]))
+            else:
+                sidx, kk = shard
+                parts = shard_body.setdefault(sidx, {})
+                parts[kk] = host[o:o + z].tobytes()
+                if shard_last[sidx] == idx:
+                    futures.append(pool.submit(write_shard, sidx, shard_body.pop(sidx)))
+        group = max(1, -(-len(plain) // (4 * n_workers)))
+        futures += [pool.submit(write_files, plain[i:i + group]) for i in range(0, len(plain), group)]
+        return futures
+
+    shard_last = {sh[0]: idx for idx, sh in order if sh is not None}
+    batches = [order[i:i + per] for i in range(0, len(order), per)]
+    writes = [[], []]                                        # the file writes still reading pinned[0] / pinned[1]
+    n_workers = min(8, os.cpu_count() or 1)
+    with ThreadPoolExecutor(max_workers=n_workers) as pool:
+        pending = None
+        for k, batch in enumerate(batches):
+            pl = kernels(batch)
+            if pending is not None:                          # batch k - 1 arrives and is written while batch k's kernels run
+                writes[(k - 1) % 2] = finish(*pending, pool)
+            for f in writes[k % 2]:                          # (batch k - 2's files: its page-locked buffer is about to be overwritten)
+                f.result()
+            pending = (k, batch, pl) + pack(k, pl)
+        writes[(len(batches) - 1) % 2] = finish(*pending, pool)
+        for w in writes:
+            for f in w:
+                f.result()
+    torch.cuda.synchronize(dev)
+
+
 def _encode_time(t):
     if isinstance(t, CFTimeIndex):
         return (t.seconds / 3600.0), {"units": "hours since 0000-01-01 00:00:00", "calendar": t.calendar}
@@ -1587,20 +1772,46 @@ def _auto_chunks(sizes: dict, itemsize: int, target_mb: float = 256) -> dict:
 
 
 def dataset_to_zarr(dataset: Dataset, path: str, var: str = "var", chunks=None, compress=True, mode: str = "w", zarr_format: int = 2,
-                    shards=None):
+                    shards=None, encode: str = "auto"):
     """`dataset_to_zarr` (`zarr_convert.py:50-121`): write a time-major, time-contiguous store.
     ``compress``: True / "blosc" -> Blosc-1 LZ4 + byte shuffle (what zarr-python 2 / numcodecs write by
     default and read back), "blosc-zstd" / "blosc-bitshuffle" / "blosc-zstd-bitshuffle" -> Blosc-1 with Zstandard streams and the byte
     shuffle, LZ4 streams and the bit shuffle, or both (the Zarr v3 ``blosc`` codec's default ``cname`` is zstd), "zstd" (zarr-python
     3's default codec), "zlib" -> zlib level 1, False -> raw.
     ``zarr_format``: 2 (``.zarray``) or 3 (``zarr.json``, ``c/`` chunk keys); ``shards`` (format 3): a dict like
-    ``chunks`` giving the shard shape in which the chunks are bundled (``sharding_indexed``)."""
+    ``chunks`` giving the shard shape in which the chunks are bundled (``sharding_indexed``).
+    ``encode``: where the data variable's chunks are cut, shuffled and compressed.  "host": on host threads, from a host copy of
+    the cube.  "gpu": in HBM (`_write_chunks_gpu`; Blosc-1 LZ4 + byte shuffle only, i.e. ``compress`` True or "blosc"; a
+    host-resident cube is uploaded first) — the chunks cross PCIe compressed; anything else raises `ValueError`.  The store
+    decodes to the same values; its LZ4 streams are the GPU encoder's, not liblz4's.  "auto": the GPU route for a device-resident
+    cube of `GPU_ENCODE_AUTO_BYTES` or more (None: never) or when ``AGGFLY_HIP_GPU_ENCODE=1`` is set (``0``: never), and the call is
+    eligible; else the host route — always for a host-resident cube.  Coordinates and metadata are written by the same code on every route."""
+    if encode not in ("auto", "host", "gpu"):
+        raise ValueError(f"encode must be 'auto', 'host' or 'gpu', got {encode!r}")
     cube = dataset.cube()
-    if not isinstance(cube, np.ndarray):
-        cube = cube.cpu().numpy()
+    on_host = isinstance(cube, np.ndarray)
+    np_dtype = cube.dtype if on_host else np.dtype(str(cube.dtype).replace("torch.", ""))
     sizes = {"time": cube.shape[0], "latitude": cube.shape[1], "longitude": cube.shape[2]}
-    ch = dict(_auto_chunks(sizes, cube.dtype.itemsize)) if chunks is None else dict(chunks)
+    ch = dict(_auto_chunks(sizes, np_dtype.itemsize)) if chunks is None else dict(chunks)
     ctuple = tuple(sizes[d] if ch.get(d, -1) in (-1, None) else ch[d] for d in ("time", "latitude", "longitude"))
+    use_gpu = False
+    if encode != "host":
+        refusal = _gpu_encode_refusal(compress, np_dtype, tuple(int(min(c, s)) if s else 1 for c, s in zip(ctuple, cube.shape)))
+        if encode == "gpu":
+            if refusal:
+                raise ValueError(f"dataset_to_zarr(encode='gpu'): {refusal}")
+            use_gpu = True
+        elif refusal is None and not on_host and cube.is_cuda:
+            nbytes = int(cube.numel()) * int(cube.element_size())
+            mode = os.environ.get("AGGFLY_HIP_GPU_ENCODE", "auto")
+            use_gpu = mode == "1" or (mode != "0" and GPU_ENCODE_AUTO_BYTES is not None and nbytes >= GPU_ENCODE_AUTO_BYTES)
+    if use_gpu:
+        if on_host:
+            import torch
+            cube = torch.from_numpy(cube).to("cuda")
+        cube = _DeviceCube(cube)
+    elif not on_host:
+        cube = cube.cpu().numpy()
     os.makedirs(path, exist_ok=True)
     if zarr_format == 2:
         with open(os.path.join(path, ".zgroup"), "w") as f:
@@ -1635,8 +1846,9 @@ def dataset_to_zarr(dataset: Dataset, path: str, var: str = "var", chunks=None, 
 
 
 def zarr_from_path(src: str, dst: str, var: str, **kwargs):
-    """`zarr_from_path` (`zarr_convert.py:124-156`): convert any readable source to Zarr."""
-    ds_kw = {k: kwargs.pop(k) for k in ("xycoords", "timecoord", "lon_is_360", "time_sel") if k in kwargs}
+    """`zarr_from_path` (`zarr_convert.py:124-156`): convert any readable source to Zarr.  ``device`` goes to `dataset_from_path`
+    (the cube is read into HBM), ``encode`` with the other keywords to `dataset_to_zarr`."""
+    ds_kw = {k: kwargs.pop(k) for k in ("xycoords", "timecoord", "lon_is_360", "time_sel", "device") if k in kwargs}
     ds = dataset_from_path(src, var, **ds_kw)
     return dataset_to_zarr(ds, dst, var=var, **kwargs)
 

@@ -45,6 +45,25 @@ int64_t afcodec_blosc_encode_lz4(const void* src, int64_t nbytes, int typesize, 
 int64_t afcodec_blosc_encode(const void* src, int64_t nbytes, int typesize, int shuffle, int cname, int level, int64_t blocksize,
                              void* dst, int64_t cap);
 
+/* The write side in HBM (libaggfly_hip: afhip_take_box, afhip_shuffle_blocks, afhip_lz4_encode_streams, afhip_copy_ranges).
+ * afcodec_lz4_encode_emulate: the LZ4 block encoder of aggfly_amd/csrc/lz4_encode_pass.h exactly as the kernel runs it, its 64 lanes
+ * in loops: src[0 .. n) into dst (cap >= n) -> the stream's size: an LZ4 block of at most n - 1 bytes, or n with the raw bytes in dst
+ * (stored).  The bytes are a function of the input alone, so the kernel's output is byte-identical.
+ * afcodec_blosc_encode_plan: the geometry of n chunks of nbytes bytes each (chunk i = bytes [i * nbytes, (i + 1) * nbytes) of the
+ * chunk buffer) as afcodec_blosc_encode lays out LZ4 chunks under the byte shuffle with the automatic block size — one function
+ * computes the block size for both — into
+ *   blocks  [*n_blocks]   afhip_shuffle_block records for afhip_shuffle_blocks (out_off: the block in the chunk buffer, tmp_off: in the
+ *                         shuffle scratch, the same offset; typesize 1 where nothing is shuffled);
+ *   streams [*n_streams]  afhip_lz4_stream records for afhip_lz4_encode_streams, chunk by chunk, block by block, plane by plane:
+ *                         src_off = dst_off = the stream's offset in the scratch and of its slot, dsize its raw length, pad its block,
+ *                         to_out = 1 for the single stored stream of a chunk under 128 bytes;
+ *   layout [5]            of every chunk's container: the header's blocksize field, the entries of its bstarts table, its streams,
+ *                         its flags byte, the bytes of the length field in front of every stream (4; 0 in a stored chunk).
+ * With streams and blocks both NULL only the counts and the layout are returned.  Nothing is encoded here. */
+int64_t afcodec_lz4_encode_emulate(const void* src, int64_t n, void* dst, int64_t cap);
+int afcodec_blosc_encode_plan(int64_t n, int64_t nbytes, int typesize, void* streams, int64_t cap_streams, int64_t* n_streams,
+                              void* blocks, int64_t cap_blocks, int64_t* n_blocks, int64_t* layout);
+
 /* Plan of a GPU-side decode (libaggfly_hip: afhip_lz4_decode_streams / afhip_unshuffle_blocks, include/aggfly_hip.h): the
  * containers of n Blosc-1 chunks — chunk i = comp_size[i] bytes at base + comp_off[i], its decoded bytes wanted at offset
  * out_off[i] (capacity out_size[i]) of the output buffer — are parsed on the host and turned into

@@ -209,6 +209,32 @@ int afhip_unshuffle_blocks(const void* tmp_dev, void* out_dev, const afhip_shuff
 int afhip_bitunshuffle_blocks(const void* tmp_dev, void* out_dev, const afhip_shuffle_block* blocks_dev, int64_t n_blocks,
                               int32_t max_bsize, void* stream);
 
+/* Chunk ENCODE in HBM: the write side (dataset_to_zarr with encode="gpu"), the decode route above in reverse.  The cube stays in
+ * HBM; per batch of chunks the caller runs, in order:
+ * afhip_take_box: the inverse of afhip_place_box — the box [t0, t0+nt) x [y0, y0+ny) x [x0, x0+nx) of the time-major cube
+ * [*, NY, NX] into the contiguous chunk buffer [ct, cy, cx] at chunk_dev; every element of the buffer beyond the box (Zarr pads edge
+ * chunks to the full chunk shape) takes the low elem_size bytes of `fill` (NaN bits for floats, 0 for integers).  elem_size 1, 2, 4, 8.
+ * afhip_shuffle_blocks: Blosc's byte shuffle, out_dev (the chunk buffer) -> tmp_dev (the shuffle scratch), over the records of
+ * afhip_unshuffle_blocks with the same meaning of their fields and the same limit of 65,535 blocks a call; typesize 1 is a copy, the
+ * bsize % typesize trailing bytes are copied.
+ * afhip_lz4_encode_streams: one wave per record — src_off: the stream's raw bytes in in_dev (the shuffled input), dst_off: its slot of
+ * dsize bytes in slots_dev, dsize: the raw length, to_out != 0: store without a search; csize and pad are not read.  csize_dev[i]
+ * receives the stream's size: an LZ4 block of at most dsize - 1 bytes, or dsize with the raw bytes in the slot (stored: the rule of
+ * afcodec_blosc_encode).  The bytes are a function of the input alone (aggfly_amd/csrc/lz4_encode_pass.h; the host runs the same
+ * text as afcodec_lz4_encode_emulate).  Nothing is written outside the slot.
+ * afhip_copy_ranges: bytes [src_off, src_off + n) of src_dev to dst_dev + dst_off per record — after the host has read the sizes,
+ * every stream from its slot to its place in the batch's packed output; ranges of one call must not overlap in dst_dev.
+ * All pointers are device memory, the work is enqueued on `stream`, nothing is retained. */
+typedef struct afhip_copy_range { int64_t src_off, dst_off, n; } afhip_copy_range;
+int afhip_take_box(const void* cube_dev, void* chunk_dev, int elem_size, int64_t NY, int64_t NX,
+                   int64_t t0, int64_t y0, int64_t x0, int64_t nt, int64_t ny, int64_t nx,
+                   int64_t ct, int64_t cy, int64_t cx, uint64_t fill, void* stream);
+int afhip_shuffle_blocks(const void* out_dev, void* tmp_dev, const afhip_shuffle_block* blocks_dev, int64_t n_blocks,
+                         int32_t max_bsize, void* stream);
+int afhip_lz4_encode_streams(const void* in_dev, const afhip_lz4_stream* streams_dev, int64_t n_streams, void* slots_dev,
+                             int32_t* csize_dev, void* stream);
+int afhip_copy_ranges(const void* src_dev, void* dst_dev, const afhip_copy_range* ranges_dev, int64_t n_ranges, void* stream);
+
 /* Zstandard frames decoded in HBM (Zarr v2 compressor "zstd", Zarr v3 bytes -> zstd, shards too).  The host walks the frame,
  * block and section headers (afcodec_zstd_plan, include/aggfly_codec.h) into one record per frame and per block, which
  * travel to HBM with the compressed bytes; the tables are built, literals and sequences decoded and the LZ matches resolved
