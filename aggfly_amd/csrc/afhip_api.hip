@@ -310,6 +310,7 @@ static afhip_csr::RfTab* rf_table(afhip_csr* csr, int vec) {
 struct afhip_plan : PlanLayout {             // what the planner made (afhip_planner.h) + device tables, scratch and run state
     int device = 0;                       // the device the plan's tables and scratch live on (current device at afhip_plan_create)
     int last_route = 0;                    // 1: the last afhip_plan_run took the region-fused route (afhip_plan_describe tells)
+    int last_spatial = 0;                  // the last run's per-cell route: 1 = slot gather (k_csr_spmm_slots), 2 = cell-major panel + k_csr_spmm* (likewise)
     int last_counts_lanes = -1;            // lanes per (row, period) pair of the last run's packed-count gather (1, 4, 8, 16; -1: it did not run)
     // device tables
     DevBuf<int64_t> d_ob;
@@ -415,6 +416,9 @@ extern "C" int afhip_csr_create(const int64_t* indptr, const int64_t* cols, cons
         if (cols[j] < 0 || cols[j] >= n_cells)
             return fail(AFHIP_E_INVALID, "csr_create: column %lld out of range at entry %lld", (long long)cols[j], (long long)j);
         c32[(size_t)j] = (int32_t)cols[j];
+        // (a NaN or infinite weight: np.add.at then turns every sum of the region into NaN through w * 0 of the cells that are not valid,
+        // empty periods included, while the routes here add nothing for a period without steps — not a table the sums are defined for)
+        if (!std::isfinite(w[j])) return fail(AFHIP_E_INVALID, "csr_create: weight at entry %lld is not finite", (long long)j);
     }
     auto* h = new afhip_csr();
     h->device = current_device();
@@ -1070,6 +1074,7 @@ extern "C" int afhip_plan_describe(const afhip_plan* plan, char* buf, int buf_le
     char tmp[1024], cg[48] = "", cm[24] = "";
     if (feat_has(plan->variant->feat, FEAT_CELL_MAP)) snprintf(cm, sizeof cm, " cells=%d", plan->hb_cells);
     if (plan->last_counts_lanes > 0) snprintf(cg, sizeof cg, " last-run=count-gather/%d-lane", plan->last_counts_lanes);
+    else if (plan->last_spatial) snprintf(cg, sizeof cg, "%s", plan->last_spatial == 1 ? " last-run=slot-gather" : " last-run=panel");
     int n = snprintf(tmp, sizeof tmp,
                      "variant=%s pipe=%d vec=%d stat=%d slots=%d kmax=%d depth=%d%s | T=%lld cells=%lld K=%d G1=%lld P=%lld | "
                      "wg=%d tiles=%lld chunks=%zu (steps %lld..%lld) out_slots=%lld%s%s | workspace=%.1f MiB%s%s",
@@ -1334,7 +1339,8 @@ extern "C" int afhip_plan_run(afhip_plan* plan, const void* cube_dev, const afhi
     if (kernel_ms) HIP_TRY(hipEventRecord(plan->ev[1], st));
     plan->last_route = rf ? 1 : 0;
     plan->last_counts_lanes = -1;
-    bool divided = false;           // the count gather wrote num / den / res itself
+    plan->last_spatial = 0;
+    bool divided = false;          // the count gather wrote num / den / res itself
     if (rf) {
         // a region's runs added in run order -> sums[r][p][K + 1] (no pieces: rows [0, R) only)
         const int64_t n = csr->R * P * (K + 1);
@@ -1388,7 +1394,9 @@ extern "C" int afhip_plan_run(afhip_plan* plan, const void* cube_dev, const afhi
     } else if (!exact && !cells_dev && !plan->packed && K > 0 && !plan->no_slot_spmm) {
         // no per-cell output wanted, no table-order promise: the weighted sums gather the slots directly (no panel)
         if ((rc = launch_spmm_slots(plan, csr, partial, st, num_dev, den_dev, res_dev, &divided))) return rc;
+        plan->last_spatial = 1;
     } else {
+        plan->last_spatial = 2;
         if ((rc = launch_combine(plan, partial, cells_dev, panel, st))) return rc;
         if ((rc = launch_spmm(csr, panel, plan->sums, Q, st, exact))) return rc;
     }

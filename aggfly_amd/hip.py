@@ -501,7 +501,8 @@ class CSR:
     """Region x cell weights resident in HBM (`_weight_triplets`, `aggfly/aggregate/spatial.py:157-178`).
 
     Built from COO triplets in table order; a stable sort by region row keeps the table's
-    entry order inside each row, which is the order `np.add.at` sums in.
+    entry order inside each row, which is the order `np.add.at` sums in.  Regions without entries
+    and an empty table are fine; a NaN or infinite weight raises ``ValueError``.
     """
 
     def __init__(self, region_idx, cell_idx, w_vals, n_regions: int, n_cells: int, device=None):

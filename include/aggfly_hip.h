@@ -130,7 +130,9 @@ int afhip_group_sine_dd(const void* cube_dev, int dtype, int64_t T, int64_t n_ce
  * Rows are regions in sorted-region-id order; inside a row the entries keep the weights
  * table's order, so sums run in the order np.add.at visits them (spatial.py:185).
  * indptr HOST int64[R+1]; cols HOST int64[nnz] (cell positions, 0 <= col < n_cells);
- * w HOST double[nnz].  The handle owns device copies; free with afhip_csr_destroy.
+ * w HOST double[nnz], every weight finite (zero and negative weights are fine; a NaN or infinite one is refused with AFHIP_E_INVALID).
+ * Regions without entries and a table without any (nnz == 0) are valid: their sums are 0 and their results NaN.
+ * The handle owns device copies; free with afhip_csr_destroy.
  * ---------------------------------------------------------------------------------- */
 typedef struct afhip_csr afhip_csr;
 int afhip_csr_create(const int64_t* indptr, const int64_t* cols, const double* w, int64_t R,
@@ -380,7 +382,10 @@ int afhip_unpack_u16(const void* q_dev, int64_t n, const afhip_packing* p, float
  * cell-major panel + the [rows][P][K+1] sums of that table).  A caller-owned workspace must be 256-byte aligned. */
 int64_t afhip_plan_workspace_bytes(const afhip_plan* plan);
 int64_t afhip_plan_run_workspace_bytes(const afhip_plan* plan, const afhip_csr* csr);
-/* Human-readable lowering (kernel variant, chunks, slots) into buf; returns bytes needed. */
+/* Human-readable lowering (kernel variant, chunks, slots) into buf; returns bytes needed.  After an afhip_plan_run it names the
+ * spatial route that run took: last-run=region-fused, last-run=slot-gather (one gather over the period partials),
+ * last-run=panel (cell-major panel, then weighted sums: exact_order, per-cell output, AFHIP_NO_SLOT_SPMM) or
+ * last-run=count-gather/N-lane (bin-count plans). */
 int afhip_plan_describe(const afhip_plan* plan, char* buf, int buf_len);
 
 /* Temporal stage only: cells_dev[K, P, n_cells] float64 = the per-cell, per-period value
