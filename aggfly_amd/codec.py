@@ -84,6 +84,11 @@ def load():
         lib.afcodec_lz4_encode_emulate.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
         lib.afcodec_blosc_encode_plan.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
                                                   C.POINTER(C.c_int64), C.c_void_p]
+        lib.afcodec_zstd_encode_block_emulate.restype = C.c_int64
+        lib.afcodec_zstd_encode_block_emulate.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64]
+        lib.afcodec_zstd_encode_scratch_bytes.restype = C.c_int64
+        lib.afcodec_zstd_encode_scratch_bytes.argtypes = [C.c_int64]
+        lib.afcodec_blosc_zstd_encode_plan.argtypes = lib.afcodec_blosc_encode_plan.argtypes
         lib.afcodec_read_packed.argtypes = [C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
                                             C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
         _lib = lib
@@ -95,7 +100,8 @@ EXPORTS = ("afcodec_last_error", "afcodec_have", "afcodec_blosc_info", "afcodec_
            "afcodec_blosc_bound", "afcodec_blosc_encode_lz4", "afcodec_zstd_decode", "afcodec_zstd_bound", "afcodec_zstd_encode", "afcodec_lz4_decode", "afcodec_blosc_lz4_plan", "afcodec_read_packed",
            "afcodec_zstd_plan", "afcodec_zstd_scratch_bytes", "afcodec_zstd_emulate",
            "afcodec_inflate_plan", "afcodec_inflate_scratch_bytes", "afcodec_inflate_emulate",
-           "afcodec_blosc_plan", "afcodec_blosc_encode", "afcodec_lz4_encode_emulate", "afcodec_blosc_encode_plan")
+           "afcodec_blosc_plan", "afcodec_blosc_encode", "afcodec_lz4_encode_emulate", "afcodec_blosc_encode_plan",
+           "afcodec_zstd_encode_block_emulate", "afcodec_zstd_encode_scratch_bytes", "afcodec_blosc_zstd_encode_plan")
 
 
 def _err(lib, what):
@@ -402,6 +408,122 @@ class BloscEncodePlan:
         buf = np.zeros(int(size.sum()), dtype=np.uint8)
         for r in ranges:
             buf[r["dst_off"]:r["dst_off"] + r["n"]] = slots[r["src_off"]:r["src_off"] + r["n"]]
+        self.finish(buf)
+        return [buf[o:o + z].tobytes() for o, z in zip(off, size)]
+
+
+# ---- the same with Zstandard streams: `hip.zstd_encode_blocks` (io.dataset_to_zarr, compress="blosc-zstd", encode="gpu") ----
+ZSTD_ENCODE_BLOCK = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("scratch_off", "<i8"), ("n", "<i4"), ("last", "<i4")])   # == afhip_zstd_encode_block
+ZSTD_FRAME_HEADER = 9              # magic, Frame_Header_Descriptor (Single_Segment_Flag, 4-byte Frame_Content_Size), the size
+
+
+def zstd_frame_header(size: int) -> bytes:
+    """The 9-byte header of the frames the GPU route writes: no window descriptor, no dictionary, no checksum."""
+    return b"\x28\xb5\x2f\xfd\xa0" + int(size).to_bytes(4, "little")
+
+
+def zstd_encode_block_emulate(data, last: bool = True) -> bytes:
+    """`afcodec_zstd_encode_block_emulate`: the Zstandard block encoder of `zstd_encode_pass.h` as `hip.zstd_encode_blocks` runs it, on
+    the host.  ``data``: 1 .. 131072 bytes -> one block with its 3-byte header (at most ``len(data) + 3`` bytes)."""
+    lib = load()
+    arr = np.ascontiguousarray(data).view(np.uint8).reshape(-1) if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), dtype=np.uint8)
+    dst = np.empty(arr.nbytes + 3, dtype=np.uint8)
+    r = lib.afcodec_zstd_encode_block_emulate(arr.ctypes.data, arr.nbytes, int(bool(last)), dst.ctypes.data, dst.nbytes)
+    if r < 0:
+        raise _err(lib, "zstd_encode_block_emulate")
+    return dst[:r].tobytes()
+
+
+class BloscZstdEncodePlan:
+    """`afcodec_blosc_zstd_encode_plan` for ``n`` chunks of ``nbytes`` bytes each: the Zstandard twin of `BloscEncodePlan` (byte shuffle,
+    unsplit 256 KiB blocks, one frame per block behind its int32 length, as `blosc_encode(cname="zstd")` lays them out).  ``blocks``
+    (`SHUFFLE_BLOCK`) for `hip.shuffle_blocks`, ``streams`` (`ZSTD_ENCODE_BLOCK`) for `hip.zstd_encode_blocks`: a frame is cut at the
+    byte planes of its shuffled block (128 KiB pieces where a plane is longer), every piece one block of the frame.  The shuffled input
+    and the slots share ONE work buffer (the slots from ``slot_base`` on), so that `hip.copy_ranges` takes a frame's blocks from their
+    slots or, for a frame that is stored, the shuffled bytes.  `place` and `finish` as in `BloscEncodePlan`."""
+
+    def __init__(self, n: int, nbytes: int, typesize: int):
+        lib = load()
+        ns, nb = C.c_int64(0), C.c_int64(0)
+        layout = np.zeros(8, dtype=np.int64)
+        if lib.afcodec_blosc_zstd_encode_plan(int(n), int(nbytes), int(typesize), None, 0, C.byref(ns), None, 0, C.byref(nb), layout.ctypes.data):
+            raise _err(lib, "blosc_zstd_encode_plan")
+        self.n, self.nbytes, self.typesize = int(n), int(nbytes), int(typesize)
+        self.streams = np.zeros(ns.value, dtype=ZSTD_ENCODE_BLOCK)
+        self.blocks = np.zeros(nb.value, dtype=SHUFFLE_BLOCK)
+        if lib.afcodec_blosc_zstd_encode_plan(int(n), int(nbytes), int(typesize), self.streams.ctypes.data, len(self.streams), C.byref(ns),
+                                              self.blocks.ctypes.data, len(self.blocks), C.byref(nb), layout.ctypes.data):
+            raise _err(lib, "blosc_zstd_encode_plan")
+        (self.blocksize, self.n_bstarts, self.per_chunk, self.flags, self.len_bytes, self.slot_base, self.slot_bytes,
+         self.scratch_bytes) = (int(v) for v in layout)
+        self.header_bytes = 16 + 4 * self.n_bstarts
+        self.max_bsize = int(self.blocks["bsize"].max()) if len(self.blocks) else 0
+        self.work_bytes = self.slot_base + self.slot_bytes
+        self.stored = self.n_bstarts == 0                                      # chunks under 128 bytes: the raw bytes behind the header
+        self.frames = max(1, self.n_bstarts)                                   # per chunk
+        last = self.streams["last"][:self.per_chunk]
+        self.frame_first = np.concatenate([[0], np.nonzero(last)[0][:-1] + 1]).astype(np.int64) if self.per_chunk else np.zeros(0, np.int64)
+        self.frame_of = np.cumsum(np.concatenate([[0], last[:-1]])).astype(np.int64) if self.per_chunk else np.zeros(0, np.int64)
+        self.bsize = self.blocks["bsize"][:self.frames].astype(np.int64)       # of every frame of a chunk
+
+    def place(self, csizes):
+        """``csizes[n * per_chunk]`` (bytes of every Zstandard block) -> (ranges, chunk_off[n], chunk_size[n]); a frame that would not be
+        shorter than its block's size - 1 is stored: one range takes the shuffled bytes instead (``stored_frames`` counts them)."""
+        if self.stored:
+            size = np.full(self.n, 16 + self.nbytes, dtype=np.int64)
+            off = np.cumsum(size) - size
+            ranges = np.zeros(self.n, dtype=COPY_RANGE)
+            ranges["src_off"], ranges["dst_off"], ranges["n"] = self.blocks["tmp_off"], off + 16, self.nbytes
+            self._off, self._size, self.stored_frames = off, size, self.n
+            return ranges, off, size
+        cs = np.asarray(csizes, dtype=np.int64).reshape(self.n, self.per_chunk)
+        fsize = ZSTD_FRAME_HEADER + np.add.reduceat(cs, self.frame_first, axis=1)               # (n, frames)
+        kept = fsize < self.bsize[None, :] - 1
+        fsize = np.where(kept, fsize, self.bsize[None, :])
+        step = fsize + self.len_bytes
+        rel = self.header_bytes + np.cumsum(step, axis=1) - step                                  # each frame's length field, from the chunk's start
+        size = self.header_bytes + step.sum(axis=1)
+        off = np.cumsum(size) - size
+        inner = np.cumsum(cs, axis=1) - cs
+        inner = inner - inner[:, self.frame_first][:, self.frame_of]                             # each block, from its frame's first block
+        kept_b = kept[:, self.frame_of]
+        at = (off[:, None] + rel + self.len_bytes)[:, self.frame_of] + ZSTD_FRAME_HEADER + inner
+        packed = np.zeros(int(kept_b.sum()), dtype=COPY_RANGE)
+        packed["src_off"] = self.slot_base + self.streams["dst_off"].reshape(self.n, self.per_chunk)[kept_b]
+        packed["dst_off"], packed["n"] = at[kept_b], cs[kept_b]
+        raw = np.zeros(int((~kept).sum()), dtype=COPY_RANGE)
+        raw["src_off"] = self.blocks["tmp_off"].reshape(self.n, self.frames)[~kept]
+        raw["dst_off"], raw["n"] = (off[:, None] + rel + self.len_bytes)[~kept], np.broadcast_to(self.bsize, kept.shape)[~kept]
+        self._kept, self._fsize, self._rel, self._off, self._size = kept, fsize, rel, off, size
+        self.stored_frames = int((~kept).sum())
+        return np.concatenate([packed, raw]), off, size
+
+    def finish(self, buf: np.ndarray):
+        """The 16-byte headers, the bstarts tables, the frame lengths and the frame headers of the containers `place` laid out."""
+        off, size = self._off, self._size
+        head = np.zeros((self.n, 16), dtype=np.uint8)
+        head[:, 0], head[:, 1], head[:, 2], head[:, 3] = 2, 1, self.flags, self.typesize
+        head[:, 4:8] = np.frombuffer(np.uint32(self.nbytes).astype("<u4").tobytes(), dtype=np.uint8)
+        head[:, 8:12] = np.frombuffer(np.uint32(self.blocksize).astype("<u4").tobytes(), dtype=np.uint8)
+        head[:, 12:16] = size.astype("<u4").view(np.uint8).reshape(-1, 4)
+        buf[off[:, None] + np.arange(16)] = head
+        if self.stored:
+            return
+        _put_u32(buf, off[:, None] + 16 + 4 * np.arange(self.n_bstarts), self._rel)
+        _put_u32(buf, off[:, None] + self._rel, self._fsize)
+        at = (off[:, None] + self._rel + self.len_bytes)[self._kept]
+        fh = np.zeros((len(at), ZSTD_FRAME_HEADER), dtype=np.uint8)
+        fh[:, :5] = np.frombuffer(zstd_frame_header(0)[:5], dtype=np.uint8)
+        fh[:, 5:] = np.broadcast_to(self.bsize, self._kept.shape)[self._kept].astype("<u4").view(np.uint8).reshape(-1, 4)
+        buf[at[:, None] + np.arange(ZSTD_FRAME_HEADER)] = fh
+
+    def assemble_host(self, work: np.ndarray, csizes):
+        """`place` + the range copies + `finish` on the host -> the n containers (the CPU tests' stand-in for `hip.copy_ranges`);
+        ``work``: the work buffer, shuffled input and slots."""
+        ranges, off, size = self.place(csizes)
+        buf = np.zeros(int(size.sum()), dtype=np.uint8)
+        for r in ranges:
+            buf[r["dst_off"]:r["dst_off"] + r["n"]] = work[r["src_off"]:r["src_off"] + r["n"]]
         self.finish(buf)
         return [buf[o:o + z].tobytes() for o, z in zip(off, size)]
 

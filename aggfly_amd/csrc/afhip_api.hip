@@ -18,6 +18,7 @@
 #include "afhip_panel_kernels.h"
 #include "afhip_lz4_kernels.h"
 #include "afhip_lz4_encode_kernels.h"
+#include "afhip_zstd_encode_kernels.h"
 #include "afhip_zstd_kernels.h"
 #include "afhip_inflate_kernels.h"
 #include "afhip_planner.h"
@@ -755,6 +756,27 @@ extern "C" int afhip_lz4_encode_streams(const void* in_dev, const afhip_lz4_stre
     GUARD_DEVICE(pointer_device(slots_dev));
     hipLaunchKernelGGL(k_lz4_encode_streams, dim3((unsigned)n_streams), dim3(64), 0, (hipStream_t)stream, (const uint8_t*)in_dev,
                        (const Lz4Stream*)streams_dev, (uint8_t*)slots_dev, csize_dev);
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
+extern "C" int64_t afhip_zstd_encode_scratch_bytes(int64_t n) {
+    if (n <= 0) return AFZE_TAB_BYTES + (256 - AFZE_TAB_BYTES % 256) % 256;
+    return n > AFZ_BLOCK_MAX ? -1 : afze_scratch_bytes((int32_t)n);
+}
+
+extern "C" int afhip_zstd_encode_blocks(const void* in_dev, const afhip_zstd_encode_block* blocks_dev, int64_t n_blocks, void* scratch_dev,
+                                        void* slots_dev, int32_t* csize_dev, void* stream) {
+    static_assert(sizeof(afhip_zstd_encode_block) == sizeof(ZstdEncodeBlock), "record layouts");
+    if (!in_dev || !blocks_dev || !scratch_dev || !slots_dev || !csize_dev || n_blocks < 0)
+        return fail(AFHIP_E_INVALID, "zstd_encode_blocks: bad arguments");
+    if (n_blocks == 0) return AFHIP_OK;
+    if (n_blocks > (int64_t)65535 * 65535) return fail(AFHIP_E_INVALID, "zstd_encode_blocks: too many blocks for one launch");
+    GUARD_DEVICE(pointer_device(slots_dev));
+    hipLaunchKernelGGL(k_zstd_encode_tables, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint8_t*)scratch_dev);
+    const dim3 grid((unsigned)std::min<int64_t>(n_blocks, 65535), (unsigned)((n_blocks + 65534) / 65535));
+    hipLaunchKernelGGL(k_zstd_encode_blocks, grid, dim3(64), 0, (hipStream_t)stream, (const uint8_t*)in_dev,
+                       (const ZstdEncodeBlock*)blocks_dev, n_blocks, (uint8_t*)scratch_dev, (uint8_t*)slots_dev, csize_dev);
     HIP_TRY(hipGetLastError());
     return AFHIP_OK;
 }

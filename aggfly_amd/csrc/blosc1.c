@@ -1085,6 +1085,110 @@ int afcodec_blosc_encode_plan(int64_t n, int64_t nbytes, int typesize, void* str
     return AFCODEC_OK;
 }
 
+/* ---- the same for Zstandard streams (libaggfly_hip: afhip_zstd_encode_blocks) ---- */
+#include "zstd_encode_pass.h"
+
+/* The encoder of zstd_encode_pass.h as the kernel runs it, on the host: src[0 .. n) -> one block (header and content) at dst
+ * (cap >= n + 3) -> its bytes. */
+int64_t afcodec_zstd_encode_block_emulate(const void* src, int64_t n, int last, void* dst, int64_t cap) {
+    if (n < 1 || n > AFZ_BLOCK_MAX || !src || !dst) return fail(AFCODEC_E_SIZE, "zstd_encode_block_emulate: a block holds 1 .. 131072 bytes");
+    if (cap < n + 3) return fail(AFCODEC_E_SIZE, "zstd_encode_block_emulate: the slot holds fewer than n + 3 bytes");
+    uint32_t* lds = (uint32_t*)malloc(sizeof(uint32_t) * AFZE_LDS_WORDS);
+    uint8_t* tables = (uint8_t*)malloc(AFZE_TAB_BYTES);
+    uint8_t* scratch = (uint8_t*)malloc((size_t)afze_scratch_bytes((int32_t)n));
+    int64_t c = fail(AFCODEC_E_SIZE, "out of memory");
+    if (lds && tables && scratch) {
+        afze_build_tables(tables);
+        c = afze_encode_block((const uint8_t*)src, (int32_t)n, last, (uint8_t*)dst, scratch, tables, lds, 0);
+    }
+    free(scratch);
+    free(tables);
+    free(lds);
+    return c;
+}
+
+int64_t afcodec_zstd_encode_scratch_bytes(int64_t n) {
+    return n <= 0 ? AFZE_TAB_BYTES + (256 - AFZE_TAB_BYTES % 256) % 256 : (n > AFZ_BLOCK_MAX ? -1 : afze_scratch_bytes((int32_t)n));
+}
+
+/* The pieces a shuffled Blosc block of bsize bytes is cut into, each one block of its frame: the byte planes when a plane holds 1 ..
+ * 128 KiB (then the bsize % typesize trailing bytes, if any), else pieces of 128 KiB.  piece k -> its offset in the block; -> its bytes
+ * (0: no such piece). */
+static int64_t zstd_encode_piece(int64_t bsize, int typesize, int64_t k, int64_t* off) {
+    const int64_t plane = bsize / typesize;
+    if (typesize > 1 && plane >= 1 && plane <= AFZ_BLOCK_MAX) {
+        if (k < typesize) { *off = k * plane; return plane; }
+        *off = (int64_t)typesize * plane;
+        return k == typesize ? bsize - *off : 0;
+    }
+    *off = k * AFZ_BLOCK_MAX;
+    return *off >= bsize ? 0 : (bsize - *off < AFZ_BLOCK_MAX ? bsize - *off : AFZ_BLOCK_MAX);
+}
+
+/* Geometry of n chunks of nbytes bytes each, written as afcodec_blosc_encode writes Zstandard chunks under the byte shuffle with the
+ * automatic block size: unsplit blocks, one frame per block, every frame cut into blocks by zstd_encode_piece. */
+int afcodec_blosc_zstd_encode_plan(int64_t n, int64_t nbytes, int typesize, void* zblocks_v, int64_t cap_zblocks, int64_t* n_zblocks,
+                                   void* blocks_v, int64_t cap_blocks, int64_t* n_blocks, int64_t* layout) {
+    typedef struct { int64_t src_off, dst_off, scratch_off; int32_t n, last; } zblock_rec;      /* == afhip_zstd_encode_block */
+    typedef struct { int64_t tmp_off, out_off; int32_t bsize, typesize; } shuf_rec;            /* == afhip_shuffle_block */
+    zblock_rec* zb = (zblock_rec*)zblocks_v;
+    shuf_rec* bl = (shuf_rec*)blocks_v;
+    if (n < 0 || nbytes <= 0 || nbytes > 0x7fffffffLL - 64 || typesize < 1 || typesize > 255 || !n_zblocks || !n_blocks || !layout)
+        return fail(AFCODEC_E_SIZE, "blosc_zstd_encode_plan: bad n / nbytes / typesize");
+    const int cname = 4, filter = typesize > 1 ? 0x01 : 0;
+    const int stored = nbytes < 128;                         /* tiny buffers are stored */
+    const int64_t blocksize = stored ? nbytes : blosc_encode_blocksize(cname, typesize, 0, nbytes);
+    const int64_t nblocks = stored ? 1 : (nbytes + blocksize - 1) / blocksize, leftover = stored ? 0 : nbytes % blocksize;
+    int64_t per_chunk = 0, slot_chunk = 0, scratch_chunk = 0;
+    for (int64_t b = 0; b < nblocks && !stored; ++b) {
+        const int64_t bsize = b == nblocks - 1 && leftover > 0 ? leftover : blocksize;
+        int64_t off, len;
+        for (int64_t k = 0; (len = zstd_encode_piece(bsize, filter ? typesize : 1, k, &off)) > 0; ++k) {
+            ++per_chunk;
+            slot_chunk += len + 3;
+            scratch_chunk += afze_scratch_bytes((int32_t)len);
+        }
+    }
+    const int64_t tables = afcodec_zstd_encode_scratch_bytes(0);
+    layout[0] = stored ? nbytes : blocksize;                 /* header field */
+    layout[1] = stored ? 0 : nblocks;                        /* entries of the bstarts table = frames */
+    layout[2] = per_chunk;                                   /* Zstandard blocks per chunk */
+    layout[3] = stored ? (0x02 | filter | (cname << 5) | 0x10) : (filter | 0x10 | (cname << 5));
+    layout[4] = stored ? 0 : 4;                              /* bytes of the length field in front of every frame */
+    layout[5] = (n * nbytes + 255) & ~(int64_t)255;          /* the slots' first byte in the work buffer, behind the shuffled input */
+    layout[6] = n * slot_chunk;                              /* bytes of the slots */
+    layout[7] = tables + n * scratch_chunk;                  /* bytes of the encoder's scratch */
+    *n_zblocks = n * per_chunk;
+    *n_blocks = n * nblocks;
+    if (!zb && !bl) return AFCODEC_OK;                       /* the counts and the layout alone */
+    if (!bl || (!zb && *n_zblocks) || *n_zblocks > cap_zblocks || *n_blocks > cap_blocks)
+        return fail(AFCODEC_E_SIZE, "blosc_zstd_encode_plan: record list too small");
+    int64_t zi = 0, bi = 0, slot = 0, scratch = tables;
+    for (int64_t c = 0; c < n; ++c) {
+        for (int64_t b = 0; b < nblocks; ++b) {
+            const int last_short = b == nblocks - 1 && leftover > 0;
+            const int64_t bsize = last_short ? leftover : blocksize, at = c * nbytes + b * blocksize;
+            bl[bi].tmp_off = bl[bi].out_off = at;
+            bl[bi].bsize = (int32_t)bsize;
+            bl[bi].typesize = (filter && !stored) ? typesize : 1;        /* (a stored chunk holds the raw bytes: a copy) */
+            ++bi;
+            if (stored) continue;
+            int64_t off, len;
+            for (int64_t k = 0; (len = zstd_encode_piece(bsize, filter ? typesize : 1, k, &off)) > 0; ++k, ++zi) {
+                int64_t off2;
+                zb[zi].src_off = at + off;
+                zb[zi].dst_off = slot;
+                zb[zi].scratch_off = scratch;
+                zb[zi].n = (int32_t)len;
+                zb[zi].last = zstd_encode_piece(bsize, filter ? typesize : 1, k + 1, &off2) == 0;
+                slot += len + 3;
+                scratch += afze_scratch_bytes((int32_t)len);
+            }
+        }
+    }
+    return AFCODEC_OK;
+}
+
 /* Plain Zstandard frames (Zarr compressor id "zstd"). */
 int64_t afcodec_zstd_decode(const void* src, int64_t n, void* dst, int64_t cap) {
     int rc = need_zstd();

@@ -40,7 +40,8 @@ EXPORTS = (
     "afhip_plan_profile_begin", "afhip_plan_profile_end", "afhip_plan_bind_inter", "afhip_csr_device", "afhip_plan_device", "afhip_transform", "afhip_panel_divide", "afhip_lz4_decode_streams", "afhip_unshuffle_blocks", "afhip_read_probe",
     "afhip_zstd_scratch_bytes", "afhip_zstd_decode", "afhip_inflate_scratch_bytes", "afhip_inflate_decode", "afhip_bitunshuffle_blocks",
     "afhip_plan_bind_packing", "afhip_unpack_i16", "afhip_unpack_u16", "afhip_plan_bind_packings",
-    "afhip_take_box", "afhip_shuffle_blocks", "afhip_lz4_encode_streams", "afhip_copy_ranges",
+    "afhip_take_box", "afhip_shuffle_blocks", "afhip_lz4_encode_streams", "afhip_copy_ranges", "afhip_zstd_encode_blocks",
+    "afhip_zstd_encode_scratch_bytes",
 )
 
 
@@ -132,6 +133,9 @@ def load():
     lib.afhip_shuffle_blocks.argtypes = [vp, vp, vp, i64, i32, vp]
     lib.afhip_lz4_encode_streams.argtypes = [vp, vp, i64, vp, vp, vp]
     lib.afhip_copy_ranges.argtypes = [vp, vp, vp, i64, vp]
+    lib.afhip_zstd_encode_blocks.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    lib.afhip_zstd_encode_scratch_bytes.restype = i64
+    lib.afhip_zstd_encode_scratch_bytes.argtypes = [i64]
     lib.afhip_zstd_scratch_bytes.restype = i64
     lib.afhip_zstd_scratch_bytes.argtypes = [i64] * 5
     lib.afhip_zstd_decode.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, i64, vp, i64, vp, vp, vp, vp]
@@ -286,6 +290,14 @@ def lz4_encode_streams(inp, streams, n_streams: int, slots, csize):
     ``inp[src_off : src_off + dsize]`` into ``slots[dst_off : dst_off + dsize]``; the sizes go to the int32 HBM tensor ``csize``."""
     _check(load().afhip_lz4_encode_streams(inp.data_ptr(), streams.data_ptr(), int(n_streams), slots.data_ptr(), csize.data_ptr(),
                                            _stream_ptr(slots)))
+
+
+def zstd_encode_blocks(inp, blocks, n_blocks: int, scratch, slots, csize):
+    """`afhip_zstd_encode_blocks`: one wave per record of ``blocks`` (uint8 HBM tensor of `codec.ZSTD_ENCODE_BLOCK` records) encodes
+    ``inp[src_off : src_off + n]`` into one Zstandard block at ``slots[dst_off : dst_off + n + 3]``; ``csize[i]`` (int32) = its bytes.
+    ``scratch``: `codec.BloscZstdEncodePlan.scratch_bytes` bytes."""
+    _check(load().afhip_zstd_encode_blocks(inp.data_ptr(), blocks.data_ptr(), int(n_blocks), scratch.data_ptr(), slots.data_ptr(),
+                                           csize.data_ptr(), _stream_ptr(slots)))
 
 
 def copy_ranges(src, dst, ranges, n_ranges: int):

@@ -1514,7 +1514,7 @@ def _write_array(path, name, data, dims, chunks, attrs, compressor, zarr_format:
     if shards is not None and zarr_format != 3:
         raise ValueError("shards need zarr_format=3")
     if isinstance(data, _DeviceCube):
-        return _write_chunks_gpu(d, data, chunks, zarr_format, shards)
+        return _write_chunks_gpu(d, data, chunks, zarr_format, shards, compressor.get("cname", "lz4"))
 
     def encode_chunk(idx):
         sl = tuple(slice(i * c, min((i + 1) * c, s)) for i, c, s in zip(idx, chunks, data.shape))
@@ -1587,14 +1587,20 @@ def _write_array(path, name, data, dims, chunks, attrs, compressor, zarr_format:
 # AND the store it writes is at most 1.10 x the host-written one.  Measured (profiles/lz4_encode.txt): 0.68 / 0.61 / 0.46 / 0.45 x at
 # 128 / 256 / 512 / 860 MB on the worst layout, 1.07 x at 64 MiB; stores 1.005-1.007 x.  None would mean: never without the environment.
 GPU_ENCODE_AUTO_BYTES = 128 << 20
+# The same rule for compress="blosc-zstd" (Zstandard streams from `hip.zstd_encode_blocks`), the host-written store being libzstd's at
+# level 3.  Measured (profiles/zstd_encode.txt): stores 0.97-1.093 x, within the rule; the time rule fails on the (24, ny, nx) layout at
+# every size — 1.36 / 0.99 / 0.95 / 0.93 x at 64 / 256 / 512 / 860 MB — while whole-series tiles run at 0.18-0.34 x.  No size meets the rule
+# on every layout, so None: "auto" never takes the route for Zstandard streams without AGGFLY_HIP_GPU_ENCODE=1.
+GPU_ENCODE_AUTO_BYTES_BLOSC_ZSTD = None
 GPU_ENCODE_BATCH_BYTES = 256 << 20                # decoded bytes of a batch of chunks (one chunk at least)
 _GPU_ENCODE_DTYPES = ("f4", "f8", "i1", "u1", "i2", "u2", "i4", "u4", "i8", "u8")
 
 
 def _gpu_encode_refusal(compress, np_dtype, ctuple) -> Optional[str]:
     """None, or why `dataset_to_zarr` cannot take the GPU route for this call."""
-    if compress not in (True, "blosc"):
-        return f"compress={compress!r}: the GPU route writes Blosc-1 chunks of LZ4 streams under the byte shuffle (compress=True or 'blosc') only"
+    if compress not in (True, "blosc", "blosc-zstd"):
+        return (f"compress={compress!r}: the GPU route writes Blosc-1 chunks of LZ4 or Zstandard streams under the byte shuffle "
+                "(compress=True, 'blosc' or 'blosc-zstd') only")
     if np.dtype(np_dtype).str[1:] not in _GPU_ENCODE_DTYPES:
         return f"dtype {np.dtype(np_dtype)}: the GPU route takes float32, float64 and integers of 1, 2, 4 or 8 bytes"
     if int(np.prod(ctuple)) * np.dtype(np_dtype).itemsize > 0x7fffffff - 64:
@@ -1602,10 +1608,12 @@ def _gpu_encode_refusal(compress, np_dtype, ctuple) -> Optional[str]:
     return None
 
 
-def _write_chunks_gpu(d, data: "_DeviceCube", chunks, zarr_format, shards):
+def _write_chunks_gpu(d, data: "_DeviceCube", chunks, zarr_format, shards, cname="lz4"):
     """The chunk files (or shard files) of one array, encoded in HBM.  Per batch of chunks of up to GPU_ENCODE_BATCH_BYTES:
     `hip.take_box` per chunk (edge chunks padded with the fill value) -> `hip.shuffle_blocks` -> `hip.lz4_encode_streams` into one
-    slot per stream -> the sizes to the host (a small D2H) -> `hip.copy_ranges` packs the streams into their containers -> one D2H
+    slot per stream (``cname`` "zstd": `hip.zstd_encode_blocks` into one slot per block of a frame, planned by
+    `codec.BloscZstdEncodePlan`; everything else is shared) -> the sizes to the host (a small D2H) -> `hip.copy_ranges` packs the
+    streams into their containers (a Zstandard frame that did not shrink: the shuffled bytes instead) -> one D2H
     into a page-locked buffer -> `codec.BloscEncodePlan.finish` fills headers, block tables and stream lengths -> files, from a small
     thread pool.  Two packed buffers on each side: batch i's D2H and file writes overlap batch i + 1's kernels.  Shard bodies and the
     shard index with its crc32c are host work over the compressed chunks."""
@@ -1634,18 +1642,34 @@ def _write_chunks_gpu(d, data: "_DeviceCube", chunks, zarr_format, shards):
         return
     per = max(1, min(len(order), GPU_ENCODE_BATCH_BYTES // cb))
     plans = {}
+    zstd = cname == "zstd"                                   # the flavour decides the plan class, the buffers and the encode call: nothing else
+    plan_class = codec.BloscZstdEncodePlan if zstd else codec.BloscEncodePlan
 
     def plan_of(n):                                         # (two at most: the full batch and the last one)
         if n not in plans:
-            pl = codec.BloscEncodePlan(n, cb, item)
+            pl = plan_class(n, cb, item)
             rec = np.concatenate([pl.streams.view(np.uint8), pl.blocks.view(np.uint8)])
             plans[n] = (pl, torch.from_numpy(rec).to(dev), pl.streams.nbytes)
         return plans[n]
 
     pl0 = plan_of(per)[0]
-    packed_cap = per * (cb + pl0.header_bytes + 4 * pl0.per_chunk)
-    chunk_dev, tmp_dev, slots_dev = (torch.empty(per * cb, dtype=torch.uint8, device=dev) for _ in range(3))
-    csize_dev = torch.empty(per * pl0.per_chunk, dtype=torch.int32, device=dev)
+    if zstd:                                                 # one work buffer, the shuffled input and behind it the slots: `copy_ranges` takes either
+        packed_cap = per * (cb + pl0.header_bytes + 4 * pl0.frames)
+        chunk_dev = torch.empty(per * cb, dtype=torch.uint8, device=dev)
+        tmp_dev = torch.empty(pl0.work_bytes, dtype=torch.uint8, device=dev)
+        scratch_dev = torch.empty(pl0.scratch_bytes, dtype=torch.uint8, device=dev)
+        slots_dev = tmp_dev
+
+        def encode(pl, rec_dev):
+            if len(pl.streams):                              # (chunks under 128 bytes are stored: nothing to encode)
+                hip.zstd_encode_blocks(tmp_dev, rec_dev, len(pl.streams), scratch_dev, tmp_dev[pl.slot_base:], csize_dev)
+    else:
+        packed_cap = per * (cb + pl0.header_bytes + 4 * pl0.per_chunk)
+        chunk_dev, tmp_dev, slots_dev = (torch.empty(per * cb, dtype=torch.uint8, device=dev) for _ in range(3))
+
+        def encode(pl, rec_dev):
+            hip.lz4_encode_streams(tmp_dev, rec_dev, len(pl.streams), slots_dev, csize_dev)
+    csize_dev = torch.empty(max(1, per * pl0.per_chunk), dtype=torch.int32, device=dev)
     packed_dev = [torch.empty(packed_cap, dtype=torch.uint8, device=dev) for _ in range(2)]
     pinned = _pinned_stage(packed_cap, 2, dev)
     work, copy = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
@@ -1693,7 +1717,7 @@ def _write_chunks_gpu(d, data: "_DeviceCube", chunks, zarr_format, shards):
         nb = len(pl.blocks)
         for b0 in range(0, nb, 65535):
             hip.shuffle_blocks(chunk_dev, tmp_dev, rec_dev[blocks_at + b0 * codec.SHUFFLE_BLOCK.itemsize:], min(65535, nb - b0), pl.max_bsize)
-        hip.lz4_encode_streams(tmp_dev, rec_dev, len(pl.streams), slots_dev, csize_dev)
+        encode(pl, rec_dev)
         return pl
 
     def pack(k, pl):
@@ -1781,10 +1805,11 @@ def dataset_to_zarr(dataset: Dataset, path: str, var: str = "var", chunks=None, 
     ``zarr_format``: 2 (``.zarray``) or 3 (``zarr.json``, ``c/`` chunk keys); ``shards`` (format 3): a dict like
     ``chunks`` giving the shard shape in which the chunks are bundled (``sharding_indexed``).
     ``encode``: where the data variable's chunks are cut, shuffled and compressed.  "host": on host threads, from a host copy of
-    the cube.  "gpu": in HBM (`_write_chunks_gpu`; Blosc-1 LZ4 + byte shuffle only, i.e. ``compress`` True or "blosc"; a
-    host-resident cube is uploaded first) — the chunks cross PCIe compressed; anything else raises `ValueError`.  The store
-    decodes to the same values; its LZ4 streams are the GPU encoder's, not liblz4's.  "auto": the GPU route for a device-resident
-    cube of `GPU_ENCODE_AUTO_BYTES` or more (None: never) or when ``AGGFLY_HIP_GPU_ENCODE=1`` is set (``0``: never), and the call is
+    the cube.  "gpu": in HBM (`_write_chunks_gpu`; Blosc-1 under the byte shuffle with LZ4 streams, ``compress`` True or "blosc", or
+    Zstandard streams, "blosc-zstd"; a host-resident cube is uploaded first) — the chunks cross PCIe compressed; anything else
+    raises `ValueError`.  The store decodes to the same values; its streams are the GPU encoders', not liblz4's or libzstd's.
+    "auto": the GPU route for a device-resident cube of `GPU_ENCODE_AUTO_BYTES` (``compress="blosc-zstd"``: `GPU_ENCODE_AUTO_BYTES_BLOSC_ZSTD`) or more (None: never) or when
+    ``AGGFLY_HIP_GPU_ENCODE=1`` is set (``0``: never), and the call is
     eligible; else the host route — always for a host-resident cube.  Coordinates and metadata are written by the same code on every route."""
     if encode not in ("auto", "host", "gpu"):
         raise ValueError(f"encode must be 'auto', 'host' or 'gpu', got {encode!r}")
@@ -1804,7 +1829,8 @@ def dataset_to_zarr(dataset: Dataset, path: str, var: str = "var", chunks=None, 
         elif refusal is None and not on_host and cube.is_cuda:
             nbytes = int(cube.numel()) * int(cube.element_size())
             mode = os.environ.get("AGGFLY_HIP_GPU_ENCODE", "auto")
-            use_gpu = mode == "1" or (mode != "0" and GPU_ENCODE_AUTO_BYTES is not None and nbytes >= GPU_ENCODE_AUTO_BYTES)
+            auto_bytes = GPU_ENCODE_AUTO_BYTES_BLOSC_ZSTD if compress == "blosc-zstd" else GPU_ENCODE_AUTO_BYTES
+            use_gpu = mode == "1" or (mode != "0" and auto_bytes is not None and nbytes >= auto_bytes)
     if use_gpu:
         if on_host:
             import torch

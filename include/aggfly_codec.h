@@ -61,6 +61,21 @@ int64_t afcodec_blosc_encode(const void* src, int64_t nbytes, int typesize, int 
  *                         its flags byte, the bytes of the length field in front of every stream (4; 0 in a stored chunk).
  * With streams and blocks both NULL only the counts and the layout are returned.  Nothing is encoded here. */
 int64_t afcodec_lz4_encode_emulate(const void* src, int64_t n, void* dst, int64_t cap);
+/* The same for Zstandard streams (afhip_zstd_encode_blocks).
+ * afcodec_zstd_encode_block_emulate: the block encoder of aggfly_amd/csrc/zstd_encode_pass.h exactly as the kernel runs it: src[0 .. n),
+ * 1 <= n <= 131072, into dst (cap >= n + 3) -> the bytes of one complete Zstandard block with its header (last: the Last_Block bit).
+ * afcodec_zstd_encode_scratch_bytes: afhip_zstd_encode_scratch_bytes.
+ * afcodec_blosc_zstd_encode_plan: afcodec_blosc_encode_plan for the chunks afcodec_blosc_encode writes with cname 4 under the byte
+ * shuffle — unsplit 256 KiB blocks (flag 0x10), one frame per block behind its int32 length — with afhip_zstd_encode_block records in
+ * place of the stream records: a frame is cut at the byte planes of its shuffled block when a plane holds at most 128 KiB, else into
+ * 128 KiB pieces, each piece one block of the frame (`last` on its last); src_off in the shuffled input, dst_off in the slots (n + 3
+ * bytes each, in order), scratch_off in the encoder's scratch.  layout [8]: the five of afcodec_blosc_encode_plan (streams = Zstandard
+ * blocks per chunk), then the offset of the slots in a work buffer that starts with the shuffled input, the bytes of the slots, the
+ * bytes of the scratch. */
+int64_t afcodec_zstd_encode_block_emulate(const void* src, int64_t n, int last, void* dst, int64_t cap);
+int64_t afcodec_zstd_encode_scratch_bytes(int64_t n);
+int afcodec_blosc_zstd_encode_plan(int64_t n, int64_t nbytes, int typesize, void* zblocks, int64_t cap_zblocks, int64_t* n_zblocks,
+                                   void* blocks, int64_t cap_blocks, int64_t* n_blocks, int64_t* layout);
 int afcodec_blosc_encode_plan(int64_t n, int64_t nbytes, int typesize, void* streams, int64_t cap_streams, int64_t* n_streams,
                               void* blocks, int64_t cap_blocks, int64_t* n_blocks, int64_t* layout);
 

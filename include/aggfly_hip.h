@@ -224,6 +224,14 @@ int afhip_bitunshuffle_blocks(const void* tmp_dev, void* out_dev, const afhip_sh
  * receives the stream's size: an LZ4 block of at most dsize - 1 bytes, or dsize with the raw bytes in the slot (stored: the rule of
  * afcodec_blosc_encode).  The bytes are a function of the input alone (aggfly_amd/csrc/lz4_encode_pass.h; the host runs the same
  * text as afcodec_lz4_encode_emulate).  Nothing is written outside the slot.
+ * afhip_zstd_encode_blocks: the same place in the route for Zstandard streams (compress="blosc-zstd"): one wave per record — src_off:
+ * the block's n raw bytes (1 .. 131072) in in_dev, dst_off: its slot of n + 3 bytes in slots_dev, scratch_off: its own
+ * afhip_zstd_encode_scratch_bytes(n) bytes in scratch_dev, 256-aligned and behind the first afhip_zstd_encode_scratch_bytes(0) bytes,
+ * which hold the launch's code tables; last != 0: the Last_Block bit.  csize_dev[i] receives the size of one complete Zstandard block,
+ * Block_Header included: RLE, compressed (its own Huffman tree, predefined sequence codes, no repeat offsets, no match before the
+ * block) or raw, at most n + 3 bytes.  Blocks in the order of their records behind a frame header are a frame; the caller writes the
+ * header.  The bytes are a function of the input alone (aggfly_amd/csrc/zstd_encode_pass.h; the host runs the same text as
+ * afcodec_zstd_encode_block_emulate).  Nothing is written outside the slot and the block's scratch.
  * afhip_copy_ranges: bytes [src_off, src_off + n) of src_dev to dst_dev + dst_off per record — after the host has read the sizes,
  * every stream from its slot to its place in the batch's packed output; ranges of one call must not overlap in dst_dev.
  * All pointers are device memory, the work is enqueued on `stream`, nothing is retained. */
@@ -236,6 +244,10 @@ int afhip_shuffle_blocks(const void* out_dev, void* tmp_dev, const afhip_shuffle
 int afhip_lz4_encode_streams(const void* in_dev, const afhip_lz4_stream* streams_dev, int64_t n_streams, void* slots_dev,
                              int32_t* csize_dev, void* stream);
 int afhip_copy_ranges(const void* src_dev, void* dst_dev, const afhip_copy_range* ranges_dev, int64_t n_ranges, void* stream);
+typedef struct afhip_zstd_encode_block { int64_t src_off, dst_off, scratch_off; int32_t n, last; } afhip_zstd_encode_block;
+int64_t afhip_zstd_encode_scratch_bytes(int64_t n);
+int afhip_zstd_encode_blocks(const void* in_dev, const afhip_zstd_encode_block* blocks_dev, int64_t n_blocks, void* scratch_dev,
+                             void* slots_dev, int32_t* csize_dev, void* stream);
 
 /* Zstandard frames decoded in HBM (Zarr v2 compressor "zstd", Zarr v3 bytes -> zstd, shards too).  The host walks the frame,
  * block and section headers (afcodec_zstd_plan, include/aggfly_codec.h) into one record per frame and per block, which

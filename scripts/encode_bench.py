@@ -12,7 +12,10 @@ routes, one JSON line per (layout, size).  Then per layout the kernel times of o
 <= 0.9 x the host route's minimum AND the GPU-written store is at most 1.10 x the host-written one; null when there is none, with the
 condition that fails.
 
-    python scripts/encode_bench.py [--reps 3] [--sizes 64,821]      # (MiB; default: 64 ... the whole cube)
+--compress blosc-zstd is the same bench for Zstandard streams (`afhip_zstd_encode_blocks` in place of the LZ4 kernel; the host route:
+libzstd level 3 through `afcodec_blosc_encode`); its last line names `io.GPU_ENCODE_AUTO_BYTES_BLOSC_ZSTD`.
+
+    python scripts/encode_bench.py [--reps 3] [--sizes 64,821] [--compress blosc|blosc-zstd]      # (MiB; default: 64 ... the whole cube)
 """
 import argparse
 import json
@@ -47,11 +50,14 @@ def dataset(cube):
                                     "longitude": 230 + 0.25 * np.arange(NX)}), lon_is_360=True)
 
 
+COMPRESS = "blosc"
+
+
 def write(ds, base, chunks, route):
     with tempfile.TemporaryDirectory(dir=base) as d:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        af.dataset_to_zarr(ds, d, var="t2m", chunks=chunks, encode=route)
+        af.dataset_to_zarr(ds, d, var="t2m", chunks=chunks, encode=route, compress=COMPRESS)
         torch.cuda.synchronize()
         s = time.perf_counter() - t0
         var = os.path.join(d, "t2m")
@@ -67,9 +73,15 @@ def kernel_times(cube_dev, chunks, reps):
     grid = [-(-s // c) for s, c in zip(shape, ct)]
     idxs = list(np.ndindex(*grid))[:max(1, afio.GPU_ENCODE_BATCH_BYTES // cb)]
     n = len(idxs)
-    pl = codec.BloscEncodePlan(n, cb, 4)
+    zstd = COMPRESS == "blosc-zstd"
+    pl = (codec.BloscZstdEncodePlan if zstd else codec.BloscEncodePlan)(n, cb, 4)
     rec = torch.from_numpy(np.concatenate([pl.streams.view(np.uint8), pl.blocks.view(np.uint8)])).cuda()
-    chunk_dev, tmp_dev, slots_dev = (torch.empty(n * cb, dtype=torch.uint8, device="cuda") for _ in range(3))
+    if zstd:                                                                   # (the route's buffers: the shuffled input and the slots in one)
+        chunk_dev = torch.empty(n * cb, dtype=torch.uint8, device="cuda")
+        tmp_dev = slots_dev = torch.empty(pl.work_bytes, dtype=torch.uint8, device="cuda")
+        scratch = torch.empty(pl.scratch_bytes, dtype=torch.uint8, device="cuda")
+    else:
+        chunk_dev, tmp_dev, slots_dev = (torch.empty(n * cb, dtype=torch.uint8, device="cuda") for _ in range(3))
     packed = torch.empty(n * (cb + pl.header_bytes + 4 * pl.per_chunk), dtype=torch.uint8, device="cuda")
     csize = torch.empty(len(pl.streams), dtype=torch.int32, device="cuda")
     fill = int(np.array([np.nan], dtype=np.float32).view(np.uint32)[0])
@@ -104,12 +116,15 @@ def kernel_times(cube_dev, chunks, reps):
     for _ in range(reps + 1):
         timed("take_box", take)
         timed("shuffle_blocks", shuffle)
-        timed("lz4_encode_streams", lambda: hip.lz4_encode_streams(tmp_dev, rec, len(pl.streams), slots_dev, csize))
+        if zstd:
+            timed("zstd_encode_blocks", lambda: hip.zstd_encode_blocks(tmp_dev, rec, len(pl.streams), scratch, tmp_dev[pl.slot_base:], csize))
+        else:
+            timed("lz4_encode_streams", lambda: hip.lz4_encode_streams(tmp_dev, rec, len(pl.streams), slots_dev, csize))
         cs = csize.cpu().numpy()
         ranges, off, size = pl.place(cs)
         rdev = torch.from_numpy(ranges.view(np.uint8)).cuda()
         timed("copy_ranges", lambda: hip.copy_ranges(slots_dev, packed, rdev, len(ranges)))
-    stored = int((cs == pl.streams["dsize"]).sum())
+    stored = pl.stored_frames if zstd else int((cs == pl.streams["dsize"]).sum())
     return {"chunks": n, "batch_bytes": n * cb, "streams": len(pl.streams), "stored_streams": stored, "packed_bytes": int(size.sum()),
             "ms": {k: round(v, 3) for k, v in best.items()},
             "GB_per_s": {k: round(n * cb / v / 1e6, 1) for k, v in best.items()}}
@@ -119,7 +134,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sizes", default="")
+    ap.add_argument("--compress", default="blosc", choices=("blosc", "blosc-zstd"))
     a = ap.parse_args()
+    global COMPRESS
+    COMPRESS = a.compress
     cube = synth.temperature_cube(T, NY, NX, dtype=np.float32, seed=1) + np.float32(273.15)
     step = NY * NX * 4
     sizes = [s for s in (64 << 20, 128 << 20, 256 << 20, 512 << 20) if s < T * step] + [T * step]
@@ -157,7 +175,7 @@ def main():
         if not (ok_time[s] and ok_size[s]):
             break
         from_size = s
-    print(json.dumps({"GPU_ENCODE_AUTO_BYTES": from_size,
+    print(json.dumps({"GPU_ENCODE_AUTO_BYTES_BLOSC_ZSTD" if COMPRESS == "blosc-zstd" else "GPU_ENCODE_AUTO_BYTES": from_size,
                       "time_rule_holds_at_bytes": [s for s in sizes if ok_time[s]], "size_rule_holds_at_bytes": [s for s in sizes if ok_size[s]],
                       "worst_gpu_median_over_host_min_by_size": {str(s): round(worst[s][0], 3) for s in sizes},
                       "worst_gpu_store_over_host_store_by_size": {str(s): round(worst[s][1], 4) for s in sizes}}), flush=True)
