@@ -56,7 +56,7 @@ def store_route_ok(config, paths) -> bool:
     p = paths[0]
     if not isinstance(p, str) or any(ch in p for ch in "*?[") or "://" in p:
         return False
-    if not (afio._looks_like_zarr(p) or (os.path.isfile(p) and afio._is_hdf5(p))):
+    if not (afio._looks_like_zarr(p) or (os.path.isfile(p) and (afio._is_hdf5(p) or _streams_classic(config, p)))):
         return False
     try:
         D.output_freq(config.to_aggregator_dict())
@@ -152,19 +152,27 @@ def find_weights_table(config) -> str:
         "aggfly's calculate_weights() (weights are computed on the CPU by aggfly.weights, not by this engine)")
 
 
-def _streams_from_store(path) -> bool:
-    """Is `path` a file the streaming route takes (one Zarr store or netCDF-4 file, a GPU to stream to)?  Only there does
+def _streams_classic(config, path) -> bool:
+    """Is `path` a NetCDF classic file whose variable the streaming route takes (`io._netcdf3_source`: a readable header, a 3-D
+    time-leading variable of type short / int / float / double)?"""
+    from .. import io as afio
+    return afio._is_netcdf3(path) and afio._netcdf3_source(path, config.var, config.timecoord) is not None
+
+
+def _streams_from_store(config, path) -> bool:
+    """Is `path` a file the streaming route takes (one Zarr store, netCDF-4 file or NetCDF classic file whose variable
+    ``config.var`` qualifies, a GPU to stream to)?  Only there does
     ``time_window`` cut the read itself; everywhere else `dataset_from_path` reads the file whole and cuts on the host."""
     from .. import hip, io as afio
     if hip.device_count() == 0 or not isinstance(path, str) or any(ch in path for ch in "*?[") or "://" in path:
         return False
-    return afio._looks_like_zarr(path) or (os.path.isfile(path) and afio._is_hdf5(path))
+    return afio._looks_like_zarr(path) or (os.path.isfile(path) and (afio._is_hdf5(path) or _streams_classic(config, path)))
 
 
 def load_grid(config, path, georegions):
     """`path` opened for its grid and coordinates only (no time step is read), the way `distributed.aggregate_store_cells`
     opens its ``head``; today's full load where the streaming route does not take the file."""
-    if not _streams_from_store(path):
+    if not _streams_from_store(config, path):
         return load_dataset(config, path, georegions)
     return af.dataset_from_path(path, var=config.var, device="cuda", time_window=(0, 0), **_open_kwargs(config, georegions))
 

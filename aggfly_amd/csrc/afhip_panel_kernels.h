@@ -796,6 +796,27 @@ __global__ __launch_bounds__(WG) void k_place_box(const TE* __restrict__ src, TE
 }
 
 // ---------------------------------------------------------------------------------------
+// k_place_box_swapped: k_place_box for a staged block of BIG-ENDIAN elements (the planes of a NetCDF classic file as they lie
+// in the file: aggfly_amd/io.py, `_netcdf3_to_device`): the same box, the same indexing, and the bytes of every element
+// reversed between the load and the store — one pass, each staged byte read once, each cube byte written once, no LDS.
+// The swap is the compiler's byte permute (v_perm_b32 / v_alignbit for 16 bits), plain C++.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ uint16_t bswap_elem(uint16_t v) { return __builtin_bswap16(v); }
+__device__ __forceinline__ uint32_t bswap_elem(uint32_t v) { return __builtin_bswap32(v); }
+__device__ __forceinline__ uint64_t bswap_elem(uint64_t v) { return __builtin_bswap64(v); }
+
+template <typename TE>
+__global__ __launch_bounds__(WG) void k_place_box_swapped(const TE* __restrict__ src, TE* __restrict__ dst,
+                                                          int64_t by, int64_t bx, int64_t st, int64_t sy, int64_t sx,
+                                                          int64_t nt, int64_t ny, int64_t nx,
+                                                          int64_t NY, int64_t NX, int64_t t0, int64_t y0, int64_t x0) {
+    const int64_t i = (int64_t)blockIdx.x * WG + threadIdx.x;
+    if (i >= nt * ny * nx) return;
+    const int64_t x = i % nx, r = i / nx, y = r % ny, t = r / ny;
+    dst[((t0 + t) * NY + (y0 + y)) * NX + (x0 + x)] = bswap_elem(src[((st + t) * by + (sy + y)) * bx + (sx + x)]);
+}
+
+// ---------------------------------------------------------------------------------------
 // k_read_probe: the temporal kernel's access pattern with no arithmetic — the box's read ceiling for this shape, measured beside
 // the kernel it bounds (afhip_read_probe; bench.py: roofline.measured_read_ceiling_GBps).  Every lane owns 8 bytes of a row, a
 // single-wave workgroup one column tile, four row loads in flight (non-temporal), integer adds, one dword stored per lane at the

@@ -305,6 +305,11 @@ def _step_bytes(path, var, keep_packed=False):
             from . import hdf5
             with hdf5.H5File(path) as f:
                 shape, dt, packing = f.datasets[var].shape, np.dtype(f.datasets[var].dtype), afio.packing_of(f.datasets[var])
+        elif afio._is_netcdf3(path):
+            src = afio._netcdf3_source(path, var)
+            if src is None:
+                return None
+            shape, dt, packing = src.shape, np.dtype(src.dtype), afio.packing_of(src)
         else:
             return None
         item = dt.itemsize if dt.kind == "f" else 4           # packed integers are unpacked to float32 in HBM ...

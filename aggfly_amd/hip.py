@@ -41,7 +41,7 @@ EXPORTS = (
     "afhip_zstd_scratch_bytes", "afhip_zstd_decode", "afhip_inflate_scratch_bytes", "afhip_inflate_decode", "afhip_bitunshuffle_blocks",
     "afhip_plan_bind_packing", "afhip_unpack_i16", "afhip_unpack_u16", "afhip_plan_bind_packings",
     "afhip_take_box", "afhip_shuffle_blocks", "afhip_lz4_encode_streams", "afhip_copy_ranges", "afhip_zstd_encode_blocks",
-    "afhip_zstd_encode_scratch_bytes",
+    "afhip_zstd_encode_scratch_bytes", "afhip_place_box_swapped",
 )
 
 
@@ -116,6 +116,7 @@ def load():
     lib.afhip_csr_destroy.argtypes = [vp]
     lib.afhip_scatter_block.argtypes = [vp, vp, i64, vp, vp]
     lib.afhip_place_box.argtypes = [vp, vp, i32] + [i64] * 13 + [vp]
+    lib.afhip_place_box_swapped.argtypes = [vp, vp, i32] + [i64] * 13 + [vp]
     lib.afhip_spatial_wavg.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp]
     lib.afhip_plan_create.argtypes = [C.POINTER(PlanDesc), C.POINTER(vp)]
     lib.afhip_plan_destroy.argtypes = [vp]
@@ -212,6 +213,19 @@ def place_box(chunk, cube, box_in_chunk, at):
     (st, sy, sx, nt, ny, nx), (t0, y0, x0) = box_in_chunk, at
     _check(load().afhip_place_box(chunk.data_ptr(), cube.data_ptr(), chunk.element_size(), chunk.shape[1], chunk.shape[2],
                                   st, sy, sx, nt, ny, nx, cube.shape[1], cube.shape[2], t0, y0, x0, _stream_ptr(cube)))
+
+
+def place_box_swapped(block, cube, box_in_block, at):
+    """`place_box` for a staged block of big-endian elements (`afhip_place_box_swapped`): the bytes of every element are reversed
+    on the way into the cube.  The NetCDF classic route's placement (`io._netcdf3_to_device`): ``block`` holds the file's bytes
+    as uploaded, viewed in the cube's dtype.  The time extents, which the library cannot know, are checked here."""
+    (st, sy, sx, nt, ny, nx), (t0, y0, x0) = box_in_block, at
+    if block.dim() != 3 or cube.dim() != 3 or block.element_size() != cube.element_size() or not (block.is_contiguous() and cube.is_contiguous()):
+        raise ValueError("place_box_swapped: block and cube must be contiguous 3-D tensors of one element size")
+    if st < 0 or t0 < 0 or nt < 0 or st + nt > block.shape[0] or t0 + nt > cube.shape[0]:
+        raise ValueError("place_box_swapped: box outside the block or the cube along time")
+    _check(load().afhip_place_box_swapped(block.data_ptr(), cube.data_ptr(), block.element_size(), block.shape[1], block.shape[2],
+                                          st, sy, sx, nt, ny, nx, cube.shape[1], cube.shape[2], t0, y0, x0, _stream_ptr(cube)))
 
 
 def lz4_decode_streams(comp, streams, n_streams: int, max_dsize: int, tmp, out, errors):
@@ -379,6 +393,8 @@ def unpack_i16(cube):
     require_gpu()
     q = cube.q if cube.q.is_cuda else cube.q.cuda(non_blocking=True)
     fn = load().afhip_unpack_u16 if cube.unsigned else load().afhip_unpack_i16
+    if q.numel() == 0:                        # no steps (a file of zero records, an empty window): nothing to unpack, and no pointer to hand over
+        return torch.empty(q.shape, dtype=torch.float32, device=q.device)
 
     def run(q1, p, out1=None):
         q1 = q1.contiguous()

@@ -14,9 +14,13 @@ and the native chunk codecs of `csrc/blosc1.c`:
 * netCDF-4 / HDF5 files through the built-in reader ``hdf5.py`` (chunked + shuffle + deflate variables,
   dimension scales, either group style; no netCDF4 / h5py needed);
 * ``.npz`` bundles with ``data``, ``time``, ``latitude``, ``longitude``;
-* NetCDF-3 classic files through ``scipy.io.netcdf_file``.
+* NetCDF classic files (CDF-1 / CDF-2): with ``device=`` set, the header is read by ``netcdf3.py`` and the time steps of a
+  short / int / float / double variable go from the file to HBM as stored — ``pread`` into page-locked slabs, big-endian
+  bytes over PCIe, swapped and placed by one kernel (``hip.place_box_swapped``), CF mask and unpack in HBM, ``keep_packed``,
+  windows and several files as on the Zarr route (``_netcdf3_part_to_device``); on the host, and for whatever that route
+  declines (byte / char variables, arrays that are not time-leading, CDF-5), through ``scipy.io.netcdf_file``.
 
-Chunks are decoded on host threads into one time-major host buffer, which
+On the host route chunks are decoded on host threads into one time-major host buffer, which
 ``Dataset.to_device()`` then uploads in a single copy.
 """
 from __future__ import annotations
@@ -437,7 +441,8 @@ def _pinned_stage(nbytes: int, count: int, device=None):
     return bufs[:count]
 
 
-def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: int, device="cuda", post=None, out_dtype=None, wire_dtype=None):
+def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: int, device="cuda", post=None, out_dtype=None, wire_dtype=None,
+                     place=None, stage_step_bytes=None):
     """Fill a (T, *spatial) HBM tensor slab by slab through two cached page-locked staging buffers.
 
     ``read_slab(k0, k1, out)`` fills ``out[:k1-k0]`` with time steps [k0, k1) (a Zarr chunk
@@ -445,7 +450,11 @@ def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: in
     i+1 is decoded, and the host never holds a second full copy of the cube.  Measured on the
     MI355X box (16 host cores, `profiles/r01_ingest_bench.json`): native Blosc decode 66 GB/s,
     pageable H2D 56 GB/s.  ``wire_dtype`` (`_wire_dtype`): the dtype of the same size the bits are uploaded as where torch
-    cannot hold ``np_dtype`` (uint16 as int16); ``read_slab`` still fills an array of ``np_dtype``."""
+    cannot hold ``np_dtype`` (uint16 as int16); ``read_slab`` still fills an array of ``np_dtype``.
+    ``place(raw, dst, n)`` with ``stage_step_bytes`` (the NetCDF classic route, `_netcdf3_part_to_device`): a slab is then
+    ``stage_step_bytes`` raw bytes per step, as they lie in the file — ``read_slab`` fills a uint8 array —, uploaded as they are
+    into one HBM staging buffer, and ``place`` (a kernel on the copy stream) writes the ``n`` steps of ``raw`` into ``dst`` =
+    ``cube[k0:k1]``; ``post`` follows as usual.  One HBM buffer serves every slab: upload and kernel are ordered on the copy stream."""
     import torch
     np_dtype = np.dtype(np_dtype)
     tdt = _torch_dtype(np_dtype if wire_dtype is None else wire_dtype)     # as stored (packed integers stay packed on the wire)
@@ -453,10 +462,15 @@ def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: in
     if T == 0:
         return cube
     slab_steps = max(1, min(slab_steps, T))
-    row = int(np.prod(spatial)) * np_dtype.itemsize
+    row = int(np.prod(spatial)) * np_dtype.itemsize if place is None else int(stage_step_bytes)
     nstage = 2 if T > slab_steps else 1
-    stage_t = [b[:slab_steps * row].view(tdt).reshape((slab_steps,) + tuple(spatial)) for b in _pinned_stage(slab_steps * row, nstage, device)]
-    stage = [t.numpy().view(np_dtype) for t in stage_t]
+    if place is None:
+        stage_t = [b[:slab_steps * row].view(tdt).reshape((slab_steps,) + tuple(spatial)) for b in _pinned_stage(slab_steps * row, nstage, device)]
+        stage = [t.numpy().view(np_dtype) for t in stage_t]
+    else:
+        stage_t = [b[:slab_steps * row] for b in _pinned_stage(slab_steps * row, nstage, device)]
+        stage = [t.numpy() for t in stage_t]
+        raw_dev = torch.empty(slab_steps * row, dtype=torch.uint8, device=device)
     copy_stream = torch.cuda.Stream(device=device)
     # the cube (and the staging tensors) come from the caching allocator on the CURRENT stream: a block freed there may
     # still be read by queued kernels (the previous HBM window's fused pass) — order the copies behind them
@@ -471,7 +485,12 @@ def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: in
         read_slab(k0, k1, stage[b])
         with torch.cuda.stream(copy_stream):
             dst = cube[k0:k1]
-            dst.copy_(stage_t[b][:k1 - k0], non_blocking=True)
+            if place is None:
+                dst.copy_(stage_t[b][:k1 - k0], non_blocking=True)
+            else:
+                raw = raw_dev[:(k1 - k0) * row]
+                raw.copy_(stage_t[b][:(k1 - k0) * row], non_blocking=True)
+                place(raw, dst, k1 - k0)
             if post is not None:
                 post(dst)                                # e.g. fill-value masking, applied in HBM
             ev = torch.cuda.Event()
@@ -529,6 +548,39 @@ def packed_rules_of(packings):
     return packings
 
 
+def _cf_in_hbm(np_dtype, attrs):
+    """How a streamed array of stored ``np_dtype`` (native byte order) under ``attrs`` becomes values in HBM: -> (post, need_post,
+    out_np, wire).  ``post(dst)`` is the CF mask + unpack of one uploaded slab, ``need_post`` whether it has anything to do, ``out_np``
+    the cube's dtype — CF decoding as on the host route (`_cf_mask_scale`): int8/int16 -> float32, wider integers -> float64 —
+    and ``wire`` the dtype the stored bits travel as (`_wire_dtype`)."""
+    np_dtype = np.dtype(np_dtype)
+    sf, ao = attrs.get("scale_factor"), attrs.get("add_offset")
+    packed = np_dtype.kind in "iu" or sf is not None or ao is not None
+    if np_dtype.kind not in "fiu":
+        raise ValueError(f"dtype {np_dtype} is not streamed")
+    out_np = np_dtype if np_dtype.kind == "f" else np.dtype(np.float64 if np_dtype.itemsize > 2 else np.float32)
+    wire, modulus = _wire_dtype(np_dtype, attrs)                    # uint16 (and int16 / int8 under _Unsigned) travel as signed bits
+    _torch_dtype(wire)                                              # refuses what torch cannot hold (uint32, ...)
+    fv = _attr_fill(attrs)
+    has_fv = fv is not None and not (isinstance(fv, float) and np.isnan(fv))
+    if has_fv and modulus is not None and np_dtype.kind == "i" and fv < 0:
+        fv = fv + modulus                                   # a fill written in the signed type, read as the unsigned value (xarray)
+
+    def post(dst):
+        """CF mask + unpack in HBM, in the order and precision of the host route: the packed integers travel
+        over PCIe as stored (half / quarter of the decoded bytes) and are unpacked at HBM speed."""
+        if modulus is not None:
+            dst.remainder_(modulus)                         # unsigned bits that came as signed: -1 -> 65535, in place and exact
+        if has_fv:
+            dst[dst == fv] = float("nan")                   # exact: the cast from the stored integers is exact
+        if sf is not None:
+            dst.mul_(sf)
+        if ao is not None:
+            dst.add_(ao)
+
+    return post, has_fv or packed, out_np, wire
+
+
 def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 << 20, t_range=None, yx_box=None, keep_packed=False):
     """Stream a chunked (time, y, x) array — a `ZarrArray` or an `hdf5.ChunkSource` — straight into HBM: each
     slab is a whole number of time chunks, decoded chunk-parallel by the native codec into page-locked memory
@@ -538,14 +590,7 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
         raise ValueError("zarr_to_device expects a (time, y, x) array")
     if os.environ.get("AGGFLY_HIP_SLAB_MB"):                       # tuning knob (scripts/e2e_bench.py sweeps it)
         slab_bytes = int(float(os.environ["AGGFLY_HIP_SLAB_MB"]) * (1 << 20))
-    sf, ao = za.attrs.get("scale_factor"), za.attrs.get("add_offset")
-    packed = za.dtype.kind in "iu" or sf is not None or ao is not None
-    if za.dtype.kind not in "fiu":
-        raise ValueError(f"dtype {za.dtype} is not streamed")
-    # CF decoding as on the host route (`_cf_mask_scale`): int8/int16 -> float32, wider integers -> float64
-    out_np = za.dtype if za.dtype.kind == "f" else np.dtype(np.float64 if za.dtype.itemsize > 2 else np.float32)
-    wire, modulus = _wire_dtype(za.dtype, za.attrs)                 # uint16 (and int16 / int8 under _Unsigned) travel as signed bits
-    _torch_dtype(wire)                                              # refuses what torch cannot hold (uint32, ...)
+    post, need_post, out_np, wire = _cf_in_hbm(za.dtype, za.attrs)
     T, ny, nx = za.shape
     tc = za.chunks[0]
     grid_yx = [(iy, ix) for iy in range((ny + za.chunks[1] - 1) // za.chunks[1]) for ix in range((nx + za.chunks[2] - 1) // za.chunks[2])]
@@ -601,24 +646,6 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
             for j in jobs:
                 work(j)
 
-    fv = _attr_fill(za.attrs)
-    has_fv = fv is not None and not (isinstance(fv, float) and np.isnan(fv))
-    if has_fv and modulus is not None and za.dtype.kind == "i" and fv < 0:
-        fv = fv + modulus                                   # a fill written in the signed type, read as the unsigned value (xarray)
-
-    def post(dst):
-        """CF mask + unpack in HBM, in the order and precision of the host route: the packed integers travel
-        over PCIe as stored (half / quarter of the decoded bytes) and are unpacked at HBM speed."""
-        if modulus is not None:
-            dst.remainder_(modulus)                         # unsigned bits that came as signed: -1 -> 65535, in place and exact
-        if has_fv:
-            dst[dst == fv] = float("nan")                   # exact: the cast from the stored integers is exact
-        if sf is not None:
-            dst.mul_(sf)
-        if ao is not None:
-            dst.add_(ao)
-
-    need_post = has_fv or packed
     if keep_packed and packing_of(za) is not None:
         need_post, out_np = False, wire
     if t_range is not None and tuple(t_range) == (0, T):
@@ -1406,10 +1433,12 @@ def _cf_mask_scale(arr, attrs):
     unsigned = arr.dtype.kind in "iu" and _stored_unsigned(arr.dtype, attrs)      # (refuses _Unsigned = "false" on unsigned storage)
     if unsigned and arr.dtype.kind == "i":
         # _Unsigned = "true": the same bits read as the unsigned type, and a fill written in the signed type likewise (xarray)
-        arr = arr.view(np.dtype(f"u{arr.dtype.itemsize}"))
+        arr = arr.view(np.dtype(f"u{arr.dtype.itemsize}").newbyteorder(arr.dtype.byteorder))    # (a classic file's integers are big-endian)
         if fv is not None and not isinstance(fv, str) and not (isinstance(fv, float) and np.isnan(fv)) and int(fv) == fv and fv < 0:
             fv = int(fv) + (1 << (8 * arr.dtype.itemsize))
-    sf, ao = attrs.get("scale_factor"), attrs.get("add_offset")
+    # numbers, not numpy scalars: a float64 scalar (a classic file's attribute, as scipy hands it on) would widen `out *= sf` to
+    # float64 under NumPy 2's promotion rules, where every other container — and every device route — unpacks in the cube's type
+    sf, ao = (a.item() if isinstance(a, np.generic) else a for a in (attrs.get("scale_factor"), attrs.get("add_offset")))
     if fv is None and sf is None and ao is None:
         return arr
     out = arr.astype(np.float64 if arr.dtype.itemsize > 2 and arr.dtype.kind != "f" else (arr.dtype if arr.dtype.kind == "f" else np.float32))
@@ -1946,7 +1975,7 @@ def _open_netcdf3(path, var):
 
 
 def read_time_coordinate(path, var, timecoord="time"):
-    """The decoded time coordinate of a Zarr store (or of the dimension ``timecoord`` of a netCDF-4 file) without
+    """The decoded time coordinate of a Zarr store (or of the dimension ``timecoord`` of a netCDF-4 or NetCDF classic file) without
     touching the data variable."""
     if _looks_like_zarr(path):
         c = ZarrArray(os.path.join(path, timecoord))
@@ -1958,6 +1987,13 @@ def read_time_coordinate(path, var, timecoord="time"):
             c = f.datasets[timecoord]
             cattrs = {k: (v.item() if isinstance(v, np.generic) else v) for k, v in c.attrs.items()}
             return _decode_time(c.read(threads=1), cattrs)
+    if _is_netcdf3(path):
+        from . import netcdf3
+        nc = netcdf3.NC3File(path)
+        if timecoord in nc.variables:
+            c = nc.variables[timecoord]
+            cattrs = {k: (v.item() if isinstance(v, np.generic) else v) for k, v in c.attrs.items()}
+            return _decode_time(nc.read(timecoord), cattrs)
     raise ValueError(f"cannot read a time coordinate from {path}")
 
 
@@ -2037,6 +2073,147 @@ def _hdf5_to_device(path, var, xycoords, timecoord, time_sel, georegions, lon_is
         return data, src, coords
     finally:
         f.close()
+
+
+class _Nc3Source:
+    """A 3-D, time-leading short / int / float / double variable of a NetCDF classic file, from the header alone (`netcdf3.py`): what
+    `packing_of`, `_cf_in_hbm` and `DataArray` ask of a streamed source — ``dims``, ``shape``, ``dtype`` (native byte order;
+    ``var.dtype`` is big-endian as stored) and ``attrs``, in the Python forms the netCDF-4 route gives (numbers, not numpy scalars)."""
+
+    def __init__(self, nc, var):
+        self.nc, self.var = nc, var
+        self.dims, self.shape, self.dtype = var.dims, var.shape, var.dtype.newbyteorder("=")
+        self.attrs = {k: (v.item() if isinstance(v, np.generic) else v) for k, v in var.attrs.items()}
+
+    def coords(self):
+        out = {}
+        for d in self.dims:
+            c = self.nc.variables.get(d)
+            if c is not None and len(c.shape) == 1:
+                cattrs = {k: (v.item() if isinstance(v, np.generic) else v) for k, v in c.attrs.items()}
+                vals = self.nc.read(d)
+                vals = vals.astype(vals.dtype.newbyteorder("="))
+                out[d] = _decode_time(vals, cattrs) if " since " in str(cattrs.get("units", "")) else vals
+        return out
+
+
+def _is_netcdf3(path) -> bool:
+    from . import netcdf3
+    return isinstance(path, str) and os.path.isfile(path) and netcdf3.is_classic(path)
+
+
+def _netcdf3_source(path, var, timecoord="time"):
+    """The `_Nc3Source` of ``var`` when the streaming route takes it — a header `netcdf3.NC3File` reads, a 3-D time-leading variable
+    of type short / int / float / double — else None: the host route (scipy) then reads the file."""
+    from . import netcdf3
+    try:
+        nc = netcdf3.NC3File(path)
+    except (ValueError, OSError):
+        return None
+    v = nc.variables.get(var)
+    if v is None or len(v.shape) != 3 or v.dims[0] != timecoord or v.dtype.str[1:] not in netcdf3.STREAMED_TYPES:
+        return None
+    return _Nc3Source(nc, v)
+
+
+def _netcdf3_part_to_device(src, xycoords, timecoord, time_sel, georegions, lon_is_360, device, time_window=None, lat_window=None,
+                            keep_packed=False, threads: int = 16, slab_bytes: int = 128 << 20):
+    """One classic file into HBM: -> (tensor, source, coords).  Step ``t`` of the variable is one run of big-endian bytes at
+    ``plane_offset(t)``; slabs are whole time steps, a thread pool (the native reader's OpenMP team) `pread`s the rows of the
+    requested box of every step into the page-locked slab, packed densely, the slab crosses PCIe as stored (2 bytes per value for int16), and one kernel
+    (`hip.place_box_swapped`) reverses the bytes of every element and writes the box — the x clip included — into the cube.  The
+    host never touches the data.  CF mask and unpack follow in HBM as for every other format (`_cf_in_hbm`)."""
+    import torch
+    from . import hip
+    v = src.var
+    if os.environ.get("AGGFLY_HIP_SLAB_MB"):
+        slab_bytes = int(float(os.environ["AGGFLY_HIP_SLAB_MB"]) * (1 << 20))
+    post, need_post, out_np, wire = _cf_in_hbm(src.dtype, src.attrs)
+    if keep_packed and packing_of(src) is not None:
+        need_post, out_np = False, wire
+    coords = src.coords()
+    T, NY, NX = src.shape
+    if time_window is not None:
+        window = (int(time_window[0]), int(time_window[1]))
+        if not (0 <= window[0] <= window[1] <= T):
+            raise ValueError(f"time_window {window} outside the {T} steps of {v.name!r}")
+    else:
+        window = _time_window(coords[timecoord], time_sel) if time_sel is not None and timecoord in coords else None
+    box = None
+    if georegions is not None:
+        box = _clip_box(src.dims, coords, xycoords, georegions, lon_is_360)
+        if box is None and lat_window is not None:
+            raise ValueError("lat_window on a non-contiguous clip goes through the host route")
+    if lat_window is not None:
+        box = _band_of_box(src.dims, src.shape, xycoords, box, lat_window)
+    k_lo, k_hi = window if window is not None else (0, T)
+    a0, a1, b0, b1 = box if box is not None else (0, NY, 0, NX)
+    isz = src.dtype.itemsize
+    step_bytes = (a1 - a0) * NX * isz                                 # the rows of the box, whole: one run of the file per step
+    n = k_hi - k_lo
+    slab = max(1, min(slab_bytes, 1 << 30) // max(step_bytes, 1))
+    wire_t, out_t = _torch_dtype(wire), _torch_dtype(out_np)
+    # integers that become floats in HBM: the kernel writes the stored type beside the cube, the conversion is the copy into it
+    beside = torch.empty((min(slab, max(n, 1)), a1 - a0, b1 - b0), dtype=wire_t, device=device) if wire_t != out_t else None
+    stride, first = v.step_stride, (v.plane_offset(k_lo) if n > 0 else 0) + a0 * NX * isz
+    path = src.nc.path
+
+    def read(k0, k1, out):
+        # the native reader's team (`afcodec_read_packed`: pread, the ranges packed back to back): one range per step — or one for
+        # the slab where the steps follow each other in the file, which the team cuts into pieces itself.  (Python threads, each
+        # reading a run of steps, took 44 - 57 ms for the 8760 steps of the configs[0] cube where the team takes 18:
+        # profiles/netcdf3_ingest.txt.)
+        from . import codec
+        if stride == step_bytes:
+            locs = [(path, first + k0 * stride, (k1 - k0) * step_bytes)]
+        else:
+            locs = [(path, first + k * stride, step_bytes) for k in range(k0, k1)]
+        _, got = codec.read_packed(locs, out[:(k1 - k0) * step_bytes], align=1, threads=threads)
+        if any(int(g) != loc[2] for g, loc in zip(got, locs)):
+            raise OSError(f"{path}: the file ends inside the steps {k_lo + k0}..{k_lo + k1} of {v.name!r}")
+
+    def place(raw, dst, m):
+        blk = raw.view(wire_t).view(m, a1 - a0, NX)
+        into = dst if beside is None else beside[:m]
+        hip.place_box_swapped(blk, into, (0, 0, b0, m, a1 - a0, b1 - b0), (0, 0, 0))
+        if beside is not None:
+            dst.copy_(into)
+
+    data = stream_to_device(n, (a1 - a0, b1 - b0), src.dtype, read, slab, device, post if need_post else None, out_np, wire,
+                            place=place, stage_step_bytes=step_bytes)
+    if window is not None:
+        coords[timecoord] = coords[timecoord][window[0]:window[1]]
+    if box is not None:
+        coords[src.dims[1]] = coords[src.dims[1]][box[0]:box[1]]
+        coords[src.dims[2]] = coords[src.dims[2]][box[2]:box[3]]
+    return data, src, coords
+
+
+def _join_device_parts(got, rules, timecoord):
+    """(data, source, coords) of a dataset streamed part by part — [(tensor, source, coords)], one per store or file in time order —,
+    concatenated along time like open_mfdataset.  ``rules``: the parts' unpack rules when they stayed packed (`packed_rules_of`), else None."""
+    if len(got) == 1:
+        data, src, coords = got[0]
+        if rules is not None:
+            from .packed import PackedCube
+            data = PackedCube(data, *rules[0])
+        return data, src, coords
+    import torch
+    if any(g[1].dims != got[0][1].dims or g[1].dims[0] != timecoord for g in got):
+        raise ValueError("stores of a multi-file dataset must share their (time-leading) dimensions")
+    t0 = got[0][2][timecoord]
+    if isinstance(t0, CFTimeIndex):
+        time = CFTimeIndex(np.concatenate([g[2][timecoord].seconds for g in got]), t0.calendar)
+    else:
+        time = pd.DatetimeIndex(np.concatenate([np.asarray(g[2][timecoord]) for g in got]))
+    coords = dict(got[0][2])
+    coords[timecoord] = time
+    if rules is not None:                   # (the parts were cut by time_window / time_sel already: the bounds are those of what was read)
+        from .packed import PackedCube
+        data = PackedCube.concat([PackedCube(g[0], *r) for g, r in zip(got, rules)])
+    else:
+        data = torch.cat([g[0] for g in got], dim=0)
+    return data, got[0][1], coords
 
 
 def _is_hdf5(path) -> bool:
@@ -2138,29 +2315,7 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
             return data, za, coords
 
         try:
-            got = [part_to_device(p_) for p_ in paths]
-            if len(got) > 1:                        # a list / glob of stores: concatenated along time like open_mfdataset
-                import torch
-                if any(g[1].dims != got[0][1].dims or g[1].dims[0] != timecoord for g in got):
-                    raise ValueError("stores of a multi-file dataset must share their (time-leading) dimensions")
-                t0 = got[0][2][timecoord]
-                if isinstance(t0, CFTimeIndex):
-                    time = CFTimeIndex(np.concatenate([g[2][timecoord].seconds for g in got]), t0.calendar)
-                else:
-                    time = pd.DatetimeIndex(np.concatenate([np.asarray(g[2][timecoord]) for g in got]))
-                coords = dict(got[0][2])
-                coords[timecoord] = time
-                if stay_packed:                     # (the parts were cut by time_window / time_sel already: the bounds are those of what was read)
-                    from .packed import PackedCube
-                    data = PackedCube.concat([PackedCube(g[0], *r) for g, r in zip(got, rules)])
-                else:
-                    data = torch.cat([g[0] for g in got], dim=0)
-                za = got[0][1]
-            else:
-                data, za, coords = got[0]
-                if stay_packed:
-                    from .packed import PackedCube
-                    data = PackedCube(data, *rules[0])
+            data, za, coords = _join_device_parts([part_to_device(p_) for p_ in paths], rules, timecoord)
         except ValueError:
             data = None
         if data is not None:
@@ -2175,6 +2330,24 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
             da = DataArray(data, src.dims, coords, name=var, attrs=src.attrs)
             return Dataset(da, xycoords=xycoords, timecoord=timecoord, time_sel=time_sel, lon_is_360=lon_is_360,
                            preprocess=preprocess, georegions=georegions, time_fix=time_fix, name=name)
+    if device is not None and engine in (None, "scipy") and (len(paths) == 1 or time_window is None) and all(_is_netcdf3(p) for p in paths):
+        # NetCDF classic files: the steps' big-endian bytes go from the file to HBM as stored and are swapped there; several
+        # files — one per year or month, each with its own packing — stay packed under the Zarr branch's rule (a time_window on
+        # several files counts steps of the concatenation: the host route below cuts it, as before)
+        srcs = [_netcdf3_source(p, var, timecoord) for p in paths]
+        data = None
+        if all(s_ is not None for s_ in srcs):
+            try:
+                rules = packed_rules_of([packing_of(s_) for s_ in srcs]) if keep_packed else None
+                data, src, coords = _join_device_parts(
+                    [_netcdf3_part_to_device(s_, xycoords, timecoord, time_sel, georegions, lon_is_360, device, time_window, lat_window,
+                                             keep_packed=rules is not None) for s_ in srcs], rules, timecoord)
+            except ValueError:
+                data = None
+        if data is not None:
+            da = DataArray(data, src.dims, coords, name=var, attrs=src.attrs)
+            return Dataset(da, xycoords=xycoords, timecoord=timecoord, time_sel=time_sel, lon_is_360=lon_is_360,
+                           preprocess=preprocess, georegions=None if lat_window is not None else georegions, time_fix=time_fix, name=name)
     parts = []
     for p in paths:
         if engine == "zarr" or (engine is None and _looks_like_zarr(p)):

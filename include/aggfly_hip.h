@@ -188,6 +188,15 @@ int afhip_place_box(const void* chunk_dev, void* cube_dev, int elem_size,
                     int64_t nt, int64_t ny, int64_t nx,
                     int64_t NY, int64_t NX, int64_t t0, int64_t y0, int64_t x0, void* stream);
 
+/* afhip_place_box for a staged block of BIG-ENDIAN elements — the time steps of a NetCDF classic file (CDF-1 / CDF-2) as they lie in
+ * the file, uploaded as raw bytes: the same box arguments, bounds checks and launch-size refusal, and the bytes of every element
+ * are reversed on the way (elem_size 2, 4 or 8; block_dev element-aligned).  One pass: each staged byte is read once, each cube
+ * byte written once. */
+int afhip_place_box_swapped(const void* block_dev, void* cube_dev, int elem_size,
+                            int64_t by, int64_t bx, int64_t st, int64_t sy, int64_t sx,
+                            int64_t nt, int64_t ny, int64_t nx,
+                            int64_t NY, int64_t NX, int64_t t0, int64_t y0, int64_t x0, void* stream);
+
 /* Chunk decode in HBM ("or GPU-side decode"; the reference decodes on host threads inside its dask
  * graph, aggfly/dataset/dataset.py:697-728).  Blosc-1 chunks whose streams are LZ4 cross PCIe compressed; the host parses
  * the containers (afcodec_blosc_lz4_plan, include/aggfly_codec.h) into the two record lists below, which travel to HBM with
