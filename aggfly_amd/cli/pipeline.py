@@ -56,7 +56,7 @@ def store_route_ok(config, paths) -> bool:
     p = paths[0]
     if not isinstance(p, str) or any(ch in p for ch in "*?[") or "://" in p:
         return False
-    if not (afio._looks_like_zarr(p) or (os.path.isfile(p) and (afio._is_hdf5(p) or _streams_classic(config, p)))):
+    if not (afio._looks_like_zarr(p) or (os.path.isfile(p) and (afio._is_hdf5(p) or _streams_classic(config, p) or _streams_grib(config, p)))):
         return False
     try:
         D.output_freq(config.to_aggregator_dict())
@@ -159,14 +159,27 @@ def _streams_classic(config, path) -> bool:
     return afio._is_netcdf3(path) and afio._netcdf3_source(path, config.var, config.timecoord) is not None
 
 
+def _streams_grib(config, path) -> bool:
+    """Is `path` a GRIB file whose variable ``config.var`` the streaming route takes (`io._grib_source`: an index `grib.py` reads, one
+    level, one grid)?"""
+    from .. import io as afio
+    if not afio._is_grib(path):
+        return False
+    try:
+        afio._grib_source(path, config.var, timecoord=config.timecoord)
+    except (ValueError, KeyError, OSError):
+        return False
+    return True
+
+
 def _streams_from_store(config, path) -> bool:
-    """Is `path` a file the streaming route takes (one Zarr store, netCDF-4 file or NetCDF classic file whose variable
+    """Is `path` a file the streaming route takes (one Zarr store, netCDF-4 file, or NetCDF classic or GRIB file whose variable
     ``config.var`` qualifies, a GPU to stream to)?  Only there does
     ``time_window`` cut the read itself; everywhere else `dataset_from_path` reads the file whole and cuts on the host."""
     from .. import hip, io as afio
     if hip.device_count() == 0 or not isinstance(path, str) or any(ch in path for ch in "*?[") or "://" in path:
         return False
-    return afio._looks_like_zarr(path) or (os.path.isfile(path) and (afio._is_hdf5(path) or _streams_classic(config, path)))
+    return afio._looks_like_zarr(path) or (os.path.isfile(path) and (afio._is_hdf5(path) or _streams_classic(config, path) or _streams_grib(config, path)))
 
 
 def load_grid(config, path, georegions):

@@ -21,6 +21,7 @@
 #include "afhip_zstd_encode_kernels.h"
 #include "afhip_zstd_kernels.h"
 #include "afhip_inflate_kernels.h"
+#include "afhip_grib_kernels.h"
 #include "afhip_planner.h"
 #include "afhip_variants.h"
 #include "afhip_sine_p2_table.h"
@@ -568,6 +569,44 @@ extern "C" int afhip_place_box_swapped(const void* block_dev, void* cube_dev, in
                                        int64_t nt, int64_t ny, int64_t nx,
                                        int64_t NY, int64_t NX, int64_t t0, int64_t y0, int64_t x0, void* stream) {
     return place_box_launch<true>("place_box_swapped", block_dev, cube_dev, elem_size, by, bx, st, sy, sx, nt, ny, nx, NY, NX, t0, y0, x0, stream);
+}
+
+extern "C" int64_t afhip_grib_rank_bytes(int64_t n_steps, int64_t n_points) {
+    if (n_steps < 0 || n_points < 0 || n_points > 0x7fffffff) return -1;
+    return n_steps * grib_rank_words(n_points) * (int64_t)sizeof(uint32_t);
+}
+
+extern "C" int afhip_grib_unpack(const void* stage_dev, int64_t stage_bytes, const afhip_grib_step* steps_dev, int64_t n_steps,
+                                 int64_t NY, int64_t NX, int64_t y0, int64_t x0, int64_t ny, int64_t nx,
+                                 void* cube_dev, int cube_elem_size, int64_t cube_nt, int64_t cube_NY, int64_t cube_NX,
+                                 int64_t t0, int64_t cy, int64_t cx, void* rank_dev, int64_t rank_bytes, int32_t* errors_dev, void* stream) {
+    static_assert(sizeof(afhip_grib_step) == sizeof(GribStep) && sizeof(GribStep) == 64, "record layouts");
+    if (!stage_dev || !steps_dev || !cube_dev || !rank_dev || !errors_dev || stage_bytes < 0 || n_steps < 0)
+        return fail(AFHIP_E_INVALID, "grib_unpack: bad arguments");
+    if (cube_elem_size != 4) return fail(AFHIP_E_INVALID, "grib_unpack: the cube must be float32 (4-byte elements, got %d)", cube_elem_size);
+    if (NY <= 0 || NX <= 0 || NY > 0x7fffffff / NX || y0 < 0 || x0 < 0 || ny < 0 || nx < 0 || ny > NY - y0 || nx > NX - x0)
+        return fail(AFHIP_E_INVALID, "grib_unpack: box outside the grid");
+    if (cube_nt < 0 || cube_NY <= 0 || cube_NX <= 0 || t0 < 0 || cy < 0 || cx < 0 || n_steps > cube_nt - t0 || ny > cube_NY - cy || nx > cube_NX - cx)
+        return fail(AFHIP_E_INVALID, "grib_unpack: box outside the cube");
+    if (stage_bytes & 3) return fail(AFHIP_E_INVALID, "grib_unpack: the stage must be a whole number of 4-byte words (%lld bytes)", (long long)stage_bytes);
+    if (((uintptr_t)stage_dev & 3) || ((uintptr_t)cube_dev & 3) || ((uintptr_t)rank_dev & 3) || ((uintptr_t)steps_dev & 7))
+        return fail(AFHIP_E_INVALID, "grib_unpack: the stage, the cube and the rank scratch must be 4-byte aligned, the records 8-byte aligned");
+    if (rank_bytes < afhip_grib_rank_bytes(n_steps, NY * NX)) return fail(AFHIP_E_INVALID, "grib_unpack: rank scratch too small (afhip_grib_rank_bytes)");
+    const int dev = pointer_device(cube_dev);
+    if (dev < 0 || pointer_device(stage_dev) != dev || pointer_device(steps_dev) != dev || pointer_device(rank_dev) != dev || pointer_device(errors_dev) != dev)
+        return fail(AFHIP_E_INVALID, "grib_unpack: the stage, the records, the scratch, the error counter and the cube must lie on one device");
+    if (n_steps == 0 || ny == 0 || nx == 0) return AFHIP_OK;
+    const int64_t lanes = n_steps * ny * ((nx + GRIB_RUN - 1) / GRIB_RUN);
+    if (n_steps > 0x7fffffff || lanes > (int64_t)0x7fffffff * GRIB_WG) return fail(AFHIP_E_INVALID, "grib_unpack: box too large for one launch");
+    GUARD_DEVICE(dev);
+    hipStream_t s = (hipStream_t)stream;
+    const GribBox g{NY, NX, y0, x0, ny, nx, cube_NY, cube_NX, t0, cy, cx};
+    hipLaunchKernelGGL(k_grib_rank, dim3((unsigned)n_steps), dim3(GRIB_WG), 0, s, (const uint8_t*)stage_dev, stage_bytes, (const GribStep*)steps_dev, g,
+                       (uint32_t*)rank_dev, errors_dev);
+    hipLaunchKernelGGL(k_grib_unpack, dim3((unsigned)((lanes + GRIB_WG - 1) / GRIB_WG)), dim3(GRIB_WG), 0, s, (const uint8_t*)stage_dev, stage_bytes,
+                       (const GribStep*)steps_dev, n_steps, g, (const uint32_t*)rank_dev, (float*)cube_dev);
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
 }
 
 extern "C" int afhip_lz4_decode_streams(const void* comp_dev, const afhip_lz4_stream* streams_dev, int64_t n_streams, int32_t max_dsize,

@@ -310,6 +310,9 @@ def _step_bytes(path, var, keep_packed=False):
             if src is None:
                 return None
             shape, dt, packing = src.shape, np.dtype(src.dtype), afio.packing_of(src)
+        elif afio._is_grib(path):
+            src = afio._grib_source(path, var)                # (float32 in HBM whatever the messages' bits per value)
+            shape, dt, packing = src.shape, np.dtype(src.dtype), None
         else:
             return None
         item = dt.itemsize if dt.kind == "f" else 4           # packed integers are unpacked to float32 in HBM ...

@@ -41,7 +41,7 @@ EXPORTS = (
     "afhip_zstd_scratch_bytes", "afhip_zstd_decode", "afhip_inflate_scratch_bytes", "afhip_inflate_decode", "afhip_bitunshuffle_blocks",
     "afhip_plan_bind_packing", "afhip_unpack_i16", "afhip_unpack_u16", "afhip_plan_bind_packings",
     "afhip_take_box", "afhip_shuffle_blocks", "afhip_lz4_encode_streams", "afhip_copy_ranges", "afhip_zstd_encode_blocks",
-    "afhip_zstd_encode_scratch_bytes", "afhip_place_box_swapped",
+    "afhip_zstd_encode_scratch_bytes", "afhip_place_box_swapped", "afhip_grib_rank_bytes", "afhip_grib_unpack",
 )
 
 
@@ -135,6 +135,9 @@ def load():
     lib.afhip_lz4_encode_streams.argtypes = [vp, vp, i64, vp, vp, vp]
     lib.afhip_copy_ranges.argtypes = [vp, vp, vp, i64, vp]
     lib.afhip_zstd_encode_blocks.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    lib.afhip_grib_rank_bytes.restype = i64
+    lib.afhip_grib_rank_bytes.argtypes = [i64, i64]
+    lib.afhip_grib_unpack.argtypes = [vp, i64, vp, i64] + [i64] * 6 + [vp, i32] + [i64] * 6 + [vp, i64, vp, vp]
     lib.afhip_zstd_encode_scratch_bytes.restype = i64
     lib.afhip_zstd_encode_scratch_bytes.argtypes = [i64]
     lib.afhip_zstd_scratch_bytes.restype = i64
@@ -226,6 +229,37 @@ def place_box_swapped(block, cube, box_in_block, at):
         raise ValueError("place_box_swapped: box outside the block or the cube along time")
     _check(load().afhip_place_box_swapped(block.data_ptr(), cube.data_ptr(), block.element_size(), block.shape[1], block.shape[2],
                                           st, sy, sx, nt, ny, nx, cube.shape[1], cube.shape[2], t0, y0, x0, _stream_ptr(cube)))
+
+
+# one record of `afhip_grib_unpack` per time step (`afhip_grib_step`, include/aggfly_hip.h)
+GRIB_STEP = np.dtype([("data_off", "<i8"), ("data_bytes", "<i8"), ("first_point", "<i8"), ("bitmap_off", "<i8"), ("first_bit", "<i4"),
+                      ("nbits", "<i4"), ("R", "<f8"), ("s", "<f8"), ("d", "<f8")])
+
+
+def grib_rank_bytes(n_steps: int, n_points: int) -> int:
+    """`afhip_grib_rank_bytes`: the rank scratch `grib_unpack` needs for ``n_steps`` fields of ``n_points`` grid points."""
+    n = int(load().afhip_grib_rank_bytes(int(n_steps), int(n_points)))
+    if n < 0:
+        raise ValueError(f"grib_rank_bytes: {n_steps} steps of {n_points} grid points")
+    return n
+
+
+def grib_unpack(stage, steps, n_steps: int, grid, box, cube, at, rank, errors):
+    """`afhip_grib_unpack`: the GRIB fields (simple packing) staged in the uint8 HBM tensor ``stage`` — a whole number of 4-byte words —
+    under the ``n_steps`` `GRIB_STEP` records of the uint8 HBM tensor ``steps``, unpacked into the float32 ``cube``:
+    ``grid`` = (NY, NX) of the fields, ``box`` = (y0, x0, ny, nx) of the grid, written at ``at`` = (t0, y, x) of the cube.
+    ``rank``: a uint8 HBM tensor of `grib_rank_bytes` bytes; refused records count in the int32 HBM counter ``errors`` and their steps
+    are left unwritten.  The work goes to the current stream."""
+    import torch
+    if cube.dtype != torch.float32 or cube.dim() != 3 or not cube.is_contiguous():
+        raise ValueError("grib_unpack: the cube must be a contiguous 3-D float32 tensor")
+    if steps.numel() * steps.element_size() < int(n_steps) * GRIB_STEP.itemsize:
+        raise ValueError(f"grib_unpack: {n_steps} records need {int(n_steps) * GRIB_STEP.itemsize} bytes")
+    (NY, NX), (y0, x0, ny, nx), (t0, cy, cx) = grid, box, at
+    _check(load().afhip_grib_unpack(stage.data_ptr(), stage.numel() * stage.element_size(), steps.data_ptr(), int(n_steps), int(NY), int(NX),
+                                    int(y0), int(x0), int(ny), int(nx), cube.data_ptr(), cube.element_size(), cube.shape[0], cube.shape[1],
+                                    cube.shape[2], int(t0), int(cy), int(cx), rank.data_ptr(), rank.numel() * rank.element_size(),
+                                    errors.data_ptr(), _stream_ptr(cube)))
 
 
 def lz4_decode_streams(comp, streams, n_streams: int, max_dsize: int, tmp, out, errors):

@@ -18,7 +18,11 @@ and the native chunk codecs of `csrc/blosc1.c`:
   short / int / float / double variable go from the file to HBM as stored — ``pread`` into page-locked slabs, big-endian
   bytes over PCIe, swapped and placed by one kernel (``hip.place_box_swapped``), CF mask and unpack in HBM, ``keep_packed``,
   windows and several files as on the Zarr route (``_netcdf3_part_to_device``); on the host, and for whatever that route
-  declines (byte / char variables, arrays that are not time-leading, CDF-5), through ``scipy.io.netcdf_file``.
+  declines (byte / char variables, arrays that are not time-leading, CDF-5), through ``scipy.io.netcdf_file``;
+* GRIB files (editions 1 and 2, regular latitude / longitude grids, simple packing; ``engine="cfgrib"`` or none): ``grib.py`` indexes
+  the messages from their section headers; with ``device=`` set the packed bits go from the file to HBM as stored and one kernel
+  (``hip.grib_unpack``) extracts, scales and places them (``_grib_part_to_device``), on the host ``grib.GribFile.read`` decodes
+  them in numpy; what ``grib.py`` refuses raises with its reason.
 
 On the host route chunks are decoded on host threads into one time-major host buffer, which
 ``Dataset.to_device()`` then uploads in a single copy.
@@ -1975,8 +1979,8 @@ def _open_netcdf3(path, var):
 
 
 def read_time_coordinate(path, var, timecoord="time"):
-    """The decoded time coordinate of a Zarr store (or of the dimension ``timecoord`` of a netCDF-4 or NetCDF classic file) without
-    touching the data variable."""
+    """The decoded time coordinate of a Zarr store (or of the dimension ``timecoord`` of a netCDF-4 or NetCDF classic file, or the valid
+    times of the messages of ``var`` in a GRIB file) without touching the data variable."""
     if _looks_like_zarr(path):
         c = ZarrArray(os.path.join(path, timecoord))
         v = c.read(threads=1)
@@ -1994,6 +1998,9 @@ def read_time_coordinate(path, var, timecoord="time"):
             c = nc.variables[timecoord]
             cattrs = {k: (v.item() if isinstance(v, np.generic) else v) for k, v in c.attrs.items()}
             return _decode_time(nc.read(timecoord), cattrs)
+    if _is_grib(path):
+        from . import grib
+        return grib.open_index(path).select(var).time               # the valid times of the variable's messages, in time order
     raise ValueError(f"cannot read a time coordinate from {path}")
 
 
@@ -2189,6 +2196,137 @@ def _netcdf3_part_to_device(src, xycoords, timecoord, time_sel, georegions, lon_
     return data, src, coords
 
 
+class _GribSource:
+    """The messages of one variable of a GRIB file in time order (`grib.Field`), from the section headers alone: what `DataArray` and the
+    streaming route ask of a source — ``dims``, ``shape``, ``dtype`` (float32: a GRIB field has no stored type to keep) and ``attrs``."""
+
+    def __init__(self, field, xycoords, timecoord):
+        self.field, self.path = field, field.path
+        self.dims, self.shape, self.dtype, self.attrs = (timecoord, xycoords[1], xycoords[0]), field.shape, np.dtype(np.float32), dict(field.attrs)
+
+    def coords(self):
+        c = self.field.coords()
+        return {self.dims[0]: c["time"], self.dims[1]: c["latitude"], self.dims[2]: c["longitude"]}
+
+
+def _is_grib(path) -> bool:
+    from . import grib
+    return isinstance(path, str) and os.path.isfile(path) and grib.is_grib(path)
+
+
+def _grib_filter(kwargs) -> dict | None:
+    """``filter_by_keys`` as cfgrib takes it: a keyword of its own, or inside ``backend_kwargs``."""
+    fbk = dict((kwargs.get("backend_kwargs") or {}).get("filter_by_keys") or {})
+    fbk.update(kwargs.get("filter_by_keys") or {})
+    return fbk or None
+
+
+def _grib_source(path, var, xycoords=("longitude", "latitude"), timecoord="time", filter_by_keys=None):
+    """The `_GribSource` of ``var`` in the GRIB file ``path``.  Whatever `grib.py` refuses raises here, with its reason: a GRIB file has
+    no other route to fall back to."""
+    from . import grib
+    return _GribSource(grib.open_index(path).select(var, filter_by_keys), xycoords, timecoord)
+
+
+def _open_grib(path, var, xycoords=("longitude", "latitude"), timecoord="time", filter_by_keys=None):
+    """A GRIB file on the host: the index of `grib.py` and its numpy decode (float32, NaN where a bitmap has 0)."""
+    src = _grib_source(path, var, xycoords, timecoord, filter_by_keys)
+    return DataArray(src.field.file.read(src.field), src.dims, src.coords(), name=var, attrs=src.attrs)
+
+
+def _grib_part_to_device(src, xycoords, timecoord, time_sel, georegions, lon_is_360, device, time_window=None, lat_window=None,
+                         threads: int = 16, slab_bytes: int = 128 << 20):
+    """One GRIB file into HBM: -> (tensor, source, coords), as `_netcdf3_part_to_device` does it for a classic file.  Step ``t`` is one
+    message: slabs are whole time steps, the native reader's team `pread`s the packed bits of every step — without a bitmap only the
+    bytes that hold the rows of the requested box, with one the bitmap and the data section whole — into the page-locked slab, the slab
+    crosses PCIe as stored (2 bytes per value for ERA5's 16 bits), and `hip.grib_unpack` extracts the integers, scales them, writes NaN
+    where the bitmap has 0 and places the box — the x clip included — in the float32 cube.  The host never touches the data.  The
+    steps' ``nbits`` / ``E`` / ``D`` / ``R`` differ: each step has its record, with ``R``, ``2.0 ** E`` and ``10.0 ** -D`` as the
+    host route computes them."""
+    import torch
+    from . import codec, hip
+    if os.environ.get("AGGFLY_HIP_SLAB_MB"):
+        slab_bytes = int(float(os.environ["AGGFLY_HIP_SLAB_MB"]) * (1 << 20))
+    coords = src.coords()
+    T, NY, NX = src.shape
+    if time_window is not None:
+        window = (int(time_window[0]), int(time_window[1]))
+        if not (0 <= window[0] <= window[1] <= T):
+            raise ValueError(f"time_window {window} outside the {T} steps of {src.field.var!r}")
+    else:
+        window = _time_window(coords[timecoord], time_sel) if time_sel is not None else None
+    box = None
+    if georegions is not None:
+        box = _clip_box(src.dims, coords, xycoords, georegions, lon_is_360)
+        if box is None and lat_window is not None:
+            raise ValueError("lat_window on a non-contiguous clip goes through the host route")
+    if lat_window is not None:
+        box = _band_of_box(src.dims, src.shape, xycoords, box, lat_window)
+    k_lo, k_hi = window if window is not None else (0, T)
+    a0, a1, b0, b1 = box if box is not None else (0, NY, 0, NX)
+    msgs = src.field.messages[k_lo:k_hi]
+    n = len(msgs)
+    path = src.path
+    # what is staged of every step: (file offset, bytes) of the bitmap and of the packed bits, and the record that says so
+    rec = np.zeros(n, dtype=hip.GRIB_STEP)
+    arr = {k: v[k_lo:k_hi] for k, v in src.field.arrays().items()}
+    nb, d_off, d_len, m_off = arr["nbits"], arr["data_offset"], arr["data_length"], arr["bitmap_offset"]
+    has_map = m_off >= 0
+    lo = np.where(has_map, 0, (a0 * NX * nb) // 8)                       # without a bitmap: the bytes of rows [a0, a1) only
+    hi = np.where(has_map, d_len, -((-a1 * NX * nb) // 8))
+    short = hi > d_len
+    if short.any():
+        k = int(np.argmax(short))
+        raise ValueError(f"{path}: the data section of the message at offset {msgs[k].offset} holds {int(d_len[k])} bytes, "
+                         f"{NY * NX} values of {int(nb[k])} bits need {int(hi[k])}")
+    map_bytes = np.where(has_map, (NY * NX + 7) // 8, 0)
+    rec["nbits"], rec["first_bit"] = nb, np.where(has_map, 0, (a0 * NX * nb) & 7)
+    rec["first_point"], rec["data_bytes"] = np.where(has_map, 0, a0 * NX), hi - lo
+    rec["R"], rec["s"], rec["d"] = arr["R"], arr["s"], arr["d"]
+    pad4 = lambda v: (v + 3) // 4 * 4                                     # every staged range begins on a 4-byte boundary (`read_packed`, align=4)
+    step_bytes = pad4(map_bytes) + pad4(hi - lo)
+    row = int(step_bytes.max()) if n else 4
+    row = max(row, 4)
+    slab = max(1, min(slab_bytes, 1 << 30) // row)
+    rank = torch.empty(hip.grib_rank_bytes(min(slab, max(n, 1)), NY * NX), dtype=torch.uint8, device=device)
+    errors = torch.zeros(1, dtype=torch.int32, device=device)
+    pending = []                                                          # the records of the slab just read, for `place`
+
+    def read(k0, k1, out):
+        # one range per staged piece, packed back to back by the reader's team; a step's ranges follow each other in the slab
+        start = np.concatenate([[0], np.cumsum(step_bytes[k0:k1])])[:-1]
+        r = rec[k0:k1].copy()
+        r["bitmap_off"] = np.where(has_map[k0:k1], start, -1)
+        r["data_off"] = start + pad4(map_bytes[k0:k1])
+        # per step the bitmap, then the packed bits; pieces of no bytes (a field of 0 bits per value) are not asked for
+        two = lambda a_, b_: np.stack([a_, b_], axis=1).ravel()
+        keep = two(has_map[k0:k1], hi[k0:k1] > lo[k0:k1])
+        src_off, nbytes = two(m_off[k0:k1], (d_off + lo)[k0:k1])[keep], two(map_bytes[k0:k1], (hi - lo)[k0:k1])[keep]
+        want = two(r["bitmap_off"], r["data_off"])[keep]
+        if len(want):
+            locs = [(path, o, nby) for o, nby in zip(src_off.tolist(), nbytes.tolist())]
+            offs, got = codec.read_packed(locs, out[:(k1 - k0) * row], align=4, threads=threads)
+            if not np.array_equal(got, nbytes):
+                raise OSError(f"{path}: the file ends inside the steps {k_lo + k0}..{k_lo + k1} of {src.field.var!r}")
+            if not np.array_equal(offs[:-1], want):
+                raise RuntimeError("grib: the reader packed the staged ranges differently from the records")
+        pending[:] = [r]
+
+    def place(raw, dst, m):
+        steps = torch.from_numpy(pending[0].view(np.uint8).reshape(-1)).to(dst.device)
+        hip.grib_unpack(raw, steps, m, (NY, NX), (a0, b0, a1 - a0, b1 - b0), dst, (0, 0, 0), rank, errors)
+
+    data = stream_to_device(n, (a1 - a0, b1 - b0), np.float32, read, slab, device, None, np.float32, None, place=place, stage_step_bytes=row)
+    if n and int(errors.item()):
+        raise ValueError(f"{path}: {int(errors.item())} step(s) of {src.field.var!r} were refused by the unpack kernel (records outside the staged bytes)")
+    if window is not None:
+        coords[timecoord] = coords[timecoord][window[0]:window[1]]
+    if box is not None:
+        coords[src.dims[1]] = coords[src.dims[1]][box[0]:box[1]]
+        coords[src.dims[2]] = coords[src.dims[2]][box[2]:box[3]]
+    return data, src, coords
+
+
 def _join_device_parts(got, rules, timecoord):
     """(data, source, coords) of a dataset streamed part by part — [(tensor, source, coords)], one per store or file in time order —,
     concatenated along time like open_mfdataset.  ``rules``: the parts' unpack rules when they stayed packed (`packed_rules_of`), else None."""
@@ -2348,6 +2486,18 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
             da = DataArray(data, src.dims, coords, name=var, attrs=src.attrs)
             return Dataset(da, xycoords=xycoords, timecoord=timecoord, time_sel=time_sel, lon_is_360=lon_is_360,
                            preprocess=preprocess, georegions=None if lat_window is not None else georegions, time_fix=time_fix, name=name)
+    grib_filter = _grib_filter(kwargs)
+    if device is not None and engine in (None, "cfgrib") and (len(paths) == 1 or time_window is None) and all(_is_grib(p) for p in paths):
+        # GRIB files: the packed bits of every message go from the file to HBM as stored and are unpacked there — always: the only other
+        # route is the numpy decode below.  What `grib.py` refuses raises with its reason.  (A time_window on several files counts steps
+        # of the concatenation: the host route below cuts it.)  ``keep_packed`` leaves the cube float32: every step has its own R / E / D.
+        srcs = [_grib_source(p, var, xycoords, timecoord, grib_filter) for p in paths]
+        data, src, coords = _join_device_parts(
+            [_grib_part_to_device(s_, xycoords, timecoord, time_sel, georegions, lon_is_360, device, time_window, lat_window) for s_ in srcs],
+            None, timecoord)
+        da = DataArray(data, src.dims, coords, name=var, attrs=src.attrs)
+        return Dataset(da, xycoords=xycoords, timecoord=timecoord, time_sel=time_sel, lon_is_360=lon_is_360,
+                       preprocess=preprocess, georegions=None if lat_window is not None else georegions, time_fix=time_fix, name=name)
     parts = []
     for p in paths:
         if engine == "zarr" or (engine is None and _looks_like_zarr(p)):
@@ -2357,6 +2507,8 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
         elif _is_hdf5(p):
             # (a packed variable outside the streaming route stays packed for its one upload: a single file bound for a device)
             da = _open_hdf5(p, var, xycoords, timecoord, keep_packed=keep_packed and device is not None and len(paths) == 1)
+        elif engine == "cfgrib" or _is_grib(p):
+            da = _open_grib(p, var, xycoords, timecoord, grib_filter)
         else:
             da = _open_netcdf3(p, var)
         if preprocess is not None and (preprocess_at_load or len(paths) > 1):

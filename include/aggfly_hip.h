@@ -197,6 +197,27 @@ int afhip_place_box_swapped(const void* block_dev, void* cube_dev, int elem_size
                             int64_t nt, int64_t ny, int64_t nx,
                             int64_t NY, int64_t NX, int64_t t0, int64_t y0, int64_t x0, void* stream);
 
+/* GRIB fields (editions 1 and 2, simple packing) unpacked in HBM: aggfly_amd/io.py `_grib_part_to_device`, aggfly_amd/grib.py.
+ * stage_dev (4-byte aligned, stage_bytes a multiple of 4) holds, as they lie in the file, the packed bits (and the bitmaps) of n_steps fields of one NY x NX grid; steps_dev one
+ * record per field: data_off / data_bytes — its staged packed bits; first_point / first_bit — the value index (= grid point; only
+ * without a bitmap) and the bit (0..7, from the most significant) of the first staged byte where that value begins, so that a step
+ * may be staged from the middle of its data section; bitmap_off — its bitmap of ceil(NY * NX / 8) bytes (one bit per grid point in
+ * scan order, most significant bit first, 1 = a value is there), or -1 (with a bitmap first_point and first_bit are 0: the data
+ * section is staged whole); nbits 0..32; R, s, d — the value of a point is (float)(((X * s) + R) * d) in float64, X its nbits
+ * big-endian bits at bit (index * nbits), index its grid point or, with a bitmap, the number of 1-bits before it; a point whose bit
+ * is 0 becomes NaN (0x7fc00000).  The box [y0, y0 + ny) x [x0, x0 + nx) of step i is written to the float32 cube [cube_nt, cube_NY,
+ * cube_NX] at (t0 + i, cy, cx).  rank_dev: caller-owned scratch of afhip_grib_rank_bytes(n_steps, NY * NX) bytes (-1: absurd sizes).
+ * A record whose ranges leave [0, stage_bytes), whose nbits > 32, whose staged bytes are too few for the last value the box needs or
+ * whose bitmap is shorter than the grid is refused: the step is not written and *errors_dev grows by one.  Whatever the records say,
+ * nothing is read outside the stage and the scratch and nothing is written outside the box.  AFHIP_E_INVALID: a box outside the grid
+ * or the cube, cube_elem_size != 4, buffers on different devices.  The work is enqueued on `stream`; nothing is retained. */
+typedef struct afhip_grib_step { int64_t data_off, data_bytes, first_point, bitmap_off; int32_t first_bit, nbits; double R, s, d; } afhip_grib_step;
+int64_t afhip_grib_rank_bytes(int64_t n_steps, int64_t n_points);
+int afhip_grib_unpack(const void* stage_dev, int64_t stage_bytes, const afhip_grib_step* steps_dev, int64_t n_steps,
+                      int64_t NY, int64_t NX, int64_t y0, int64_t x0, int64_t ny, int64_t nx,
+                      void* cube_dev, int cube_elem_size, int64_t cube_nt, int64_t cube_NY, int64_t cube_NX,
+                      int64_t t0, int64_t cy, int64_t cx, void* rank_dev, int64_t rank_bytes, int32_t* errors_dev, void* stream);
+
 /* Chunk decode in HBM ("or GPU-side decode"; the reference decodes on host threads inside its dask
  * graph, aggfly/dataset/dataset.py:697-728).  Blosc-1 chunks whose streams are LZ4 cross PCIe compressed; the host parses
  * the containers (afcodec_blosc_lz4_plan, include/aggfly_codec.h) into the two record lists below, which travel to HBM with
