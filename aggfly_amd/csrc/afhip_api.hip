@@ -571,6 +571,35 @@ extern "C" int afhip_place_box_swapped(const void* block_dev, void* cube_dev, in
     return place_box_launch<true>("place_box_swapped", block_dev, cube_dev, elem_size, by, bx, st, sy, sx, nt, ny, nx, NY, NX, t0, y0, x0, stream);
 }
 
+// afhip_place_box_tlast: the checks of place_box_launch, and the chunk's time extent too (bt is a parameter here)
+extern "C" int afhip_place_box_tlast(const void* chunk_dev, void* cube_dev, int elem_size,
+                                     int64_t by, int64_t bx, int64_t bt, int64_t sy, int64_t sx, int64_t st,
+                                     int64_t ny, int64_t nx, int64_t nt,
+                                     int64_t NY, int64_t NX, int64_t t0, int64_t y0, int64_t x0, void* stream) {
+    if (!chunk_dev || !cube_dev || by <= 0 || bx <= 0 || bt <= 0 || NY <= 0 || NX <= 0 || nt < 0 || ny < 0 || nx < 0 ||
+        st < 0 || sy < 0 || sx < 0 || t0 < 0 || y0 < 0 || x0 < 0 || sy + ny > by || sx + nx > bx || st + nt > bt || y0 + ny > NY || x0 + nx > NX)
+        return fail(AFHIP_E_INVALID, "place_box_tlast: box outside the chunk or the cube");
+    if (nt * ny * nx == 0) return AFHIP_OK;
+    const int64_t tiles_x = (nx + TLAST_TILE - 1) / TLAST_TILE, tiles_t = (nt + TLAST_TILE - 1) / TLAST_TILE;
+    if (tiles_x > 0x7fffffff || tiles_t > 0x7fffffff || tiles_x * tiles_t > 0x7fffffff || ny * tiles_x * tiles_t > 0x7fffffff)
+        return fail(AFHIP_E_INVALID, "place_box_tlast: box too large for one launch");
+    if (elem_size != 2 && elem_size != 4 && elem_size != 8) return fail(AFHIP_E_INVALID, "place_box_tlast: elem_size must be 2, 4 or 8");
+    GUARD_DEVICE(pointer_device(cube_dev));
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)(ny * tiles_x * tiles_t)), block(WG);
+#define PLACE_TLAST_AS(TE)                                                                                                        \
+    hipLaunchKernelGGL(k_place_box_tlast<TE>, grid, block, 0, s, (const TE*)chunk_dev, (TE*)cube_dev, bx, bt, sy, sx, st, ny, nx, nt, \
+                       NY, NX, t0, y0, x0, tiles_x, tiles_t)
+    switch (elem_size) {
+        case 2: PLACE_TLAST_AS(uint16_t); break;
+        case 4: PLACE_TLAST_AS(uint32_t); break;
+        default: PLACE_TLAST_AS(uint64_t); break;
+    }
+#undef PLACE_TLAST_AS
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
 extern "C" int64_t afhip_grib_rank_bytes(int64_t n_steps, int64_t n_points) {
     if (n_steps < 0 || n_points < 0 || n_points > 0x7fffffff) return -1;
     return n_steps * grib_rank_words(n_points) * (int64_t)sizeof(uint32_t);

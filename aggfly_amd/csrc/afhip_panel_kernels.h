@@ -817,6 +817,46 @@ __global__ __launch_bounds__(WG) void k_place_box_swapped(const TE* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------
+// k_place_box_tlast: k_place_box for a chunk stored with time LAST — a decoded chunk [by][bx][bt] (contiguous, time fastest: what
+// the reference's converter writes, one square tile of cells with the whole series) -> the same time-major cube [T][NY][NX] at
+// (t0, y0, x0), only the part [sy, sy+ny) x [sx, sx+nx) x [st, st+nt) of the chunk.  For every y that is the transpose of an
+// nx x nt matrix (source row stride bt, destination row stride NY * NX), done in 64 x 64 tiles through LDS: one workgroup per
+// (y, x tile, t tile); on the load the 64 lanes of a wave run along time, where the chunk is contiguous, and the four waves take
+// every fourth x row; on the store the lanes run along x, where the cube is contiguous, and the waves take every fourth time
+// step.  Each staged byte is read once, each cube byte written once; every access is one element wide (st, sx, x0, bt, NX, nx
+// and nt are arbitrary, so no wider access is assumed), and partial tiles are bounded by nt and nx, not by the chunk.
+// LDS image [x][t] with rows of 64 elements + one dword of padding (65 elements of 4 or 8 bytes, 66 of 2): a row write puts
+// consecutive lanes on consecutive dwords (two 2-byte lanes share one), the column read of lane x starts at dword x * 65 + j
+// (4 bytes; bank (x + j) % 32 over a 32-lane half), x * 130 + 2j (8 bytes, ds_read_b64; bank pair (2x + 2j) % 64), x * 33 + j / 2
+// (2 bytes; bank (x + j / 2) % 32): distinct banks within each 32-lane half, so neither side conflicts.
+// The compiler's resource lines (gfx950, -O3, -Rpass-analysis=kernel-resource-usage): uint16_t 40 VGPRs, 8448 B LDS, scratch 0,
+// 8 waves per SIMD; uint32_t 26 VGPRs, 16640 B LDS, scratch 0, 8 waves per SIMD; uint64_t 10 VGPRs, 33280 B LDS, scratch 0,
+// 4 waves per SIMD (four workgroups' LDS per CU); no spills.
+// ---------------------------------------------------------------------------------------
+constexpr int TLAST_TILE = 64;
+template <typename TE>
+__global__ __launch_bounds__(WG) void k_place_box_tlast(const TE* __restrict__ src, TE* __restrict__ dst,
+                                                        int64_t bx, int64_t bt, int64_t sy, int64_t sx, int64_t st,
+                                                        int64_t ny, int64_t nx, int64_t nt,
+                                                        int64_t NY, int64_t NX, int64_t t0, int64_t y0, int64_t x0,
+                                                        int64_t tiles_x, int64_t tiles_t) {
+    static_assert(WG % TLAST_TILE == 0, "a wave per tile row");
+    constexpr int PITCH = TLAST_TILE + (sizeof(TE) >= 4 ? 1 : 4 / (int)sizeof(TE));
+    __shared__ TE tile[TLAST_TILE * PITCH];
+    const int64_t b = blockIdx.x;
+    const int64_t tb = (b % tiles_t) * TLAST_TILE, r = b / tiles_t, xb = (r % tiles_x) * TLAST_TILE, y = r / tiles_x;   // y < ny by the launch
+    const int lane = threadIdx.x % TLAST_TILE, row = threadIdx.x / TLAST_TILE;
+    const int64_t mx = (nx - xb) < TLAST_TILE ? (nx - xb) : TLAST_TILE, mt = (nt - tb) < TLAST_TILE ? (nt - tb) : TLAST_TILE;
+    const TE* s = src + ((sy + y) * bx + (sx + xb)) * bt + (st + tb);
+    if (lane < mt)
+        for (int i = row; i < mx; i += WG / TLAST_TILE) tile[i * PITCH + lane] = s[(int64_t)i * bt + lane];
+    __syncthreads();
+    TE* d = dst + ((t0 + tb) * NY + (y0 + y)) * NX + (x0 + xb);
+    if (lane < mx)
+        for (int j = row; j < mt; j += WG / TLAST_TILE) d[(int64_t)j * NY * NX + lane] = tile[lane * PITCH + j];
+}
+
+// ---------------------------------------------------------------------------------------
 // k_read_probe: the temporal kernel's access pattern with no arithmetic — the box's read ceiling for this shape, measured beside
 // the kernel it bounds (afhip_read_probe; bench.py: roofline.measured_read_ceiling_GBps).  Every lane owns 8 bytes of a row, a
 // single-wave workgroup one column tile, four row loads in flight (non-temporal), integer adds, one dword stored per lane at the

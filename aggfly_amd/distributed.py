@@ -291,16 +291,19 @@ def aggregate_dataset_sharded(weights, dataset=None, aggregator_dict=None, engin
     return agg._merge_regions(df, weights)
 
 
-def _step_bytes(path, var, keep_packed=False):
+def _step_bytes(path, var, keep_packed=False, timecoord="time"):
     """Bytes one time step of ``var`` takes in HBM (full stored grid: a clipped read takes less), or None when
     the container's shape cannot be told without reading it.  ``keep_packed`` (or AGGFLY_HIP_KEEP_PACKED=1): an int16- or uint16-packed
-    variable that `io.dataset_from_path` will keep packed counts its 2 stored bytes per cell."""
+    variable that `io.dataset_from_path` will keep packed counts its 2 stored bytes per cell.  A Zarr array whose LAST dimension is
+    ``timecoord`` (the reference's converter's layout) counts its first two extents."""
     import numpy as np
     from . import io as afio
     try:
         if afio._looks_like_zarr(path):
             za = afio.ZarrArray(os.path.join(path, var))
             shape, dt, packing = za.shape, np.dtype(za.dtype), afio.packing_of(za)
+            if len(shape) == 3 and za.dims[2] == timecoord:
+                shape = (shape[2], shape[0], shape[1])
         elif afio._is_hdf5(path):
             from . import hdf5
             with hdf5.H5File(path) as f:
@@ -395,7 +398,7 @@ def aggregate_store_sharded(weights_of, path, var, aggregator_dict, engine="auto
     names = agg._lower_all(aggregator_dict)[3]
     if max_window_bytes is None and torch.cuda.is_available():
         max_window_bytes = int(0.6 * torch.cuda.mem_get_info()[0])
-    windows = plan_windows(bounds, p_lo, p_hi, _step_bytes(path, var, open_kwargs.get("keep_packed", False)), max_window_bytes)
+    windows = plan_windows(bounds, p_lo, p_hi, _step_bytes(path, var, open_kwargs.get("keep_packed", False), timecoord), max_window_bytes)
     weights, parts, region_ids = None, [], None
     # an empty share still opens the store (coordinates, grid) so that every rank builds the same weights
     for q_lo, q_hi in (windows or [(p_lo, p_lo)]):

@@ -41,7 +41,7 @@ EXPORTS = (
     "afhip_zstd_scratch_bytes", "afhip_zstd_decode", "afhip_inflate_scratch_bytes", "afhip_inflate_decode", "afhip_bitunshuffle_blocks",
     "afhip_plan_bind_packing", "afhip_unpack_i16", "afhip_unpack_u16", "afhip_plan_bind_packings",
     "afhip_take_box", "afhip_shuffle_blocks", "afhip_lz4_encode_streams", "afhip_copy_ranges", "afhip_zstd_encode_blocks",
-    "afhip_zstd_encode_scratch_bytes", "afhip_place_box_swapped", "afhip_grib_rank_bytes", "afhip_grib_unpack",
+    "afhip_zstd_encode_scratch_bytes", "afhip_place_box_swapped", "afhip_grib_rank_bytes", "afhip_grib_unpack", "afhip_place_box_tlast",
 )
 
 
@@ -117,6 +117,7 @@ def load():
     lib.afhip_scatter_block.argtypes = [vp, vp, i64, vp, vp]
     lib.afhip_place_box.argtypes = [vp, vp, i32] + [i64] * 13 + [vp]
     lib.afhip_place_box_swapped.argtypes = [vp, vp, i32] + [i64] * 13 + [vp]
+    lib.afhip_place_box_tlast.argtypes = [vp, vp, i32] + [i64] * 14 + [vp]
     lib.afhip_spatial_wavg.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp]
     lib.afhip_plan_create.argtypes = [C.POINTER(PlanDesc), C.POINTER(vp)]
     lib.afhip_plan_destroy.argtypes = [vp]
@@ -229,6 +230,20 @@ def place_box_swapped(block, cube, box_in_block, at):
         raise ValueError("place_box_swapped: box outside the block or the cube along time")
     _check(load().afhip_place_box_swapped(block.data_ptr(), cube.data_ptr(), block.element_size(), block.shape[1], block.shape[2],
                                           st, sy, sx, nt, ny, nx, cube.shape[1], cube.shape[2], t0, y0, x0, _stream_ptr(cube)))
+
+
+def place_box_tlast(chunk, cube, box_in_chunk, at):
+    """`place_box` for a chunk stored with time last (`afhip_place_box_tlast`): cube[t0:t0+nt, y0:y0+ny, x0:x0+nx] =
+    chunk[sy:sy+ny, sx:sx+nx, st:st+nt] moved to time-major order, on the current stream — a tiled transpose through LDS.
+    ``box_in_chunk = (sy, sx, st, ny, nx, nt)``, ``at = (t0, y0, x0)``.  Both tensors contiguous, elements of one size (2 / 4 / 8
+    bytes).  The cube's time extent, which the library cannot know, is checked here."""
+    (sy, sx, st, ny, nx, nt), (t0, y0, x0) = box_in_chunk, at
+    if chunk.dim() != 3 or cube.dim() != 3 or chunk.element_size() != cube.element_size() or not (chunk.is_contiguous() and cube.is_contiguous()):
+        raise ValueError("place_box_tlast: chunk and cube must be contiguous 3-D tensors of one element size")
+    if t0 < 0 or nt < 0 or t0 + nt > cube.shape[0]:
+        raise ValueError("place_box_tlast: box outside the cube along time")
+    _check(load().afhip_place_box_tlast(chunk.data_ptr(), cube.data_ptr(), chunk.element_size(), chunk.shape[0], chunk.shape[1], chunk.shape[2],
+                                        sy, sx, st, ny, nx, nt, cube.shape[1], cube.shape[2], t0, y0, x0, _stream_ptr(cube)))
 
 
 # one record of `afhip_grib_unpack` per time step (`afhip_grib_step`, include/aggfly_hip.h)

@@ -10,7 +10,9 @@ and the native chunk codecs of `csrc/blosc1.c`:
 * Zarr directory stores, format 2 and format 3 (``zarr.json``): C-order chunks, ``compressor`` null / zlib / gzip / lz4 / blosc (every
   Blosc-1 codec and shuffle, decoded natively by ``csrc/blosc1.c``) / zstd, ``_ARRAY_DIMENSIONS``
   attributes, CF time decoding (``units`` + ``calendar``; non-standard calendars go to
-  ``cfcalendar``), ``scale_factor`` / ``add_offset`` / ``_FillValue``;
+  ``cfcalendar``), ``scale_factor`` / ``add_offset`` / ``_FillValue``; time-major stores and, with ``device=`` set, time-last ones —
+  ``(latitude, longitude, time)``, the reference's converter's own order, written here by ``dataset_to_zarr(layout="time-last")`` —,
+  whose chunks one kernel transposes into the time-major cube (``hip.place_box_tlast``);
 * netCDF-4 / HDF5 files through the built-in reader ``hdf5.py`` (chunked + shuffle + deflate variables,
   dimension scales, either group style; no netCDF4 / h5py needed);
 * ``.npz`` bundles with ``data``, ``time``, ``latitude``, ``longitude``;
@@ -505,9 +507,10 @@ def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: in
     return cube
 
 
-def zarr_to_device(path: str, var: str, device="cuda", threads: int = 16, slab_bytes: int = 128 << 20, t_range=None, yx_box=None, keep_packed=False):
-    """Decode a time-major Zarr array straight into HBM.  Returns (tensor, ZarrArray)."""
-    return array_to_device(ZarrArray(os.path.join(path, var)), device, threads, slab_bytes, t_range, yx_box, keep_packed)
+def zarr_to_device(path: str, var: str, device="cuda", threads: int = 16, slab_bytes: int = 128 << 20, t_range=None, yx_box=None, keep_packed=False,
+                   time_axis=0):
+    """Decode a time-major Zarr array — or, ``time_axis=2``, a time-last one (`array_to_device`) — straight into HBM.  Returns (tensor, ZarrArray)."""
+    return array_to_device(ZarrArray(os.path.join(path, var)), device, threads, slab_bytes, t_range, yx_box, keep_packed, time_axis)
 
 
 def keep_packed_requested(keep_packed=False) -> bool:
@@ -585,16 +588,25 @@ def _cf_in_hbm(np_dtype, attrs):
     return post, has_fv or packed, out_np, wire
 
 
-def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 << 20, t_range=None, yx_box=None, keep_packed=False):
+def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 << 20, t_range=None, yx_box=None, keep_packed=False,
+                    time_axis=0):
     """Stream a chunked (time, y, x) array — a `ZarrArray` or an `hdf5.ChunkSource` — straight into HBM: each
     slab is a whole number of time chunks, decoded chunk-parallel by the native codec into page-locked memory
     and uploaded while the next slab decodes.  Returns (tensor, source).  ``keep_packed`` (int16 / uint16 storage, `packing_of`): the
-    tensor stays int16 as stored (uint16: the int16 of the same bits) — the CF unpacking in HBM is skipped and left to the kernels that read a `packed.PackedCube`."""
+    tensor stays int16 as stored (uint16: the int16 of the same bits) — the CF unpacking in HBM is skipped and left to the kernels that read a `packed.PackedCube`.
+    ``time_axis=2``: the array is (y, x, time) — what the reference's converter writes — and a codec the native decoder handles:
+    the tensor comes back TIME-MAJOR, (time, y, x), through `_stream_chunks_scatter` (each chunk transposed into the cube in HBM);
+    ``t_range`` counts steps of the last axis and ``yx_box`` cells of the first two.  A codec chain without a native kind ignores
+    ``time_axis``: the array streams as stored."""
     if len(za.shape) != 3:
         raise ValueError("zarr_to_device expects a (time, y, x) array")
     if os.environ.get("AGGFLY_HIP_SLAB_MB"):                       # tuning knob (scripts/e2e_bench.py sweeps it)
         slab_bytes = int(float(os.environ["AGGFLY_HIP_SLAB_MB"]) * (1 << 20))
     post, need_post, out_np, wire = _cf_in_hbm(za.dtype, za.attrs)
+    if time_axis == 2 and za.native_kind is not None:
+        if keep_packed and packing_of(za) is not None:
+            need_post, out_np = False, wire
+        return _stream_chunks_scatter(za, device, threads, slab_bytes, post if need_post else None, out_np, t_range, yx_box, time_axis=2), za
     T, ny, nx = za.shape
     tc = za.chunks[0]
     grid_yx = [(iy, ix) for iy in range((ny + za.chunks[1] - 1) // za.chunks[1]) for ix in range((nx + za.chunks[2] - 1) // za.chunks[2])]
@@ -810,11 +822,16 @@ class _ScatterJob:
     """What both routes of `_stream_chunks_scatter` share: the window, the chunks that touch it, the cube, and the
     placement of decoded chunks into it."""
 
-    def __init__(self, za, device, out_dtype, t_range, yx_box):
+    def __init__(self, za, device, out_dtype, t_range, yx_box, time_axis=0):
+        """``time_axis``: 0 — the array is (time, y, x) —, or 2 — (y, x, time), the reference's converter's layout: ``idxs`` stay
+        chunk indices in the store's own order, the cube is time-major either way and `place` transposes each chunk into it."""
         import torch
-        self.za, self.device = za, device
-        T, ny, nx = za.shape
-        self.tc, self.yc, self.xc = za.chunks
+        if time_axis not in (0, 2):
+            raise ValueError("time_axis must be 0 or 2")
+        self.za, self.device, self.time_axis = za, device, time_axis
+        tm = (lambda s: (s[2], s[0], s[1])) if time_axis == 2 else tuple      # the store's own order -> (time, y, x)
+        T, ny, nx = tm(za.shape)
+        self.tc, self.yc, self.xc = tm(za.chunks)
         self.wire = wire = _wire_dtype(za.dtype, za.attrs)[0]              # the stored bits as torch holds them (uint16: int16)
         self.tdt = _torch_dtype(wire)
         self.same_dtype = (out_dtype is None or np.dtype(out_dtype) == wire) and za.dtype.itemsize in (2, 4, 8)
@@ -823,11 +840,15 @@ class _ScatterJob:
         self.cube = torch.empty((self.kb - self.ka, self.yb - self.ya, self.xb - self.xa),
                                 dtype=_torch_dtype(out_dtype) if out_dtype is not None else self.tdt, device=device)
         self.cb = za.chunk_nbytes
-        tc, yc, xc = za.chunks
-        self.idxs = [(it, iy, ix) for it in range(self.ka // tc, -(-self.kb // tc)) for iy in range(self.ya // yc, -(-self.yb // yc))
-                     for ix in range(self.xa // xc, -(-self.xb // xc))]
-        # a chunk of whole time steps of the window (full grid, same dtype) is one contiguous run of the cube
-        self.whole_steps = self.same_dtype and (self.ya, self.xa) == (0, 0) and (yc, xc) == (self.yb, self.xb) == (ny, nx)
+        tc, yc, xc = self.tc, self.yc, self.xc
+        its, iys, ixs = range(self.ka // tc, -(-self.kb // tc)), range(self.ya // yc, -(-self.yb // yc)), range(self.xa // xc, -(-self.xb // xc))
+        if time_axis == 2:
+            self.idxs = [(iy, ix, it) for iy in iys for ix in ixs for it in its]
+        else:
+            self.idxs = [(it, iy, ix) for it in its for iy in iys for ix in ixs]
+        # a chunk of whole time steps of the window (full grid, same dtype) is one contiguous run of the cube — never a time-last one
+        self.whole_steps = (time_axis == 0 and self.same_dtype and (self.ya, self.xa) == (0, 0)
+                            and (yc, xc) == (self.yb, self.xb) == (ny, nx))
         self.step_bytes = ny * nx * za.dtype.itemsize
 
     def absent_value(self) -> float:
@@ -847,9 +868,11 @@ class _ScatterJob:
         chunks (``res[i] == -100``) become the fill value.  ``skip_present``: the present chunks are in place already."""
         from . import hip
         tc, yc, xc, ka, kb, ya, yb, xa, xb, cb, cube = self.tc, self.yc, self.xc, self.ka, self.kb, self.ya, self.yb, self.xa, self.xb, self.cb, self.cube
-        for i, ((it, iy, ix), r) in enumerate(zip(batch, res)):
+        tlast = self.time_axis == 2
+        for i, (idx, r) in enumerate(zip(batch, res)):
             if skip_present and r != -100:
                 continue
+            it, iy, ix = (idx[2], idx[0], idx[1]) if tlast else idx
             c0 = it * tc                            # first step of the chunk
             t0, t1 = max(c0, ka), min(c0 + tc, kb)  # the part of it inside the window
             y0, y1 = max(iy * yc, ya), min((iy + 1) * yc, yb)
@@ -857,6 +880,13 @@ class _ScatterJob:
             dst = cube[t0 - ka:t1 - ka, y0 - ya:y1 - ya, x0 - xa:x1 - xa]
             if r == -100:                           # absent chunk = fill value
                 dst.fill_(self.absent_value())
+                continue
+            if tlast:                               # a chunk [yc][xc][tc]: transposed into the cube by one kernel
+                blk = staged[i * cb:(i + 1) * cb].view(self.tdt).view(yc, xc, tc)
+                if self.same_dtype:
+                    hip.place_box_tlast(blk, cube, (y0 - iy * yc, x0 - ix * xc, t0 - c0, y1 - y0, x1 - x0, t1 - t0), (t0 - ka, y0 - ya, x0 - xa))
+                else:                               # packed integers read to float32: the cast happens in this (strided) copy
+                    dst.copy_(blk[y0 - iy * yc:y1 - iy * yc, x0 - ix * xc:x1 - ix * xc, t0 - c0:t1 - c0].permute(2, 0, 1))
                 continue
             blk = staged[i * cb:(i + 1) * cb].view(self.tdt).view(tc, yc, xc)
             if self.same_dtype:                     # one coalesced pass (torch's strided copy ran at 22 GB/s here)
@@ -898,13 +928,15 @@ class _IngestTrace:
         print("ingest trace:", {**head, **{k_: round(v * 1e3, 2) for k_, v in self.phase.items()}}, flush=True)
 
 
-def _stream_chunks_scatter(za: "ZarrArray", device, threads: int, slab_bytes: int, post=None, out_dtype=None, t_range=None, yx_box=None):
+def _stream_chunks_scatter(za: "ZarrArray", device, threads: int, slab_bytes: int, post=None, out_dtype=None, t_range=None, yx_box=None,
+                           time_axis=0):
     """Any chunk grid, any time / space window: batches of chunks reach HBM through page-locked staging and the GPU
     places every chunk into its (time, y, x) box of the cube (a strided device-to-device copy at HBM speed — the part a
     CPU is bad at: 472-byte row pieces).  Two routes: the chunks decoded by the host's OpenMP team
     (`_scatter_host_decode`), or — Blosc-LZ4, larger requests — uploaded compressed and decoded in HBM
-    (`_scatter_gpu_decode`, `_gpu_decodable`)."""
-    job = _ScatterJob(za, device, out_dtype, t_range, yx_box)
+    (`_scatter_gpu_decode`, `_gpu_decodable`).  ``time_axis=2``: a (y, x, time) array — both routes decode its chunks as they
+    are and `_ScatterJob.place` transposes them into the same time-major cube."""
+    job = _ScatterJob(za, device, out_dtype, t_range, yx_box, time_axis)
     if _gpu_decodable(za, len(job.idxs) * job.cb):
         try:
             return _scatter_gpu_decode(job, threads, post)
@@ -1366,7 +1398,7 @@ def _gpu_decode_batches(job, threads, cuts, per, cmax, route, nstage, host, comp
         trace.lap("read")
         present = np.nonzero(sizes != -100)[0]
         rec0 = int(offs[-1])
-        direct = job.whole_steps and all(job.inside(it) for it, _, _ in batch)
+        direct = job.whole_steps and all(job.inside(it) for it, _, _ in batch)       # (whole_steps: a time-leading array)
         out_offs = (np.array([batch[i][0] * job.tc - job.ka for i in present], dtype=np.int64) * job.step_bytes if direct
                     else present.astype(np.int64) * cb)
         pres, ranges = route.plan(k, hall, rec0, offs, sizes, present, out_offs)
@@ -1829,8 +1861,12 @@ def _auto_chunks(sizes: dict, itemsize: int, target_mb: float = 256) -> dict:
 
 
 def dataset_to_zarr(dataset: Dataset, path: str, var: str = "var", chunks=None, compress=True, mode: str = "w", zarr_format: int = 2,
-                    shards=None, encode: str = "auto"):
+                    shards=None, encode: str = "auto", layout: str = "time-major"):
     """`dataset_to_zarr` (`zarr_convert.py:50-121`): write a time-major, time-contiguous store.
+    ``layout``: "time-major" — the data variable is (time, latitude, longitude) — or "time-last" — (latitude, longitude, time), the
+    reference's converter's own layout (it writes `Dataset.da` as it stands, `zarr_convert.py:83-113`): the same ``chunks`` /
+    `_auto_chunks` policy and ``shards``, reordered.  "time-last" is encoded on the host: ``encode="gpu"`` raises `ValueError`
+    (the encoder's `take_box` cuts time-major chunks only), "auto" takes the host route.
     ``compress``: True / "blosc" -> Blosc-1 LZ4 + byte shuffle (what zarr-python 2 / numcodecs write by
     default and read back), "blosc-zstd" / "blosc-bitshuffle" / "blosc-zstd-bitshuffle" -> Blosc-1 with Zstandard streams and the byte
     shuffle, LZ4 streams and the bit shuffle, or both (the Zarr v3 ``blosc`` codec's default ``cname`` is zstd), "zstd" (zarr-python
@@ -1846,6 +1882,14 @@ def dataset_to_zarr(dataset: Dataset, path: str, var: str = "var", chunks=None, 
     eligible; else the host route — always for a host-resident cube.  Coordinates and metadata are written by the same code on every route."""
     if encode not in ("auto", "host", "gpu"):
         raise ValueError(f"encode must be 'auto', 'host' or 'gpu', got {encode!r}")
+    if layout not in ("time-major", "time-last"):
+        raise ValueError(f"layout must be 'time-major' or 'time-last', got {layout!r}")
+    tlast = layout == "time-last"
+    if tlast:
+        if encode == "gpu":
+            raise ValueError("dataset_to_zarr(encode='gpu'): layout='time-last' is encoded on the host (the GPU encoder cuts "
+                             "time-major chunks only)")
+        encode = "host"
     cube = dataset.cube()
     on_host = isinstance(cube, np.ndarray)
     np_dtype = cube.dtype if on_host else np.dtype(str(cube.dtype).replace("torch.", ""))
@@ -1896,7 +1940,12 @@ def dataset_to_zarr(dataset: Dataset, path: str, var: str = "var", chunks=None, 
     if shards is not None:
         stuple = tuple(sizes[d] if shards.get(d, -1) in (-1, None) else shards[d] for d in ("time", "latitude", "longitude"))
         stuple = tuple(-(-s_ // c_) * c_ for s_, c_ in zip(stuple, ctuple))          # whole chunks per shard
-    _write_array(path, var, cube, ("time", "latitude", "longitude"), ctuple, {}, comp, zarr_format, stuple)
+    if tlast:                                               # (latitude, longitude, time): chunks and shards reordered alike
+        last = lambda t: (t[1], t[2], t[0])
+        _write_array(path, var, np.ascontiguousarray(cube.transpose(1, 2, 0)), ("latitude", "longitude", "time"), last(ctuple), {}, comp,
+                     zarr_format, None if stuple is None else last(stuple))
+    else:
+        _write_array(path, var, cube, ("time", "latitude", "longitude"), ctuple, {}, comp, zarr_format, stuple)
     tv, tattrs = _encode_time(dataset.time)
     _write_array(path, "time", np.asarray(tv, dtype=np.float64), ("time",), (len(tv),), tattrs, None, zarr_format)
     _write_array(path, "latitude", dataset.latitude, ("latitude",), (len(dataset.latitude),), {}, None, zarr_format)
@@ -2327,6 +2376,14 @@ def _grib_part_to_device(src, xycoords, timecoord, time_sel, georegions, lon_is_
     return data, src, coords
 
 
+class _TimeMajor:
+    """A time-last `ZarrArray` as its tensor lies in HBM after `array_to_device(time_axis=2)`: the dimensions in time-major order,
+    the attributes as stored — what `_join_device_parts` and the `DataArray` of `dataset_from_path` ask of a source."""
+
+    def __init__(self, za, dims):
+        self.za, self.dims, self.attrs = za, tuple(dims), za.attrs
+
+
 def _join_device_parts(got, rules, timecoord):
     """(data, source, coords) of a dataset streamed part by part — [(tensor, source, coords)], one per store or file in time order —,
     concatenated along time like open_mfdataset.  ``rules``: the parts' unpack rules when they stayed packed (`packed_rules_of`), else None."""
@@ -2426,31 +2483,39 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
                     c = ZarrArray(cp)
                     v = c.read(threads=1)
                     coords[d] = _decode_time(v, c.attrs) if " since " in str(c.attrs.get("units", "")) else v
-            # a time selection on a time-leading store: only the chunks that hold the selected steps are
+            # a time-last store (latitude, longitude, time) — what the reference's converter writes — comes back time-major:
+            # below, `dims` / `shape` are those of the tensor in HBM, and every window is cut on them
+            dims, shape = za.dims, za.shape
+            tlast = (len(dims) == 3 and dims[2] == timecoord and set(dims[:2]) == set(xycoords) and len(set(xycoords)) == 2
+                     and za.native_kind is not None)
+            if tlast:
+                dims, shape = (dims[2], dims[0], dims[1]), (shape[2], shape[0], shape[1])
+            # a time selection on a time-leading (or time-last) store: only the chunks that hold the selected steps are
             # read and decoded (a decade out of a 40-year store reads a quarter of it)
             window = None
             if time_window is not None:
-                if not (za.dims and za.dims[0] == timecoord):
-                    raise ValueError("time_window needs a time-leading array")
+                if not (dims and dims[0] == timecoord):
+                    raise ValueError("time_window needs a time-leading or a time-last array")
                 window = (int(time_window[0]), int(time_window[1]))
-            elif time_sel is not None and za.dims and za.dims[0] == timecoord and timecoord in coords:
+            elif time_sel is not None and dims and dims[0] == timecoord and timecoord in coords:
                 window = _time_window(coords[timecoord], time_sel)
             # a clip to the regions' extent (`dataset.py:150-175`): only the chunks that touch the box are read,
             # and only the box reaches HBM; `Dataset` repeats the clip on the clipped grid (a no-op)
             box = None
-            if georegions is not None and len(za.dims) == 3:
-                box = _clip_box(za.dims, coords, xycoords, georegions, lon_is_360)
+            if georegions is not None and len(dims) == 3:
+                box = _clip_box(dims, coords, xycoords, georegions, lon_is_360)
                 if box is None and lat_window is not None:
                     raise ValueError("lat_window on a non-contiguous clip goes through the host route")
             if lat_window is not None:
-                box = _band_of_box(za.dims, za.shape, xycoords, box, lat_window)
-            data, za = zarr_to_device(path1, var, device=device, t_range=window, yx_box=box, keep_packed=stay_packed)
+                box = _band_of_box(dims, shape, xycoords, box, lat_window)
+            data, za = zarr_to_device(path1, var, device=device, t_range=window, yx_box=box, keep_packed=stay_packed,
+                                      time_axis=2 if tlast else 0)
             if window is not None:
                 coords[timecoord] = coords[timecoord][window[0]:window[1]]
             if box is not None:
-                coords[za.dims[1]] = coords[za.dims[1]][box[0]:box[1]]
-                coords[za.dims[2]] = coords[za.dims[2]][box[2]:box[3]]
-            return data, za, coords
+                coords[dims[1]] = coords[dims[1]][box[0]:box[1]]
+                coords[dims[2]] = coords[dims[2]][box[2]:box[3]]
+            return data, (_TimeMajor(za, dims) if tlast else za), coords
 
         try:
             data, za, coords = _join_device_parts([part_to_device(p_) for p_ in paths], rules, timecoord)

@@ -197,6 +197,17 @@ int afhip_place_box_swapped(const void* block_dev, void* cube_dev, int elem_size
                             int64_t nt, int64_t ny, int64_t nx,
                             int64_t NY, int64_t NX, int64_t t0, int64_t y0, int64_t x0, void* stream);
 
+/* afhip_place_box for a chunk stored with time LAST — the layout the reference's converter writes (aggfly/dataset/zarr_convert.py:83-113:
+ * `Dataset.da` is (latitude, longitude, time)): copies the part [sy, sy+ny) x [sx, sx+nx) x [st, st+nt) of a decoded chunk
+ * [by, bx, bt] (contiguous, time fastest, in HBM) into the time-major cube [*, NY, NX] at (t0, y0, x0) — a tiled transpose through
+ * LDS, each staged byte read once, each cube byte written once.  elem_size 2, 4 or 8 bytes; the box is checked against all three
+ * extents of the chunk and against NY and NX (the cube's time extent is the caller's to check); an empty box returns AFHIP_OK
+ * without a launch; nothing is retained. */
+int afhip_place_box_tlast(const void* chunk_dev, void* cube_dev, int elem_size,
+                          int64_t by, int64_t bx, int64_t bt, int64_t sy, int64_t sx, int64_t st,
+                          int64_t ny, int64_t nx, int64_t nt,
+                          int64_t NY, int64_t NX, int64_t t0, int64_t y0, int64_t x0, void* stream);
+
 /* GRIB fields (editions 1 and 2, simple packing) unpacked in HBM: aggfly_amd/io.py `_grib_part_to_device`, aggfly_amd/grib.py.
  * stage_dev (4-byte aligned, stage_bytes a multiple of 4) holds, as they lie in the file, the packed bits (and the bitmaps) of n_steps fields of one NY x NX grid; steps_dev one
  * record per field: data_off / data_bytes — its staged packed bits; first_point / first_bit — the value index (= grid point; only
