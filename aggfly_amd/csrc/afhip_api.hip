@@ -22,6 +22,7 @@
 #include "afhip_zstd_kernels.h"
 #include "afhip_inflate_kernels.h"
 #include "afhip_grib_kernels.h"
+#include "afhip_filter_kernels.h"
 #include "afhip_planner.h"
 #include "afhip_variants.h"
 #include "afhip_sine_p2_table.h"
@@ -596,6 +597,109 @@ extern "C" int afhip_place_box_tlast(const void* chunk_dev, void* cube_dev, int 
         default: PLACE_TLAST_AS(uint64_t); break;
     }
 #undef PLACE_TLAST_AS
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
+// ---- numcodecs element filters undone in HBM (afhip_filter_kernels.h) ----
+// The number of tile sums a call needs, or -1: what afhip_delta_decode refuses (sizes, an overflow, a launch beyond the grid limit).
+static int64_t delta_total_tiles(int64_t n_chunks, int64_t chunk_elems, int elem_size) {
+    if (n_chunks < 0 || chunk_elems <= 0 || (elem_size != 1 && elem_size != 2 && elem_size != 4 && elem_size != 8)) return -1;
+    if (n_chunks == 0) return 0;
+    if (chunk_elems > INT64_MAX / elem_size / n_chunks) return -1;                       // n_chunks * chunk_elems * elem_size overflows
+    const int64_t tiles = delta_tiles_per_chunk(chunk_elems, elem_size);
+    if (n_chunks > 0x7fffffff || tiles > 0x7fffffff / n_chunks) return -1;               // one workgroup per tile: the grid limit
+    return n_chunks * tiles;
+}
+
+extern "C" int64_t afhip_delta_scratch_bytes(int64_t n_chunks, int64_t chunk_elems, int elem_size) {
+    const int64_t total = delta_total_tiles(n_chunks, chunk_elems, elem_size);
+    if (total < 0) return -1;
+    // (chunks of one tile need no sums; 16 bytes at least, so that a caller may always allocate what this says)
+    const int64_t need = delta_tiles_per_chunk(chunk_elems, elem_size) > 1 ? total * elem_size : 0;
+    return (need + 15) / 16 * 16 + 16;
+}
+
+template <typename T>
+static void delta_launch(void* stage_dev, void* scratch_dev, int64_t n_chunks, int64_t chunk_elems, int64_t tiles, hipStream_t s) {
+    // 16-byte accesses when every chunk begins on a 16-byte boundary
+    const bool vec = (uintptr_t)stage_dev % 16 == 0 && (chunk_elems * (int64_t)sizeof(T)) % 16 == 0;
+    const dim3 grid((unsigned)(n_chunks * tiles)), block(DELTA_WG);
+    T* sums = tiles > 1 ? (T*)scratch_dev : nullptr;
+    if (sums) {
+        if (vec) hipLaunchKernelGGL((k_delta_tile_sums<T, true>), grid, block, 0, s, (const T*)stage_dev, sums, chunk_elems, tiles);
+        else hipLaunchKernelGGL((k_delta_tile_sums<T, false>), grid, block, 0, s, (const T*)stage_dev, sums, chunk_elems, tiles);
+        hipLaunchKernelGGL(k_delta_scan_sums<T>, dim3((unsigned)n_chunks), block, 0, s, sums, tiles);
+    }
+    if (vec) hipLaunchKernelGGL((k_delta_scan_tiles<T, true>), grid, block, 0, s, (T*)stage_dev, (const T*)sums, chunk_elems, tiles);
+    else hipLaunchKernelGGL((k_delta_scan_tiles<T, false>), grid, block, 0, s, (T*)stage_dev, (const T*)sums, chunk_elems, tiles);
+}
+
+extern "C" int afhip_delta_decode(void* stage_dev, int64_t n_chunks, int64_t chunk_elems, int elem_size,
+                                  void* scratch_dev, int64_t scratch_bytes, void* stream) {
+    if (elem_size != 1 && elem_size != 2 && elem_size != 4 && elem_size != 8)
+        return fail(AFHIP_E_INVALID, "delta_decode: elem_size must be 1, 2, 4 or 8");
+    if (n_chunks < 0 || chunk_elems <= 0) return fail(AFHIP_E_INVALID, "delta_decode: n_chunks < 0 or chunk_elems <= 0");
+    const int64_t total = delta_total_tiles(n_chunks, chunk_elems, elem_size);
+    if (total < 0) return fail(AFHIP_E_INVALID, "delta_decode: n_chunks * chunk_elems overflows or is too large for one launch");
+    if (n_chunks == 0) return AFHIP_OK;
+    if (!stage_dev || (uintptr_t)stage_dev % (uintptr_t)elem_size) return fail(AFHIP_E_INVALID, "delta_decode: stage_dev is null or not element-aligned");
+    const int64_t tiles = delta_tiles_per_chunk(chunk_elems, elem_size);
+    if (tiles > 1 && (!scratch_dev || (uintptr_t)scratch_dev % 8 || scratch_bytes < afhip_delta_scratch_bytes(n_chunks, chunk_elems, elem_size)))
+        return fail(AFHIP_E_INVALID, "delta_decode: scratch_dev is null, not 8-byte aligned or smaller than afhip_delta_scratch_bytes says");
+    GUARD_DEVICE(pointer_device(stage_dev));
+    hipStream_t s = (hipStream_t)stream;
+    switch (elem_size) {
+        case 1: delta_launch<uint8_t>(stage_dev, scratch_dev, n_chunks, chunk_elems, tiles, s); break;
+        case 2: delta_launch<uint16_t>(stage_dev, scratch_dev, n_chunks, chunk_elems, tiles, s); break;
+        case 4: delta_launch<uint32_t>(stage_dev, scratch_dev, n_chunks, chunk_elems, tiles, s); break;
+        default: delta_launch<uint64_t>(stage_dev, scratch_dev, n_chunks, chunk_elems, tiles, s); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
+template <typename S, typename D>
+static void fso_launch(const void* src_dev, void* dst_dev, int64_t n, double scale, double offset, hipStream_t s) {
+    constexpr int V = 16 / (int)sizeof(D);
+    constexpr uintptr_t src_align = sizeof(S) * V >= 16 ? 16 : sizeof(S) * V;
+    const bool vec = (uintptr_t)src_dev % src_align == 0 && (uintptr_t)dst_dev % 16 == 0;
+    const int64_t lanes = vec ? (n + V - 1) / V : n;
+    const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
+    if (vec) hipLaunchKernelGGL((k_fso_decode<S, D, true>), grid, block, 0, s, (const S*)src_dev, (D*)dst_dev, n, scale, offset);
+    else hipLaunchKernelGGL((k_fso_decode<S, D, false>), grid, block, 0, s, (const S*)src_dev, (D*)dst_dev, n, scale, offset);
+}
+
+extern "C" int afhip_fso_decode(const void* src_dev, void* dst_dev, int64_t n, int src_type, int dst_type,
+                                double scale, double offset, void* stream) {
+    static const int size_of[8] = {1, 1, 2, 2, 4, 4, 4, 8};
+    if (src_type < AFHIP_T_I8 || src_type > AFHIP_T_F64) return fail(AFHIP_E_INVALID, "fso_decode: src_type must be one of AFHIP_T_I8 ... AFHIP_T_F64");
+    if (dst_type != AFHIP_T_F32 && dst_type != AFHIP_T_F64) return fail(AFHIP_E_INVALID, "fso_decode: dst_type must be AFHIP_T_F32 or AFHIP_T_F64");
+    if (n < 0 || !(scale == scale) || scale == 0.0) return fail(AFHIP_E_INVALID, "fso_decode: n < 0, or a scale that is 0 or NaN");
+    if (n == 0) return AFHIP_OK;
+    if (n > (int64_t)0x7fffffff * 256) return fail(AFHIP_E_INVALID, "fso_decode: too many elements for one launch");
+    if (!src_dev || !dst_dev || (uintptr_t)src_dev % (uintptr_t)size_of[src_type] || (uintptr_t)dst_dev % (uintptr_t)size_of[dst_type])
+        return fail(AFHIP_E_INVALID, "fso_decode: a buffer is null or not element-aligned");
+    const char *a = (const char*)src_dev, *b = (const char*)dst_dev;
+    if (a < b + n * size_of[dst_type] && b < a + n * size_of[src_type]) return fail(AFHIP_E_INVALID, "fso_decode: src and dst overlap");
+    GUARD_DEVICE(pointer_device(dst_dev));
+    hipStream_t s = (hipStream_t)stream;
+#define FSO_FROM(S)                                                                                         \
+    do {                                                                                                    \
+        if (dst_type == AFHIP_T_F32) fso_launch<S, float>(src_dev, dst_dev, n, scale, offset, s);           \
+        else fso_launch<S, double>(src_dev, dst_dev, n, scale, offset, s);                                  \
+    } while (0)
+    switch (src_type) {
+        case AFHIP_T_I8: FSO_FROM(int8_t); break;
+        case AFHIP_T_U8: FSO_FROM(uint8_t); break;
+        case AFHIP_T_I16: FSO_FROM(int16_t); break;
+        case AFHIP_T_U16: FSO_FROM(uint16_t); break;
+        case AFHIP_T_I32: FSO_FROM(int32_t); break;
+        case AFHIP_T_U32: FSO_FROM(uint32_t); break;
+        case AFHIP_T_F32: FSO_FROM(float); break;
+        default: FSO_FROM(double); break;
+    }
+#undef FSO_FROM
     HIP_TRY(hipGetLastError());
     return AFHIP_OK;
 }

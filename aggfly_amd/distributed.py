@@ -295,13 +295,17 @@ def _step_bytes(path, var, keep_packed=False, timecoord="time"):
     """Bytes one time step of ``var`` takes in HBM (full stored grid: a clipped read takes less), or None when
     the container's shape cannot be told without reading it.  ``keep_packed`` (or AGGFLY_HIP_KEEP_PACKED=1): an int16- or uint16-packed
     variable that `io.dataset_from_path` will keep packed counts its 2 stored bytes per cell.  A Zarr array whose LAST dimension is
-    ``timecoord`` (the reference's converter's layout) counts its first two extents."""
+    ``timecoord`` (the reference's converter's layout) counts its first two extents.  A Zarr array with converting element filters
+    (``fixedscaleoffset`` to int16, ...) counts its stored bytes on top: while it is read, the stored elements lie beside the cube."""
     import numpy as np
     from . import io as afio
+    beside = 0                                                # bytes per cell of a stored-type buffer beside the cube
     try:
         if afio._looks_like_zarr(path):
             za = afio.ZarrArray(os.path.join(path, var))
             shape, dt, packing = za.shape, np.dtype(za.dtype), afio.packing_of(za)
+            if za.elem_filters and za.stored_dtype != za.dtype:
+                beside = za.stored_dtype.itemsize
             if len(shape) == 3 and za.dims[2] == timecoord:
                 shape = (shape[2], shape[0], shape[1])
         elif afio._is_hdf5(path):
@@ -321,7 +325,7 @@ def _step_bytes(path, var, keep_packed=False, timecoord="time"):
         item = dt.itemsize if dt.kind == "f" else 4           # packed integers are unpacked to float32 in HBM ...
         if packing is not None and afio.keep_packed_requested(keep_packed):
             item = 2                                          # ... unless the cube stays packed
-        return int(np.prod(shape[1:], dtype=np.int64)) * item
+        return int(np.prod(shape[1:], dtype=np.int64)) * (item + beside)
     except Exception:
         return None
 

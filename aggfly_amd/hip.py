@@ -42,6 +42,7 @@ EXPORTS = (
     "afhip_plan_bind_packing", "afhip_unpack_i16", "afhip_unpack_u16", "afhip_plan_bind_packings",
     "afhip_take_box", "afhip_shuffle_blocks", "afhip_lz4_encode_streams", "afhip_copy_ranges", "afhip_zstd_encode_blocks",
     "afhip_zstd_encode_scratch_bytes", "afhip_place_box_swapped", "afhip_grib_rank_bytes", "afhip_grib_unpack", "afhip_place_box_tlast",
+    "afhip_delta_scratch_bytes", "afhip_delta_decode", "afhip_fso_decode",
 )
 
 
@@ -136,6 +137,10 @@ def load():
     lib.afhip_lz4_encode_streams.argtypes = [vp, vp, i64, vp, vp, vp]
     lib.afhip_copy_ranges.argtypes = [vp, vp, vp, i64, vp]
     lib.afhip_zstd_encode_blocks.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    lib.afhip_delta_scratch_bytes.restype = i64
+    lib.afhip_delta_scratch_bytes.argtypes = [i64, i64, i32]
+    lib.afhip_delta_decode.argtypes = [vp, i64, i64, i32, vp, i64, vp]
+    lib.afhip_fso_decode.argtypes = [vp, vp, i64, i32, i32, C.c_double, C.c_double, vp]
     lib.afhip_grib_rank_bytes.restype = i64
     lib.afhip_grib_rank_bytes.argtypes = [i64, i64]
     lib.afhip_grib_unpack.argtypes = [vp, i64, vp, i64] + [i64] * 6 + [vp, i32] + [i64] * 6 + [vp, i64, vp, vp]
@@ -244,6 +249,46 @@ def place_box_tlast(chunk, cube, box_in_chunk, at):
         raise ValueError("place_box_tlast: box outside the cube along time")
     _check(load().afhip_place_box_tlast(chunk.data_ptr(), cube.data_ptr(), chunk.element_size(), chunk.shape[0], chunk.shape[1], chunk.shape[2],
                                         sy, sx, st, ny, nx, nt, cube.shape[1], cube.shape[2], t0, y0, x0, _stream_ptr(cube)))
+
+
+# element type codes of `afhip_fso_decode` (AFHIP_T_*, include/aggfly_hip.h), by numpy type name
+FSO_TYPE = {"int8": 0, "uint8": 1, "int16": 2, "uint16": 3, "int32": 4, "uint32": 5, "float32": 6, "float64": 7}
+
+
+def delta_scratch_bytes(n_chunks: int, chunk_elems: int, elem_size: int) -> int:
+    """`afhip_delta_scratch_bytes`: the tile-sum scratch `delta_decode` needs for ``n_chunks`` chunks of ``chunk_elems`` elements."""
+    n = int(load().afhip_delta_scratch_bytes(int(n_chunks), int(chunk_elems), int(elem_size)))
+    if n < 0:
+        raise ValueError(f"delta_scratch_bytes: {n_chunks} chunks of {chunk_elems} elements of {elem_size} bytes")
+    return n
+
+
+def delta_decode(stage, n_chunks: int, chunk_elems: int, elem_size: int, scratch):
+    """`afhip_delta_decode`: numcodecs Delta undone in place — an inclusive wrapping prefix sum over each of the ``n_chunks`` decoded
+    chunks (``chunk_elems`` integers of ``elem_size`` bytes) that lie back to back at the start of the HBM tensor ``stage``; ``scratch``: an
+    HBM tensor of `delta_scratch_bytes` bytes.  Both sizes are checked against the tensors here; the work goes to the current stream."""
+    if not (stage.is_contiguous() and scratch.is_contiguous()):
+        raise ValueError("delta_decode: stage and scratch must be contiguous")
+    if stage.numel() * stage.element_size() < int(n_chunks) * int(chunk_elems) * int(elem_size):
+        raise ValueError(f"delta_decode: {n_chunks} chunks of {chunk_elems} elements of {elem_size} bytes do not fit the stage")
+    _check(load().afhip_delta_decode(stage.data_ptr(), int(n_chunks), int(chunk_elems), int(elem_size), scratch.data_ptr(),
+                                     scratch.numel() * scratch.element_size(), _stream_ptr(stage)))
+
+
+def fso_decode(src, dst, n: int, src_type: str, scale: float, offset: float):
+    """`afhip_fso_decode`: numcodecs FixedScaleOffset undone, ``dst[i] = src[i] / scale + offset`` for the first ``n`` elements — ``src`` an
+    HBM tensor that holds stored elements of numpy type ``src_type`` (`FSO_TYPE`; torch's own dtype of it is not looked at: uint16
+    travels as int16), ``dst`` a float32 or float64 HBM tensor.  Integer sources are divided and added in float64, float sources in their own type, as
+    numpy does; the result is rounded once to ``dst``'s type.  The work goes to the current stream."""
+    torch = _torch()
+    if src_type not in FSO_TYPE:
+        raise ValueError(f"fso_decode: stored type {src_type!r} is not one of {sorted(FSO_TYPE)}")
+    if dst.dtype not in (torch.float32, torch.float64) or not (src.is_contiguous() and dst.is_contiguous()):
+        raise ValueError("fso_decode: dst must be float32 or float64, and both tensors contiguous")
+    if n < 0 or src.numel() * src.element_size() < n * np.dtype(src_type).itemsize or dst.numel() < n:
+        raise ValueError(f"fso_decode: {n} elements do not fit the tensors")
+    _check(load().afhip_fso_decode(src.data_ptr(), dst.data_ptr(), int(n), FSO_TYPE[src_type], FSO_TYPE[str(dst.dtype).replace("torch.", "")],
+                                   float(scale), float(offset), _stream_ptr(dst)))
 
 
 # one record of `afhip_grib_unpack` per time step (`afhip_grib_step`, include/aggfly_hip.h)

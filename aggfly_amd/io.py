@@ -12,7 +12,9 @@ and the native chunk codecs of `csrc/blosc1.c`:
   attributes, CF time decoding (``units`` + ``calendar``; non-standard calendars go to
   ``cfcalendar``), ``scale_factor`` / ``add_offset`` / ``_FillValue``; time-major stores and, with ``device=`` set, time-last ones —
   ``(latitude, longitude, time)``, the reference's converter's own order, written here by ``dataset_to_zarr(layout="time-last")`` —,
-  whose chunks one kernel transposes into the time-major cube (``hip.place_box_tlast``);
+  whose chunks one kernel transposes into the time-major cube (``hip.place_box_tlast``); format-2 ``filters``: the byte shuffle and
+  numcodecs' element filters (``fixedscaleoffset``, ``delta``, ``quantize``, ``bitround``, ``astype``), undone on the host by
+  ``unfilter_elements`` and, with ``device=`` set, in HBM on the stored elements (``hip.delta_decode``, ``hip.fso_decode``);
 * netCDF-4 / HDF5 files through the built-in reader ``hdf5.py`` (chunked + shuffle + deflate variables,
   dimension scales, either group style; no netCDF4 / h5py needed);
 * ``.npz`` bundles with ``data``, ``time``, ``latitude``, ``longitude``;
@@ -103,10 +105,114 @@ def is_zarr_array(path: str) -> bool:
     return False
 
 
+_ELEM_FILTER_IDS = ("fixedscaleoffset", "delta", "quantize", "bitround", "astype")
+
+
+def _parse_elem_filters(filters, array_dtype):
+    """The ``filters`` of a format-2 array -> (element filters, byte shuffles), both in write order.  An element filter is
+    ``{"id", "dtype", "astype"}`` (numpy dtypes: what the filter decodes to and what it stores) plus ``scale`` / ``offset`` for
+    ``fixedscaleoffset``; the configs are numcodecs' (FixedScaleOffset, Delta, Quantize, BitRound, AsType), restated from its documentation.  ``bitround`` decodes to its input: it is
+    checked and dropped.  Refused, by name: an unknown id, a chain whose types do not connect, a big-endian type inside a chain, an
+    element size other than 1, 2, 4 or 8 bytes, ``delta`` on floating-point data, and a byte shuffle that is not the last step before
+    the compressor."""
+    elem, shuffles = [], []
+    cur = np.dtype(array_dtype)
+    for k, flt in enumerate(filters):
+        fid = flt.get("id")
+        if fid == "shuffle":
+            shuffles.append(flt)
+            continue
+        if fid not in _ELEM_FILTER_IDS:
+            raise ValueError(f"Zarr filter {fid!r} is not supported (the byte shuffle and the element filters "
+                             f"{', '.join(_ELEM_FILTER_IDS)} are)")
+        if shuffles:
+            raise ValueError(f"Zarr filter {fid!r} follows a byte shuffle: element filters are read before the shuffle only")
+        if fid == "bitround":
+            if cur.kind != "f":
+                raise ValueError(f"Zarr filter 'bitround' on {cur.name} data: it rounds floating-point mantissas only")
+            continue
+        if fid == "astype":
+            dec, enc = flt.get("decode_dtype"), flt.get("encode_dtype")
+        else:
+            dec = flt.get("dtype")
+            enc = flt.get("astype") or dec
+        if dec is None or enc is None:
+            raise ValueError(f"Zarr filter {fid!r} does not name its types ({'decode_dtype / encode_dtype' if fid == 'astype' else 'dtype'})")
+        dec, enc = np.dtype(dec), np.dtype(enc)
+        for dt in (cur, dec, enc):
+            if not dt.isnative:
+                raise ValueError(f"Zarr filter {fid!r}: big-endian type {dt.str} inside a filter chain is not supported")
+            if dt.kind not in "iuf" or dt.itemsize not in (1, 2, 4, 8):
+                raise ValueError(f"Zarr filter {fid!r}: type {dt.str} is not supported (integers and floats of 1, 2, 4 or 8 bytes are)")
+        if dec != cur:
+            what = "the array's dtype" if not elem else f"astype of filter {k - 1} ({elem[-1]['id']!r})"
+            raise ValueError(f"Zarr filter {fid!r} (filter {k}) decodes to {dec.str}, but {what} is {cur.str}: the chain's types do not connect")
+        if fid == "delta" and (dec.kind == "f" or enc.kind == "f"):
+            # (refused since before the element filters were read: a float running sum is rounded at every step, so the values
+            # depend on the order of the additions, and one order is all a reader could offer)
+            raise ValueError(f"Zarr filter 'delta' on floating-point data ({dec.str}) is not supported: integer differences are read "
+                             "(a fixedscaleoffset in front of it makes them)")
+        e = {"id": fid, "dtype": dec, "astype": enc}
+        if fid == "fixedscaleoffset":
+            if flt.get("scale") is None or flt.get("offset") is None or float(flt["scale"]) == 0.0:
+                raise ValueError("Zarr filter 'fixedscaleoffset' needs an offset and a scale other than 0")
+            e["scale"], e["offset"] = float(flt["scale"]), float(flt["offset"])
+        elif fid == "quantize":
+            e["digits"] = int(flt.get("digits", 0))
+        elem.append(e)
+        cur = enc
+    return elem, shuffles
+
+
+def unfilter_elements(enc, elem_filters):
+    """The flattened C-order elements of one decoded chunk (the last filter's ``astype``) -> the array's values: every element
+    filter undone in reverse write order, by numcodecs' decode definitions.  ``fixedscaleoffset``: ``enc / scale + offset``, in
+    float64 for stored integers (numpy's true division of an integer array) and in the stored float type otherwise, rounded once
+    to ``dtype``; ``delta``: a running sum in ``dtype`` (integers wrap); ``quantize`` / ``astype``: a conversion."""
+    x = np.asarray(enc).reshape(-1)
+    for f in reversed(elem_filters):
+        if f["id"] == "fixedscaleoffset":
+            w = np.float64 if x.dtype.kind in "iu" else x.dtype.type
+            y = x.astype(w) / w(f["scale"])
+            y += w(f["offset"])
+            x = y.astype(f["dtype"], copy=False)
+        elif f["id"] == "delta":
+            x = np.cumsum(x, dtype=f["dtype"])
+        else:
+            x = x.astype(f["dtype"], copy=False)
+    return x
+
+
+def filter_elements(values, elem_filters):
+    """`unfilter_elements` the other way, by numcodecs' encode definitions: the flattened C-order values of one chunk -> what the
+    compressor is given.  ``fixedscaleoffset``: ``around((x - offset) * scale)``; ``delta``: differences with the first element kept;
+    ``quantize``: ``around(x, digits)`` scaled by the power of two that keeps ``digits`` decimal digits."""
+    x = np.asarray(values).reshape(-1)
+    for f in elem_filters:
+        if f["id"] == "fixedscaleoffset":
+            x = np.around((x - f["offset"]) * f["scale"]).astype(f["astype"])
+        elif f["id"] == "delta":
+            x = x.astype(f["dtype"], copy=False)             # differences in ``dtype`` (integers wrap), stored as ``astype``
+            d = np.empty(x.shape, dtype=f["astype"])
+            d[:1] = x[:1]
+            d[1:] = x[1:] - x[:-1]
+            x = d
+        elif f["id"] == "quantize":
+            exp = np.log10(10.0 ** -int(f["digits"]))
+            exp = int(np.floor(exp)) if exp < 0 else int(np.ceil(exp))
+            scale = 2.0 ** int(np.ceil(np.log2(10.0 ** -exp)))
+            x = (np.around(scale * x.astype(f["dtype"], copy=False)) / scale).astype(f["astype"])
+        else:
+            x = x.astype(f["astype"], copy=False)
+    return x
+
+
 class ZarrArray:
     """One array of a Zarr directory store, format 2 (``.zarray`` / ``.zattrs``, chunk files ``i.j.k``)
     or format 3 (``zarr.json``, chunk files ``c/i/j/k``, codec pipeline) — what zarr-python 2 and 3
-    write by default.  Both reduce to: a chunk file name, a chain of bytes -> bytes decoders, a dtype.
+    write by default.  Both reduce to: a chunk file name, a chain of bytes -> bytes decoders, a dtype — and, for format-2 arrays
+    written with numcodecs element filters, ``elem_filters`` (`_parse_elem_filters`) that turn the decoded elements of
+    ``stored_dtype`` into values of ``dtype``.
 
     Format 3 is implemented from the specification (bytes / gzip / zstd / blosc / crc32c codecs, default
     and v2 chunk-key encodings, ``dimension_names``, ``sharding_indexed`` shards); no zarr-python 3 is available
@@ -114,6 +220,7 @@ class ZarrArray:
 
     def __init__(self, path: str):
         self.path = path
+        self.elem_filters = []                                          # element filters, in write order (format 2 only)
         if os.path.exists(os.path.join(path, ".zarray")):
             self._init_v2()
         elif os.path.exists(os.path.join(path, "zarr.json")):
@@ -122,7 +229,9 @@ class ZarrArray:
             raise FileNotFoundError(f"{path} is not a Zarr array (no .zarray / zarr.json)")
         self.disk_dtype = self.dtype                                    # as stored (may be big-endian)
         self.dtype = self.dtype.newbyteorder("=") if not self.dtype.isnative else self.dtype
-        self.chunk_nbytes = int(np.prod(self.chunks)) * self.dtype.itemsize if self.shape else self.dtype.itemsize
+        # what a decoded chunk holds: the array's type, or what the element filters (`_parse_elem_filters`) left for the compressor
+        self.stored_dtype = self.elem_filters[-1]["astype"] if self.elem_filters else self.dtype
+        self.chunk_nbytes = int(np.prod(self.chunks)) * self.stored_dtype.itemsize if self.shape else self.stored_dtype.itemsize
 
     # ---- format 2 ----
     def _init_v2(self):
@@ -133,9 +242,6 @@ class ZarrArray:
         if self.meta.get("order", "C") != "C":
             raise ValueError("only C-order Zarr chunks are supported")
         self.filters = list(self.meta.get("filters") or [])
-        for flt in self.filters:
-            if flt.get("id") != "shuffle":
-                raise ValueError(f"Zarr filter {flt.get('id')!r} is not supported (only the byte shuffle is)")
         self.format = 2
         self.shard_shape = None
         self.shape = tuple(self.meta["shape"])
@@ -145,8 +251,10 @@ class ZarrArray:
         self.key_prefix = ""
         comp = self.meta.get("compressor")
         self.codecs = [] if comp is None else [dict(comp)]             # bytes -> bytes decoders, in decode order
-        # numcodecs filters run before the compressor on write, so they are undone after it on read
-        for flt in reversed(self.filters):
+        # numcodecs filters run before the compressor on write, so they are undone after it on read: the byte shuffle with the
+        # bytes -> bytes decoders, the element filters (in ``elem_filters``, write order) on the decoded elements after them
+        self.elem_filters, shuffles = _parse_elem_filters(self.filters, self.dtype)
+        for flt in reversed(shuffles):
             self.codecs.append({"id": "unshuffle", "elementsize": int(flt.get("elementsize", 4))})
         self.fill_value = self.meta.get("fill_value")
         self.attrs = {}
@@ -233,11 +341,17 @@ class ZarrArray:
         """'raw' / 'blosc' / 'zstd' / 'zlib' / 'gzip' when a chunk file is at most ONE codec the native
         batch decoder handles (the common case), else None."""
         if not self.disk_dtype.isnative or len(self.codecs) > 1:
-            return None
+            return None                                                 # (element filters do not count: they follow the decode)
         if not self.codecs:
             return "raw"
         cid = self.codecs[0].get("id")
         return cid if cid in ("blosc", "zstd", "zlib", "gzip", "lz4") else None
+
+    @property
+    def scatter_kind(self):
+        """`native_kind`, or None when the array has element filters that are not undone in HBM (`_hbm_filter_plan`): what decides
+        between the scatter routes of `array_to_device` and the host's `_chunk`."""
+        return self.native_kind if not self.elem_filters or _hbm_filter_plan(self) is not None else None
 
     @property
     def blosc_only(self) -> bool:
@@ -317,6 +431,9 @@ class ZarrArray:
         with open(loc[0], "rb") as f:
             f.seek(loc[1])
             raw = self.decode(f.read() if loc[2] < 0 else f.read(loc[2]))
+        if self.elem_filters:
+            enc = np.frombuffer(raw, dtype=self.stored_dtype, count=int(np.prod(self.chunks)) if self.shape else 1)
+            return unfilter_elements(enc, self.elem_filters).reshape(self.chunks)
         arr = np.frombuffer(raw, dtype=self.disk_dtype, count=int(np.prod(self.chunks)) if self.shape else 1).reshape(self.chunks)
         return arr if self.disk_dtype.isnative else arr.astype(self.dtype)
 
@@ -588,6 +705,34 @@ def _cf_in_hbm(np_dtype, attrs):
     return post, has_fv or packed, out_np, wire
 
 
+def _scatter_kind(za):
+    """`ZarrArray.scatter_kind`; sources without element filters (`hdf5.ChunkSource`): their ``native_kind``."""
+    return za.scatter_kind if hasattr(za, "scatter_kind") else za.native_kind
+
+
+def _hbm_filter_plan(za):
+    """How the element filters of ``za`` are undone in HBM: -> None (there are none, or they go through the host's `ZarrArray._chunk`),
+    or (n_delta, conv) — ``n_delta`` running sums over each staged chunk in the stored integer type (`hip.delta_decode`), then, after
+    the placement, ``conv``: None (the stored type is the array's), ("fso", scale, offset) or ("cast",), from the stored type to the array's float32 /
+    float64 (`hip.fso_decode`; a cast from stored floats is torch's).  The chains taken: in write order one converting filter at most,
+    first, then ``delta`` filters on its integers.  The host keeps ``delta`` with ``astype`` other than ``dtype``,
+    several conversions, conversions to integers and 64-bit or 16-bit-float stored types under a conversion."""
+    from . import hip
+    chain = list(getattr(za, "elem_filters", ()))
+    if not chain or za.native_kind is None:                      # (a byte shuffle in the chain, a compressor without a native kind)
+        return None
+    conv = None
+    if chain[0]["id"] != "delta":
+        f = chain.pop(0)
+        if f["dtype"].name not in ("float32", "float64") or f["astype"].name not in hip.FSO_TYPE:
+            return None
+        conv = ("fso", f["scale"], f["offset"]) if f["id"] == "fixedscaleoffset" else ("cast",)
+    for f in chain:
+        if f["id"] != "delta" or f["dtype"].kind not in "iu" or f["astype"] != f["dtype"]:
+            return None
+    return len(chain), conv
+
+
 def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 << 20, t_range=None, yx_box=None, keep_packed=False,
                     time_axis=0):
     """Stream a chunked (time, y, x) array — a `ZarrArray` or an `hdf5.ChunkSource` — straight into HBM: each
@@ -597,13 +742,17 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
     ``time_axis=2``: the array is (y, x, time) — what the reference's converter writes — and a codec the native decoder handles:
     the tensor comes back TIME-MAJOR, (time, y, x), through `_stream_chunks_scatter` (each chunk transposed into the cube in HBM);
     ``t_range`` counts steps of the last axis and ``yx_box`` cells of the first two.  A codec chain without a native kind ignores
-    ``time_axis``: the array streams as stored."""
+    ``time_axis``: the array streams as stored.  Element filters (`ZarrArray.elem_filters`): the chains `_hbm_filter_plan` takes always
+    go through `_stream_chunks_scatter`, which un-filters the stored elements in HBM; the others count as a codec chain without a
+    native kind (`ZarrArray.scatter_kind`) and are un-filtered by `ZarrArray._chunk`."""
     if len(za.shape) != 3:
         raise ValueError("zarr_to_device expects a (time, y, x) array")
     if os.environ.get("AGGFLY_HIP_SLAB_MB"):                       # tuning knob (scripts/e2e_bench.py sweeps it)
         slab_bytes = int(float(os.environ["AGGFLY_HIP_SLAB_MB"]) * (1 << 20))
     post, need_post, out_np, wire = _cf_in_hbm(za.dtype, za.attrs)
-    if time_axis == 2 and za.native_kind is not None:
+    kind = _scatter_kind(za)                                       # (None also for element filters that the host undoes)
+    filtered = bool(getattr(za, "elem_filters", ()))
+    if time_axis == 2 and kind is not None:
         if keep_packed and packing_of(za) is not None:
             need_post, out_np = False, wire
         return _stream_chunks_scatter(za, device, threads, slab_bytes, post if need_post else None, out_np, t_range, yx_box, time_axis=2), za
@@ -644,7 +793,7 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
                 out[t0 - k0:t1 - k0] = tmp[:t1 - t0]
 
     def read(k0, k1, out):
-        if whole_rows and za.native_kind is not None and out.flags.c_contiguous:
+        if whole_rows and kind is not None and not filtered and out.flags.c_contiguous:
             return read_blosc_slab(k0, k1, out)
         jobs = [(it, iy, ix) for it in range(k0 // tc, (k1 + tc - 1) // tc) for (iy, ix) in grid_yx]
 
@@ -670,12 +819,12 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
         yx_box = None
     try:
         if t_range is not None or yx_box is not None:
-            if za.native_kind is None:
+            if kind is None:
                 raise ValueError("a time / space window on a codec chain goes through the host route")
             return _stream_chunks_scatter(za, device, threads, slab_bytes, post if need_post else None, out_np, t_range, yx_box), za
-        if not whole_rows and za.native_kind is not None:
+        if (not whole_rows or filtered) and kind is not None:     # (element filters are undone on the scatter route only)
             return _stream_chunks_scatter(za, device, threads, slab_bytes, post if need_post else None, out_np), za
-        if (za.native_kind in ("blosc", "zstd") or _deflate_typesize(za.native_kind)) and _gpu_decodable(za, T * ny * nx * za.dtype.itemsize):
+        if (kind in ("blosc", "zstd") or _deflate_typesize(kind)) and _gpu_decodable(za, T * ny * nx * za.dtype.itemsize):
             # Blosc-LZ4 / Zstandard / deflate chunks cross PCIe compressed and are decoded in HBM: the scatter route, whatever the chunk grid
             return _stream_chunks_scatter(za, device, threads, slab_bytes, post if need_post else None, out_np), za
         return stream_to_device(T, (ny, nx), za.dtype, read, slab, device, post if need_post else None, out_np, wire), za
@@ -835,10 +984,24 @@ class _ScatterJob:
         self.wire = wire = _wire_dtype(za.dtype, za.attrs)[0]              # the stored bits as torch holds them (uint16: int16)
         self.tdt = _torch_dtype(wire)
         self.same_dtype = (out_dtype is None or np.dtype(out_dtype) == wire) and za.dtype.itemsize in (2, 4, 8)
+        # element filters (`_hbm_filter_plan`): running sums over the staged chunks, then — with a conversion — the placement goes to a
+        # buffer of the STORED type beside the cube, which `finish` converts into the cube
+        filtered = bool(getattr(za, "elem_filters", ()))
+        fplan = _hbm_filter_plan(za)
+        if filtered and fplan is None:
+            raise ValueError("these element filters are undone on the host")
+        self.n_delta, self.conv = fplan if fplan else (0, None)
+        self.sdt = sdt = np.dtype(getattr(za, "stored_dtype", za.dtype))
+        if self.conv is not None:                                          # (an integer of the stored size stands for unsigned types)
+            self.tdt = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[sdt.itemsize] if sdt.kind in "iu" else _torch_dtype(sdt)
+            self.same_dtype = sdt.itemsize in (2, 4, 8)
         self.ka, self.kb = (0, T) if t_range is None else (max(0, int(t_range[0])), min(T, int(t_range[1])))   # time window [ka, kb)
         self.ya, self.yb, self.xa, self.xb = (0, ny, 0, nx) if yx_box is None else yx_box                    # spatial box
         self.cube = torch.empty((self.kb - self.ka, self.yb - self.ya, self.xb - self.xa),
                                 dtype=_torch_dtype(out_dtype) if out_dtype is not None else self.tdt, device=device)
+        self.dest = self.cube if self.conv is None else torch.empty(tuple(self.cube.shape), dtype=self.tdt, device=device)
+        self.absent = []                                                   # boxes of absent chunks, filled after the conversion
+        self._delta_scratch = {}                                           # stream -> tile-sum scratch of `undelta`
         self.cb = za.chunk_nbytes
         tc, yc, xc = self.tc, self.yc, self.xc
         its, iys, ixs = range(self.ka // tc, -(-self.kb // tc)), range(self.ya // yc, -(-self.yb // yc)), range(self.xa // xc, -(-self.xb // xc))
@@ -848,8 +1011,8 @@ class _ScatterJob:
             self.idxs = [(it, iy, ix) for it in its for iy in iys for ix in ixs]
         # a chunk of whole time steps of the window (full grid, same dtype) is one contiguous run of the cube — never a time-last one
         self.whole_steps = (time_axis == 0 and self.same_dtype and (self.ya, self.xa) == (0, 0)
-                            and (yc, xc) == (self.yb, self.xb) == (ny, nx))
-        self.step_bytes = ny * nx * za.dtype.itemsize
+                            and (yc, xc) == (self.yb, self.xb) == (ny, nx) and not filtered)
+        self.step_bytes = ny * nx * sdt.itemsize
 
     def absent_value(self) -> float:
         """The array's fill value as the cube holds it: an unsigned one in a cube of the signed bits (a uint16 cube kept packed) is
@@ -859,6 +1022,39 @@ class _ScatterJob:
             return float(np.array(fill).astype(self.za.dtype).view(self.wire))
         return float(fill)
 
+    def undelta(self, staged, n_chunks: int):
+        """Queue (on the current stream) numcodecs Delta's decode over the ``n_chunks`` decoded chunks at the start of ``staged``: one
+        running sum per ``delta`` filter over each flattened chunk, in place, before `place` — the sum runs over the chunk, not the cube."""
+        if not self.n_delta or not n_chunks:
+            return
+        import torch
+        from . import hip
+        es = self.sdt.itemsize
+        # one scratch per stream for the whole job (batches on one stream run in order; two streams never share one), grown if a
+        # later batch holds more chunks
+        key, need = torch.cuda.current_stream(self.device).cuda_stream, hip.delta_scratch_bytes(n_chunks, self.cb // es, es)
+        scratch = self._delta_scratch.get(key)
+        if scratch is None or scratch.numel() < need:
+            scratch = self._delta_scratch[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        for _ in range(self.n_delta):
+            hip.delta_decode(staged, n_chunks, self.cb // es, es, scratch)
+
+    def finish(self):
+        """Queue (on the current stream, after every `place`) what turns the stored elements into the array's values: the conversion
+        from the stored-type buffer into the cube, then the fill value — in the decoded type — over the boxes of absent chunks."""
+        if self.conv is None:
+            return
+        from . import hip
+        if self.conv[0] == "fso":
+            hip.fso_decode(self.dest, self.cube, self.cube.numel(), self.sdt.name, self.conv[1], self.conv[2])
+        elif self.sdt.kind in "iu":                  # Quantize / AsType from integers: x / 1.0 + 0.0 in float64 is the cast
+            hip.fso_decode(self.dest, self.cube, self.cube.numel(), self.sdt.name, 1.0, 0.0)
+        else:                                        # from floats: the cast itself (it keeps -0.0, which x + 0.0 does not)
+            self.cube.copy_(self.dest)
+        for box in self.absent:
+            self.cube[box].fill_(float(self.za._fill()))
+        self.dest = None
+
     def inside(self, it) -> bool:
         """All time steps of chunk row ``it`` lie in the window."""
         return self.ka <= it * self.tc and (it + 1) * self.tc <= self.kb
@@ -867,7 +1063,7 @@ class _ScatterJob:
         """Queue (on the current stream) the placement of a batch: decoded chunk i sits at ``staged[i * cb:]``; absent
         chunks (``res[i] == -100``) become the fill value.  ``skip_present``: the present chunks are in place already."""
         from . import hip
-        tc, yc, xc, ka, kb, ya, yb, xa, xb, cb, cube = self.tc, self.yc, self.xc, self.ka, self.kb, self.ya, self.yb, self.xa, self.xb, self.cb, self.cube
+        tc, yc, xc, ka, kb, ya, yb, xa, xb, cb, cube = self.tc, self.yc, self.xc, self.ka, self.kb, self.ya, self.yb, self.xa, self.xb, self.cb, self.dest
         tlast = self.time_axis == 2
         for i, (idx, r) in enumerate(zip(batch, res)):
             if skip_present and r != -100:
@@ -878,8 +1074,11 @@ class _ScatterJob:
             y0, y1 = max(iy * yc, ya), min((iy + 1) * yc, yb)
             x0, x1 = max(ix * xc, xa), min((ix + 1) * xc, xb)
             dst = cube[t0 - ka:t1 - ka, y0 - ya:y1 - ya, x0 - xa:x1 - xa]
-            if r == -100:                           # absent chunk = fill value
-                dst.fill_(self.absent_value())
+            if r == -100:                           # absent chunk = fill value (with a conversion: after it, in `finish`)
+                if self.conv is not None:
+                    self.absent.append((slice(t0 - ka, t1 - ka), slice(y0 - ya, y1 - ya), slice(x0 - xa, x1 - xa)))
+                else:
+                    dst.fill_(self.absent_value())
                 continue
             if tlast:                               # a chunk [yc][xc][tc]: transposed into the cube by one kernel
                 blk = staged[i * cb:(i + 1) * cb].view(self.tdt).view(yc, xc, tc)
@@ -987,11 +1186,13 @@ def _scatter_host_decode(job: _ScatterJob, threads: int, slab_bytes: int, post):
         trace.lap("read")
         with torch.cuda.stream(copy_stream):
             dev[k][:len(batch) * cb].copy_(host[k][:len(batch) * cb], non_blocking=True)
+            job.undelta(dev[k], len(batch))
             job.place(batch, res, dev[k])
             done[k] = torch.cuda.Event()
             done[k].record(copy_stream)
         trace.lap("enqueue")
     with torch.cuda.stream(copy_stream):
+        job.finish()
         if post is not None:
             post(job.cube)
     trace.skip()
@@ -1352,6 +1553,7 @@ def _scatter_gpu_decode(job: _ScatterJob, threads: int, post):
             trace.lap("read")
             with torch.cuda.stream(copy_stream):        # behind the compressed uploads; the placement runs on the copy stream too
                 tdev.copy_(thost[:n_tail * cb], non_blocking=True)
+                job.undelta(tdev, n_tail)
                 job.place(tail, res, tdev)
             trace.lap("enqueue")
     except BaseException:
@@ -1363,6 +1565,7 @@ def _scatter_gpu_decode(job: _ScatterJob, threads: int, post):
     if n_tail:
         last.wait_stream(copy_stream)                    # (the tail's placement ran there)
     with torch.cuda.stream(last):
+        job.finish()
         if post is not None:
             post(cube)
     trace.skip()
@@ -1427,6 +1630,8 @@ def _gpu_decode_batches(job, threads, cuts, per, cmax, route, nstage, host, comp
                 staged[k] = torch.empty(per * cb, dtype=torch.uint8, device=device)
             target = cube_bytes if direct else staged[k]
             route.decode(k, comp_dev[k], target, errors)
+            if not direct:
+                job.undelta(staged[k], len(batch))
             job.place(batch, res, staged[k], skip_present=direct)
             done[k] = torch.cuda.Event()
             done[k].record(work_streams[k])
@@ -1532,16 +1737,27 @@ class _DeviceCube:
         self.nbytes = int(tensor.numel()) * int(tensor.element_size())
 
 
-def _write_array(path, name, data, dims, chunks, attrs, compressor, zarr_format: int = 2, shards=None):
+def _write_array(path, name, data, dims, chunks, attrs, compressor, zarr_format: int = 2, shards=None, filters=None):
+    """``filters`` (format 2, host arrays): numcodecs element-filter configs in write order; every chunk goes through
+    `filter_elements` before the compressor and the configs are written into ``.zarray`` as given."""
     d = os.path.join(path, name)
     os.makedirs(d, exist_ok=True)
     if not isinstance(data, _DeviceCube):
         data = np.ascontiguousarray(data)
     chunks = tuple(int(min(c, s)) if s else 1 for c, s in zip(chunks, data.shape))
     cid = compressor["id"] if compressor else None
+    elem = []
+    if filters:
+        if zarr_format != 2 or isinstance(data, _DeviceCube):
+            raise ValueError("filters are written into format-2 stores, from a host array")
+        elem, shuffles = _parse_elem_filters(filters, data.dtype)
+        if shuffles:
+            raise ValueError("filters: the byte shuffle is the compressor's (compress='blosc'); element filters only")
+    stored_itemsize = elem[-1]["astype"].itemsize if elem else data.dtype.itemsize
     if zarr_format == 2:
         meta = {"zarr_format": 2, "shape": list(data.shape), "chunks": list(chunks), "dtype": data.dtype.str,
-                "compressor": compressor, "fill_value": "NaN" if data.dtype.kind == "f" else 0, "order": "C", "filters": None}
+                "compressor": compressor, "fill_value": "NaN" if data.dtype.kind == "f" else 0, "order": "C",
+                "filters": [dict(f) for f in filters] if filters else None}
         with open(os.path.join(d, ".zarray"), "w") as f:
             json.dump(meta, f)
         with open(os.path.join(d, ".zattrs"), "w") as f:
@@ -1589,6 +1805,9 @@ def _write_array(path, name, data, dims, chunks, attrs, compressor, zarr_format:
         else:                                               # edge chunk: padded with the fill value
             blk = np.full(chunks, np.nan if data.dtype.kind == "f" else 0, dtype=data.dtype)
             blk[tuple(slice(0, n) for n in part.shape)] = part
+        if elem:                                            # (the padding of an edge chunk is NaN: its stored integer is arbitrary)
+            with np.errstate(invalid="ignore"):
+                blk = filter_elements(blk, elem)
         raw = blk.tobytes() if cid in (None, "zlib", "gzip") else None
         if cid == "zlib":
             raw = zlib.compress(raw, compressor.get("level", 1))
@@ -1596,7 +1815,7 @@ def _write_array(path, name, data, dims, chunks, attrs, compressor, zarr_format:
             raw = gzip.compress(raw, compressor.get("level", 1))
         elif cid == "blosc":
             from . import codec
-            raw = codec.blosc_encode(blk, data.dtype.itemsize, shuffle=compressor.get("shuffle", 1) == 1,
+            raw = codec.blosc_encode(blk, stored_itemsize, shuffle=compressor.get("shuffle", 1) == 1,
                                      blocksize=compressor.get("blocksize", 0), cname=compressor.get("cname", "lz4"),
                                      bitshuffle=compressor.get("shuffle", 1) == 2)
         elif cid == "zstd":
@@ -1861,7 +2080,7 @@ def _auto_chunks(sizes: dict, itemsize: int, target_mb: float = 256) -> dict:
 
 
 def dataset_to_zarr(dataset: Dataset, path: str, var: str = "var", chunks=None, compress=True, mode: str = "w", zarr_format: int = 2,
-                    shards=None, encode: str = "auto", layout: str = "time-major"):
+                    shards=None, encode: str = "auto", layout: str = "time-major", filters=None):
     """`dataset_to_zarr` (`zarr_convert.py:50-121`): write a time-major, time-contiguous store.
     ``layout``: "time-major" — the data variable is (time, latitude, longitude) — or "time-last" — (latitude, longitude, time), the
     reference's converter's own layout (it writes `Dataset.da` as it stands, `zarr_convert.py:83-113`): the same ``chunks`` /
@@ -1879,9 +2098,19 @@ def dataset_to_zarr(dataset: Dataset, path: str, var: str = "var", chunks=None, 
     raises `ValueError`.  The store decodes to the same values; its streams are the GPU encoders', not liblz4's or libzstd's.
     "auto": the GPU route for a device-resident cube of `GPU_ENCODE_AUTO_BYTES` (``compress="blosc-zstd"``: `GPU_ENCODE_AUTO_BYTES_BLOSC_ZSTD`) or more (None: never) or when
     ``AGGFLY_HIP_GPU_ENCODE=1`` is set (``0``: never), and the call is
-    eligible; else the host route — always for a host-resident cube.  Coordinates and metadata are written by the same code on every route."""
+    eligible; else the host route — always for a host-resident cube.  Coordinates and metadata are written by the same code on every route.
+    ``filters`` (format 2 only): numcodecs element filters for the data variable, a list of their configs in write order — e.g.
+    ``[{"id": "fixedscaleoffset", "scale": 10.0, "offset": 273.15, "dtype": "<f4", "astype": "<i2"}, {"id": "delta", "dtype": "<i2"}]``
+    — applied by numcodecs' encode definitions (`filter_elements`) on the host and written into ``.zarray``; ``encode="gpu"`` raises
+    `ValueError`, "auto" takes the host route.  Such a store is read back through `ZarrArray`'s element filters."""
     if encode not in ("auto", "host", "gpu"):
         raise ValueError(f"encode must be 'auto', 'host' or 'gpu', got {encode!r}")
+    if filters:
+        if zarr_format != 2:
+            raise ValueError("dataset_to_zarr(filters=...): element filters are a format-2 feature (zarr_format=3 has no such codecs)")
+        if encode == "gpu":
+            raise ValueError("dataset_to_zarr(encode='gpu'): filters are applied on the host (the GPU encoder takes the cube's own elements)")
+        encode = "host"
     if layout not in ("time-major", "time-last"):
         raise ValueError(f"layout must be 'time-major' or 'time-last', got {layout!r}")
     tlast = layout == "time-last"
@@ -1943,9 +2172,9 @@ def dataset_to_zarr(dataset: Dataset, path: str, var: str = "var", chunks=None, 
     if tlast:                                               # (latitude, longitude, time): chunks and shards reordered alike
         last = lambda t: (t[1], t[2], t[0])
         _write_array(path, var, np.ascontiguousarray(cube.transpose(1, 2, 0)), ("latitude", "longitude", "time"), last(ctuple), {}, comp,
-                     zarr_format, None if stuple is None else last(stuple))
+                     zarr_format, None if stuple is None else last(stuple), filters=filters or None)
     else:
-        _write_array(path, var, cube, ("time", "latitude", "longitude"), ctuple, {}, comp, zarr_format, stuple)
+        _write_array(path, var, cube, ("time", "latitude", "longitude"), ctuple, {}, comp, zarr_format, stuple, filters=filters or None)
     tv, tattrs = _encode_time(dataset.time)
     _write_array(path, "time", np.asarray(tv, dtype=np.float64), ("time",), (len(tv),), tattrs, None, zarr_format)
     _write_array(path, "latitude", dataset.latitude, ("latitude",), (len(dataset.latitude),), {}, None, zarr_format)
@@ -2487,7 +2716,7 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
             # below, `dims` / `shape` are those of the tensor in HBM, and every window is cut on them
             dims, shape = za.dims, za.shape
             tlast = (len(dims) == 3 and dims[2] == timecoord and set(dims[:2]) == set(xycoords) and len(set(xycoords)) == 2
-                     and za.native_kind is not None)
+                     and za.scatter_kind is not None)
             if tlast:
                 dims, shape = (dims[2], dims[0], dims[1]), (shape[2], shape[0], shape[1])
             # a time selection on a time-leading (or time-last) store: only the chunks that hold the selected steps are

@@ -208,6 +208,33 @@ int afhip_place_box_tlast(const void* chunk_dev, void* cube_dev, int elem_size,
                           int64_t ny, int64_t nx, int64_t nt,
                           int64_t NY, int64_t NX, int64_t t0, int64_t y0, int64_t x0, void* stream);
 
+/* numcodecs element filters of Zarr format-2 arrays undone in HBM (aggfly_amd/io.py `_ScatterJob`; kernels in afhip_filter_kernels.h).
+ *
+ * afhip_delta_decode: Delta's decode — an in-place inclusive WRAPPING prefix sum over each of n_chunks decoded chunks that lie back
+ * to back in stage_dev, chunk_elems integer elements of elem_size 1, 2, 4 or 8 bytes each (stage_dev element-aligned; 16-byte
+ * accesses when it is 16-byte aligned and chunk_elems * elem_size a multiple of 16).  Three launches on `stream` — per-tile sums,
+ * a scan of each chunk's tile sums, a per-tile scan seeded with the tile's prefix (tiles of 16 KiB; one launch when a chunk is one
+ * tile) —, none of which waits for another workgroup.  scratch_dev: caller-owned, 8-byte aligned, at least
+ * afhip_delta_scratch_bytes(n_chunks, chunk_elems, elem_size) bytes (-1 for what the call below refuses); it holds one element per
+ * tile and is not read after the call's work is done.  Reads and writes [stage_dev, stage_dev + n_chunks * chunk_elems * elem_size)
+ * and that part of the scratch, nothing else.  AFHIP_E_INVALID, with nothing launched: n_chunks < 0, chunk_elems <= 0, a product that overflows int64, another
+ * elem_size, more than 2^31 - 1 tiles (or chunks) in one call, a misaligned or null buffer, a scratch that is too small.  n_chunks
+ * == 0 returns AFHIP_OK without a launch.
+ *
+ * afhip_fso_decode: FixedScaleOffset's decode, dst[i] = src[i] / scale + offset for i in [0, n), src_type one of AFHIP_T_I8 ...
+ * AFHIP_T_F64, dst_type AFHIP_T_F32 or AFHIP_T_F64.  Integer sources: the division and the sum in float64 (IEEE division, no
+ * contraction), rounded once to dst_type.  AFHIP_T_F32 sources: both in float32, scale and offset rounded to float32 first, then
+ * converted; AFHIP_T_F64 sources: in float64.  (What numpy gives for `enc / scale + offset` followed by `astype`.)  With scale 1 and
+ * offset 0 an integer source is converted exactly as a cast would.  src_dev and dst_dev are distinct, element-aligned device buffers
+ * of n elements (16-byte accesses where both are aligned for them); AFHIP_E_INVALID, with nothing launched: another type code, n < 0
+ * or beyond one launch (2^31 - 1 workgroups of 256), a scale of 0 or NaN, null, misaligned or overlapping buffers.  Nothing is retained. */
+enum { AFHIP_T_I8 = 0, AFHIP_T_U8 = 1, AFHIP_T_I16 = 2, AFHIP_T_U16 = 3, AFHIP_T_I32 = 4, AFHIP_T_U32 = 5, AFHIP_T_F32 = 6, AFHIP_T_F64 = 7 };
+int64_t afhip_delta_scratch_bytes(int64_t n_chunks, int64_t chunk_elems, int elem_size);
+int afhip_delta_decode(void* stage_dev, int64_t n_chunks, int64_t chunk_elems, int elem_size,
+                       void* scratch_dev, int64_t scratch_bytes, void* stream);
+int afhip_fso_decode(const void* src_dev, void* dst_dev, int64_t n, int src_type, int dst_type,
+                     double scale, double offset, void* stream);
+
 /* GRIB fields (editions 1 and 2, simple packing) unpacked in HBM: aggfly_amd/io.py `_grib_part_to_device`, aggfly_amd/grib.py.
  * stage_dev (4-byte aligned, stage_bytes a multiple of 4) holds, as they lie in the file, the packed bits (and the bitmaps) of n_steps fields of one NY x NX grid; steps_dev one
  * record per field: data_off / data_bytes — its staged packed bits; first_point / first_bit — the value index (= grid point; only
