@@ -1,8 +1,8 @@
-"""Index and host decode of GRIB files (editions 1 and 2, regular latitude / longitude grids, simple packing), written from the
-format's octet tables (WMO Manual on Codes, FM 92 GRIB; edition 1 as in the ECMWF / NCEP descriptions of its sections).  `GribFile`
+"""Index and host decode of GRIB files (editions 1 and 2, regular latitude / longitude grids; simple packing, and in edition 2 complex
+packing with and without spatial differencing, data representation templates 5.2 and 5.3), written from the format's octet tables (WMO Manual on Codes, FM 92 GRIB; edition 1 as in the ECMWF / NCEP descriptions of its sections).  `GribFile`
 walks the file message by message and reads the section HEADERS only: it tells where the packed bits and the bitmap of every field
-lie and how they unpack; `io._grib_part_to_device` `pread`s those bytes into page-locked memory and a kernel (`hip.grib_unpack`)
-extracts, scales and places them in the cube in HBM.  `GribFile.read` is the same decode in numpy: the ``device=None`` route.
+lie and how they unpack; `io._grib_part_to_device` `pread`s those bytes into page-locked memory and kernels (`hip.grib_unpack`,
+`hip.grib_unpack_complex`) extract, scale and place them in the cube in HBM.  `GribFile.read` is the same decode in numpy: the ``device=None`` route.
 
     edition 1   0 indicator (8)  1 product definition  2 grid description  [3 bitmap]  4 binary data  5 '7777'
     edition 2   0 indicator (16) 1 identification [2 local use] 3 grid definition 4 product definition
@@ -13,12 +13,26 @@ Simple packing: a field is a big-endian bit stream of ``nbits``-bit unsigned int
 ``d = 10.0 ** -D`` and rounded to float32.  A bitmap, one bit per grid point in scan order, marks the points that have a value; the
 others are NaN.
 
-Everything else is refused with a ValueError that names it: other grids (Gaussian, reduced, rotated), other packings (second-order /
-complex, JPEG 2000, PNG, CCSDS, spherical harmonics), -i / column-major / alternating-row scanning, predefined bitmaps, several fields
+Complex packing (5.2 / 5.3; what NCEP writes, and `wgrib2 -set_grib_type c3`): the N values are cut into NG groups, and section 7 is one
+bit stream, most significant bit first: [5.3: ``order`` first values ival1 [, ival2] and the smallest difference minsd, ``extra`` octets
+each, sign-magnitude;] NG group references of ``nbits_ref`` bits; NG widths of ``nbits_width`` bits (``width = ref_width + stored``); NG
+scaled lengths of ``nbits_len`` bits (``len = ref_len + len_inc * stored``, the last group's length is ``last_len`` whatever was stored)
+- each table padded with zero bits to an octet boundary, a table of 0 bits absent and all 0 -; then group after group ``len[g]``
+fields of ``width[g]`` bits, ``raw[n] = ref[g] + field``.  5.2: ``X = raw``.  Order 1: ``X[0] = ival1``, ``X[n] = X[n-1] + raw[n] +
+minsd``.  Order 2: ``X[0] = ival1``, ``X[1] = ival2``, ``X[n] = raw[n] + minsd + 2 X[n-1] - X[n-2]`` (``raw[0]``, ``raw[1]`` are
+placeholders).  As plain running sums: ``g[0] = 0``, ``g[1] = ival2 - ival1`` (order 2) and ``g[n] = raw[n] + minsd`` otherwise; ``X =
+ival1 + cumsum(g)`` for order 1, ``ival1 + cumsum(cumsum(g))`` for order 2 - in int64, wrapping, here and in the kernels.  The value is
+the same ``((X * s) + R) * d`` with X a signed int64, exact while ``|X| < 2**53``.  With NG = 0 every X is 0.
+
+Everything else is refused with a ValueError that names it: other grids (Gaussian, reduced, rotated), other packings (edition 1's
+second-order packing, complex packing with missing value management 1 / 2, a spatial differencing order outside 1..2, extra
+descriptors of more than 4 octets, group widths above 32 bits, group lengths that do not sum to N, a section 7 too short for what
+section 5 announces, JPEG 2000, PNG, CCSDS, spherical harmonics, IEEE floating point), -i / column-major / alternating-row scanning, predefined bitmaps, several fields
 in one edition-2 message, ECMWF's large-message extension of edition 1.
 
-No file written by ecCodes was at hand when this was written: the reader is held to hand-assembled messages and to the independent
-writer of ``tests/grib_cases.py``, not to real archive files.
+No file written by ecCodes, g2clib or wgrib2 was at hand when this was written: the reader is held to hand-assembled messages and to
+the independent writers of ``tests/grib_cases.py`` and ``tests/grib_complex_cases.py``, not to real archive files.  Parity with the
+output of those libraries is unverified.
 """
 from __future__ import annotations
 
@@ -39,7 +53,7 @@ ED2_NAMES = {"t2m": (0, 0, 0, 103, 2), "d2m": (0, 0, 6, 103, 2), "u10": (0, 2, 2
 _ED1_NAMES = {v: k for k, v in ED1_TABLE128.items()}
 _UNIT_SECONDS = {0: 60, 1: 3600, 2: 86400, 10: 10800, 11: 21600, 12: 43200}       # + second: 254 in edition 1, 13 in edition 2
 _SCAN_REFUSED = ((0x80, "-i (east to west)"), (0x20, "j-consecutive (column-major)"), (0x10, "alternating-row"))
-_DRT_NAMES = {2: "complex packing", 3: "complex packing with spatial differencing", 40: "JPEG 2000", 41: "PNG", 42: "CCSDS",
+_DRT_NAMES = {0: "simple packing", 2: "complex packing", 3: "complex packing with spatial differencing", 40: "JPEG 2000", 41: "PNG", 42: "CCSDS",
               50: "spherical harmonics", 51: "spherical harmonics, complex packing", 4: "IEEE floating point"}
 
 
@@ -82,7 +96,10 @@ def _refuse_scan(scan: int):
 class Message:
     """One field: what its headers say and where its packed bits (and its bitmap) lie in the file.  No data."""
     __slots__ = ("offset", "length", "edition", "param", "level_type", "level", "valid_time", "Ni", "Nj", "La1", "La2", "Lo1", "Lo2",
-                 "scan", "nbits", "E", "D", "R", "data_offset", "data_length", "bitmap_offset", "bitmap_length", "n_values")
+                 "scan", "nbits", "E", "D", "R", "data_offset", "data_length", "bitmap_offset", "bitmap_length", "n_values",
+                 # complex packing (edition 2, templates 5.2 / 5.3): ``packing`` 0 / 2 / 3; ``nbits`` is then the bits of a group reference
+                 "packing", "n_groups", "ref_width", "nbits_width", "ref_len", "len_inc", "last_len", "nbits_len", "order", "extra")
+    COMPLEX_FIELDS = ("n_groups", "ref_width", "nbits_width", "ref_len", "len_inc", "last_len", "nbits_len", "order", "extra")
 
     @property
     def grid(self):
@@ -139,10 +156,13 @@ class Field:
 
     def arrays(self) -> dict:
         """The messages' numbers as arrays, one element per step (built once): ``nbits``, ``R``, ``s``, ``d``, ``data_offset``,
-        ``data_length``, ``bitmap_offset`` (-1: none) — what the device route lays its staging plan out from."""
+        ``data_length``, ``bitmap_offset`` (-1: none), ``packing`` (0 / 2 / 3), ``n_values`` and the group parameters of complex
+        packing (`Message.COMPLEX_FIELDS`; 0 for a simple-packed step) — what the device route lays its staging plan out from."""
         if self._arrays is None:
             ms = self.messages
             self._arrays = {
+                "packing": np.array([m.packing for m in ms], dtype=np.int64), "n_values": np.array([m.n_values for m in ms], dtype=np.int64),
+                **{k: np.array([getattr(m, k) for m in ms], dtype=np.int64) for k in Message.COMPLEX_FIELDS},
                 "nbits": np.array([m.nbits for m in ms], dtype=np.int64), "R": np.array([m.R for m in ms], dtype=np.float64),
                 "s": np.array([m.s for m in ms], dtype=np.float64), "d": np.array([m.d for m in ms], dtype=np.float64),
                 "data_offset": np.array([m.data_offset for m in ms], dtype=np.int64), "data_length": np.array([m.data_length for m in ms], dtype=np.int64),
@@ -234,6 +254,9 @@ class GribFile:
     def _edition1(fd, off, total, head) -> Message:
         m = Message()
         m.offset, m.length, m.edition = off, total, 1
+        m.packing = 0
+        for k in Message.COMPLEX_FIELDS:
+            setattr(m, k, 0)
         end = off + total - 4
         # the indicator, the PDS and the GDS in one read (8 + 28 + 32 bytes as a rule), then one read per later section header
         buf = os.pread(fd, 128, off)
@@ -310,6 +333,9 @@ class GribFile:
     def _edition2(fd, off, total, head) -> Message:
         m = Message()
         m.offset, m.length, m.edition = off, total, 2
+        m.packing = 0
+        for k in Message.COMPLEX_FIELDS:
+            setattr(m, k, 0)
         discipline = head[6]
         end = off + total - 4
         pos = off + 16
@@ -370,10 +396,13 @@ class GribFile:
                     m.valid_time = _dt.datetime(int.from_bytes(sec[34:36], "big"), sec[36], sec[37], sec[38], sec[39], sec[40])
             elif num == 5:
                 tmpl = int.from_bytes(sec[9:11], "big")
-                if tmpl != 0:
-                    raise ValueError(f"data representation template 5.{tmpl} ({_DRT_NAMES.get(tmpl, 'unknown')}) is not read: only 5.0, simple packing")
-                if n < 20:
-                    raise ValueError(f"data representation section of {n} bytes")
+                if tmpl not in (0, 2, 3):
+                    raise ValueError(f"data representation template 5.{tmpl} ({_DRT_NAMES.get(tmpl, 'unknown')}) is not read: only 5.0, "
+                                     "simple packing, and 5.2 / 5.3, complex packing")
+                if n < (20, 0, 47, 49)[tmpl]:
+                    raise ValueError(f"data representation section of {n} bytes" + (f" for template 5.{tmpl} ({_DRT_NAMES[tmpl]}), which takes "
+                                                                                    f"{(0, 0, 47, 49)[tmpl]}" if tmpl else ""))
+                m.packing = tmpl
                 m.n_values = int.from_bytes(sec[5:9], "big")
                 m.R = struct.unpack(">f", sec[11:15])[0]
                 m.E = sign_magnitude(int.from_bytes(sec[15:17], "big"), 16)
@@ -381,6 +410,20 @@ class GribFile:
                 m.nbits = sec[19]
                 if m.nbits > 32:
                     raise ValueError(f"{m.nbits} bits per value (at most 32)")
+                if tmpl:                                                # complex packing: octets 21 - 47 (5.2), - 49 (5.3)
+                    if sec[22] != 0:
+                        raise ValueError(f"template 5.{tmpl}: missing value management {sec[22]} (primary / secondary missing values "
+                                         "inside the groups) is not read, only 0")
+                    m.n_groups, m.ref_width, m.nbits_width = int.from_bytes(sec[31:35], "big"), sec[35], sec[36]
+                    m.ref_len, m.len_inc, m.last_len, m.nbits_len = int.from_bytes(sec[37:41], "big"), sec[41], int.from_bytes(sec[42:46], "big"), sec[46]
+                    if m.nbits_width > 32 or m.nbits_len > 32:
+                        raise ValueError(f"template 5.{tmpl}: group widths of {m.nbits_width} bits and lengths of {m.nbits_len} bits (at most 32)")
+                    if tmpl == 3:
+                        m.order, m.extra = sec[47], sec[48]
+                        if m.order not in (1, 2):
+                            raise ValueError(f"template 5.3: spatial differencing of order {m.order} is not read (1 and 2 are)")
+                        if m.extra > 4:
+                            raise ValueError(f"template 5.3: extra descriptors of {m.extra} octets are not read (at most 4)")
             elif num == 6:
                 ind = sec[5]
                 if ind == 0:
@@ -399,6 +442,8 @@ class GribFile:
             m.valid_time = ref + _dt.timedelta(seconds=step_s)
         if m.bitmap_length is not None and m.bitmap_length * 8 < m.Ni * m.Nj:
             raise ValueError(f"bitmap of {m.bitmap_length} bytes for {m.Ni * m.Nj} grid points")
+        if m.packing and (m.n_values > m.Ni * m.Nj or (m.bitmap_offset is None and m.n_values != m.Ni * m.Nj)):
+            raise ValueError(f"template 5.{m.packing}: {m.n_values} packed values on a grid of {m.Ni * m.Nj} points")
         return m
 
     # ---- choosing a variable ----
@@ -485,9 +530,84 @@ def unpack_bits(data: bytes, nbits: int, count: int) -> np.ndarray:
     return (win >> (np.uint64(40 - nbits) - off)) & np.uint64((1 << nbits) - 1)
 
 
+def _cut_bits(buf: np.ndarray, bit: np.ndarray, width) -> np.ndarray:
+    """The big-endian unsigned integers of ``width`` bits (0..32; an array or one number) that begin at the bits ``bit`` of ``buf``, as
+    uint64: the 40-bit window of `unpack_bits`, with a width of its own for every value.  ``buf`` has 8 bytes of slack at its end."""
+    byte, off = bit >> 3, (bit & 7).astype(np.uint64)
+    win = np.zeros(len(bit), dtype=np.uint64)
+    for k in range(5):
+        win |= buf[byte + k].astype(np.uint64) << np.uint64(8 * (4 - k))
+    w = np.broadcast_to(np.asarray(width, dtype=np.uint64), win.shape)
+    return (win >> (np.uint64(40) - w - off)) & ((np.uint64(1) << w) - np.uint64(1))
+
+
+def unpack_complex(m, data: bytes) -> np.ndarray:
+    """The ``m.n_values`` integers X (int64) of a complex-packed message (templates 5.2 / 5.3) from the body of its section 7: the
+    group tables, the values cut out group by group, and the spatial differencing undone by one or two running sums (the module
+    docstring has the layout).  int64 throughout, wrapping like the kernels."""
+    N, NG, tag = int(m.n_values), int(m.n_groups), f"template 5.{m.packing}"
+    if NG == 0:
+        return np.zeros(N, dtype=np.int64)
+    total = len(data) * 8
+    buf = np.zeros(len(data) + 8, dtype=np.uint8)
+    buf[:len(data)] = np.frombuffer(data, dtype=np.uint8)
+    pos = 0
+
+    def need(bits, what):
+        if pos + bits > total:
+            raise ValueError(f"{tag}: section 7 holds {len(data)} bytes, too short for {what} ({(pos + bits + 7) // 8} bytes)")
+
+    ival = [0, 0, 0]                                                          # ival1, ival2, minsd
+    if m.packing == 3 and m.extra:
+        need(8 * m.extra * (m.order + 1), "the extra descriptors")
+        words = [sign_magnitude(int.from_bytes(data[k * m.extra:(k + 1) * m.extra], "big"), 8 * m.extra) for k in range(m.order + 1)]
+        ival[:m.order], ival[2] = words[:m.order], words[m.order]
+        pos = 8 * m.extra * (m.order + 1)
+    tables = []
+    for nb, what in ((m.nbits, "group references"), (m.nbits_width, "group widths"), (m.nbits_len, "group lengths")):
+        need(nb * NG, f"{NG} {what} of {nb} bits")
+        tables.append(_cut_bits(buf, pos + np.arange(NG, dtype=np.int64) * nb, nb).astype(np.int64))
+        pos = (pos + nb * NG + 7) // 8 * 8
+    refs, widths, lens = tables[0], m.ref_width + tables[1], m.ref_len + m.len_inc * tables[2]
+    lens[-1] = m.last_len
+    if int(widths.max()) > 32:
+        raise ValueError(f"{tag}: a group of {int(widths.max())} bits per value (at most 32)")
+    if int(lens.sum()) != N:
+        raise ValueError(f"{tag}: the group lengths sum to {int(lens.sum())}, the section announces {N} values")
+    w = np.repeat(widths, lens)
+    bit = np.cumsum(w) - w + pos
+    need(int(w.sum()), f"{N} values in {NG} groups")
+    raw = np.repeat(refs, lens) + _cut_bits(buf, bit, w).astype(np.int64)
+    if m.packing == 2:
+        return raw
+    g = raw + np.int64(ival[2])
+    g[0] = 0
+    if m.order == 2 and N > 1:
+        g[1] = ival[1] - ival[0]
+    for _ in range(m.order):
+        g = np.cumsum(g, dtype=np.int64)
+    return g + np.int64(ival[0])
+
+
 def decode_message(m, data: bytes, bitmap: bytes | None) -> np.ndarray:
-    """float32 (Nj, Ni) of one message from its packed bits and its bitmap: ``((X * s) + R) * d`` in float64, rounded once."""
+    """float32 (Nj, Ni) of one message from its packed bits and its bitmap: ``((X * s) + R) * d`` in float64, rounded once.  X is an
+    unsigned integer of at most 32 bits under simple packing and a signed int64 under complex packing; the conversion to float64 is
+    exact while ``|X| < 2**53``."""
     n = m.Ni * m.Nj
+    if m.packing:
+        have = None
+        if bitmap is not None:
+            if len(bitmap) * 8 < n:
+                raise ValueError(f"bitmap of {len(bitmap)} bytes for {n} grid points")
+            have = np.unpackbits(np.frombuffer(bitmap, dtype=np.uint8), count=n).astype(bool)
+        if m.n_values != (n if have is None else int(have.sum())):
+            raise ValueError(f"template 5.{m.packing}: {m.n_values} packed values for {n if have is None else int(have.sum())} present grid points")
+        v = (((unpack_complex(m, data).astype(np.float64) * m.s) + m.R) * m.d).astype(np.float32)
+        if have is None:
+            return v.reshape(m.Nj, m.Ni)
+        out = np.full(n, np.nan, dtype=np.float32)
+        out[have] = v
+        return out.reshape(m.Nj, m.Ni)
     if bitmap is None:
         x = unpack_bits(data, m.nbits, n)
         return (((x.astype(np.float64) * m.s) + m.R) * m.d).astype(np.float32).reshape(m.Nj, m.Ni)

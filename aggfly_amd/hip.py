@@ -42,7 +42,7 @@ EXPORTS = (
     "afhip_plan_bind_packing", "afhip_unpack_i16", "afhip_unpack_u16", "afhip_plan_bind_packings",
     "afhip_take_box", "afhip_shuffle_blocks", "afhip_lz4_encode_streams", "afhip_copy_ranges", "afhip_zstd_encode_blocks",
     "afhip_zstd_encode_scratch_bytes", "afhip_place_box_swapped", "afhip_grib_rank_bytes", "afhip_grib_unpack", "afhip_place_box_tlast",
-    "afhip_delta_scratch_bytes", "afhip_delta_decode", "afhip_fso_decode",
+    "afhip_delta_scratch_bytes", "afhip_delta_decode", "afhip_fso_decode", "afhip_grib_complex_scratch_bytes", "afhip_grib_unpack_complex",
 )
 
 
@@ -144,6 +144,9 @@ def load():
     lib.afhip_grib_rank_bytes.restype = i64
     lib.afhip_grib_rank_bytes.argtypes = [i64, i64]
     lib.afhip_grib_unpack.argtypes = [vp, i64, vp, i64] + [i64] * 6 + [vp, i32] + [i64] * 6 + [vp, i64, vp, vp]
+    lib.afhip_grib_complex_scratch_bytes.restype = i64
+    lib.afhip_grib_complex_scratch_bytes.argtypes = [i64, i64, i64]
+    lib.afhip_grib_unpack_complex.argtypes = [vp, i64, vp, i64, i32, i64] + [i64] * 6 + [vp, i32] + [i64] * 6 + [vp, i64, vp, vp]
     lib.afhip_zstd_encode_scratch_bytes.restype = i64
     lib.afhip_zstd_encode_scratch_bytes.argtypes = [i64]
     lib.afhip_zstd_scratch_bytes.restype = i64
@@ -320,6 +323,40 @@ def grib_unpack(stage, steps, n_steps: int, grid, box, cube, at, rank, errors):
                                     int(y0), int(x0), int(ny), int(nx), cube.data_ptr(), cube.element_size(), cube.shape[0], cube.shape[1],
                                     cube.shape[2], int(t0), int(cy), int(cx), rank.data_ptr(), rank.numel() * rank.element_size(),
                                     errors.data_ptr(), _stream_ptr(cube)))
+
+
+# one record of `afhip_grib_unpack_complex` per time step (`afhip_grib_cstep`, include/aggfly_hip.h)
+GRIB_CSTEP = np.dtype([("data_off", "<i8"), ("data_bytes", "<i8"), ("bitmap_off", "<i8"), ("n_values", "<i8"), ("n_groups", "<i8"),
+                       ("ref_len", "<i8"), ("last_len", "<i8"), ("nbits_ref", "<i4"), ("ref_width", "<i4"), ("nbits_width", "<i4"),
+                       ("len_inc", "<i4"), ("nbits_len", "<i4"), ("order", "<i4"), ("extra", "<i4"), ("pad", "<i4"),
+                       ("R", "<f8"), ("s", "<f8"), ("d", "<f8")])
+
+
+def grib_complex_scratch_bytes(n_steps: int, n_points: int, max_groups: int) -> int:
+    """`afhip_grib_complex_scratch_bytes`: the scratch `grib_unpack_complex` needs for ``n_steps`` fields of ``n_points`` grid points in
+    at most ``max_groups`` groups each (the rank tables, the group tables, 8 bytes per value and the tile sums of the running sums)."""
+    n = int(load().afhip_grib_complex_scratch_bytes(int(n_steps), int(n_points), int(max_groups)))
+    if n < 0:
+        raise ValueError(f"grib_complex_scratch_bytes: {n_steps} steps of {n_points} grid points in {max_groups} groups")
+    return n
+
+
+def grib_unpack_complex(stage, steps, n_steps: int, order: int, max_groups: int, grid, box, cube, at, scratch, errors):
+    """`afhip_grib_unpack_complex`: the GRIB fields in complex packing (templates 5.2 / 5.3) staged in the uint8 HBM tensor ``stage`` under the
+    ``n_steps`` `GRIB_CSTEP` records of the uint8 HBM tensor ``steps``, unpacked into the float32 ``cube``.  ``order``: 0 (template 5.2),
+    1 or 2, the same for every record; ``max_groups``: at least every record's ``n_groups``; ``grid``, ``box``, ``at`` as in
+    `grib_unpack`; ``scratch``: a uint8 HBM tensor of `grib_complex_scratch_bytes` bytes.  Refused records count in the int32 HBM counter
+    ``errors`` and their steps are left unwritten.  The work goes to the current stream."""
+    import torch
+    if cube.dtype != torch.float32 or cube.dim() != 3 or not cube.is_contiguous():
+        raise ValueError("grib_unpack_complex: the cube must be a contiguous 3-D float32 tensor")
+    if steps.numel() * steps.element_size() < int(n_steps) * GRIB_CSTEP.itemsize:
+        raise ValueError(f"grib_unpack_complex: {n_steps} records need {int(n_steps) * GRIB_CSTEP.itemsize} bytes")
+    (NY, NX), (y0, x0, ny, nx), (t0, cy, cx) = grid, box, at
+    _check(load().afhip_grib_unpack_complex(stage.data_ptr(), stage.numel() * stage.element_size(), steps.data_ptr(), int(n_steps), int(order),
+                                            int(max_groups), int(NY), int(NX), int(y0), int(x0), int(ny), int(nx), cube.data_ptr(),
+                                            cube.element_size(), cube.shape[0], cube.shape[1], cube.shape[2], int(t0), int(cy), int(cx),
+                                            scratch.data_ptr(), scratch.numel() * scratch.element_size(), errors.data_ptr(), _stream_ptr(cube)))
 
 
 def lz4_decode_streams(comp, streams, n_streams: int, max_dsize: int, tmp, out, errors):

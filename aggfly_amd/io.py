@@ -23,9 +23,9 @@ and the native chunk codecs of `csrc/blosc1.c`:
   bytes over PCIe, swapped and placed by one kernel (``hip.place_box_swapped``), CF mask and unpack in HBM, ``keep_packed``,
   windows and several files as on the Zarr route (``_netcdf3_part_to_device``); on the host, and for whatever that route
   declines (byte / char variables, arrays that are not time-leading, CDF-5), through ``scipy.io.netcdf_file``;
-* GRIB files (editions 1 and 2, regular latitude / longitude grids, simple packing; ``engine="cfgrib"`` or none): ``grib.py`` indexes
+* GRIB files (editions 1 and 2, regular latitude / longitude grids, simple packing and edition 2's complex packing; ``engine="cfgrib"`` or none): ``grib.py`` indexes
   the messages from their section headers; with ``device=`` set the packed bits go from the file to HBM as stored and one kernel
-  (``hip.grib_unpack``) extracts, scales and places them (``_grib_part_to_device``), on the host ``grib.GribFile.read`` decodes
+  (``hip.grib_unpack``; for complex packing ``hip.grib_unpack_complex``) extracts, scales and places them (``_grib_part_to_device``), on the host ``grib.GribFile.read`` decodes
   them in numpy; what ``grib.py`` refuses raises with its reason.
 
 On the host route chunks are decoded on host threads into one time-major host buffer, which
@@ -2520,7 +2520,9 @@ def _grib_part_to_device(src, xycoords, timecoord, time_sel, georegions, lon_is_
     crosses PCIe as stored (2 bytes per value for ERA5's 16 bits), and `hip.grib_unpack` extracts the integers, scales them, writes NaN
     where the bitmap has 0 and places the box — the x clip included — in the float32 cube.  The host never touches the data.  The
     steps' ``nbits`` / ``E`` / ``D`` / ``R`` differ: each step has its record, with ``R``, ``2.0 ** E`` and ``10.0 ** -D`` as the
-    host route computes them."""
+    host route computes them.  Steps in complex packing (edition 2, templates 5.2 / 5.3) stage the whole body of their section 7 and go
+    to `hip.grib_unpack_complex`, which reads the group tables, cuts the values out, undoes the spatial differencing by running sums and
+    places the box; a file may mix them with simple-packed steps (a writer falls back to simple packing for a constant field)."""
     import torch
     from . import codec, hip
     if os.environ.get("AGGFLY_HIP_SLAB_MB"):
@@ -2550,22 +2552,39 @@ def _grib_part_to_device(src, xycoords, timecoord, time_sel, georegions, lon_is_
     arr = {k: v[k_lo:k_hi] for k, v in src.field.arrays().items()}
     nb, d_off, d_len, m_off = arr["nbits"], arr["data_offset"], arr["data_length"], arr["bitmap_offset"]
     has_map = m_off >= 0
-    lo = np.where(has_map, 0, (a0 * NX * nb) // 8)                       # without a bitmap: the bytes of rows [a0, a1) only
-    hi = np.where(has_map, d_len, -((-a1 * NX * nb) // 8))
+    # a step in complex packing (templates 5.2 / 5.3) has no random access: its section 7 is staged whole, like a step with a bitmap.
+    # kind: 0 simple packing, 1 + order complex packing (order 0: template 5.2) - `place` calls one entry per run of one kind
+    is_cx = arr["packing"] != 0
+    kind = np.where(is_cx, 1 + arr["order"], 0)
+    whole = has_map | is_cx
+    lo = np.where(whole, 0, (a0 * NX * nb) // 8)                         # simple packing without a bitmap: the bytes of rows [a0, a1) only
+    hi = np.where(whole, d_len, -((-a1 * NX * nb) // 8))
     short = hi > d_len
     if short.any():
         k = int(np.argmax(short))
         raise ValueError(f"{path}: the data section of the message at offset {msgs[k].offset} holds {int(d_len[k])} bytes, "
                          f"{NY * NX} values of {int(nb[k])} bits need {int(hi[k])}")
     map_bytes = np.where(has_map, (NY * NX + 7) // 8, 0)
-    rec["nbits"], rec["first_bit"] = nb, np.where(has_map, 0, (a0 * NX * nb) & 7)
-    rec["first_point"], rec["data_bytes"] = np.where(has_map, 0, a0 * NX), hi - lo
+    rec["nbits"], rec["first_bit"] = nb, np.where(whole, 0, (a0 * NX * nb) & 7)
+    rec["first_point"], rec["data_bytes"] = np.where(whole, 0, a0 * NX), hi - lo
     rec["R"], rec["s"], rec["d"] = arr["R"], arr["s"], arr["d"]
+    crec = np.zeros(n, dtype=hip.GRIB_CSTEP)                              # the records of the complex steps (unused rows for the others)
+    crec["data_bytes"], crec["nbits_ref"] = d_len, nb
+    for k in ("n_values", "n_groups", "ref_len", "last_len", "ref_width", "nbits_width", "len_inc", "nbits_len", "order", "extra", "R", "s", "d"):
+        crec[k] = arr[k]
+    max_groups = int(arr["n_groups"][is_cx].max()) if is_cx.any() else 0
     pad4 = lambda v: (v + 3) // 4 * 4                                     # every staged range begins on a 4-byte boundary (`read_packed`, align=4)
     step_bytes = pad4(map_bytes) + pad4(hi - lo)
     row = int(step_bytes.max()) if n else 4
     row = max(row, 4)
     slab = max(1, min(slab_bytes, 1 << 30) // row)
+    scratch = None
+    if is_cx.any():
+        # the scratch of the complex steps (8 bytes per value and step, 16 per group, the rank tables, the tile sums) is capped at four
+        # slabs of staged bytes, and a slab holds no more steps than that serves
+        per_step = hip.grib_complex_scratch_bytes(1, NY * NX, max_groups)
+        slab = max(1, min(slab, (4 * min(slab_bytes, 1 << 30)) // per_step))
+        scratch = torch.empty(hip.grib_complex_scratch_bytes(min(slab, n), NY * NX, max_groups), dtype=torch.uint8, device=device)
     rank = torch.empty(hip.grib_rank_bytes(min(slab, max(n, 1)), NY * NX), dtype=torch.uint8, device=device)
     errors = torch.zeros(1, dtype=torch.int32, device=device)
     pending = []                                                          # the records of the slab just read, for `place`
@@ -2573,9 +2592,9 @@ def _grib_part_to_device(src, xycoords, timecoord, time_sel, georegions, lon_is_
     def read(k0, k1, out):
         # one range per staged piece, packed back to back by the reader's team; a step's ranges follow each other in the slab
         start = np.concatenate([[0], np.cumsum(step_bytes[k0:k1])])[:-1]
-        r = rec[k0:k1].copy()
-        r["bitmap_off"] = np.where(has_map[k0:k1], start, -1)
-        r["data_off"] = start + pad4(map_bytes[k0:k1])
+        r, c = rec[k0:k1].copy(), crec[k0:k1].copy()
+        r["bitmap_off"] = c["bitmap_off"] = np.where(has_map[k0:k1], start, -1)
+        r["data_off"] = c["data_off"] = start + pad4(map_bytes[k0:k1])
         # per step the bitmap, then the packed bits; pieces of no bytes (a field of 0 bits per value) are not asked for
         two = lambda a_, b_: np.stack([a_, b_], axis=1).ravel()
         keep = two(has_map[k0:k1], hi[k0:k1] > lo[k0:k1])
@@ -2588,15 +2607,30 @@ def _grib_part_to_device(src, xycoords, timecoord, time_sel, georegions, lon_is_
                 raise OSError(f"{path}: the file ends inside the steps {k_lo + k0}..{k_lo + k1} of {src.field.var!r}")
             if not np.array_equal(offs[:-1], want):
                 raise RuntimeError("grib: the reader packed the staged ranges differently from the records")
-        pending[:] = [r]
+        pending[:] = [(r, c, kind[k0:k1])]
 
     def place(raw, dst, m):
-        steps = torch.from_numpy(pending[0].view(np.uint8).reshape(-1)).to(dst.device)
-        hip.grib_unpack(raw, steps, m, (NY, NX), (a0, b0, a1 - a0, b1 - b0), dst, (0, 0, 0), rank, errors)
+        r, c, kd = pending[0]
+        grid, box = (NY, NX), (a0, b0, a1 - a0, b1 - b0)
+        if not kd.any():                                                  # simple packing throughout: one call, as ever
+            steps = torch.from_numpy(r.view(np.uint8).reshape(-1)).to(dst.device)
+            hip.grib_unpack(raw, steps, m, grid, box, dst, (0, 0, 0), rank, errors)
+            return
+        # runs of consecutive steps of one kind, each with its own records and its offset along time
+        cuts = np.concatenate([[0], np.flatnonzero(kd[1:] != kd[:-1]) + 1, [m]])
+        for i, j in zip(cuts[:-1].tolist(), cuts[1:].tolist()):
+            if kd[i] == 0:
+                steps = torch.from_numpy(r[i:j].view(np.uint8).reshape(-1)).to(dst.device)
+                hip.grib_unpack(raw, steps, j - i, grid, box, dst, (i, 0, 0), rank, errors)
+            else:
+                steps = torch.from_numpy(c[i:j].view(np.uint8).reshape(-1)).to(dst.device)
+                hip.grib_unpack_complex(raw, steps, j - i, int(kd[i]) - 1, max_groups, grid, box, dst, (i, 0, 0), scratch, errors)
 
     data = stream_to_device(n, (a1 - a0, b1 - b0), np.float32, read, slab, device, None, np.float32, None, place=place, stage_step_bytes=row)
     if n and int(errors.item()):
-        raise ValueError(f"{path}: {int(errors.item())} step(s) of {src.field.var!r} were refused by the unpack kernel (records outside the staged bytes)")
+        raise ValueError(f"{path}: {int(errors.item())} step(s) of {src.field.var!r} were refused by the unpack kernels (records outside the staged bytes"
+                         + ("; or group tables of complex packing that are unsound: widths above 32 bits, lengths that do not sum to the number "
+                            "of values, values beyond section 7 - `grib.GribFile.read` names which" if is_cx.any() else "") + ")")
     if window is not None:
         coords[timecoord] = coords[timecoord][window[0]:window[1]]
     if box is not None:

@@ -256,6 +256,30 @@ int afhip_grib_unpack(const void* stage_dev, int64_t stage_bytes, const afhip_gr
                       void* cube_dev, int cube_elem_size, int64_t cube_nt, int64_t cube_NY, int64_t cube_NX,
                       int64_t t0, int64_t cy, int64_t cx, void* rank_dev, int64_t rank_bytes, int32_t* errors_dev, void* stream);
 
+/* GRIB fields in complex packing (edition 2, data representation templates 5.2 and 5.3: complex packing without and with spatial
+ * differencing) unpacked in HBM; the layout of section 7 is written out in aggfly_amd/grib.py.  stage_dev as above; steps_dev one record
+ * per field: data_off / data_bytes - the body of its section 7 (from octet 6 on), staged whole; bitmap_off as above; n_values - N, the
+ * number of packed values (NY * NX, or with a bitmap its 1-bits); n_groups, ref_len, last_len, nbits_ref, ref_width, nbits_width,
+ * len_inc, nbits_len - octets 32-47 and 20 of section 5; order - 0 for template 5.2, 1 or 2 for 5.3; extra - the octets (0..4) of
+ * ival1 [, ival2] and minsd at the head of the body; R, s, d as above.  `order` is one number for the whole call, and a record of another
+ * order is refused.  X is a signed 64-bit integer here (wrapping sums), and the value (float)(((X * s) + R) * d) is exact while
+ * |X| < 2^53.  scratch_dev: caller-owned, 16-byte aligned, afhip_grib_complex_scratch_bytes(n_steps, NY * NX, max_groups) bytes (-1:
+ * absurd sizes), max_groups >= every record's n_groups.  Refused - the step is not written and *errors_dev grows by one -: ranges
+ * that leave [0, stage_bytes), n_groups > max_groups, table widths above 32 bits, a group width above 32, group lengths that do not sum to
+ * n_values, tables or values that run past data_bytes, a bitmap whose 1-bits are not n_values, another order than the call's.  Whatever
+ * the records say, nothing is read outside the stage and the scratch and nothing is written outside the box and the scratch.
+ * AFHIP_E_INVALID as above, and for an order outside 0..2.  The work is enqueued on `stream`; nothing is retained. */
+typedef struct afhip_grib_cstep {
+    int64_t data_off, data_bytes, bitmap_off, n_values, n_groups, ref_len, last_len;
+    int32_t nbits_ref, ref_width, nbits_width, len_inc, nbits_len, order, extra, pad;
+    double R, s, d;
+} afhip_grib_cstep;
+int64_t afhip_grib_complex_scratch_bytes(int64_t n_steps, int64_t n_points, int64_t max_groups);
+int afhip_grib_unpack_complex(const void* stage_dev, int64_t stage_bytes, const afhip_grib_cstep* steps_dev, int64_t n_steps, int order,
+                              int64_t max_groups, int64_t NY, int64_t NX, int64_t y0, int64_t x0, int64_t ny, int64_t nx,
+                              void* cube_dev, int cube_elem_size, int64_t cube_nt, int64_t cube_NY, int64_t cube_NX,
+                              int64_t t0, int64_t cy, int64_t cx, void* scratch_dev, int64_t scratch_bytes, int32_t* errors_dev, void* stream);
+
 /* Chunk decode in HBM ("or GPU-side decode"; the reference decodes on host threads inside its dask
  * graph, aggfly/dataset/dataset.py:697-728).  Blosc-1 chunks whose streams are LZ4 cross PCIe compressed; the host parses
  * the containers (afcodec_blosc_lz4_plan, include/aggfly_codec.h) into the two record lists below, which travel to HBM with
