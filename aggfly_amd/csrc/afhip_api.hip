@@ -1158,7 +1158,9 @@ extern "C" int afhip_spatial_wavg(const afhip_csr* csr, const double* x_dev, int
         if (!rc) rc = launch_spmm(csr, panel, sums, Q, st, false);
         const int64_t m = csr->R * nt;                            // one thread per (region, time step)
         if (!rc && m) {
-            hipLaunchKernelGGL(k_panel_divide, dim3((unsigned)((m + WG - 1) / WG)), dim3(WG), 0, st, sums, num_dev, den_dev, res_dev, csr->R, nt, (int)K);
+            // (more names than one pass holds: k_panel_divide keeps a record of MAX_COLS + 1 values in registers)
+            if (K > MAX_COLS) hipLaunchKernelGGL(k_panel_divide_wide, dim3((unsigned)((m + WG - 1) / WG)), dim3(WG), 0, st, sums, num_dev, den_dev, res_dev, csr->R, nt, (int)K);
+            else hipLaunchKernelGGL(k_panel_divide, dim3((unsigned)((m + WG - 1) / WG)), dim3(WG), 0, st, sums, num_dev, den_dev, res_dev, csr->R, nt, (int)K);
             if ((e = hipGetLastError()) != hipSuccess) rc = fail(AFHIP_E_HIP, "k_panel_divide launch failed: %s", hipGetErrorString(e));
         }
     }

@@ -671,6 +671,24 @@ __global__ __launch_bounds__(WG) void k_panel_divide(const double* __restrict__ 
     }
 }
 
+// The same for K > MAX_COLS: afhip_spatial_wavg on the outputs of several passes (a spec of more than sixteen columns), whose
+// record k_panel_divide's MAX_COLS + 1 registers do not hold.  A plain loop over the record.
+__global__ __launch_bounds__(WG) void k_panel_divide_wide(const double* __restrict__ sums, double* __restrict__ num,
+                                                          double* __restrict__ den, double* __restrict__ res,
+                                                          int64_t R, int64_t P, int K) {
+    const int64_t rp = (int64_t)blockIdx.x * WG + threadIdx.x;
+    const int64_t RP = R * P;
+    if (rp >= RP) return;
+    const double* rec = sums + rp * (K + 1);
+    const double de = rec[K];
+    if (den) den[rp] = de;
+    for (int k = 0; k < K; ++k) {
+        const double v = rec[k];
+        if (num) num[(int64_t)k * RP + rp] = v;
+        res[(int64_t)k * RP + rp] = (de != 0.0) ? v / de : nan64();
+    }
+}
+
 // res[k][rp] = num[k][rp] / den[rp] where den != 0 else NaN (spatial.py:127-133) on separate arrays: the divide after the
 // all-reduce of a cell-sharded job.
 __global__ __launch_bounds__(WG) void k_divide_num_den(const double* __restrict__ num, const double* __restrict__ den,

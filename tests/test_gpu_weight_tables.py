@@ -146,6 +146,20 @@ def test_wavg(torch_cuda, monkeypatch, name):
                     assert np.array_equal(hip.panel_divide(num, den).cpu().numpy(), res.cpu().numpy(), equal_nan=True), f"{name} {regime}: panel_divide"
 
 
+@pytest.mark.parametrize("K,nt", [(17, 1), (17, 4), (23, 3)])
+def test_wavg_of_more_names_than_one_pass_holds(torch_cuda, K, nt):
+    """`aggregate_dataset` on a spec of more than sixteen columns gathers the passes' outputs and hands all K of them to ONE
+    `CSR.wavg` (found by tests/test_gpu_packed_fuzz.py, seed 10: seventeen columns): the divide then reads records of K + 1 > 17 sums."""
+    for name in ("row_lengths", NAMES[0]):
+        t = BY_NAME[name]
+        for regime in _regimes(t):
+            w = _weights(t, regime)
+            x = _wavg_input(t.n_cells, K, nt, regime)
+            num, den, res = _csr(t, w).wavg(torch_cuda.from_numpy(x).cuda())
+            _check_panel(t, w, regime, x, dict(num=num, den=den, res=res), f"wavg K={K} nt={nt} {regime}")
+            assert np.isfinite(res.cpu().numpy()[K - 1]).any()
+
+
 def test_segment_rule_piece_counts(torch_cuda, monkeypatch):
     """The pieces `afhip_csr_create` cuts the rows of the row-length table into, read off the scratch rows a run's workspace holds for them
     (sums [R + pieces][Q]): 234 with the default segment length — 257 -> 5, 320 -> 5, 321 -> 6, 511 -> 8, 512 -> 8, 513 -> 9, 8192 -> 128,
