@@ -50,13 +50,7 @@ def store_route_ok(config, paths) -> bool:
     """One un-templated Zarr store / netCDF-4 file whose outputs share a nestable output frequency can be cut along
     time INSIDE the store: ranks (and, beyond the HBM budget, windows) take runs of output periods
     (`distributed.aggregate_store_sharded`)."""
-    from .. import hip, io as afio
-    if len(paths) != 1 or hip.device_count() == 0:
-        return False
-    p = paths[0]
-    if not isinstance(p, str) or any(ch in p for ch in "*?[") or "://" in p:
-        return False
-    if not (afio._looks_like_zarr(p) or (os.path.isfile(p) and (afio._is_hdf5(p) or _streams_classic(config, p) or _streams_grib(config, p)))):
+    if len(paths) != 1 or not _streams_from_store(config, paths[0]):
         return False
     try:
         D.output_freq(config.to_aggregator_dict())
@@ -152,34 +146,34 @@ def find_weights_table(config) -> str:
         "aggfly's calculate_weights() (weights are computed on the CPU by aggfly.weights, not by this engine)")
 
 
-def _streams_classic(config, path) -> bool:
-    """Is `path` a NetCDF classic file whose variable the streaming route takes (`io._netcdf3_source`: a readable header, a 3-D
-    time-leading variable of type short / int / float / double)?"""
+def _streams(config, path) -> bool:
+    """Does a streaming route take the variable ``config.var`` of `path` (`io._streamed_source`: a Zarr store, a chunked time-leading
+    netCDF-4 variable, a 3-D time-leading short / int / float / double variable of a NetCDF classic file with a readable header, a GRIB
+    file with an index `grib.py` reads, one level, one grid)?"""
     from .. import io as afio
-    return afio._is_netcdf3(path) and afio._netcdf3_source(path, config.var, config.timecoord) is not None
+    try:
+        return afio._streamed_source(path, config.var, timecoord=config.timecoord) is not None
+    except (ValueError, KeyError, OSError):
+        return False
+
+
+def _streams_classic(config, path) -> bool:
+    from .. import io as afio
+    return afio._is_netcdf3(path) and _streams(config, path)
 
 
 def _streams_grib(config, path) -> bool:
-    """Is `path` a GRIB file whose variable ``config.var`` the streaming route takes (`io._grib_source`: an index `grib.py` reads, one
-    level, one grid)?"""
     from .. import io as afio
-    if not afio._is_grib(path):
-        return False
-    try:
-        afio._grib_source(path, config.var, timecoord=config.timecoord)
-    except (ValueError, KeyError, OSError):
-        return False
-    return True
+    return afio._is_grib(path) and _streams(config, path)
 
 
 def _streams_from_store(config, path) -> bool:
-    """Is `path` a file the streaming route takes (one Zarr store, netCDF-4 file, or NetCDF classic or GRIB file whose variable
-    ``config.var`` qualifies, a GPU to stream to)?  Only there does
+    """Is `path` a single store or file the streaming route takes (`_streams`), with a GPU to stream to?  Only there does
     ``time_window`` cut the read itself; everywhere else `dataset_from_path` reads the file whole and cuts on the host."""
-    from .. import hip, io as afio
+    from .. import hip
     if hip.device_count() == 0 or not isinstance(path, str) or any(ch in path for ch in "*?[") or "://" in path:
         return False
-    return afio._looks_like_zarr(path) or (os.path.isfile(path) and (afio._is_hdf5(path) or _streams_classic(config, path) or _streams_grib(config, path)))
+    return _streams(config, path)
 
 
 def load_grid(config, path, georegions):

@@ -1,4 +1,4 @@
-// afhip_grib_kernels.h — GRIB simple and complex packing unpacked in HBM (aggfly_amd/io.py: `_grib_part_to_device`).
+// afhip_grib_kernels.h — GRIB simple and complex packing unpacked in HBM (aggfly_amd/io.py: `_GribSource.to_device`).
 //
 // A GRIB field (editions 1 and 2, simple packing) is a big-endian bit stream of nbits-bit unsigned integers X, nbits 0..32, and the
 // value is ((X * s) + R) * d with s = 2^E, d = 10^-D; an optional bitmap, one bit per grid point in scan order, most significant bit

@@ -291,41 +291,19 @@ def aggregate_dataset_sharded(weights, dataset=None, aggregator_dict=None, engin
     return agg._merge_regions(df, weights)
 
 
-def _step_bytes(path, var, keep_packed=False, timecoord="time"):
-    """Bytes one time step of ``var`` takes in HBM (full stored grid: a clipped read takes less), or None when
-    the container's shape cannot be told without reading it.  ``keep_packed`` (or AGGFLY_HIP_KEEP_PACKED=1): an int16- or uint16-packed
-    variable that `io.dataset_from_path` will keep packed counts its 2 stored bytes per cell.  A Zarr array whose LAST dimension is
-    ``timecoord`` (the reference's converter's layout) counts its first two extents.  A Zarr array with converting element filters
-    (``fixedscaleoffset`` to int16, ...) counts its stored bytes on top: while it is read, the stored elements lie beside the cube."""
-    import numpy as np
+def _step_bytes(path, var, keep_packed=False, timecoord="time", xycoords=("longitude", "latitude")):
+    """Bytes one time step of ``var`` takes in HBM (full stored grid: a clipped read takes less), or None when no streaming route takes
+    the container (`io._streamed_source`) or its shape cannot be told without reading it.  ``keep_packed`` (or AGGFLY_HIP_KEEP_PACKED=1):
+    an int16- or uint16-packed variable that `io.dataset_from_path` will keep packed counts its 2 stored bytes per cell.  A Zarr array
+    whose LAST dimension is ``timecoord`` (the reference's converter's layout) counts its first two extents.  A Zarr array with
+    converting element filters (``fixedscaleoffset`` to int16, ...) counts its stored bytes on top: while it is read, the stored
+    elements lie beside the cube (`io._StreamedSource.step_bytes`)."""
     from . import io as afio
-    beside = 0                                                # bytes per cell of a stored-type buffer beside the cube
     try:
-        if afio._looks_like_zarr(path):
-            za = afio.ZarrArray(os.path.join(path, var))
-            shape, dt, packing = za.shape, np.dtype(za.dtype), afio.packing_of(za)
-            if za.elem_filters and za.stored_dtype != za.dtype:
-                beside = za.stored_dtype.itemsize
-            if len(shape) == 3 and za.dims[2] == timecoord:
-                shape = (shape[2], shape[0], shape[1])
-        elif afio._is_hdf5(path):
-            from . import hdf5
-            with hdf5.H5File(path) as f:
-                shape, dt, packing = f.datasets[var].shape, np.dtype(f.datasets[var].dtype), afio.packing_of(f.datasets[var])
-        elif afio._is_netcdf3(path):
-            src = afio._netcdf3_source(path, var)
-            if src is None:
-                return None
-            shape, dt, packing = src.shape, np.dtype(src.dtype), afio.packing_of(src)
-        elif afio._is_grib(path):
-            src = afio._grib_source(path, var)                # (float32 in HBM whatever the messages' bits per value)
-            shape, dt, packing = src.shape, np.dtype(src.dtype), None
-        else:
-            return None
-        item = dt.itemsize if dt.kind == "f" else 4           # packed integers are unpacked to float32 in HBM ...
-        if packing is not None and afio.keep_packed_requested(keep_packed):
-            item = 2                                          # ... unless the cube stays packed
-        return int(np.prod(shape[1:], dtype=np.int64)) * (item + beside)
+        src = afio._streamed_source(path, var, xycoords, timecoord)
+        if src is None and afio._is_hdf5(path):               # (a contiguous variable: uploaded whole by the host route, packed if asked)
+            src = afio._hdf5_source(path, var, timecoord, any_layout=True)
+        return None if src is None else src.step_bytes(keep_packed)
     except Exception:
         return None
 
@@ -402,7 +380,8 @@ def aggregate_store_sharded(weights_of, path, var, aggregator_dict, engine="auto
     names = agg._lower_all(aggregator_dict)[3]
     if max_window_bytes is None and torch.cuda.is_available():
         max_window_bytes = int(0.6 * torch.cuda.mem_get_info()[0])
-    windows = plan_windows(bounds, p_lo, p_hi, _step_bytes(path, var, open_kwargs.get("keep_packed", False), timecoord), max_window_bytes)
+    step_bytes = _step_bytes(path, var, open_kwargs.get("keep_packed", False), timecoord, open_kwargs.get("xycoords", ("longitude", "latitude")))
+    windows = plan_windows(bounds, p_lo, p_hi, step_bytes, max_window_bytes)
     weights, parts, region_ids = None, [], None
     # an empty share still opens the store (coordinates, grid) so that every rank builds the same weights
     for q_lo, q_hi in (windows or [(p_lo, p_lo)]):

@@ -1,7 +1,7 @@
 """Index and host decode of GRIB files (editions 1 and 2, regular latitude / longitude grids; simple packing, and in edition 2 complex
 packing with and without spatial differencing, data representation templates 5.2 and 5.3), written from the format's octet tables (WMO Manual on Codes, FM 92 GRIB; edition 1 as in the ECMWF / NCEP descriptions of its sections).  `GribFile`
 walks the file message by message and reads the section HEADERS only: it tells where the packed bits and the bitmap of every field
-lie and how they unpack; `io._grib_part_to_device` `pread`s those bytes into page-locked memory and kernels (`hip.grib_unpack`,
+lie and how they unpack; `io._GribSource.to_device` `pread`s those bytes into page-locked memory and kernels (`hip.grib_unpack`,
 `hip.grib_unpack_complex`) extract, scale and place them in the cube in HBM.  `GribFile.read` is the same decode in numpy: the ``device=None`` route.
 
     edition 1   0 indicator (8)  1 product definition  2 grid description  [3 bitmap]  4 binary data  5 '7777'

@@ -21,11 +21,11 @@ and the native chunk codecs of `csrc/blosc1.c`:
 * NetCDF classic files (CDF-1 / CDF-2): with ``device=`` set, the header is read by ``netcdf3.py`` and the time steps of a
   short / int / float / double variable go from the file to HBM as stored — ``pread`` into page-locked slabs, big-endian
   bytes over PCIe, swapped and placed by one kernel (``hip.place_box_swapped``), CF mask and unpack in HBM, ``keep_packed``,
-  windows and several files as on the Zarr route (``_netcdf3_part_to_device``); on the host, and for whatever that route
+  windows and several files as on the Zarr route (``_Nc3Source.to_device``); on the host, and for whatever that route
   declines (byte / char variables, arrays that are not time-leading, CDF-5), through ``scipy.io.netcdf_file``;
 * GRIB files (editions 1 and 2, regular latitude / longitude grids, simple packing and edition 2's complex packing; ``engine="cfgrib"`` or none): ``grib.py`` indexes
   the messages from their section headers; with ``device=`` set the packed bits go from the file to HBM as stored and one kernel
-  (``hip.grib_unpack``; for complex packing ``hip.grib_unpack_complex``) extracts, scales and places them (``_grib_part_to_device``), on the host ``grib.GribFile.read`` decodes
+  (``hip.grib_unpack``; for complex packing ``hip.grib_unpack_complex``) extracts, scales and places them (``_GribSource.to_device``), on the host ``grib.GribFile.read`` decodes
   them in numpy; what ``grib.py`` refuses raises with its reason.
 
 On the host route chunks are decoded on host threads into one time-major host buffer, which
@@ -574,7 +574,7 @@ def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: in
     MI355X box (16 host cores, `profiles/r01_ingest_bench.json`): native Blosc decode 66 GB/s,
     pageable H2D 56 GB/s.  ``wire_dtype`` (`_wire_dtype`): the dtype of the same size the bits are uploaded as where torch
     cannot hold ``np_dtype`` (uint16 as int16); ``read_slab`` still fills an array of ``np_dtype``.
-    ``place(raw, dst, n)`` with ``stage_step_bytes`` (the NetCDF classic route, `_netcdf3_part_to_device`): a slab is then
+    ``place(raw, dst, n)`` with ``stage_step_bytes`` (the NetCDF classic route, `_Nc3Source.to_device`): a slab is then
     ``stage_step_bytes`` raw bytes per step, as they lie in the file — ``read_slab`` fills a uint8 array —, uploaded as they are
     into one HBM staging buffer, and ``place`` (a kernel on the copy stream) writes the ``n`` steps of ``raw`` into ``dst`` =
     ``cube[k0:k1]``; ``post`` follows as usual.  One HBM buffer serves every slab: upload and kernel are ordered on the copy stream."""
@@ -733,6 +733,12 @@ def _hbm_filter_plan(za):
     return len(chain), conv
 
 
+def _slab_bytes(default: int) -> int:
+    """The bytes of one staging slab: ``default``, or AGGFLY_HIP_SLAB_MB from the environment (a tuning knob; scripts/e2e_bench.py sweeps it)."""
+    mb = os.environ.get("AGGFLY_HIP_SLAB_MB")
+    return int(float(mb) * (1 << 20)) if mb else default
+
+
 def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 << 20, t_range=None, yx_box=None, keep_packed=False,
                     time_axis=0):
     """Stream a chunked (time, y, x) array — a `ZarrArray` or an `hdf5.ChunkSource` — straight into HBM: each
@@ -747,8 +753,7 @@ def array_to_device(za, device="cuda", threads: int = 16, slab_bytes: int = 128 
     native kind (`ZarrArray.scatter_kind`) and are un-filtered by `ZarrArray._chunk`."""
     if len(za.shape) != 3:
         raise ValueError("zarr_to_device expects a (time, y, x) array")
-    if os.environ.get("AGGFLY_HIP_SLAB_MB"):                       # tuning knob (scripts/e2e_bench.py sweeps it)
-        slab_bytes = int(float(os.environ["AGGFLY_HIP_SLAB_MB"]) * (1 << 20))
+    slab_bytes = _slab_bytes(slab_bytes)
     post, need_post, out_np, wire = _cf_in_hbm(za.dtype, za.attrs)
     kind = _scatter_kind(za)                                       # (None also for element filters that the host undoes)
     filtered = bool(getattr(za, "elem_filters", ()))
@@ -1653,6 +1658,31 @@ def _decode_time(values, attrs):
     return decode_cf_time(values, units, cal)
 
 
+def _decoded_coord(values, attrs):
+    """A coordinate as its container stores it: the decoded time index where ``units`` read "<unit> since <epoch>" (CF), else the values."""
+    return _decode_time(values, attrs) if " since " in str(attrs.get("units", "")) else values
+
+
+def _py(v):
+    """A numpy scalar (an attribute of an HDF5 or a classic file) as the Python number it holds; anything else as it is."""
+    return v.item() if isinstance(v, np.generic) else v
+
+
+def _py_attrs(attrs, skip=()) -> dict:
+    return {k: _py(v) for k, v in attrs.items() if k not in skip}
+
+
+def _zarr_coords(path, dims) -> dict:
+    """{dim: values} of the dimensions of a Zarr store that have a coordinate array, the time axis decoded."""
+    coords = {}
+    for d in dims:
+        cp = os.path.join(path, d)
+        if is_zarr_array(cp):
+            c = ZarrArray(cp)
+            coords[d] = _decoded_coord(c.read(threads=1), c.attrs)
+    return coords
+
+
 def _attr_fill(attrs):
     """``_FillValue`` / ``missing_value`` attribute; xarray writes it base64-packed into format-3 stores."""
     fv = attrs.get("_FillValue", attrs.get("missing_value"))
@@ -1679,7 +1709,7 @@ def _cf_mask_scale(arr, attrs):
             fv = int(fv) + (1 << (8 * arr.dtype.itemsize))
     # numbers, not numpy scalars: a float64 scalar (a classic file's attribute, as scipy hands it on) would widen `out *= sf` to
     # float64 under NumPy 2's promotion rules, where every other container — and every device route — unpacks in the cube's type
-    sf, ao = (a.item() if isinstance(a, np.generic) else a for a in (attrs.get("scale_factor"), attrs.get("add_offset")))
+    sf, ao = _py(attrs.get("scale_factor")), _py(attrs.get("add_offset"))
     if fv is None and sf is None and ao is None:
         return arr
     out = arr.astype(np.float64 if arr.dtype.itemsize > 2 and arr.dtype.kind != "f" else (arr.dtype if arr.dtype.kind == "f" else np.float32))
@@ -1696,14 +1726,7 @@ def open_zarr(path: str, var: str, threads: int = 8) -> DataArray:
     arr = ZarrArray(os.path.join(path, var))
     dims = arr.dims
     data = _cf_mask_scale(arr.read(threads=threads), arr.attrs)
-    coords = {}
-    for d in dims:
-        cp = os.path.join(path, d)
-        if is_zarr_array(cp):
-            c = ZarrArray(cp)
-            v = c.read(threads=1)
-            coords[d] = _decode_time(v, c.attrs) if ("units" in c.attrs and " since " in str(c.attrs["units"])) else v
-    return DataArray(data, dims, coords, name=var, attrs=arr.attrs)
+    return DataArray(data, dims, _zarr_coords(path, dims), name=var, attrs=arr.attrs)
 
 
 _CRC32C_TABLE = None
@@ -2222,21 +2245,39 @@ def _open_hdf5(path, var, xycoords=("longitude", "latitude"), timecoord="time", 
                 names += [c for c, d in cands.items() if d.shape[0] == n and c not in dims and c not in names]
                 dims.append(names[0] if names else f"dim_{ax}")
             dims = tuple(dims)
-        attrs = {k: (v.item() if isinstance(v, np.generic) else v) for k, v in ds.attrs.items()
-                 if k not in ("DIMENSION_LIST", "REFERENCE_LIST", "CLASS", "NAME", "_Netcdf4Dimid", "_Netcdf4Coordinates")}
+        attrs = _py_attrs(ds.attrs, _H5_INTERNAL_ATTRS)
         if keep_packed and packing_of(ds) is not None:
             from .packed import PackedCube
             data = PackedCube(np.ascontiguousarray(ds.read()), *packing_of(ds))
         else:
             data = _cf_mask_scale(ds.read(), attrs)
-        coords = {}
-        for d in dims:
-            if d in f.datasets and len(f.datasets[d].shape) == 1:
-                c = f.datasets[d]
-                cattrs = {k: (v.item() if isinstance(v, np.generic) else v) for k, v in c.attrs.items()}
-                vals = c.read(threads=1)
-                coords[d] = _decode_time(vals, cattrs) if " since " in str(cattrs.get("units", "")) else vals
+        coords = _hdf5_coords(f, dims)
     return DataArray(data, dims, coords, name=var, attrs=attrs)
+
+
+_H5_INTERNAL_ATTRS = ("DIMENSION_LIST", "REFERENCE_LIST", "CLASS", "NAME", "_Netcdf4Dimid", "_Netcdf4Coordinates")
+
+
+def _hdf5_coords(f, dims) -> dict:
+    """{dim: values} of the dimensions of an open `hdf5.H5File` that have a 1-D dataset of their name, the time axis decoded."""
+    coords = {}
+    for d in dims:
+        c = f.datasets.get(d)
+        if c is not None and len(c.shape) == 1:
+            coords[d] = _decoded_coord(c.read(threads=1), _py_attrs(c.attrs))
+    return coords
+
+
+def _nc3_coords(nc, dims) -> dict:
+    """{dim: values} of the dimensions of a `netcdf3.NC3File` that have a 1-D variable of their name, in native byte order, the time
+    axis decoded."""
+    coords = {}
+    for d in dims:
+        c = nc.variables.get(d)
+        if c is not None and len(c.shape) == 1:
+            vals = nc.read(d)
+            coords[d] = _decoded_coord(vals.astype(vals.dtype.newbyteorder("=")), _py_attrs(c.attrs))
+    return coords
 
 
 def _open_netcdf3(path, var):
@@ -2251,35 +2292,29 @@ def _open_netcdf3(path, var):
             if d in nc.variables:
                 cv = nc.variables[d]
                 cattrs = {k: (val.decode() if isinstance(val, bytes) else val) for k, val in cv._attributes.items()}
-                vals = np.array(cv.data)
-                coords[d] = _decode_time(vals, cattrs) if " since " in str(cattrs.get("units", "")) else vals
+                coords[d] = _decoded_coord(np.array(cv.data), cattrs)
     return DataArray(data, dims, coords, name=var, attrs=attrs)
 
 
 def read_time_coordinate(path, var, timecoord="time"):
     """The decoded time coordinate of a Zarr store (or of the dimension ``timecoord`` of a netCDF-4 or NetCDF classic file, or the valid
     times of the messages of ``var`` in a GRIB file) without touching the data variable."""
+    t = None
     if _looks_like_zarr(path):
-        c = ZarrArray(os.path.join(path, timecoord))
-        v = c.read(threads=1)
-        return _decode_time(v, c.attrs) if " since " in str(c.attrs.get("units", "")) else pd.DatetimeIndex(v)
-    if _is_hdf5(path):
+        t = _zarr_coords(path, (timecoord,)).get(timecoord)
+    elif _is_hdf5(path):
         from . import hdf5
         with hdf5.H5File(path) as f:
-            c = f.datasets[timecoord]
-            cattrs = {k: (v.item() if isinstance(v, np.generic) else v) for k, v in c.attrs.items()}
-            return _decode_time(c.read(threads=1), cattrs)
-    if _is_netcdf3(path):
+            t = _hdf5_coords(f, (timecoord,)).get(timecoord)
+    elif _is_netcdf3(path):
         from . import netcdf3
-        nc = netcdf3.NC3File(path)
-        if timecoord in nc.variables:
-            c = nc.variables[timecoord]
-            cattrs = {k: (v.item() if isinstance(v, np.generic) else v) for k, v in c.attrs.items()}
-            return _decode_time(nc.read(timecoord), cattrs)
-    if _is_grib(path):
+        t = _nc3_coords(netcdf3.NC3File(path), (timecoord,)).get(timecoord)
+    elif _is_grib(path):
         from . import grib
         return grib.open_index(path).select(var).time               # the valid times of the variable's messages, in time order
-    raise ValueError(f"cannot read a time coordinate from {path}")
+    if t is None:
+        raise ValueError(f"cannot read a time coordinate from {path}")
+    return t if isinstance(t, (pd.DatetimeIndex, CFTimeIndex)) else pd.DatetimeIndex(t)     # (datetime64 values stored as such)
 
 
 def _clip_box(dims, coords, xycoords, georegions, lon_is_360):
@@ -2321,65 +2356,126 @@ def _band_of_box(dims, shape, xycoords, box, lat_window):
     return tuple(out)
 
 
-def _hdf5_to_device(path, var, xycoords, timecoord, time_sel, georegions, lon_is_360, device, time_window=None, keep_packed=False):
-    """A chunked netCDF-4 variable through the streaming route (native inflate + unshuffle, GPU-side placement);
-    None when the variable does not qualify (contiguous, not time-leading, ...): the host route then reads it."""
-    from . import hdf5
-    f = hdf5.H5File(path)
-    try:
-        ds = f.datasets.get(var)
-        if ds is None or ds.layout[0] != "chunked" or ds.dims is None or len(ds.shape) != 3 or ds.dims[0] != timecoord:
-            return None
-        src = hdf5.ChunkSource(ds)
-        coords = {}
-        for d in src.dims:
-            if d in f.datasets and len(f.datasets[d].shape) == 1:
-                c = f.datasets[d]
-                cattrs = {k: (v.item() if isinstance(v, np.generic) else v) for k, v in c.attrs.items()}
-                vals = c.read(threads=1)
-                coords[d] = _decode_time(vals, cattrs) if " since " in str(cattrs.get("units", "")) else vals
-        if time_window is not None:
-            window = (int(time_window[0]), int(time_window[1]))
-        else:
-            window = _time_window(coords[timecoord], time_sel) if time_sel is not None and timecoord in coords else None
-        box = _clip_box(src.dims, coords, xycoords, georegions, lon_is_360) if georegions is not None else None
-        try:
-            data, _ = array_to_device(src, device=device, t_range=window, yx_box=box, keep_packed=keep_packed)
-        except ValueError:
-            return None
-        if keep_packed and packing_of(src) is not None:
-            from .packed import PackedCube
-            data = PackedCube(data, *packing_of(src))
-        if window is not None:
-            coords[timecoord] = coords[timecoord][window[0]:window[1]]
-        if box is not None:
-            coords[src.dims[1]] = coords[src.dims[1]][box[0]:box[1]]
-            coords[src.dims[2]] = coords[src.dims[2]][box[2]:box[3]]
-        return data, src, coords
-    finally:
-        f.close()
+class _StreamedSource:
+    """One variable of one store or file that a store-to-HBM route takes — what `_streamed_source` returns and `dataset_from_path`,
+    `distributed._step_bytes` and the CLI ask of it, whatever the container:
+
+    * ``dims``, ``shape``: time-major, as the tensor will lie in HBM (a time-last Zarr array reports its transposed order);
+    * ``dtype``: the stored type in native byte order; ``attrs``: the variable's attributes, Python numbers, not numpy scalars;
+    * ``name``: the variable's; ``packing``: what `packing_of` says of it (None: it cannot stay packed);
+    * ``coords()``: {dim: values} of the dimensions that have a coordinate, the time axis decoded;
+    * ``to_device(device, window, box, keep_packed)`` -> the tensor of steps ``window`` (None: all) and stored-axes ``box`` (None:
+      the whole grid), by the format's own streaming.  `ValueError`: the request is not for this route;
+    * ``takes(n_parts, time_window, lat_window)``: whether the route serves such a request on ``n_parts`` stores or files at all;
+    * ``host_route``: whether a `ValueError` sends the request on to the host route (a GRIB file has no other: it raises)."""
+
+    beside_bytes = 0                # bytes per cell of a stored-type buffer that lies beside the cube while it is read
+    host_route = True
+
+    def takes(self, n_parts, time_window, lat_window) -> bool:
+        return True
+
+    def step_bytes(self, keep_packed=False) -> int:
+        """Bytes one time step takes in HBM (the full stored grid: a clipped read takes less).  ``keep_packed`` (or
+        AGGFLY_HIP_KEEP_PACKED=1): a variable that stays packed counts its 2 stored bytes per cell."""
+        dt = np.dtype(self.dtype)
+        item = dt.itemsize if dt.kind == "f" else 4           # packed integers are unpacked to float32 in HBM ...
+        if self.packing is not None and keep_packed_requested(keep_packed):
+            item = 2                                          # ... unless the cube stays packed
+        return int(np.prod(self.shape[1:], dtype=np.int64)) * (item + self.beside_bytes)
 
 
-class _Nc3Source:
-    """A 3-D, time-leading short / int / float / double variable of a NetCDF classic file, from the header alone (`netcdf3.py`): what
-    `packing_of`, `_cf_in_hbm` and `DataArray` ask of a streamed source — ``dims``, ``shape``, ``dtype`` (native byte order;
-    ``var.dtype`` is big-endian as stored) and ``attrs``, in the Python forms the netCDF-4 route gives (numbers, not numpy scalars)."""
+def _resolve_request(dims, shape, coords, xycoords, timecoord, time_sel=None, time_window=None, georegions=None, lon_is_360=True,
+                     lat_window=None):
+    """What a request reads of a streamed source of ``dims`` / ``shape`` / ``coords``: -> (window, box), the time steps [k0, k1) and the
+    stored-axes box (a0, a1, b0, b1), each None for "all of it"."""
+    # a time selection on a time-leading (or time-last) array: only the chunks / steps that hold the selected steps are read (a
+    # decade out of a 40-year store reads a quarter of it); one that is no contiguous run is applied by `Dataset` after the load
+    window = None
+    if time_window is not None:
+        if not (dims and dims[0] == timecoord):
+            raise ValueError("time_window needs a time-leading or a time-last array")
+        window = (int(time_window[0]), int(time_window[1]))
+    elif time_sel is not None and dims and dims[0] == timecoord and timecoord in coords:
+        window = _time_window(coords[timecoord], time_sel)
+    # a clip to the regions' extent (`dataset.py:150-175`): only the chunks / rows that touch the box are read, and only the box
+    # reaches HBM; `Dataset` repeats the clip on the clipped grid (a no-op)
+    box = None
+    if georegions is not None and len(dims) == 3:
+        box = _clip_box(dims, coords, xycoords, georegions, lon_is_360)
+        if box is None and lat_window is not None:
+            raise ValueError("lat_window on a non-contiguous clip goes through the host route")
+    if lat_window is not None:
+        box = _band_of_box(dims, shape, xycoords, box, lat_window)
+    return window, box
 
-    def __init__(self, nc, var):
-        self.nc, self.var = nc, var
-        self.dims, self.shape, self.dtype = var.dims, var.shape, var.dtype.newbyteorder("=")
-        self.attrs = {k: (v.item() if isinstance(v, np.generic) else v) for k, v in var.attrs.items()}
+
+def _cut_coords(dims, coords, window, box) -> dict:
+    """``coords`` of what `_resolve_request`'s (window, box) read."""
+    out = dict(coords)
+    if window is not None:
+        out[dims[0]] = out[dims[0]][window[0]:window[1]]
+    if box is not None:
+        out[dims[1]] = out[dims[1]][box[0]:box[1]]
+        out[dims[2]] = out[dims[2]][box[2]:box[3]]
+    return out
+
+
+class _ZarrSource(_StreamedSource):
+    """The array ``var`` of a Zarr store.  A time-last array (latitude, longitude, time) — what the reference's converter writes — with
+    a codec the native decoder handles comes back time-major (`array_to_device(time_axis=2)`): ``dims`` / ``shape`` are those of the
+    tensor in HBM, and every window is cut on them."""
+
+    def __init__(self, path, var, xycoords, timecoord):
+        self.path, self.name = path, var
+        za = self.za = ZarrArray(os.path.join(path, var))
+        self.tlast = (len(za.dims) == 3 and za.dims[2] == timecoord and set(za.dims[:2]) == set(xycoords) and len(set(xycoords)) == 2
+                      and za.scatter_kind is not None)
+        major = (lambda t: (t[2], t[0], t[1])) if self.tlast else tuple
+        self.dims, self.shape, self.dtype, self.attrs, self.packing = major(za.dims), major(za.shape), za.dtype, za.attrs, packing_of(za)
+        if za.elem_filters and za.stored_dtype != za.dtype:    # converting element filters: the stored elements lie beside the cube
+            self.beside_bytes = za.stored_dtype.itemsize
 
     def coords(self):
-        out = {}
-        for d in self.dims:
-            c = self.nc.variables.get(d)
-            if c is not None and len(c.shape) == 1:
-                cattrs = {k: (v.item() if isinstance(v, np.generic) else v) for k, v in c.attrs.items()}
-                vals = self.nc.read(d)
-                vals = vals.astype(vals.dtype.newbyteorder("="))
-                out[d] = _decode_time(vals, cattrs) if " since " in str(cattrs.get("units", "")) else vals
-        return out
+        return _zarr_coords(self.path, self.za.dims)
+
+    def to_device(self, device, window, box, keep_packed):
+        return zarr_to_device(self.path, self.name, device=device, t_range=window, yx_box=box, keep_packed=keep_packed,
+                              time_axis=2 if self.tlast else 0)[0]
+
+
+class _H5Source(_StreamedSource):
+    """A chunked variable of a netCDF-4 file, from its object header (`hdf5.py`), through `array_to_device` (native inflate + unshuffle,
+    GPU-side placement).  The file is open only while it is read: by `_hdf5_source` for the header and the coordinates, by `to_device`
+    for the chunks."""
+
+    def __init__(self, path, ds, coords):
+        self.path, self.name, self._coords = path, ds.name, coords
+        self.dims, self.shape, self.dtype, self.attrs = tuple(ds.dims), tuple(ds.shape), ds.dtype, _py_attrs(ds.attrs, _H5_INTERNAL_ATTRS)
+        self.packing = packing_of(self)
+
+    def takes(self, n_parts, time_window, lat_window) -> bool:
+        return n_parts == 1 and lat_window is None
+
+    def coords(self):
+        return dict(self._coords)
+
+    def to_device(self, device, window, box, keep_packed):
+        from . import hdf5
+        with hdf5.H5File(self.path) as f:
+            return array_to_device(hdf5.ChunkSource(f.datasets[self.name]), device=device, t_range=window, yx_box=box, keep_packed=keep_packed)[0]
+
+
+def _hdf5_source(path, var, timecoord="time", any_layout=False):
+    """The `_H5Source` of ``var`` when the streaming route takes it — chunked, numeric, 3-D, time-leading, with dimension scales —
+    else None (contiguous, not time-leading, ...): the host route then reads the file.  ``any_layout``: a contiguous variable too,
+    for its header (`distributed._step_bytes`: the host route uploads it whole, packed if asked — the same bytes per step)."""
+    from . import hdf5
+    with hdf5.H5File(path) as f:
+        ds = f.datasets.get(var)
+        if ds is None or ds.dtype is None or ds.dims is None or len(ds.shape) != 3 or ds.dims[0] != timecoord:
+            return None
+        return _H5Source(path, ds, _hdf5_coords(f, ds.dims)) if any_layout or ds.layout[0] == "chunked" else None
 
 
 def _is_netcdf3(path) -> bool:
@@ -2401,90 +2497,203 @@ def _netcdf3_source(path, var, timecoord="time"):
     return _Nc3Source(nc, v)
 
 
-def _netcdf3_part_to_device(src, xycoords, timecoord, time_sel, georegions, lon_is_360, device, time_window=None, lat_window=None,
-                            keep_packed=False, threads: int = 16, slab_bytes: int = 128 << 20):
-    """One classic file into HBM: -> (tensor, source, coords).  Step ``t`` of the variable is one run of big-endian bytes at
-    ``plane_offset(t)``; slabs are whole time steps, a thread pool (the native reader's OpenMP team) `pread`s the rows of the
-    requested box of every step into the page-locked slab, packed densely, the slab crosses PCIe as stored (2 bytes per value for int16), and one kernel
-    (`hip.place_box_swapped`) reverses the bytes of every element and writes the box — the x clip included — into the cube.  The
-    host never touches the data.  CF mask and unpack follow in HBM as for every other format (`_cf_in_hbm`)."""
-    import torch
-    from . import hip
-    v = src.var
-    if os.environ.get("AGGFLY_HIP_SLAB_MB"):
-        slab_bytes = int(float(os.environ["AGGFLY_HIP_SLAB_MB"]) * (1 << 20))
-    post, need_post, out_np, wire = _cf_in_hbm(src.dtype, src.attrs)
-    if keep_packed and packing_of(src) is not None:
-        need_post, out_np = False, wire
-    coords = src.coords()
-    T, NY, NX = src.shape
-    if time_window is not None:
-        window = (int(time_window[0]), int(time_window[1]))
-        if not (0 <= window[0] <= window[1] <= T):
-            raise ValueError(f"time_window {window} outside the {T} steps of {v.name!r}")
-    else:
-        window = _time_window(coords[timecoord], time_sel) if time_sel is not None and timecoord in coords else None
-    box = None
-    if georegions is not None:
-        box = _clip_box(src.dims, coords, xycoords, georegions, lon_is_360)
-        if box is None and lat_window is not None:
-            raise ValueError("lat_window on a non-contiguous clip goes through the host route")
-    if lat_window is not None:
-        box = _band_of_box(src.dims, src.shape, xycoords, box, lat_window)
-    k_lo, k_hi = window if window is not None else (0, T)
-    a0, a1, b0, b1 = box if box is not None else (0, NY, 0, NX)
-    isz = src.dtype.itemsize
-    step_bytes = (a1 - a0) * NX * isz                                 # the rows of the box, whole: one run of the file per step
-    n = k_hi - k_lo
-    slab = max(1, min(slab_bytes, 1 << 30) // max(step_bytes, 1))
-    wire_t, out_t = _torch_dtype(wire), _torch_dtype(out_np)
-    # integers that become floats in HBM: the kernel writes the stored type beside the cube, the conversion is the copy into it
-    beside = torch.empty((min(slab, max(n, 1)), a1 - a0, b1 - b0), dtype=wire_t, device=device) if wire_t != out_t else None
-    stride, first = v.step_stride, (v.plane_offset(k_lo) if n > 0 else 0) + a0 * NX * isz
-    path = src.nc.path
+class _FileSource(_StreamedSource):
+    """A variable of a file whose time steps are read as they lie in it (NetCDF classic, GRIB)."""
 
-    def read(k0, k1, out):
-        # the native reader's team (`afcodec_read_packed`: pread, the ranges packed back to back): one range per step — or one for
-        # the slab where the steps follow each other in the file, which the team cuts into pieces itself.  (Python threads, each
-        # reading a run of steps, took 44 - 57 ms for the 8760 steps of the configs[0] cube where the team takes 18:
-        # profiles/netcdf3_ingest.txt.)
-        from . import codec
-        if stride == step_bytes:
-            locs = [(path, first + k0 * stride, (k1 - k0) * step_bytes)]
-        else:
-            locs = [(path, first + k * stride, step_bytes) for k in range(k0, k1)]
-        _, got = codec.read_packed(locs, out[:(k1 - k0) * step_bytes], align=1, threads=threads)
-        if any(int(g) != loc[2] for g, loc in zip(got, locs)):
-            raise OSError(f"{path}: the file ends inside the steps {k_lo + k0}..{k_lo + k1} of {v.name!r}")
+    def takes(self, n_parts, time_window, lat_window) -> bool:
+        return n_parts == 1 or time_window is None      # (on several files it counts steps of the concatenation: the host route cuts it)
 
-    def place(raw, dst, m):
-        blk = raw.view(wire_t).view(m, a1 - a0, NX)
-        into = dst if beside is None else beside[:m]
-        hip.place_box_swapped(blk, into, (0, 0, b0, m, a1 - a0, b1 - b0), (0, 0, 0))
-        if beside is not None:
-            dst.copy_(into)
-
-    data = stream_to_device(n, (a1 - a0, b1 - b0), src.dtype, read, slab, device, post if need_post else None, out_np, wire,
-                            place=place, stage_step_bytes=step_bytes)
-    if window is not None:
-        coords[timecoord] = coords[timecoord][window[0]:window[1]]
-    if box is not None:
-        coords[src.dims[1]] = coords[src.dims[1]][box[0]:box[1]]
-        coords[src.dims[2]] = coords[src.dims[2]][box[2]:box[3]]
-    return data, src, coords
+    def _steps(self, window):
+        """[k_lo, k_hi) of ``window`` (None: every step).  The chunked routes clamp a window (`_ScatterJob`); a file has no step outside its own."""
+        T = self.shape[0]
+        if window is not None and not (0 <= window[0] <= window[1] <= T):
+            raise ValueError(f"time_window {window} outside the {T} steps of {self.name!r}")
+        return window if window is not None else (0, T)
 
 
-class _GribSource:
-    """The messages of one variable of a GRIB file in time order (`grib.Field`), from the section headers alone: what `DataArray` and the
-    streaming route ask of a source — ``dims``, ``shape``, ``dtype`` (float32: a GRIB field has no stored type to keep) and ``attrs``."""
+class _Nc3Source(_FileSource):
+    """A 3-D, time-leading short / int / float / double variable of a NetCDF classic file, from the header alone (`netcdf3.py`);
+    ``var.dtype`` is big-endian as stored."""
+
+    def __init__(self, nc, var):
+        self.nc, self.var, self.name = nc, var, var.name
+        self.dims, self.shape, self.dtype, self.attrs = var.dims, var.shape, var.dtype.newbyteorder("="), _py_attrs(var.attrs)
+        self.packing = packing_of(self)
+
+    def coords(self):
+        return _nc3_coords(self.nc, self.dims)
+
+    def to_device(self, device, window, box, keep_packed, threads: int = 16, slab_bytes: int = 128 << 20):
+        """One classic file into HBM.  Step ``t`` of the variable is one run of big-endian bytes at
+        ``plane_offset(t)``; slabs are whole time steps, a thread pool (the native reader's OpenMP team) `pread`s the rows of the
+        requested box of every step into the page-locked slab, packed densely, the slab crosses PCIe as stored (2 bytes per value for int16), and one kernel
+        (`hip.place_box_swapped`) reverses the bytes of every element and writes the box — the x clip included — into the cube.  The
+        host never touches the data.  CF mask and unpack follow in HBM as for every other format (`_cf_in_hbm`)."""
+        import torch
+        from . import hip
+        src, v = self, self.var
+        slab_bytes = _slab_bytes(slab_bytes)
+        post, need_post, out_np, wire = _cf_in_hbm(src.dtype, src.attrs)
+        if keep_packed and src.packing is not None:
+            need_post, out_np = False, wire
+        T, NY, NX = src.shape
+        k_lo, k_hi = src._steps(window)
+        a0, a1, b0, b1 = box if box is not None else (0, NY, 0, NX)
+        isz = src.dtype.itemsize
+        step_bytes = (a1 - a0) * NX * isz                                 # the rows of the box, whole: one run of the file per step
+        n = k_hi - k_lo
+        slab = max(1, min(slab_bytes, 1 << 30) // max(step_bytes, 1))
+        wire_t, out_t = _torch_dtype(wire), _torch_dtype(out_np)
+        # integers that become floats in HBM: the kernel writes the stored type beside the cube, the conversion is the copy into it
+        beside = torch.empty((min(slab, max(n, 1)), a1 - a0, b1 - b0), dtype=wire_t, device=device) if wire_t != out_t else None
+        stride, first = v.step_stride, (v.plane_offset(k_lo) if n > 0 else 0) + a0 * NX * isz
+        path = src.nc.path
+
+        def read(k0, k1, out):
+            # the native reader's team (`afcodec_read_packed`: pread, the ranges packed back to back): one range per step — or one for
+            # the slab where the steps follow each other in the file, which the team cuts into pieces itself.  (Python threads, each
+            # reading a run of steps, took 44 - 57 ms for the 8760 steps of the configs[0] cube where the team takes 18:
+            # profiles/netcdf3_ingest.txt.)
+            from . import codec
+            if stride == step_bytes:
+                locs = [(path, first + k0 * stride, (k1 - k0) * step_bytes)]
+            else:
+                locs = [(path, first + k * stride, step_bytes) for k in range(k0, k1)]
+            _, got = codec.read_packed(locs, out[:(k1 - k0) * step_bytes], align=1, threads=threads)
+            if any(int(g) != loc[2] for g, loc in zip(got, locs)):
+                raise OSError(f"{path}: the file ends inside the steps {k_lo + k0}..{k_lo + k1} of {v.name!r}")
+
+        def place(raw, dst, m):
+            blk = raw.view(wire_t).view(m, a1 - a0, NX)
+            into = dst if beside is None else beside[:m]
+            hip.place_box_swapped(blk, into, (0, 0, b0, m, a1 - a0, b1 - b0), (0, 0, 0))
+            if beside is not None:
+                dst.copy_(into)
+
+        return stream_to_device(n, (a1 - a0, b1 - b0), src.dtype, read, slab, device, post if need_post else None, out_np, wire,
+                                place=place, stage_step_bytes=step_bytes)
+
+
+class _GribSource(_FileSource):
+    """The messages of one variable of a GRIB file in time order (`grib.Field`), from the section headers alone; ``dtype`` is float32
+    and ``packing`` None (a GRIB field has no stored type to keep: every step has its own R / E / D, so ``keep_packed`` is ignored).
+    Whatever `grib.py` or the unpack kernels refuse raises with its reason: a GRIB file has no other route to fall back to."""
+
+    packing, host_route = None, False
 
     def __init__(self, field, xycoords, timecoord):
-        self.field, self.path = field, field.path
+        self.field, self.path, self.name = field, field.path, field.var
         self.dims, self.shape, self.dtype, self.attrs = (timecoord, xycoords[1], xycoords[0]), field.shape, np.dtype(np.float32), dict(field.attrs)
 
     def coords(self):
         c = self.field.coords()
         return {self.dims[0]: c["time"], self.dims[1]: c["latitude"], self.dims[2]: c["longitude"]}
+
+    def to_device(self, device, window, box, keep_packed=False, threads: int = 16, slab_bytes: int = 128 << 20):
+        """One GRIB file into HBM, as `_Nc3Source.to_device` does it for a classic file.  Step ``t`` is one
+        message: slabs are whole time steps, the native reader's team `pread`s the packed bits of every step — without a bitmap only the
+        bytes that hold the rows of the requested box, with one the bitmap and the data section whole — into the page-locked slab, the slab
+        crosses PCIe as stored (2 bytes per value for ERA5's 16 bits), and `hip.grib_unpack` extracts the integers, scales them, writes NaN
+        where the bitmap has 0 and places the box — the x clip included — in the float32 cube.  The host never touches the data.  The
+        steps' ``nbits`` / ``E`` / ``D`` / ``R`` differ: each step has its record, with ``R``, ``2.0 ** E`` and ``10.0 ** -D`` as the
+        host route computes them.  Steps in complex packing (edition 2, templates 5.2 / 5.3) stage the whole body of their section 7 and go
+        to `hip.grib_unpack_complex`, which reads the group tables, cuts the values out, undoes the spatial differencing by running sums and
+        places the box; a file may mix them with simple-packed steps (a writer falls back to simple packing for a constant field)."""
+        import torch
+        from . import codec, hip
+        src = self
+        slab_bytes = _slab_bytes(slab_bytes)
+        T, NY, NX = src.shape
+        k_lo, k_hi = src._steps(window)
+        a0, a1, b0, b1 = box if box is not None else (0, NY, 0, NX)
+        msgs = src.field.messages[k_lo:k_hi]
+        n = len(msgs)
+        path = src.path
+        # what is staged of every step: (file offset, bytes) of the bitmap and of the packed bits, and the record that says so
+        rec = np.zeros(n, dtype=hip.GRIB_STEP)
+        arr = {k: v[k_lo:k_hi] for k, v in src.field.arrays().items()}
+        nb, d_off, d_len, m_off = arr["nbits"], arr["data_offset"], arr["data_length"], arr["bitmap_offset"]
+        has_map = m_off >= 0
+        # a step in complex packing (templates 5.2 / 5.3) has no random access: its section 7 is staged whole, like a step with a bitmap.
+        # kind: 0 simple packing, 1 + order complex packing (order 0: template 5.2) - `place` calls one entry per run of one kind
+        is_cx = arr["packing"] != 0
+        kind = np.where(is_cx, 1 + arr["order"], 0)
+        whole = has_map | is_cx
+        lo = np.where(whole, 0, (a0 * NX * nb) // 8)                         # simple packing without a bitmap: the bytes of rows [a0, a1) only
+        hi = np.where(whole, d_len, -((-a1 * NX * nb) // 8))
+        short = hi > d_len
+        if short.any():
+            k = int(np.argmax(short))
+            raise ValueError(f"{path}: the data section of the message at offset {msgs[k].offset} holds {int(d_len[k])} bytes, "
+                             f"{NY * NX} values of {int(nb[k])} bits need {int(hi[k])}")
+        map_bytes = np.where(has_map, (NY * NX + 7) // 8, 0)
+        rec["nbits"], rec["first_bit"] = nb, np.where(whole, 0, (a0 * NX * nb) & 7)
+        rec["first_point"], rec["data_bytes"] = np.where(whole, 0, a0 * NX), hi - lo
+        rec["R"], rec["s"], rec["d"] = arr["R"], arr["s"], arr["d"]
+        crec = np.zeros(n, dtype=hip.GRIB_CSTEP)                              # the records of the complex steps (unused rows for the others)
+        crec["data_bytes"], crec["nbits_ref"] = d_len, nb
+        for k in ("n_values", "n_groups", "ref_len", "last_len", "ref_width", "nbits_width", "len_inc", "nbits_len", "order", "extra", "R", "s", "d"):
+            crec[k] = arr[k]
+        max_groups = int(arr["n_groups"][is_cx].max()) if is_cx.any() else 0
+        pad4 = lambda v: (v + 3) // 4 * 4                                     # every staged range begins on a 4-byte boundary (`read_packed`, align=4)
+        step_bytes = pad4(map_bytes) + pad4(hi - lo)
+        row = int(step_bytes.max()) if n else 4
+        row = max(row, 4)
+        slab = max(1, min(slab_bytes, 1 << 30) // row)
+        scratch = None
+        if is_cx.any():
+            # the scratch of the complex steps (8 bytes per value and step, 16 per group, the rank tables, the tile sums) is capped at four
+            # slabs of staged bytes, and a slab holds no more steps than that serves
+            per_step = hip.grib_complex_scratch_bytes(1, NY * NX, max_groups)
+            slab = max(1, min(slab, (4 * min(slab_bytes, 1 << 30)) // per_step))
+            scratch = torch.empty(hip.grib_complex_scratch_bytes(min(slab, n), NY * NX, max_groups), dtype=torch.uint8, device=device)
+        rank = torch.empty(hip.grib_rank_bytes(min(slab, max(n, 1)), NY * NX), dtype=torch.uint8, device=device)
+        errors = torch.zeros(1, dtype=torch.int32, device=device)
+        pending = []                                                          # the records of the slab just read, for `place`
+
+        def read(k0, k1, out):
+            # one range per staged piece, packed back to back by the reader's team; a step's ranges follow each other in the slab
+            start = np.concatenate([[0], np.cumsum(step_bytes[k0:k1])])[:-1]
+            r, c = rec[k0:k1].copy(), crec[k0:k1].copy()
+            r["bitmap_off"] = c["bitmap_off"] = np.where(has_map[k0:k1], start, -1)
+            r["data_off"] = c["data_off"] = start + pad4(map_bytes[k0:k1])
+            # per step the bitmap, then the packed bits; pieces of no bytes (a field of 0 bits per value) are not asked for
+            two = lambda a_, b_: np.stack([a_, b_], axis=1).ravel()
+            keep = two(has_map[k0:k1], hi[k0:k1] > lo[k0:k1])
+            src_off, nbytes = two(m_off[k0:k1], (d_off + lo)[k0:k1])[keep], two(map_bytes[k0:k1], (hi - lo)[k0:k1])[keep]
+            want = two(r["bitmap_off"], r["data_off"])[keep]
+            if len(want):
+                locs = [(path, o, nby) for o, nby in zip(src_off.tolist(), nbytes.tolist())]
+                offs, got = codec.read_packed(locs, out[:(k1 - k0) * row], align=4, threads=threads)
+                if not np.array_equal(got, nbytes):
+                    raise OSError(f"{path}: the file ends inside the steps {k_lo + k0}..{k_lo + k1} of {src.field.var!r}")
+                if not np.array_equal(offs[:-1], want):
+                    raise RuntimeError("grib: the reader packed the staged ranges differently from the records")
+            pending[:] = [(r, c, kind[k0:k1])]
+
+        def place(raw, dst, m):
+            r, c, kd = pending[0]
+            grid, box = (NY, NX), (a0, b0, a1 - a0, b1 - b0)
+            if not kd.any():                                                  # simple packing throughout: one call, as ever
+                steps = torch.from_numpy(r.view(np.uint8).reshape(-1)).to(dst.device)
+                hip.grib_unpack(raw, steps, m, grid, box, dst, (0, 0, 0), rank, errors)
+                return
+            # runs of consecutive steps of one kind, each with its own records and its offset along time
+            cuts = np.concatenate([[0], np.flatnonzero(kd[1:] != kd[:-1]) + 1, [m]])
+            for i, j in zip(cuts[:-1].tolist(), cuts[1:].tolist()):
+                if kd[i] == 0:
+                    steps = torch.from_numpy(r[i:j].view(np.uint8).reshape(-1)).to(dst.device)
+                    hip.grib_unpack(raw, steps, j - i, grid, box, dst, (i, 0, 0), rank, errors)
+                else:
+                    steps = torch.from_numpy(c[i:j].view(np.uint8).reshape(-1)).to(dst.device)
+                    hip.grib_unpack_complex(raw, steps, j - i, int(kd[i]) - 1, max_groups, grid, box, dst, (i, 0, 0), scratch, errors)
+
+        data = stream_to_device(n, (a1 - a0, b1 - b0), np.float32, read, slab, device, None, np.float32, None, place=place, stage_step_bytes=row)
+        if n and int(errors.item()):
+            raise ValueError(f"{path}: {int(errors.item())} step(s) of {src.field.var!r} were refused by the unpack kernels (records outside the staged bytes"
+                             + ("; or group tables of complex packing that are unsound: widths above 32 bits, lengths that do not sum to the number "
+                                "of values, values beyond section 7 - `grib.GribFile.read` names which" if is_cx.any() else "") + ")")
+        return data
 
 
 def _is_grib(path) -> bool:
@@ -2512,139 +2721,38 @@ def _open_grib(path, var, xycoords=("longitude", "latitude"), timecoord="time", 
     return DataArray(src.field.file.read(src.field), src.dims, src.coords(), name=var, attrs=src.attrs)
 
 
-def _grib_part_to_device(src, xycoords, timecoord, time_sel, georegions, lon_is_360, device, time_window=None, lat_window=None,
-                         threads: int = 16, slab_bytes: int = 128 << 20):
-    """One GRIB file into HBM: -> (tensor, source, coords), as `_netcdf3_part_to_device` does it for a classic file.  Step ``t`` is one
-    message: slabs are whole time steps, the native reader's team `pread`s the packed bits of every step — without a bitmap only the
-    bytes that hold the rows of the requested box, with one the bitmap and the data section whole — into the page-locked slab, the slab
-    crosses PCIe as stored (2 bytes per value for ERA5's 16 bits), and `hip.grib_unpack` extracts the integers, scales them, writes NaN
-    where the bitmap has 0 and places the box — the x clip included — in the float32 cube.  The host never touches the data.  The
-    steps' ``nbits`` / ``E`` / ``D`` / ``R`` differ: each step has its record, with ``R``, ``2.0 ** E`` and ``10.0 ** -D`` as the
-    host route computes them.  Steps in complex packing (edition 2, templates 5.2 / 5.3) stage the whole body of their section 7 and go
-    to `hip.grib_unpack_complex`, which reads the group tables, cuts the values out, undoes the spatial differencing by running sums and
-    places the box; a file may mix them with simple-packed steps (a writer falls back to simple packing for a constant field)."""
-    import torch
-    from . import codec, hip
-    if os.environ.get("AGGFLY_HIP_SLAB_MB"):
-        slab_bytes = int(float(os.environ["AGGFLY_HIP_SLAB_MB"]) * (1 << 20))
+def _streamed_source(path, var, xycoords=("longitude", "latitude"), timecoord="time", engine=None, filter_by_keys=None):
+    """The `_StreamedSource` of ``var`` in the store or file ``path`` — the one probe of `dataset_from_path`, `distributed._step_bytes`
+    and the CLI — or None when no streaming route takes it.  ``engine``: the reader `dataset_from_path` was asked for, which narrows
+    the formats looked for.  A Zarr store or a classic file that cannot be read gives None (the host route then says why), a GRIB file
+    that `grib.py` refuses raises with its reason."""
+    if engine == "zarr" or (engine is None and _looks_like_zarr(path)):
+        try:
+            return _ZarrSource(path, var, xycoords, timecoord)
+        except ValueError:
+            return None
+    if engine in (None, "netcdf4", "h5netcdf") and _is_hdf5(path):
+        return _hdf5_source(path, var, timecoord)
+    if engine in (None, "scipy") and _is_netcdf3(path):
+        return _netcdf3_source(path, var, timecoord)
+    if engine in (None, "cfgrib") and _is_grib(path):
+        return _grib_source(path, var, xycoords, timecoord, filter_by_keys)
+    return None
+
+
+def _part_to_device(src, device, xycoords, timecoord, keep_packed=False, **request):
+    """One streamed source into HBM: -> (tensor, source, coords), tensor and coordinates cut to ``request`` (the ``time_sel``,
+    ``time_window``, ``georegions``, ``lon_is_360`` and ``lat_window`` of `dataset_from_path`; `_resolve_request`)."""
     coords = src.coords()
-    T, NY, NX = src.shape
-    if time_window is not None:
-        window = (int(time_window[0]), int(time_window[1]))
-        if not (0 <= window[0] <= window[1] <= T):
-            raise ValueError(f"time_window {window} outside the {T} steps of {src.field.var!r}")
-    else:
-        window = _time_window(coords[timecoord], time_sel) if time_sel is not None else None
-    box = None
-    if georegions is not None:
-        box = _clip_box(src.dims, coords, xycoords, georegions, lon_is_360)
-        if box is None and lat_window is not None:
-            raise ValueError("lat_window on a non-contiguous clip goes through the host route")
-    if lat_window is not None:
-        box = _band_of_box(src.dims, src.shape, xycoords, box, lat_window)
-    k_lo, k_hi = window if window is not None else (0, T)
-    a0, a1, b0, b1 = box if box is not None else (0, NY, 0, NX)
-    msgs = src.field.messages[k_lo:k_hi]
-    n = len(msgs)
-    path = src.path
-    # what is staged of every step: (file offset, bytes) of the bitmap and of the packed bits, and the record that says so
-    rec = np.zeros(n, dtype=hip.GRIB_STEP)
-    arr = {k: v[k_lo:k_hi] for k, v in src.field.arrays().items()}
-    nb, d_off, d_len, m_off = arr["nbits"], arr["data_offset"], arr["data_length"], arr["bitmap_offset"]
-    has_map = m_off >= 0
-    # a step in complex packing (templates 5.2 / 5.3) has no random access: its section 7 is staged whole, like a step with a bitmap.
-    # kind: 0 simple packing, 1 + order complex packing (order 0: template 5.2) - `place` calls one entry per run of one kind
-    is_cx = arr["packing"] != 0
-    kind = np.where(is_cx, 1 + arr["order"], 0)
-    whole = has_map | is_cx
-    lo = np.where(whole, 0, (a0 * NX * nb) // 8)                         # simple packing without a bitmap: the bytes of rows [a0, a1) only
-    hi = np.where(whole, d_len, -((-a1 * NX * nb) // 8))
-    short = hi > d_len
-    if short.any():
-        k = int(np.argmax(short))
-        raise ValueError(f"{path}: the data section of the message at offset {msgs[k].offset} holds {int(d_len[k])} bytes, "
-                         f"{NY * NX} values of {int(nb[k])} bits need {int(hi[k])}")
-    map_bytes = np.where(has_map, (NY * NX + 7) // 8, 0)
-    rec["nbits"], rec["first_bit"] = nb, np.where(whole, 0, (a0 * NX * nb) & 7)
-    rec["first_point"], rec["data_bytes"] = np.where(whole, 0, a0 * NX), hi - lo
-    rec["R"], rec["s"], rec["d"] = arr["R"], arr["s"], arr["d"]
-    crec = np.zeros(n, dtype=hip.GRIB_CSTEP)                              # the records of the complex steps (unused rows for the others)
-    crec["data_bytes"], crec["nbits_ref"] = d_len, nb
-    for k in ("n_values", "n_groups", "ref_len", "last_len", "ref_width", "nbits_width", "len_inc", "nbits_len", "order", "extra", "R", "s", "d"):
-        crec[k] = arr[k]
-    max_groups = int(arr["n_groups"][is_cx].max()) if is_cx.any() else 0
-    pad4 = lambda v: (v + 3) // 4 * 4                                     # every staged range begins on a 4-byte boundary (`read_packed`, align=4)
-    step_bytes = pad4(map_bytes) + pad4(hi - lo)
-    row = int(step_bytes.max()) if n else 4
-    row = max(row, 4)
-    slab = max(1, min(slab_bytes, 1 << 30) // row)
-    scratch = None
-    if is_cx.any():
-        # the scratch of the complex steps (8 bytes per value and step, 16 per group, the rank tables, the tile sums) is capped at four
-        # slabs of staged bytes, and a slab holds no more steps than that serves
-        per_step = hip.grib_complex_scratch_bytes(1, NY * NX, max_groups)
-        slab = max(1, min(slab, (4 * min(slab_bytes, 1 << 30)) // per_step))
-        scratch = torch.empty(hip.grib_complex_scratch_bytes(min(slab, n), NY * NX, max_groups), dtype=torch.uint8, device=device)
-    rank = torch.empty(hip.grib_rank_bytes(min(slab, max(n, 1)), NY * NX), dtype=torch.uint8, device=device)
-    errors = torch.zeros(1, dtype=torch.int32, device=device)
-    pending = []                                                          # the records of the slab just read, for `place`
-
-    def read(k0, k1, out):
-        # one range per staged piece, packed back to back by the reader's team; a step's ranges follow each other in the slab
-        start = np.concatenate([[0], np.cumsum(step_bytes[k0:k1])])[:-1]
-        r, c = rec[k0:k1].copy(), crec[k0:k1].copy()
-        r["bitmap_off"] = c["bitmap_off"] = np.where(has_map[k0:k1], start, -1)
-        r["data_off"] = c["data_off"] = start + pad4(map_bytes[k0:k1])
-        # per step the bitmap, then the packed bits; pieces of no bytes (a field of 0 bits per value) are not asked for
-        two = lambda a_, b_: np.stack([a_, b_], axis=1).ravel()
-        keep = two(has_map[k0:k1], hi[k0:k1] > lo[k0:k1])
-        src_off, nbytes = two(m_off[k0:k1], (d_off + lo)[k0:k1])[keep], two(map_bytes[k0:k1], (hi - lo)[k0:k1])[keep]
-        want = two(r["bitmap_off"], r["data_off"])[keep]
-        if len(want):
-            locs = [(path, o, nby) for o, nby in zip(src_off.tolist(), nbytes.tolist())]
-            offs, got = codec.read_packed(locs, out[:(k1 - k0) * row], align=4, threads=threads)
-            if not np.array_equal(got, nbytes):
-                raise OSError(f"{path}: the file ends inside the steps {k_lo + k0}..{k_lo + k1} of {src.field.var!r}")
-            if not np.array_equal(offs[:-1], want):
-                raise RuntimeError("grib: the reader packed the staged ranges differently from the records")
-        pending[:] = [(r, c, kind[k0:k1])]
-
-    def place(raw, dst, m):
-        r, c, kd = pending[0]
-        grid, box = (NY, NX), (a0, b0, a1 - a0, b1 - b0)
-        if not kd.any():                                                  # simple packing throughout: one call, as ever
-            steps = torch.from_numpy(r.view(np.uint8).reshape(-1)).to(dst.device)
-            hip.grib_unpack(raw, steps, m, grid, box, dst, (0, 0, 0), rank, errors)
-            return
-        # runs of consecutive steps of one kind, each with its own records and its offset along time
-        cuts = np.concatenate([[0], np.flatnonzero(kd[1:] != kd[:-1]) + 1, [m]])
-        for i, j in zip(cuts[:-1].tolist(), cuts[1:].tolist()):
-            if kd[i] == 0:
-                steps = torch.from_numpy(r[i:j].view(np.uint8).reshape(-1)).to(dst.device)
-                hip.grib_unpack(raw, steps, j - i, grid, box, dst, (i, 0, 0), rank, errors)
-            else:
-                steps = torch.from_numpy(c[i:j].view(np.uint8).reshape(-1)).to(dst.device)
-                hip.grib_unpack_complex(raw, steps, j - i, int(kd[i]) - 1, max_groups, grid, box, dst, (i, 0, 0), scratch, errors)
-
-    data = stream_to_device(n, (a1 - a0, b1 - b0), np.float32, read, slab, device, None, np.float32, None, place=place, stage_step_bytes=row)
-    if n and int(errors.item()):
-        raise ValueError(f"{path}: {int(errors.item())} step(s) of {src.field.var!r} were refused by the unpack kernels (records outside the staged bytes"
-                         + ("; or group tables of complex packing that are unsound: widths above 32 bits, lengths that do not sum to the number "
-                            "of values, values beyond section 7 - `grib.GribFile.read` names which" if is_cx.any() else "") + ")")
-    if window is not None:
-        coords[timecoord] = coords[timecoord][window[0]:window[1]]
-    if box is not None:
-        coords[src.dims[1]] = coords[src.dims[1]][box[0]:box[1]]
-        coords[src.dims[2]] = coords[src.dims[2]][box[2]:box[3]]
-    return data, src, coords
+    window, box = _resolve_request(src.dims, src.shape, coords, xycoords, timecoord, **request)
+    return src.to_device(device, window, box, keep_packed), src, _cut_coords(src.dims, coords, window, box)
 
 
-class _TimeMajor:
-    """A time-last `ZarrArray` as its tensor lies in HBM after `array_to_device(time_axis=2)`: the dimensions in time-major order,
-    the attributes as stored — what `_join_device_parts` and the `DataArray` of `dataset_from_path` ask of a source."""
-
-    def __init__(self, za, dims):
-        self.za, self.dims, self.attrs = za, tuple(dims), za.attrs
+def _concat_time(times):
+    """The time coordinates of the parts of a multi-file dataset as one index, on a CF calendar (`CFTimeIndex`) as on the standard one."""
+    if isinstance(times[0], CFTimeIndex):
+        return CFTimeIndex(np.concatenate([t.seconds for t in times]), times[0].calendar)
+    return pd.DatetimeIndex(np.concatenate([np.asarray(t) for t in times]))
 
 
 def _join_device_parts(got, rules, timecoord):
@@ -2659,14 +2767,9 @@ def _join_device_parts(got, rules, timecoord):
     import torch
     if any(g[1].dims != got[0][1].dims or g[1].dims[0] != timecoord for g in got):
         raise ValueError("stores of a multi-file dataset must share their (time-leading) dimensions")
-    t0 = got[0][2][timecoord]
-    if isinstance(t0, CFTimeIndex):
-        time = CFTimeIndex(np.concatenate([g[2][timecoord].seconds for g in got]), t0.calendar)
-    else:
-        time = pd.DatetimeIndex(np.concatenate([np.asarray(g[2][timecoord]) for g in got]))
     coords = dict(got[0][2])
-    coords[timecoord] = time
-    if rules is not None:                   # (the parts were cut by time_window / time_sel already: the bounds are those of what was read)
+    coords[timecoord] = _concat_time([g[2][timecoord] for g in got])
+    if rules is not None:                  # (the parts were cut by time_window / time_sel already: the bounds are those of what was read)
         from .packed import PackedCube
         data = PackedCube.concat([PackedCube(g[0], *r) for g, r in zip(got, rules)])
     else:
@@ -2730,102 +2833,30 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
     paths = sorted(glob.glob(path)) if isinstance(path, str) and "*" in path else (list(path) if isinstance(path, (list, tuple)) else [path])
     if not paths:
         raise FileNotFoundError(path)
-    engine = kwargs.pop("engine", None)
-    if device is not None and all(engine == "zarr" or (engine is None and _looks_like_zarr(p)) for p in paths):
-
-        # several stores stay packed when each has a packing and all share their signedness: one unpack rule per store, in time order
-        rules = packed_rules_of([packing_of(ZarrArray(os.path.join(p_, var))) for p_ in paths]) if keep_packed else None
-        stay_packed = rules is not None
-
-        def part_to_device(path1):
-            za = ZarrArray(os.path.join(path1, var))
-            coords = {}
-            for d in za.dims:
-                cp = os.path.join(path1, d)
-                if is_zarr_array(cp):
-                    c = ZarrArray(cp)
-                    v = c.read(threads=1)
-                    coords[d] = _decode_time(v, c.attrs) if " since " in str(c.attrs.get("units", "")) else v
-            # a time-last store (latitude, longitude, time) — what the reference's converter writes — comes back time-major:
-            # below, `dims` / `shape` are those of the tensor in HBM, and every window is cut on them
-            dims, shape = za.dims, za.shape
-            tlast = (len(dims) == 3 and dims[2] == timecoord and set(dims[:2]) == set(xycoords) and len(set(xycoords)) == 2
-                     and za.scatter_kind is not None)
-            if tlast:
-                dims, shape = (dims[2], dims[0], dims[1]), (shape[2], shape[0], shape[1])
-            # a time selection on a time-leading (or time-last) store: only the chunks that hold the selected steps are
-            # read and decoded (a decade out of a 40-year store reads a quarter of it)
-            window = None
-            if time_window is not None:
-                if not (dims and dims[0] == timecoord):
-                    raise ValueError("time_window needs a time-leading or a time-last array")
-                window = (int(time_window[0]), int(time_window[1]))
-            elif time_sel is not None and dims and dims[0] == timecoord and timecoord in coords:
-                window = _time_window(coords[timecoord], time_sel)
-            # a clip to the regions' extent (`dataset.py:150-175`): only the chunks that touch the box are read,
-            # and only the box reaches HBM; `Dataset` repeats the clip on the clipped grid (a no-op)
-            box = None
-            if georegions is not None and len(dims) == 3:
-                box = _clip_box(dims, coords, xycoords, georegions, lon_is_360)
-                if box is None and lat_window is not None:
-                    raise ValueError("lat_window on a non-contiguous clip goes through the host route")
-            if lat_window is not None:
-                box = _band_of_box(dims, shape, xycoords, box, lat_window)
-            data, za = zarr_to_device(path1, var, device=device, t_range=window, yx_box=box, keep_packed=stay_packed,
-                                      time_axis=2 if tlast else 0)
-            if window is not None:
-                coords[timecoord] = coords[timecoord][window[0]:window[1]]
-            if box is not None:
-                coords[dims[1]] = coords[dims[1]][box[0]:box[1]]
-                coords[dims[2]] = coords[dims[2]][box[2]:box[3]]
-            return data, (_TimeMajor(za, dims) if tlast else za), coords
-
-        try:
-            data, za, coords = _join_device_parts([part_to_device(p_) for p_ in paths], rules, timecoord)
-        except ValueError:
-            data = None
-        if data is not None:
-            da = DataArray(data, za.dims, coords, name=var, attrs=za.attrs)
-            # a band was cut out of the already clipped box: the clip is not repeated on the band's own grid
-            return Dataset(da, xycoords=xycoords, timecoord=timecoord, time_sel=time_sel, lon_is_360=lon_is_360,
-                           preprocess=preprocess, georegions=None if lat_window is not None else georegions, time_fix=time_fix, name=name)
-    if device is not None and lat_window is None and len(paths) == 1 and engine in (None, "netcdf4", "h5netcdf") and _is_hdf5(paths[0]):
-        got = _hdf5_to_device(paths[0], var, xycoords, timecoord, time_sel, georegions, lon_is_360, device, time_window, keep_packed)
+    engine, grib_filter = kwargs.pop("engine", None), _grib_filter(kwargs)
+    first = _streamed_source(paths[0], var, xycoords, timecoord, engine, grib_filter) if device is not None else None
+    if first is not None and first.takes(len(paths), time_window, lat_window):
+        # the streaming routes (`_StreamedSource`): every store or file is probed and streamed into HBM under the same request, the parts
+        # are joined along time.  Several — yearly or monthly, each with its own packing — stay packed when each has a packing and all
+        # share their signedness: one unpack rule per part.  A `ValueError` on the way sends the request on to the host route below —
+        # but for GRIB files, which have no other
+        got = None
+        srcs = [first] + [_streamed_source(p, var, xycoords, timecoord, engine, grib_filter) for p in paths[1:]]
+        if all(type(s_) is type(first) for s_ in srcs):
+            rules = packed_rules_of([s_.packing for s_ in srcs]) if keep_packed else None
+            try:
+                got = _join_device_parts([_part_to_device(s_, device, xycoords, timecoord, rules is not None, time_sel=time_sel,
+                                                          time_window=time_window, georegions=georegions, lon_is_360=lon_is_360,
+                                                          lat_window=lat_window) for s_ in srcs], rules, timecoord)
+            except ValueError:
+                if not first.host_route:
+                    raise
         if got is not None:
             data, src, coords = got
             da = DataArray(data, src.dims, coords, name=var, attrs=src.attrs)
-            return Dataset(da, xycoords=xycoords, timecoord=timecoord, time_sel=time_sel, lon_is_360=lon_is_360,
-                           preprocess=preprocess, georegions=georegions, time_fix=time_fix, name=name)
-    if device is not None and engine in (None, "scipy") and (len(paths) == 1 or time_window is None) and all(_is_netcdf3(p) for p in paths):
-        # NetCDF classic files: the steps' big-endian bytes go from the file to HBM as stored and are swapped there; several
-        # files — one per year or month, each with its own packing — stay packed under the Zarr branch's rule (a time_window on
-        # several files counts steps of the concatenation: the host route below cuts it, as before)
-        srcs = [_netcdf3_source(p, var, timecoord) for p in paths]
-        data = None
-        if all(s_ is not None for s_ in srcs):
-            try:
-                rules = packed_rules_of([packing_of(s_) for s_ in srcs]) if keep_packed else None
-                data, src, coords = _join_device_parts(
-                    [_netcdf3_part_to_device(s_, xycoords, timecoord, time_sel, georegions, lon_is_360, device, time_window, lat_window,
-                                             keep_packed=rules is not None) for s_ in srcs], rules, timecoord)
-            except ValueError:
-                data = None
-        if data is not None:
-            da = DataArray(data, src.dims, coords, name=var, attrs=src.attrs)
+            # a band was cut out of the already clipped box: the clip is not repeated on the band's own grid
             return Dataset(da, xycoords=xycoords, timecoord=timecoord, time_sel=time_sel, lon_is_360=lon_is_360,
                            preprocess=preprocess, georegions=None if lat_window is not None else georegions, time_fix=time_fix, name=name)
-    grib_filter = _grib_filter(kwargs)
-    if device is not None and engine in (None, "cfgrib") and (len(paths) == 1 or time_window is None) and all(_is_grib(p) for p in paths):
-        # GRIB files: the packed bits of every message go from the file to HBM as stored and are unpacked there — always: the only other
-        # route is the numpy decode below.  What `grib.py` refuses raises with its reason.  (A time_window on several files counts steps
-        # of the concatenation: the host route below cuts it.)  ``keep_packed`` leaves the cube float32: every step has its own R / E / D.
-        srcs = [_grib_source(p, var, xycoords, timecoord, grib_filter) for p in paths]
-        data, src, coords = _join_device_parts(
-            [_grib_part_to_device(s_, xycoords, timecoord, time_sel, georegions, lon_is_360, device, time_window, lat_window) for s_ in srcs],
-            None, timecoord)
-        da = DataArray(data, src.dims, coords, name=var, attrs=src.attrs)
-        return Dataset(da, xycoords=xycoords, timecoord=timecoord, time_sel=time_sel, lon_is_360=lon_is_360,
-                       preprocess=preprocess, georegions=None if lat_window is not None else georegions, time_fix=time_fix, name=name)
     parts = []
     for p in paths:
         if engine == "zarr" or (engine is None and _looks_like_zarr(p)):
@@ -2846,13 +2877,8 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
         tdim = timecoord
         ax = parts[0].dims.index(tdim)
         data = np.concatenate([p_.values for p_ in parts], axis=ax)
-        t0 = parts[0].coords[tdim]
-        if isinstance(t0, CFTimeIndex):
-            time = CFTimeIndex(np.concatenate([p_.coords[tdim].seconds for p_ in parts]), t0.calendar)
-        else:
-            time = pd.DatetimeIndex(np.concatenate([np.asarray(p_.coords[tdim]) for p_ in parts]))
         coords = dict(parts[0].coords)
-        coords[tdim] = time
+        coords[tdim] = _concat_time([p_.coords[tdim] for p_ in parts])
         da = DataArray(data, parts[0].dims, coords, name=var)
         preprocess = None
     else:

@@ -235,7 +235,7 @@ int afhip_delta_decode(void* stage_dev, int64_t n_chunks, int64_t chunk_elems, i
 int afhip_fso_decode(const void* src_dev, void* dst_dev, int64_t n, int src_type, int dst_type,
                      double scale, double offset, void* stream);
 
-/* GRIB fields (editions 1 and 2, simple packing) unpacked in HBM: aggfly_amd/io.py `_grib_part_to_device`, aggfly_amd/grib.py.
+/* GRIB fields (editions 1 and 2, simple packing) unpacked in HBM: aggfly_amd/io.py `_GribSource.to_device`, aggfly_amd/grib.py.
  * stage_dev (4-byte aligned, stage_bytes a multiple of 4) holds, as they lie in the file, the packed bits (and the bitmaps) of n_steps fields of one NY x NX grid; steps_dev one
  * record per field: data_off / data_bytes — its staged packed bits; first_point / first_bit — the value index (= grid point; only
  * without a bitmap) and the bit (0..7, from the most significant) of the first staged byte where that value begins, so that a step

@@ -210,7 +210,7 @@ def main():
                 (src, _), s0 = timed(lambda: head_of(path))
                 afio.stream_to_device = reads_only
                 try:
-                    _, s1 = timed(lambda: afio._netcdf3_part_to_device(src, ("longitude", "latitude"), "time", None, geo, True, "cuda"))
+                    _, s1 = timed(lambda: afio._part_to_device(src, "cuda", ("longitude", "latitude"), "time", georegions=geo))
                 finally:
                     afio.stream_to_device = real_stream
                 if i:

@@ -558,6 +558,39 @@ def test_netcdf4_chunked_variable_streams_into_hbm(torch_cuda, monkeypatch):
     assert ("zlib", 4) in calls and "raw" in calls                                 # the native route really ran
 
 
+def _nc4_box():
+    # the fixtures' grid: latitudes 50 - 0.25 i (9 rows), longitudes 230 + 0.25 j (14 cells); centroids within half a cell (0.125) of
+    # the extent: 48.6 - 0.125 .. 49.4 + 0.125 -> 49.5 .. 48.5, rows 2..6; 230.7 - 0.125 .. 232.4 + 0.125 -> 230.75 .. 232.5, cells 3..10
+    return af.GeoRegions(pd.DataFrame({"geoid": ["a"], "minx": [-129.3], "miny": [48.6], "maxx": [-127.6], "maxy": [49.4]}))
+
+
+@pytest.mark.parametrize("fn", ["nc4_like.nc", "unlimited_time.nc"])
+@pytest.mark.parametrize("asked, cut", [
+    ({"time_window": (5, 23)}, {"time": slice(5, 23)}),
+    ({"time_sel": slice("2000-01-03", "2000-01-05")}, {"time": slice(8, 20)}),             # 6-hourly from 2000-01-01 00:00
+    ({"georegions": _nc4_box}, {"latitude": slice(2, 7), "longitude": slice(3, 11)})], ids=["time_window", "time_sel", "georegions"])
+def test_netcdf4_windows_and_boxes_cut_the_streamed_read(torch_cuda, monkeypatch, fn, asked, cut):
+    """A chunked netCDF-4 variable under a step window, a time selection and a clip to the regions' extent: only that reaches HBM, and
+    it equals the host read cut to the same steps and cells, bit for bit.  The host route is not an answer here."""
+    from aggfly_amd import io as afio
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hdf5", fn)
+    want = af.dataset_from_path(path, "t2m").da.isel(**cut)
+
+    def refuse(*a, **k):
+        raise AssertionError(f"{path}: the host route was taken")
+    monkeypatch.setattr(afio, "_open_hdf5", refuse)
+    asked = {k: (v() if callable(v) else v) for k, v in asked.items()}
+    dev = af.dataset_from_path(path, "t2m", device="cuda", **asked)
+    assert dev.cube().is_cuda
+    assert tuple(dev.da.dims) == tuple(want.dims)
+    got, host = np.ascontiguousarray(dev.da.values), np.ascontiguousarray(want.values)
+    assert got.dtype == host.dtype == np.float32 and got.shape == host.shape and 0 < got.size < 37 * 9 * 14
+    np.testing.assert_array_equal(got.view(np.uint32), host.view(np.uint32))
+    assert dev.time.equals(want.coords["time"])
+    np.testing.assert_array_equal(dev.latitude, want.coords["latitude"])
+    np.testing.assert_array_equal(dev.longitude, want.coords["longitude"])
+
+
 def test_packed_int16_store_streams_packed_and_unpacks_in_hbm(torch_cuda, tmp_path):
     """ERA5-style packing (int16 + scale_factor / add_offset / _FillValue): the streaming route moves the
     packed integers over PCIe and applies the CF decoding in HBM — bit-identical to the host route, for

@@ -297,7 +297,7 @@ def test_every_case_streams_into_hbm(torch_cuda, case, files, host, no_host_rout
 
 
 def test_three_kinds_in_one_batch_around_a_clipped_box(torch_cuda, tmp_path, no_host_route, monkeypatch):
-    """Steps of 5.0, 5.2 and 5.3 (orders 2 and 1) in one slab of `_grib_part_to_device`, rows 1..3 of the grid: each run of one kind goes
+    """Steps of 5.0, 5.2 and 5.3 (orders 2 and 1) in one slab of `_GribSource.to_device`, rows 1..3 of the grid: each run of one kind goes
     to its entry with its own records and time offset.  Every call is repeated here into a larger cube full of a sentinel, at an offset:
     the cells around the box keep it."""
     torch = torch_cuda
