@@ -91,6 +91,7 @@ def load():
         lib.afcodec_blosc_zstd_encode_plan.argtypes = lib.afcodec_blosc_encode_plan.argtypes
         lib.afcodec_read_packed.argtypes = [C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
                                             C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+        lib.afcodec_aec_decode.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -101,7 +102,7 @@ EXPORTS = ("afcodec_last_error", "afcodec_have", "afcodec_blosc_info", "afcodec_
            "afcodec_zstd_plan", "afcodec_zstd_scratch_bytes", "afcodec_zstd_emulate",
            "afcodec_inflate_plan", "afcodec_inflate_scratch_bytes", "afcodec_inflate_emulate",
            "afcodec_blosc_plan", "afcodec_blosc_encode", "afcodec_lz4_encode_emulate", "afcodec_blosc_encode_plan",
-           "afcodec_zstd_encode_block_emulate", "afcodec_zstd_encode_scratch_bytes", "afcodec_blosc_zstd_encode_plan")
+           "afcodec_zstd_encode_block_emulate", "afcodec_zstd_encode_scratch_bytes", "afcodec_blosc_zstd_encode_plan", "afcodec_aec_decode")
 
 
 def _err(lib, what):
@@ -687,3 +688,14 @@ def inflate_emulate(base: np.ndarray, streams: np.ndarray, shuf: np.ndarray, pla
                                 plan.n_pblocks, plan.n_seqs, plan.n_pieces, plan.dec_bytes, plan.tmp_bytes, scratch.ctypes.data,
                                 out.ctypes.data, C.byref(err), C.byref(rounds))
     return int(err.value), int(rounds.value)
+
+
+def aec_decode(data, n_values: int, nbits: int, flags: int, block_size: int, rsi: int) -> np.ndarray:
+    """`afcodec_aec_decode`: the ``n_values`` samples (uint32) of one CCSDS / AEC stream as libaec writes it (the body of section 7 of
+    a GRIB2 message in template 5.42).  ``flags`` 8: the preprocessor; a damaged or truncated stream raises `CodecError`."""
+    lib = load()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = np.empty(int(n_values), dtype=np.uint32)
+    if lib.afcodec_aec_decode(buf.ctypes.data, buf.nbytes, int(n_values), int(nbits), int(flags), int(block_size), int(rsi), out.ctypes.data):
+        raise _err(lib, "aec_decode")
+    return out

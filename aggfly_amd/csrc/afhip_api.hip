@@ -807,8 +807,80 @@ extern "C" int afhip_grib_unpack_complex(const void* stage_dev, int64_t stage_by
     // spatial differencing undone: the launches of afhip_delta_decode, over n_steps chunks of NP int64 elements
     for (int k = 0; k < order; ++k)
         delta_launch<uint64_t>(vals, (char*)scratch_dev + L.sums, n_steps, NP, delta_tiles_per_chunk(NP, 8), s);
-    hipLaunchKernelGGL(k_grib_cplace, dim3((unsigned)((lanes + GRIB_WG - 1) / GRIB_WG)), dim3(GRIB_WG), 0, s, stage, stage_bytes, recs, n_steps, g,
-                       (const uint32_t*)rank, max_groups, (const int64_t*)groups, (const int64_t*)vals, (float*)cube_dev);
+    hipLaunchKernelGGL((k_grib_cplace<GribCStep, GribCVals>), dim3((unsigned)((lanes + GRIB_WG - 1) / GRIB_WG)), dim3(GRIB_WG), 0, s, stage, stage_bytes,
+                       recs, n_steps, g, (const uint32_t*)rank, GribCVals{max_groups, NP, (const int64_t*)groups, (const int64_t*)vals}, (float*)cube_dev);
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
+// ---- GRIB CCSDS packing (template 5.42): the scratch of one call, in bytes from its start ----
+struct GribALayout { int64_t rank, sound, table, vals, total; };
+// false: sizes that afhip_grib_unpack_ccsds refuses (negative, beyond 2^31 - 1, a product that overflows, beyond one launch)
+static bool grib_ccsds_layout(int64_t n_steps, int64_t n_points, int64_t max_rsis, GribALayout* L) {
+    if (n_steps < 0 || n_steps > 0x7fffffff || n_points <= 0 || n_points > 0x7fffffff || max_rsis < 0 || max_rsis > 0x7fffffff) return false;
+    const int64_t lim = (int64_t)1 << 60, per_step = max_rsis * 8 + n_points * 4 + grib_rank_words(n_points) * 4 + 4;
+    if (n_steps && per_step > lim / n_steps) return false;
+    auto up16 = [](int64_t v) { return (v + 15) / 16 * 16; };
+    L->rank = 0;
+    L->sound = up16(n_steps * grib_rank_words(n_points) * 4);
+    L->table = L->sound + up16(n_steps * 4);
+    L->vals = L->table + up16(n_steps * max_rsis * 8);
+    L->total = L->vals + up16(n_steps * n_points * 4);
+    return true;
+}
+
+extern "C" int64_t afhip_grib_ccsds_scratch_bytes(int64_t n_steps, int64_t n_points, int64_t max_rsis) {
+    GribALayout L;
+    return grib_ccsds_layout(n_steps, n_points, max_rsis, &L) ? L.total : -1;
+}
+
+extern "C" int afhip_grib_unpack_ccsds(const void* stage_dev, int64_t stage_bytes, const afhip_grib_astep* steps_dev, int64_t n_steps,
+                                       int64_t max_rsis, int64_t NY, int64_t NX, int64_t y0, int64_t x0, int64_t ny, int64_t nx,
+                                       void* cube_dev, int cube_elem_size, int64_t cube_nt, int64_t cube_NY, int64_t cube_NX,
+                                       int64_t t0, int64_t cy, int64_t cx, void* scratch_dev, int64_t scratch_bytes, int32_t* errors_dev, void* stream) {
+    static_assert(sizeof(afhip_grib_astep) == sizeof(aec_step) && sizeof(aec_step) == 72, "record layouts");
+    if (!stage_dev || !steps_dev || !cube_dev || !scratch_dev || !errors_dev || stage_bytes < 0 || n_steps < 0)
+        return fail(AFHIP_E_INVALID, "grib_unpack_ccsds: bad arguments");
+    if (cube_elem_size != 4) return fail(AFHIP_E_INVALID, "grib_unpack_ccsds: the cube must be float32 (4-byte elements, got %d)", cube_elem_size);
+    if (NY <= 0 || NX <= 0 || NY > 0x7fffffff / NX || y0 < 0 || x0 < 0 || ny < 0 || nx < 0 || ny > NY - y0 || nx > NX - x0)
+        return fail(AFHIP_E_INVALID, "grib_unpack_ccsds: box outside the grid");
+    if (cube_nt < 0 || cube_NY <= 0 || cube_NX <= 0 || t0 < 0 || cy < 0 || cx < 0 || n_steps > cube_nt - t0 || ny > cube_NY - cy || nx > cube_NX - cx)
+        return fail(AFHIP_E_INVALID, "grib_unpack_ccsds: box outside the cube");
+    if (stage_bytes & 3) return fail(AFHIP_E_INVALID, "grib_unpack_ccsds: the stage must be a whole number of 4-byte words (%lld bytes)", (long long)stage_bytes);
+    if (((uintptr_t)stage_dev & 3) || ((uintptr_t)cube_dev & 3) || ((uintptr_t)scratch_dev & 15) || ((uintptr_t)steps_dev & 7))
+        return fail(AFHIP_E_INVALID, "grib_unpack_ccsds: the stage and the cube must be 4-byte aligned, the records 8-byte, the scratch 16-byte aligned");
+    GribALayout L;
+    if (!grib_ccsds_layout(n_steps, NY * NX, max_rsis, &L))
+        return fail(AFHIP_E_INVALID, "grib_unpack_ccsds: %lld steps of %lld points in up to %lld reference sample intervals are too many for one call",
+                    (long long)n_steps, (long long)(NY * NX), (long long)max_rsis);
+    if (scratch_bytes < L.total) return fail(AFHIP_E_INVALID, "grib_unpack_ccsds: scratch too small (afhip_grib_ccsds_scratch_bytes)");
+    const int dev = pointer_device(cube_dev);
+    if (dev < 0 || pointer_device(stage_dev) != dev || pointer_device(steps_dev) != dev || pointer_device(scratch_dev) != dev || pointer_device(errors_dev) != dev)
+        return fail(AFHIP_E_INVALID, "grib_unpack_ccsds: the stage, the records, the scratch, the error counter and the cube must lie on one device");
+    if (n_steps == 0 || ny == 0 || nx == 0) return AFHIP_OK;
+    const int64_t NP = NY * NX, lanes = n_steps * ny * ((nx + GRIB_RUN - 1) / GRIB_RUN), items = n_steps * (max_rsis > 0 ? max_rsis : 1);
+    if (lanes > (int64_t)0x7fffffff * GRIB_WG || items > (int64_t)0x7fffffff * GRIB_WG)
+        return fail(AFHIP_E_INVALID, "grib_unpack_ccsds: box too large for one launch");
+    GUARD_DEVICE(dev);
+    hipStream_t s = (hipStream_t)stream;
+    const GribBox g{NY, NX, y0, x0, ny, nx, cube_NY, cube_NX, t0, cy, cx};
+    aec_ctx c;
+    c.stage = (const uint8_t*)stage_dev;
+    c.stage_bytes = stage_bytes;
+    c.steps = (const aec_step*)steps_dev;
+    c.n_steps = n_steps;
+    c.n_points = NP;
+    c.max_rsis = max_rsis;
+    c.sound = (int32_t*)((char*)scratch_dev + L.sound);
+    c.rsi_bit = (int64_t*)((char*)scratch_dev + L.table);
+    c.vals = (uint32_t*)((char*)scratch_dev + L.vals);
+    c.errors = errors_dev;
+    uint32_t* rank = (uint32_t*)((char*)scratch_dev + L.rank);
+    hipLaunchKernelGGL(k_grib_awalk, dim3((unsigned)n_steps), dim3(GRIB_WG), 0, s, c, g, rank);
+    if (max_rsis > 0)
+        hipLaunchKernelGGL(k_grib_arsi, dim3((unsigned)((n_steps * max_rsis + GRIB_WG - 1) / GRIB_WG)), dim3(GRIB_WG), 0, s, c);
+    hipLaunchKernelGGL((k_grib_cplace<aec_step, GribAVals>), dim3((unsigned)((lanes + GRIB_WG - 1) / GRIB_WG)), dim3(GRIB_WG), 0, s, c.stage, stage_bytes,
+                       c.steps, n_steps, g, (const uint32_t*)rank, GribAVals{NP, c.sound, c.vals}, (float*)cube_dev);
     HIP_TRY(hipGetLastError());
     return AFHIP_OK;
 }

@@ -1,4 +1,4 @@
-// afhip_grib_kernels.h — GRIB simple and complex packing unpacked in HBM (aggfly_amd/io.py: `_GribSource.to_device`).
+// afhip_grib_kernels.h — GRIB simple, complex and CCSDS packing unpacked in HBM (aggfly_amd/io.py: `_GribSource.to_device`).
 //
 // A GRIB field (editions 1 and 2, simple packing) is a big-endian bit stream of nbits-bit unsigned integers X, nbits 0..32, and the
 // value is ((X * s) + R) * d with s = 2^E, d = 10^-D; an optional bitmap, one bit per grid point in scan order, most significant bit
@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "afhip_filter_kernels.h"    // delta_wave_scan; the running sums of spatial differencing are afhip_delta_decode's launches
+#include "aec_passes.h"              // CCSDS packing: the passes of k_grib_awalk and k_grib_arsi
 
 namespace afhip {
 
@@ -457,23 +458,41 @@ __global__ __launch_bounds__(GRIB_WG) void k_grib_cvalues(const uint8_t* __restr
 }
 
 // ---------------------------------------------------------------------------------------
-// k_grib_cplace: one lane per run of GRIB_RUN x of one row of one step.
+// k_grib_cplace: one lane per run of GRIB_RUN x of one row of one step.  One text for every packing whose integers lie in a value
+// scratch: `Vals` says whether step t is sound (`open`) and what X its value idx is (`at`) — GribCVals for complex packing, GribAVals
+// for CCSDS (below) —, `Step` is the record type (bitmap_off, n_values, R, s, d).
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(GRIB_WG) void k_grib_cplace(const uint8_t* __restrict__ stage, int64_t stage_bytes, const GribCStep* __restrict__ steps,
-                                                         int64_t n_steps, GribBox g, const uint32_t* __restrict__ rank, int64_t max_groups,
-                                                         const int64_t* __restrict__ gscr, const int64_t* __restrict__ vals, float* __restrict__ cube) {
+struct GribCVals {
+    int64_t max_groups, NP;
+    const int64_t* __restrict__ gscr;
+    const int64_t* __restrict__ vals;
+    struct Of {
+        const int64_t* __restrict__ sums;
+        uint64_t ival1;
+        __device__ __forceinline__ int64_t at(int64_t idx) const { return (int64_t)(ival1 + (uint64_t)sums[idx]); }
+    };
+    __device__ __forceinline__ bool open(int64_t t, Of& o) const {
+        const int64_t* __restrict__ hdr = gscr + t * grib_cgroup_words(max_groups);
+        if (hdr[0] != 1) return false;
+        o.sums = vals + t * NP;
+        o.ival1 = (uint64_t)hdr[1];
+        return true;
+    }
+};
+
+template <class Step, class Vals>
+__global__ __launch_bounds__(GRIB_WG) void k_grib_cplace(const uint8_t* __restrict__ stage, int64_t stage_bytes, const Step* __restrict__ steps,
+                                                         int64_t n_steps, GribBox g, const uint32_t* __restrict__ rank, Vals src, float* __restrict__ cube) {
     const int64_t lpr = (g.nx + GRIB_RUN - 1) / GRIB_RUN;                       // lanes per row
     const int64_t i = (int64_t)blockIdx.x * GRIB_WG + threadIdx.x;
     if (i >= n_steps * g.ny * lpr) return;
     const int64_t xr = i % lpr, row = i / lpr, y = row % g.ny, t = row / g.ny;
     const int64_t NP = g.NY * g.NX;
-    const int64_t* __restrict__ hdr = gscr + t * grib_cgroup_words(max_groups);
-    if (hdr[0] != 1) return;                                                    // a refused step is written by nobody
+    typename Vals::Of of;
+    if (!src.open(t, of)) return;                                               // a refused step is written by nobody
     const uint32_t* __restrict__ mine = rank + t * grib_rank_words(NP);
-    const int64_t* __restrict__ sums = vals + t * NP;
-    const GribCStep& r = steps[t];
+    const Step& r = steps[t];
     const double R = r.R, s = r.s, d = r.d;
-    const uint64_t ival1 = (uint64_t)hdr[1];
     const int64_t x = xr * GRIB_RUN;
     const int cnt = (int)(g.nx - x < GRIB_RUN ? g.nx - x : GRIB_RUN);
     const int64_t p0 = (g.y0 + y) * g.NX + g.x0 + x;                            // the run's first grid point
@@ -481,7 +500,7 @@ __global__ __launch_bounds__(GRIB_WG) void k_grib_cplace(const uint8_t* __restri
     float v[GRIB_RUN];
     if (r.bitmap_off == -1) {
 #pragma unroll
-        for (int k = 0; k < GRIB_RUN; ++k) v[k] = k < cnt ? grib_cvalue((int64_t)(ival1 + (uint64_t)sums[p0 + k]), R, s, d) : 0.0f;
+        for (int k = 0; k < GRIB_RUN; ++k) v[k] = k < cnt ? grib_cvalue(of.at(p0 + k), R, s, d) : 0.0f;
     } else {
         const int64_t map_bit = r.bitmap_off * 8, N = r.n_values;
         int64_t wi = -1;
@@ -499,7 +518,7 @@ __global__ __launch_bounds__(GRIB_WG) void k_grib_cplace(const uint8_t* __restri
                 const int b = (int)(p & 31);
                 if ((word >> (31 - b)) & 1u) {
                     const int64_t idx = (int64_t)before + (b ? __builtin_popcount(word >> (32 - b)) : 0);
-                    if (idx < N) f = grib_cvalue((int64_t)(ival1 + (uint64_t)sums[idx]), R, s, d);     // (always: the 1-bits are N)
+                    if (idx < N) f = grib_cvalue(of.at(idx), R, s, d);             // (always: the 1-bits are N)
                 }
             }
             v[k] = f;
@@ -513,6 +532,64 @@ __global__ __launch_bounds__(GRIB_WG) void k_grib_cplace(const uint8_t* __restri
         for (int k = 0; k < GRIB_RUN; ++k)
             if (k < cnt) out[k] = v[k];
     }
+}
+
+// =======================================================================================
+// CCSDS packing (edition 2, data representation template 5.42): section 7 is one CCSDS 121.0-B adaptive-entropy-coded stream as libaec
+// writes it (aec_passes.h has the format, the passes and their safety contract).  The whole body of section 7 (and the bitmap) of every
+// step is staged, and three passes make values of it (afhip_grib_unpack_ccsds launches them):
+//
+//   k_grib_awalk   one workgroup per step.  Its GRIB_WG lanes check the record against the stage and build the bitmap's rank table like
+//                  k_grib_cgroups (a step whose bitmap has another number of 1-bits than n_values, or without a bitmap another number
+//                  of values than grid points, is refused); then its first wave alone runs aec_pass_walk: the block headers of the
+//                  stream are walked, the end of a block found by a prefix popcount over 64 byte-swapped dwords held one a lane and a
+//                  ballot (aec_nth_one_wave), and the stage bit where every RSI begins is left in the RSI table.
+//   k_grib_arsi    ONE LANE PER RSI (aec_pass_rsi): the blocks decoded to deltas, the preprocessor undone, X written as uint32 into the
+//                  value scratch, NP elements per step.  Neighbouring lanes hold neighbouring RSIs of one step.
+//   k_grib_cplace  with GribAVals: X read from that scratch.
+//
+// A refused step is flagged in the `sound` table, counted in `errors` once and written to the cube by nobody.  No workgroup waits for
+// another; whatever a record or a stream says, no lane reads outside [0, stage_bytes) or writes outside its step's parts of the scratch.
+// =======================================================================================
+static_assert(sizeof(aec_step) == 72, "record layout");
+
+struct GribAVals {
+    int64_t NP;
+    const int32_t* __restrict__ sound;
+    const uint32_t* __restrict__ vals;
+    struct Of {
+        const uint32_t* __restrict__ X;
+        __device__ __forceinline__ int64_t at(int64_t idx) const { return (int64_t)X[idx]; }
+    };
+    __device__ __forceinline__ bool open(int64_t t, Of& o) const {
+        o.X = vals + t * NP;
+        return sound[t] == 1;
+    }
+};
+
+__global__ __launch_bounds__(GRIB_WG) void k_grib_awalk(aec_ctx c, GribBox g, uint32_t* __restrict__ rank) {
+    __shared__ uint32_t scan[GRIB_WG];
+    __shared__ uint32_t carry_s;
+    const int64_t t = blockIdx.x;
+    const aec_step r = c.steps[t];
+    const int64_t NP = g.NY * g.NX;
+    const bool has_map = r.bitmap_off != -1;
+    bool ok = aec_record_ok(&c, &r) != 0;                                       // (uniform over the workgroup, like all that follows)
+    if (ok && has_map) ok = r.bitmap_off >= 0 && r.bitmap_off <= c.stage_bytes && (NP + 7) / 8 <= c.stage_bytes - r.bitmap_off;
+    if (ok && !has_map) ok = r.n_values == NP;
+    if (ok && has_map) {
+        uint32_t unused = 0;
+        grib_rank_scan(c.stage, c.stage_bytes, r.bitmap_off * 8, NP, NP - 1, rank + t * grib_rank_words(NP), scan, &carry_s, unused);
+        ok = (int64_t)carry_s == r.n_values;                                    // one value per 1-bit
+    }
+    if (threadIdx.x >= 64) return;                                              // the walk is the first wave's
+    aec_pass_walk(&c, t, ok ? 1 : 0);
+}
+
+__global__ __launch_bounds__(GRIB_WG) void k_grib_arsi(aec_ctx c) {
+    const int64_t i = (int64_t)blockIdx.x * GRIB_WG + threadIdx.x;
+    if (i >= c.n_steps * c.max_rsis) return;
+    aec_pass_rsi(&c, i / c.max_rsis, i % c.max_rsis);
 }
 
 }  // namespace afhip

@@ -1523,3 +1523,39 @@ int afcodec_inflate_emulate(const void* comp, int64_t comp_bytes, const void* st
     if (rounds) *rounds = r;
     return AFCODEC_OK;
 }
+
+/* ---- CCSDS / AEC (GRIB2 template 5.42): the passes of aec_passes.h in loops ---- */
+#include "aec_passes.h"
+
+/* One AEC stream of n_values samples of nbits bits -> out[n_values] (uint32): the host route of a CCSDS-packed GRIB2 field and the
+ * host reference of afhip_grib_unpack_ccsds.  The stream is copied into a buffer of whole, aligned dwords first (the passes load those). */
+int afcodec_aec_decode(const void* src, int64_t n, int64_t n_values, int nbits, int flags, int block_size, int rsi, uint32_t* out) {
+    if ((!src && n) || n < 0 || n_values < 0 || (!out && n_values)) return fail(AFCODEC_E_FORMAT, "aec_decode: bad arguments");
+    if (flags & ~(AEC_FLAGS_IGNORED | AEC_FLAG_PREPROCESS)) return fail(AFCODEC_E_UNSUPPORTED, "aec_decode: flags other than 2, 4 and 8 are not read");
+    if (nbits < 0 || nbits > 32 || (block_size != 8 && block_size != 16 && block_size != 32 && block_size != 64) || rsi < 1 || rsi > AEC_RSI_MAX)
+        return fail(AFCODEC_E_UNSUPPORTED, "aec_decode: bits per sample 0..32, block size 8 / 16 / 32 / 64, rsi 1..4096");
+    if (n > ((int64_t)1 << 56)) return fail(AFCODEC_E_SIZE, "aec_decode: stream too long");
+    const int64_t per = (int64_t)rsi * block_size, nr = (n_values + per - 1) / per, padded = (n + 3) / 4 * 4;
+    uint8_t* stage = (uint8_t*)calloc((size_t)(padded ? padded : 4), 1);
+    int64_t* table = (int64_t*)malloc((size_t)(nr ? nr : 1) * sizeof(int64_t));
+    if (!stage || !table) {
+        free(stage);
+        free(table);
+        return fail(AFCODEC_E_SIZE, "aec_decode: out of memory");
+    }
+    if (n) memcpy(stage, src, (size_t)n);
+    aec_step st;
+    memset(&st, 0, sizeof st);
+    st.data_bytes = n; st.bitmap_off = -1; st.n_values = n_values;
+    st.nbits = nbits; st.flags = flags; st.block_size = block_size; st.rsi = rsi;
+    int32_t sound = 0, errors = 0;
+    aec_ctx c;
+    memset(&c, 0, sizeof c);
+    c.stage = stage; c.stage_bytes = padded; c.steps = &st; c.n_steps = 1; c.n_points = n_values; c.max_rsis = nr;
+    c.sound = &sound; c.rsi_bit = table; c.vals = out; c.errors = &errors;
+    aec_pass_walk(&c, 0, 1);
+    for (int64_t r = 0; r < nr; ++r) aec_pass_rsi(&c, 0, r);
+    free(stage);
+    free(table);
+    return errors ? fail(AFCODEC_E_FORMAT, "aec_decode: the stream is damaged or ends before its last sample") : AFCODEC_OK;
+}

@@ -1,8 +1,8 @@
 """Index and host decode of GRIB files (editions 1 and 2, regular latitude / longitude grids; simple packing, and in edition 2 complex
-packing with and without spatial differencing, data representation templates 5.2 and 5.3), written from the format's octet tables (WMO Manual on Codes, FM 92 GRIB; edition 1 as in the ECMWF / NCEP descriptions of its sections).  `GribFile`
+packing with and without spatial differencing, data representation templates 5.2 and 5.3, and CCSDS packing, template 5.42), written from the format's octet tables (WMO Manual on Codes, FM 92 GRIB; edition 1 as in the ECMWF / NCEP descriptions of its sections).  `GribFile`
 walks the file message by message and reads the section HEADERS only: it tells where the packed bits and the bitmap of every field
 lie and how they unpack; `io._GribSource.to_device` `pread`s those bytes into page-locked memory and kernels (`hip.grib_unpack`,
-`hip.grib_unpack_complex`) extract, scale and place them in the cube in HBM.  `GribFile.read` is the same decode in numpy: the ``device=None`` route.
+`hip.grib_unpack_complex`, `hip.grib_unpack_ccsds`) extract, scale and place them in the cube in HBM.  `GribFile.read` is the same decode in numpy: the ``device=None`` route.
 
     edition 1   0 indicator (8)  1 product definition  2 grid description  [3 bitmap]  4 binary data  5 '7777'
     edition 2   0 indicator (16) 1 identification [2 local use] 3 grid definition 4 product definition
@@ -24,15 +24,25 @@ placeholders).  As plain running sums: ``g[0] = 0``, ``g[1] = ival2 - ival1`` (o
 ival1 + cumsum(g)`` for order 1, ``ival1 + cumsum(cumsum(g))`` for order 2 - in int64, wrapping, here and in the kernels.  The value is
 the same ``((X * s) + R) * d`` with X a signed int64, exact while ``|X| < 2**53``.  With NG = 0 every X is 0.
 
+CCSDS packing (5.42; what ECMWF writes for grid-point fields since IFS cycle 48r1): section 5 is 25 octets - R, E, D, nbits as in 5.0,
+octet 22 the flags, octet 23 the block size J, octets 24-25 the reference sample interval ``rsi`` - and section 7 is one CCSDS 121.0-B
+adaptive-entropy-coded stream of ``n_values`` unsigned ``nbits``-bit samples X as libaec writes it (``aggfly_amd/csrc/aec_passes.h`` has
+the blocks, the preprocessor and the passes that decode them; `codec.aec_decode` runs those on the host, `hip.grib_unpack_ccsds` in HBM).
+Flags 2 and 4 say how samples lie in memory and are ignored, flag 8 (the preprocessor) is honoured either way, flags 1 (signed), 16
+(restricted IDs), 32 (RSIs padded to bytes), 64 and 128 are refused; so are J outside 8 / 16 / 32 / 64 and rsi outside 1..4096.  With
+nbits 0 the field is constant and section 7 is empty.  The value is the same ``((X * s) + R) * d``.
+
 Everything else is refused with a ValueError that names it: other grids (Gaussian, reduced, rotated), other packings (edition 1's
 second-order packing, complex packing with missing value management 1 / 2, a spatial differencing order outside 1..2, extra
 descriptors of more than 4 octets, group widths above 32 bits, group lengths that do not sum to N, a section 7 too short for what
-section 5 announces, JPEG 2000, PNG, CCSDS, spherical harmonics, IEEE floating point), -i / column-major / alternating-row scanning, predefined bitmaps, several fields
+section 5 announces, JPEG 2000, PNG, CCSDS packing of signed samples or with restricted IDs or padded RSIs, spherical harmonics, IEEE floating point), -i / column-major / alternating-row scanning, predefined bitmaps, several fields
 in one edition-2 message, ECMWF's large-message extension of edition 1.
 
 No file written by ecCodes, g2clib or wgrib2 was at hand when this was written: the reader is held to hand-assembled messages and to
-the independent writers of ``tests/grib_cases.py`` and ``tests/grib_complex_cases.py``, not to real archive files.  Parity with the
-output of those libraries is unverified.
+the independent writers of ``tests/grib_cases.py``, ``tests/grib_complex_cases.py`` and ``tests/grib_ccsds_cases.py``, not to real archive
+files.  Parity with the output of those libraries is unverified - with one exception: the CCSDS streams are libaec's own (the library
+ecCodes writes section 7 of a 5.42 message with), so the stream decode is held to the real encoder; a whole 5.42 message ecCodes wrote
+remains unverified.
 """
 from __future__ import annotations
 
@@ -52,6 +62,8 @@ ED2_NAMES = {"t2m": (0, 0, 0, 103, 2), "d2m": (0, 0, 6, 103, 2), "u10": (0, 2, 2
              "sp": (0, 3, 0, 1), "msl": (0, 3, 1, 101), "t": (0, 0, 0)}
 _ED1_NAMES = {v: k for k, v in ED1_TABLE128.items()}
 _UNIT_SECONDS = {0: 60, 1: 3600, 2: 86400, 10: 10800, 11: 21600, 12: 43200}       # + second: 254 in edition 1, 13 in edition 2
+_DRT_BYTES = {0: 20, 2: 47, 3: 49, 42: 25}                                       # the octets of section 5 under each template that is read
+_CCSDS_REFUSED = ((1, "signed samples"), (16, "restricted block IDs"), (32, "RSIs padded to bytes"), (64, "flag 64"), (128, "flag 128"))
 _SCAN_REFUSED = ((0x80, "-i (east to west)"), (0x20, "j-consecutive (column-major)"), (0x10, "alternating-row"))
 _DRT_NAMES = {0: "simple packing", 2: "complex packing", 3: "complex packing with spatial differencing", 40: "JPEG 2000", 41: "PNG", 42: "CCSDS",
               50: "spherical harmonics", 51: "spherical harmonics, complex packing", 4: "IEEE floating point"}
@@ -98,8 +110,11 @@ class Message:
     __slots__ = ("offset", "length", "edition", "param", "level_type", "level", "valid_time", "Ni", "Nj", "La1", "La2", "Lo1", "Lo2",
                  "scan", "nbits", "E", "D", "R", "data_offset", "data_length", "bitmap_offset", "bitmap_length", "n_values",
                  # complex packing (edition 2, templates 5.2 / 5.3): ``packing`` 0 / 2 / 3; ``nbits`` is then the bits of a group reference
-                 "packing", "n_groups", "ref_width", "nbits_width", "ref_len", "len_inc", "last_len", "nbits_len", "order", "extra")
+                 "packing", "n_groups", "ref_width", "nbits_width", "ref_len", "len_inc", "last_len", "nbits_len", "order", "extra",
+                 # CCSDS packing (edition 2, template 5.42): ``packing`` 42; ``nbits`` is the bits of a sample
+                 "ccsds_flags", "block_size", "rsi")
     COMPLEX_FIELDS = ("n_groups", "ref_width", "nbits_width", "ref_len", "len_inc", "last_len", "nbits_len", "order", "extra")
+    CCSDS_FIELDS = ("ccsds_flags", "block_size", "rsi")
 
     @property
     def grid(self):
@@ -156,13 +171,13 @@ class Field:
 
     def arrays(self) -> dict:
         """The messages' numbers as arrays, one element per step (built once): ``nbits``, ``R``, ``s``, ``d``, ``data_offset``,
-        ``data_length``, ``bitmap_offset`` (-1: none), ``packing`` (0 / 2 / 3), ``n_values`` and the group parameters of complex
-        packing (`Message.COMPLEX_FIELDS`; 0 for a simple-packed step) — what the device route lays its staging plan out from."""
+        ``data_length``, ``bitmap_offset`` (-1: none), ``packing`` (0 / 2 / 3 / 42), ``n_values``, the group parameters of complex
+        packing (`Message.COMPLEX_FIELDS`; 0 for any other step) and the parameters of CCSDS packing (`Message.CCSDS_FIELDS`) — what the device route lays its staging plan out from."""
         if self._arrays is None:
             ms = self.messages
             self._arrays = {
                 "packing": np.array([m.packing for m in ms], dtype=np.int64), "n_values": np.array([m.n_values for m in ms], dtype=np.int64),
-                **{k: np.array([getattr(m, k) for m in ms], dtype=np.int64) for k in Message.COMPLEX_FIELDS},
+                **{k: np.array([getattr(m, k) for m in ms], dtype=np.int64) for k in Message.COMPLEX_FIELDS + Message.CCSDS_FIELDS},
                 "nbits": np.array([m.nbits for m in ms], dtype=np.int64), "R": np.array([m.R for m in ms], dtype=np.float64),
                 "s": np.array([m.s for m in ms], dtype=np.float64), "d": np.array([m.d for m in ms], dtype=np.float64),
                 "data_offset": np.array([m.data_offset for m in ms], dtype=np.int64), "data_length": np.array([m.data_length for m in ms], dtype=np.int64),
@@ -255,7 +270,7 @@ class GribFile:
         m = Message()
         m.offset, m.length, m.edition = off, total, 1
         m.packing = 0
-        for k in Message.COMPLEX_FIELDS:
+        for k in Message.COMPLEX_FIELDS + Message.CCSDS_FIELDS:
             setattr(m, k, 0)
         end = off + total - 4
         # the indicator, the PDS and the GDS in one read (8 + 28 + 32 bytes as a rule), then one read per later section header
@@ -334,7 +349,7 @@ class GribFile:
         m = Message()
         m.offset, m.length, m.edition = off, total, 2
         m.packing = 0
-        for k in Message.COMPLEX_FIELDS:
+        for k in Message.COMPLEX_FIELDS + Message.CCSDS_FIELDS:
             setattr(m, k, 0)
         discipline = head[6]
         end = off + total - 4
@@ -396,12 +411,12 @@ class GribFile:
                     m.valid_time = _dt.datetime(int.from_bytes(sec[34:36], "big"), sec[36], sec[37], sec[38], sec[39], sec[40])
             elif num == 5:
                 tmpl = int.from_bytes(sec[9:11], "big")
-                if tmpl not in (0, 2, 3):
+                if tmpl not in _DRT_BYTES:
                     raise ValueError(f"data representation template 5.{tmpl} ({_DRT_NAMES.get(tmpl, 'unknown')}) is not read: only 5.0, "
-                                     "simple packing, and 5.2 / 5.3, complex packing")
-                if n < (20, 0, 47, 49)[tmpl]:
+                                     "simple packing, 5.2 / 5.3, complex packing, and 5.42, CCSDS packing")
+                if n < _DRT_BYTES[tmpl]:
                     raise ValueError(f"data representation section of {n} bytes" + (f" for template 5.{tmpl} ({_DRT_NAMES[tmpl]}), which takes "
-                                                                                    f"{(0, 0, 47, 49)[tmpl]}" if tmpl else ""))
+                                                                                    f"{_DRT_BYTES[tmpl]}" if tmpl else ""))
                 m.packing = tmpl
                 m.n_values = int.from_bytes(sec[5:9], "big")
                 m.R = struct.unpack(">f", sec[11:15])[0]
@@ -410,7 +425,16 @@ class GribFile:
                 m.nbits = sec[19]
                 if m.nbits > 32:
                     raise ValueError(f"{m.nbits} bits per value (at most 32)")
-                if tmpl:                                                # complex packing: octets 21 - 47 (5.2), - 49 (5.3)
+                if tmpl == 42:                                          # CCSDS packing: octets 22 (flags), 23 (J), 24 - 25 (rsi)
+                    m.ccsds_flags, m.block_size, m.rsi = sec[21], sec[22], int.from_bytes(sec[23:25], "big")
+                    for bit, what in _CCSDS_REFUSED:
+                        if m.ccsds_flags & bit:
+                            raise ValueError(f"template 5.42: CCSDS flags {m.ccsds_flags:#04x} with bit {bit} ({what}) are not read (2, 4 and 8 are)")
+                    if m.block_size not in (8, 16, 32, 64):
+                        raise ValueError(f"template 5.42: a block size of {m.block_size} samples is not read (8, 16, 32 and 64 are)")
+                    if not 1 <= m.rsi <= 4096:
+                        raise ValueError(f"template 5.42: a reference sample interval of {m.rsi} blocks is not read (1..4096 are)")
+                elif tmpl:                                              # complex packing: octets 21 - 47 (5.2), - 49 (5.3)
                     if sec[22] != 0:
                         raise ValueError(f"template 5.{tmpl}: missing value management {sec[22]} (primary / secondary missing values "
                                          "inside the groups) is not read, only 0")
@@ -589,9 +613,22 @@ def unpack_complex(m, data: bytes) -> np.ndarray:
     return g + np.int64(ival[0])
 
 
+def unpack_ccsds(m, data: bytes) -> np.ndarray:
+    """The ``m.n_values`` integers X (int64, each below 2**32) of a CCSDS-packed message (template 5.42) from the body of its section 7:
+    the passes of ``aec_passes.h`` on the host (`codec.aec_decode`).  A stream that is damaged or ends before its last sample raises."""
+    from . import codec
+    if m.nbits == 0:
+        return np.zeros(int(m.n_values), dtype=np.int64)
+    try:
+        return codec.aec_decode(data, m.n_values, m.nbits, m.ccsds_flags, m.block_size, m.rsi).astype(np.int64)
+    except codec.CodecError as e:
+        raise ValueError(f"template 5.42: section 7 of {len(data)} bytes does not hold {m.n_values} samples of {m.nbits} bits "
+                         f"(block size {m.block_size}, rsi {m.rsi}, flags {m.ccsds_flags:#04x}): {e}") from None
+
+
 def decode_message(m, data: bytes, bitmap: bytes | None) -> np.ndarray:
     """float32 (Nj, Ni) of one message from its packed bits and its bitmap: ``((X * s) + R) * d`` in float64, rounded once.  X is an
-    unsigned integer of at most 32 bits under simple packing and a signed int64 under complex packing; the conversion to float64 is
+    unsigned integer of at most 32 bits under simple and CCSDS packing and a signed int64 under complex packing; the conversion to float64 is
     exact while ``|X| < 2**53``."""
     n = m.Ni * m.Nj
     if m.packing:
@@ -602,7 +639,8 @@ def decode_message(m, data: bytes, bitmap: bytes | None) -> np.ndarray:
             have = np.unpackbits(np.frombuffer(bitmap, dtype=np.uint8), count=n).astype(bool)
         if m.n_values != (n if have is None else int(have.sum())):
             raise ValueError(f"template 5.{m.packing}: {m.n_values} packed values for {n if have is None else int(have.sum())} present grid points")
-        v = (((unpack_complex(m, data).astype(np.float64) * m.s) + m.R) * m.d).astype(np.float32)
+        X = unpack_ccsds(m, data) if m.packing == 42 else unpack_complex(m, data)
+        v = (((X.astype(np.float64) * m.s) + m.R) * m.d).astype(np.float32)
         if have is None:
             return v.reshape(m.Nj, m.Ni)
         out = np.full(n, np.nan, dtype=np.float32)

@@ -43,6 +43,7 @@ EXPORTS = (
     "afhip_take_box", "afhip_shuffle_blocks", "afhip_lz4_encode_streams", "afhip_copy_ranges", "afhip_zstd_encode_blocks",
     "afhip_zstd_encode_scratch_bytes", "afhip_place_box_swapped", "afhip_grib_rank_bytes", "afhip_grib_unpack", "afhip_place_box_tlast",
     "afhip_delta_scratch_bytes", "afhip_delta_decode", "afhip_fso_decode", "afhip_grib_complex_scratch_bytes", "afhip_grib_unpack_complex",
+    "afhip_grib_ccsds_scratch_bytes", "afhip_grib_unpack_ccsds",
 )
 
 
@@ -147,6 +148,9 @@ def load():
     lib.afhip_grib_complex_scratch_bytes.restype = i64
     lib.afhip_grib_complex_scratch_bytes.argtypes = [i64, i64, i64]
     lib.afhip_grib_unpack_complex.argtypes = [vp, i64, vp, i64, i32, i64] + [i64] * 6 + [vp, i32] + [i64] * 6 + [vp, i64, vp, vp]
+    lib.afhip_grib_ccsds_scratch_bytes.restype = i64
+    lib.afhip_grib_ccsds_scratch_bytes.argtypes = [i64, i64, i64]
+    lib.afhip_grib_unpack_ccsds.argtypes = [vp, i64, vp, i64, i64] + [i64] * 6 + [vp, i32] + [i64] * 6 + [vp, i64, vp, vp]
     lib.afhip_zstd_encode_scratch_bytes.restype = i64
     lib.afhip_zstd_encode_scratch_bytes.argtypes = [i64]
     lib.afhip_zstd_scratch_bytes.restype = i64
@@ -357,6 +361,38 @@ def grib_unpack_complex(stage, steps, n_steps: int, order: int, max_groups: int,
                                             int(max_groups), int(NY), int(NX), int(y0), int(x0), int(ny), int(nx), cube.data_ptr(),
                                             cube.element_size(), cube.shape[0], cube.shape[1], cube.shape[2], int(t0), int(cy), int(cx),
                                             scratch.data_ptr(), scratch.numel() * scratch.element_size(), errors.data_ptr(), _stream_ptr(cube)))
+
+
+# one record of `afhip_grib_unpack_ccsds` per time step (`afhip_grib_astep`, include/aggfly_hip.h)
+GRIB_ASTEP = np.dtype([("data_off", "<i8"), ("data_bytes", "<i8"), ("bitmap_off", "<i8"), ("n_values", "<i8"), ("nbits", "<i4"),
+                       ("flags", "<i4"), ("block_size", "<i4"), ("rsi", "<i4"), ("R", "<f8"), ("s", "<f8"), ("d", "<f8")])
+
+
+def grib_ccsds_scratch_bytes(n_steps: int, n_points: int, max_rsis: int) -> int:
+    """`afhip_grib_ccsds_scratch_bytes`: the scratch `grib_unpack_ccsds` needs for ``n_steps`` fields of ``n_points`` grid points in at
+    most ``max_rsis`` reference sample intervals each (the rank tables, the RSI tables and 4 bytes per value)."""
+    n = int(load().afhip_grib_ccsds_scratch_bytes(int(n_steps), int(n_points), int(max_rsis)))
+    if n < 0:
+        raise ValueError(f"grib_ccsds_scratch_bytes: {n_steps} steps of {n_points} grid points in {max_rsis} reference sample intervals")
+    return n
+
+
+def grib_unpack_ccsds(stage, steps, n_steps: int, max_rsis: int, grid, box, cube, at, scratch, errors):
+    """`afhip_grib_unpack_ccsds`: the GRIB fields in CCSDS packing (template 5.42) staged in the uint8 HBM tensor ``stage`` under the
+    ``n_steps`` `GRIB_ASTEP` records of the uint8 HBM tensor ``steps``, unpacked into the float32 ``cube``.  ``max_rsis``: at least every
+    record's ``ceil(n_values / (rsi * block_size))``; ``grid``, ``box``, ``at`` as in `grib_unpack`; ``scratch``: a uint8 HBM tensor of
+    `grib_ccsds_scratch_bytes` bytes.  Refused records and damaged streams count in the int32 HBM counter ``errors`` and their steps are
+    left unwritten.  The work goes to the current stream."""
+    import torch
+    if cube.dtype != torch.float32 or cube.dim() != 3 or not cube.is_contiguous():
+        raise ValueError("grib_unpack_ccsds: the cube must be a contiguous 3-D float32 tensor")
+    if steps.numel() * steps.element_size() < int(n_steps) * GRIB_ASTEP.itemsize:
+        raise ValueError(f"grib_unpack_ccsds: {n_steps} records need {int(n_steps) * GRIB_ASTEP.itemsize} bytes")
+    (NY, NX), (y0, x0, ny, nx), (t0, cy, cx) = grid, box, at
+    _check(load().afhip_grib_unpack_ccsds(stage.data_ptr(), stage.numel() * stage.element_size(), steps.data_ptr(), int(n_steps), int(max_rsis),
+                                          int(NY), int(NX), int(y0), int(x0), int(ny), int(nx), cube.data_ptr(), cube.element_size(),
+                                          cube.shape[0], cube.shape[1], cube.shape[2], int(t0), int(cy), int(cx), scratch.data_ptr(),
+                                          scratch.numel() * scratch.element_size(), errors.data_ptr(), _stream_ptr(cube)))
 
 
 def lz4_decode_streams(comp, streams, n_streams: int, max_dsize: int, tmp, out, errors):

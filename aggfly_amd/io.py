@@ -23,9 +23,9 @@ and the native chunk codecs of `csrc/blosc1.c`:
   bytes over PCIe, swapped and placed by one kernel (``hip.place_box_swapped``), CF mask and unpack in HBM, ``keep_packed``,
   windows and several files as on the Zarr route (``_Nc3Source.to_device``); on the host, and for whatever that route
   declines (byte / char variables, arrays that are not time-leading, CDF-5), through ``scipy.io.netcdf_file``;
-* GRIB files (editions 1 and 2, regular latitude / longitude grids, simple packing and edition 2's complex packing; ``engine="cfgrib"`` or none): ``grib.py`` indexes
+* GRIB files (editions 1 and 2, regular latitude / longitude grids, simple packing and edition 2's complex and CCSDS packing; ``engine="cfgrib"`` or none): ``grib.py`` indexes
   the messages from their section headers; with ``device=`` set the packed bits go from the file to HBM as stored and one kernel
-  (``hip.grib_unpack``; for complex packing ``hip.grib_unpack_complex``) extracts, scales and places them (``_GribSource.to_device``), on the host ``grib.GribFile.read`` decodes
+  (``hip.grib_unpack``; for complex packing ``hip.grib_unpack_complex``, for CCSDS packing ``hip.grib_unpack_ccsds``) extracts, scales and places them (``_GribSource.to_device``), on the host ``grib.GribFile.read`` decodes
   them in numpy; what ``grib.py`` refuses raises with its reason.
 
 On the host route chunks are decoded on host threads into one time-major host buffer, which
@@ -2598,7 +2598,9 @@ class _GribSource(_FileSource):
         steps' ``nbits`` / ``E`` / ``D`` / ``R`` differ: each step has its record, with ``R``, ``2.0 ** E`` and ``10.0 ** -D`` as the
         host route computes them.  Steps in complex packing (edition 2, templates 5.2 / 5.3) stage the whole body of their section 7 and go
         to `hip.grib_unpack_complex`, which reads the group tables, cuts the values out, undoes the spatial differencing by running sums and
-        places the box; a file may mix them with simple-packed steps (a writer falls back to simple packing for a constant field)."""
+        places the box; a file may mix them with simple-packed steps (a writer falls back to simple packing for a constant field).  Steps
+        in CCSDS packing (template 5.42) are staged whole in the same way and go to `hip.grib_unpack_ccsds`: a walk over the block headers
+        of the stream, a decode of every reference sample interval on its own, and the same placement."""
         import torch
         from . import codec, hip
         src = self
@@ -2615,10 +2617,11 @@ class _GribSource(_FileSource):
         nb, d_off, d_len, m_off = arr["nbits"], arr["data_offset"], arr["data_length"], arr["bitmap_offset"]
         has_map = m_off >= 0
         # a step in complex packing (templates 5.2 / 5.3) has no random access: its section 7 is staged whole, like a step with a bitmap.
-        # kind: 0 simple packing, 1 + order complex packing (order 0: template 5.2) - `place` calls one entry per run of one kind
-        is_cx = arr["packing"] != 0
-        kind = np.where(is_cx, 1 + arr["order"], 0)
-        whole = has_map | is_cx
+        # kind: 0 simple packing, 1 + order complex packing (order 0: template 5.2), 4 CCSDS packing - `place` calls one entry per run of one kind
+        is_cc = arr["packing"] == 42
+        is_cx = (arr["packing"] != 0) & ~is_cc
+        kind = np.where(is_cc, 4, np.where(is_cx, 1 + arr["order"], 0))
+        whole = has_map | is_cx | is_cc
         lo = np.where(whole, 0, (a0 * NX * nb) // 8)                         # simple packing without a bitmap: the bytes of rows [a0, a1) only
         hi = np.where(whole, d_len, -((-a1 * NX * nb) // 8))
         short = hi > d_len
@@ -2635,6 +2638,12 @@ class _GribSource(_FileSource):
         for k in ("n_values", "n_groups", "ref_len", "last_len", "ref_width", "nbits_width", "len_inc", "nbits_len", "order", "extra", "R", "s", "d"):
             crec[k] = arr[k]
         max_groups = int(arr["n_groups"][is_cx].max()) if is_cx.any() else 0
+        arec = np.zeros(n, dtype=hip.GRIB_ASTEP)                              # the records of the CCSDS steps (unused rows for the others)
+        arec["data_bytes"], arec["nbits"], arec["flags"] = d_len, nb, arr["ccsds_flags"]
+        for k in ("n_values", "block_size", "rsi", "R", "s", "d"):
+            arec[k] = arr[k]
+        per_rsi = np.maximum(arr["rsi"] * arr["block_size"], 1)
+        max_rsis = int((-(-arr["n_values"] // per_rsi))[is_cc].max()) if is_cc.any() else 0
         pad4 = lambda v: (v + 3) // 4 * 4                                     # every staged range begins on a 4-byte boundary (`read_packed`, align=4)
         step_bytes = pad4(map_bytes) + pad4(hi - lo)
         row = int(step_bytes.max()) if n else 4
@@ -2647,6 +2656,12 @@ class _GribSource(_FileSource):
             per_step = hip.grib_complex_scratch_bytes(1, NY * NX, max_groups)
             slab = max(1, min(slab, (4 * min(slab_bytes, 1 << 30)) // per_step))
             scratch = torch.empty(hip.grib_complex_scratch_bytes(min(slab, n), NY * NX, max_groups), dtype=torch.uint8, device=device)
+        ascratch = None
+        if is_cc.any():
+            # the scratch of the CCSDS steps (4 bytes per value and step, 8 per reference sample interval, the rank tables): the same cap
+            per_step = hip.grib_ccsds_scratch_bytes(1, NY * NX, max_rsis)
+            slab = max(1, min(slab, (4 * min(slab_bytes, 1 << 30)) // per_step))
+            ascratch = torch.empty(hip.grib_ccsds_scratch_bytes(min(slab, n), NY * NX, max_rsis), dtype=torch.uint8, device=device)
         rank = torch.empty(hip.grib_rank_bytes(min(slab, max(n, 1)), NY * NX), dtype=torch.uint8, device=device)
         errors = torch.zeros(1, dtype=torch.int32, device=device)
         pending = []                                                          # the records of the slab just read, for `place`
@@ -2654,9 +2669,9 @@ class _GribSource(_FileSource):
         def read(k0, k1, out):
             # one range per staged piece, packed back to back by the reader's team; a step's ranges follow each other in the slab
             start = np.concatenate([[0], np.cumsum(step_bytes[k0:k1])])[:-1]
-            r, c = rec[k0:k1].copy(), crec[k0:k1].copy()
-            r["bitmap_off"] = c["bitmap_off"] = np.where(has_map[k0:k1], start, -1)
-            r["data_off"] = c["data_off"] = start + pad4(map_bytes[k0:k1])
+            r, c, a = rec[k0:k1].copy(), crec[k0:k1].copy(), arec[k0:k1].copy()
+            r["bitmap_off"] = c["bitmap_off"] = a["bitmap_off"] = np.where(has_map[k0:k1], start, -1)
+            r["data_off"] = c["data_off"] = a["data_off"] = start + pad4(map_bytes[k0:k1])
             # per step the bitmap, then the packed bits; pieces of no bytes (a field of 0 bits per value) are not asked for
             two = lambda a_, b_: np.stack([a_, b_], axis=1).ravel()
             keep = two(has_map[k0:k1], hi[k0:k1] > lo[k0:k1])
@@ -2669,10 +2684,10 @@ class _GribSource(_FileSource):
                     raise OSError(f"{path}: the file ends inside the steps {k_lo + k0}..{k_lo + k1} of {src.field.var!r}")
                 if not np.array_equal(offs[:-1], want):
                     raise RuntimeError("grib: the reader packed the staged ranges differently from the records")
-            pending[:] = [(r, c, kind[k0:k1])]
+            pending[:] = [(r, c, a, kind[k0:k1])]
 
         def place(raw, dst, m):
-            r, c, kd = pending[0]
+            r, c, a, kd = pending[0]
             grid, box = (NY, NX), (a0, b0, a1 - a0, b1 - b0)
             if not kd.any():                                                  # simple packing throughout: one call, as ever
                 steps = torch.from_numpy(r.view(np.uint8).reshape(-1)).to(dst.device)
@@ -2684,6 +2699,9 @@ class _GribSource(_FileSource):
                 if kd[i] == 0:
                     steps = torch.from_numpy(r[i:j].view(np.uint8).reshape(-1)).to(dst.device)
                     hip.grib_unpack(raw, steps, j - i, grid, box, dst, (i, 0, 0), rank, errors)
+                elif kd[i] == 4:
+                    steps = torch.from_numpy(a[i:j].view(np.uint8).reshape(-1)).to(dst.device)
+                    hip.grib_unpack_ccsds(raw, steps, j - i, max_rsis, grid, box, dst, (i, 0, 0), ascratch, errors)
                 else:
                     steps = torch.from_numpy(c[i:j].view(np.uint8).reshape(-1)).to(dst.device)
                     hip.grib_unpack_complex(raw, steps, j - i, int(kd[i]) - 1, max_groups, grid, box, dst, (i, 0, 0), scratch, errors)
@@ -2692,7 +2710,9 @@ class _GribSource(_FileSource):
         if n and int(errors.item()):
             raise ValueError(f"{path}: {int(errors.item())} step(s) of {src.field.var!r} were refused by the unpack kernels (records outside the staged bytes"
                              + ("; or group tables of complex packing that are unsound: widths above 32 bits, lengths that do not sum to the number "
-                                "of values, values beyond section 7 - `grib.GribFile.read` names which" if is_cx.any() else "") + ")")
+                                "of values, values beyond section 7 - `grib.GribFile.read` names which" if is_cx.any() else "")
+                             + ("; or CCSDS streams that are damaged or end before their last sample, or bitmaps whose 1-bits are not the "
+                                "number of values - `grib.GribFile.read` names which" if is_cc.any() else "") + ")")
         return data
 
 

@@ -188,6 +188,12 @@ int64_t afcodec_zstd_decode(const void* src, int64_t n, void* dst, int64_t cap);
 int64_t afcodec_zstd_bound(int64_t n);
 int64_t afcodec_zstd_encode(const void* src, int64_t n, int level, void* dst, int64_t cap);
 
+/* One CCSDS 121.0-B (AEC) stream as libaec writes it — the body of section 7 of a GRIB2 message in data representation template
+ * 5.42 — of n_values samples of nbits bits (0..32) -> out[n_values].  flags: 8 = the preprocessor; 2 and 4 are ignored, any other is
+ * refused, as are block sizes other than 8 / 16 / 32 / 64 and rsi outside 1..4096.  The passes of aec_passes.h (what
+ * afhip_grib_unpack_ccsds runs on the GPU) in loops on the calling thread. */
+int afcodec_aec_decode(const void* src, int64_t n, int64_t n_values, int nbits, int flags, int block_size, int rsi, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

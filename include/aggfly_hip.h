@@ -280,6 +280,29 @@ int afhip_grib_unpack_complex(const void* stage_dev, int64_t stage_bytes, const 
                               void* cube_dev, int cube_elem_size, int64_t cube_nt, int64_t cube_NY, int64_t cube_NX,
                               int64_t t0, int64_t cy, int64_t cx, void* scratch_dev, int64_t scratch_bytes, int32_t* errors_dev, void* stream);
 
+/* GRIB2 CCSDS packing (data representation template 5.42) unpacked in HBM: afhip_grib_unpack's arguments and placement, with one
+ * afhip_grib_astep per step.  data_off / data_bytes: the whole body of the step's section 7, one CCSDS 121.0-B adaptive-entropy-coded
+ * stream as libaec writes it (aggfly_amd/csrc/aec_passes.h has the format) of n_values samples of nbits bits (0: a constant field, no
+ * stream); bitmap_off: the step's bitmap, or -1; n_values: the grid points, or with a bitmap its 1-bits; flags, block_size, rsi: octets
+ * 22, 23 and 24-25 of section 5 (flag 8: the preprocessor; 2 and 4 are ignored); R, s, d as above.  scratch_dev: caller-owned, 16-byte
+ * aligned, afhip_grib_ccsds_scratch_bytes(n_steps, NY * NX, max_rsis) bytes (-1: absurd sizes), max_rsis >= every record's
+ * ceil(n_values / (rsi * block_size)).  Refused - the step is not written and *errors_dev grows by one -: ranges that leave
+ * [0, stage_bytes), nbits above 32, any flag other than 2, 4 and 8, a block size other than 8 / 16 / 32 / 64, rsi outside 1..4096, more
+ * reference sample intervals than max_rsis, a bitmap whose 1-bits are not n_values (without one: n_values other than NY * NX), a zero
+ * run beyond its interval's last block, a second-extension code above 90, a delta above 2^nbits - 1, a stream that runs past
+ * data_bytes.  Whatever the records and the streams say, nothing is read outside the stage and the scratch and nothing is written
+ * outside the box and the scratch.  AFHIP_E_INVALID as above.  The work is enqueued on `stream`; nothing is retained. */
+typedef struct afhip_grib_astep {
+    int64_t data_off, data_bytes, bitmap_off, n_values;
+    int32_t nbits, flags, block_size, rsi;
+    double R, s, d;
+} afhip_grib_astep;
+int64_t afhip_grib_ccsds_scratch_bytes(int64_t n_steps, int64_t n_points, int64_t max_rsis);
+int afhip_grib_unpack_ccsds(const void* stage_dev, int64_t stage_bytes, const afhip_grib_astep* steps_dev, int64_t n_steps,
+                            int64_t max_rsis, int64_t NY, int64_t NX, int64_t y0, int64_t x0, int64_t ny, int64_t nx,
+                            void* cube_dev, int cube_elem_size, int64_t cube_nt, int64_t cube_NY, int64_t cube_NX,
+                            int64_t t0, int64_t cy, int64_t cx, void* scratch_dev, int64_t scratch_bytes, int32_t* errors_dev, void* stream);
+
 /* Chunk decode in HBM ("or GPU-side decode"; the reference decodes on host threads inside its dask
  * graph, aggfly/dataset/dataset.py:697-728).  Blosc-1 chunks whose streams are LZ4 cross PCIe compressed; the host parses
  * the containers (afcodec_blosc_lz4_plan, include/aggfly_codec.h) into the two record lists below, which travel to HBM with
