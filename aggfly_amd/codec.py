@@ -92,6 +92,8 @@ def load():
         lib.afcodec_read_packed.argtypes = [C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
                                             C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
         lib.afcodec_aec_decode.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        lib.afcodec_lzw_decode_ranges.argtypes = [C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_void_p),
+                                                  C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64)]
         _lib = lib
     return _lib
 
@@ -102,7 +104,8 @@ EXPORTS = ("afcodec_last_error", "afcodec_have", "afcodec_blosc_info", "afcodec_
            "afcodec_zstd_plan", "afcodec_zstd_scratch_bytes", "afcodec_zstd_emulate",
            "afcodec_inflate_plan", "afcodec_inflate_scratch_bytes", "afcodec_inflate_emulate",
            "afcodec_blosc_plan", "afcodec_blosc_encode", "afcodec_lz4_encode_emulate", "afcodec_blosc_encode_plan",
-           "afcodec_zstd_encode_block_emulate", "afcodec_zstd_encode_scratch_bytes", "afcodec_blosc_zstd_encode_plan", "afcodec_aec_decode")
+           "afcodec_zstd_encode_block_emulate", "afcodec_zstd_encode_scratch_bytes", "afcodec_blosc_zstd_encode_plan", "afcodec_aec_decode",
+           "afcodec_lzw_decode_ranges")
 
 
 def _err(lib, what):
@@ -699,3 +702,21 @@ def aec_decode(data, n_values: int, nbits: int, flags: int, block_size: int, rsi
     if lib.afcodec_aec_decode(buf.ctypes.data, buf.nbytes, int(n_values), int(nbits), int(flags), int(block_size), int(rsi), out.ctypes.data):
         raise _err(lib, "aec_decode")
     return out
+
+
+def lzw_decode_ranges(locators, outs, threads: int = 8):
+    """`afcodec_lzw_decode_ranges`: the TIFF LZW streams ``locators[i] = (path, offset, nbytes)`` (strips or tiles of a TIFF) decoded
+    into the uint8 arrays ``outs[i]``, each of which its stream must fill exactly, on the native OpenMP team.  A damaged or truncated
+    stream, or a range beyond its file, raises `CodecError` naming the first few."""
+    lib = load()
+    n = len(locators)
+    pp = (C.c_char_p * n)(*[os.fsencode(l[0]) for l in locators])
+    offs = (C.c_int64 * n)(*[int(l[1]) for l in locators])
+    lens = (C.c_int64 * n)(*[int(l[2]) for l in locators])
+    dp = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    ds = (C.c_int64 * n)(*[o.nbytes for o in outs])
+    res = (C.c_int64 * n)()
+    if lib.afcodec_lzw_decode_ranges(n, pp, offs, lens, dp, ds, int(threads), res):
+        bad = [locators[i] for i in range(n) if res[i] < 0]
+        raise CodecError(f"lzw_decode_ranges: {len(bad)} segment(s) failed, first {bad[:4]}: {lib.afcodec_last_error().decode()}")
+    return [int(res[i]) for i in range(n)]

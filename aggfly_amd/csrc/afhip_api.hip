@@ -22,6 +22,7 @@
 #include "afhip_zstd_kernels.h"
 #include "afhip_inflate_kernels.h"
 #include "afhip_grib_kernels.h"
+#include "afhip_tiff_kernels.h"
 #include "afhip_filter_kernels.h"
 #include "afhip_planner.h"
 #include "afhip_variants.h"
@@ -881,6 +882,63 @@ extern "C" int afhip_grib_unpack_ccsds(const void* stage_dev, int64_t stage_byte
         hipLaunchKernelGGL(k_grib_arsi, dim3((unsigned)((n_steps * max_rsis + GRIB_WG - 1) / GRIB_WG)), dim3(GRIB_WG), 0, s, c);
     hipLaunchKernelGGL((k_grib_cplace<aec_step, GribAVals>), dim3((unsigned)((lanes + GRIB_WG - 1) / GRIB_WG)), dim3(GRIB_WG), 0, s, c.stage, stage_bytes,
                        c.steps, n_steps, g, (const uint32_t*)rank, GribAVals{NP, c.sound, c.vals}, (float*)cube_dev);
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
+// ---- TIFF stacks: LZW segments decoded in HBM, predictors undone and segments placed (afhip_tiff_kernels.h) ----
+extern "C" int afhip_lzw_decode(const void* stage_dev, int64_t stage_bytes, afhip_tiff_seg* records_dev, int64_t n, void* out_dev, int64_t out_bytes,
+                                int32_t* errors_dev, void* stream) {
+    static_assert(sizeof(afhip_tiff_seg) == sizeof(TiffSeg) && sizeof(TiffSeg) == 56, "record layouts");
+    if (!stage_dev || !records_dev || !out_dev || !errors_dev || stage_bytes < 0 || out_bytes < 0 || n < 0)
+        return fail(AFHIP_E_INVALID, "lzw_decode: bad arguments");
+    if (n > 0x7fffffff) return fail(AFHIP_E_INVALID, "lzw_decode: too many segments for one launch");
+    if ((uintptr_t)records_dev & 7) return fail(AFHIP_E_INVALID, "lzw_decode: the records must be 8-byte aligned");
+    const int dev = pointer_device(out_dev);
+    if (dev < 0 || pointer_device(stage_dev) != dev || pointer_device(records_dev) != dev || pointer_device(errors_dev) != dev)
+        return fail(AFHIP_E_INVALID, "lzw_decode: the stage, the records, the decoded buffer and the error counter must lie on one device");
+    if (n == 0) return AFHIP_OK;
+    GUARD_DEVICE(dev);
+    hipLaunchKernelGGL(k_lzw_decode, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, (const uint8_t*)stage_dev, stage_bytes, (TiffSeg*)records_dev,
+                       (uint8_t*)out_dev, out_bytes, errors_dev);
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
+extern "C" int afhip_tiff_place(const void* decoded_dev, int64_t decoded_bytes, const afhip_tiff_seg* records_dev, int64_t n, int64_t max_rows,
+                                int elem_size, int predictor, int swap, void* cube_dev, int64_t NT, int64_t NY, int64_t NX,
+                                int64_t y0, int64_t x0, int64_t ny, int64_t nx, int64_t t0, int64_t cy, int64_t cx, int32_t* errors_dev, void* stream) {
+    if (!decoded_dev || !records_dev || !cube_dev || !errors_dev || decoded_bytes < 0 || n < 0 || max_rows < 0)
+        return fail(AFHIP_E_INVALID, "tiff_place: bad arguments");
+    if (elem_size != 1 && elem_size != 2 && elem_size != 4 && elem_size != 8) return fail(AFHIP_E_INVALID, "tiff_place: elem_size must be 1, 2, 4 or 8 (got %d)", elem_size);
+    if (predictor < 1 || predictor > 3) return fail(AFHIP_E_INVALID, "tiff_place: predictor must be 1 (none), 2 (horizontal) or 3 (floating point), got %d", predictor);
+    if (predictor == 3 && elem_size != 4 && elem_size != 8) return fail(AFHIP_E_INVALID, "tiff_place: the floating-point predictor needs 4- or 8-byte samples");
+    if (NT < 0 || NY <= 0 || NX <= 0 || NY > 0x7fffffff || NX > 0x7fffffff || y0 < 0 || x0 < 0 || ny < 0 || nx < 0 || t0 < 0 || cy < 0 || cx < 0 ||
+        y0 > 0x7fffffff || x0 > 0x7fffffff || t0 > NT || ny > NY - cy || nx > NX - cx)
+        return fail(AFHIP_E_INVALID, "tiff_place: box outside the cube");
+    if (n > 0x7fffffff) return fail(AFHIP_E_INVALID, "tiff_place: too many segments for one launch");
+    if (((uintptr_t)decoded_dev | (uintptr_t)cube_dev) & (uintptr_t)(elem_size - 1))
+        return fail(AFHIP_E_INVALID, "tiff_place: the decoded buffer and the cube must be aligned to the element size");
+    if ((uintptr_t)records_dev & 7) return fail(AFHIP_E_INVALID, "tiff_place: the records must be 8-byte aligned");
+    const int dev = pointer_device(cube_dev);
+    if (dev < 0 || pointer_device(decoded_dev) != dev || pointer_device(records_dev) != dev || pointer_device(errors_dev) != dev)
+        return fail(AFHIP_E_INVALID, "tiff_place: the decoded buffer, the records, the error counter and the cube must lie on one device");
+    if (n == 0 || max_rows == 0 || ny == 0 || nx == 0 || NT == t0) return AFHIP_OK;
+    GUARD_DEVICE(dev);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t per = TIFF_WG / 64, gy = (max_rows + per - 1) / per;
+    const dim3 grid((unsigned)n, (unsigned)(gy < 64 ? gy : 64)), block(TIFF_WG);
+    const TiffBox g{NT, NY, NX, y0, x0, ny, nx, t0, cy, cx};
+#define TIFF_PLACE_AS(TE)                                                                                                               \
+    hipLaunchKernelGGL(k_tiff_place<TE>, grid, block, 0, s, (const uint8_t*)decoded_dev, decoded_bytes, (const TiffSeg*)records_dev, predictor, \
+                       swap != 0, (TE*)cube_dev, g, errors_dev)
+    switch (elem_size) {
+        case 1: TIFF_PLACE_AS(uint8_t); break;
+        case 2: TIFF_PLACE_AS(uint16_t); break;
+        case 4: TIFF_PLACE_AS(uint32_t); break;
+        default: TIFF_PLACE_AS(uint64_t); break;
+    }
+#undef TIFF_PLACE_AS
     HIP_TRY(hipGetLastError());
     return AFHIP_OK;
 }

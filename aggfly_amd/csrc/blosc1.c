@@ -1559,3 +1559,41 @@ int afcodec_aec_decode(const void* src, int64_t n, int64_t n_values, int nbits, 
     free(table);
     return errors ? fail(AFCODEC_E_FORMAT, "aec_decode: the stream is damaged or ends before its last sample") : AFCODEC_OK;
 }
+
+/* ---- TIFF LZW: the text of lzw_passes.h on an OpenMP team ---- */
+#include "lzw_passes.h"
+
+/* The segments of a TIFF stack: range i of paths[i] is one LZW stream and must fill dsts[i] exactly.  Each thread keeps one span
+ * table and one input buffer; the input is an exactly sized copy of the range, so the pass reads nothing else. */
+int afcodec_lzw_decode_ranges(int64_t n, const char* const* paths, const int64_t* offsets, const int64_t* lengths,
+                              void* const* dsts, const int64_t* dstsizes, int nthreads, int64_t* results) {
+    if (n < 0 || (n && (!paths || !offsets || !lengths || !dsts || !dstsizes || !results))) return fail(AFCODEC_E_FORMAT, "lzw_decode_ranges: bad arguments");
+    if (nthreads < 1) nthreads = 1;
+    int bad = 0;
+#pragma omp parallel num_threads(nthreads) reduction(+ : bad)
+    {
+        uint32_t* tab_pos = (uint32_t*)malloc(LZW_CODES * sizeof(uint32_t));
+        uint16_t* tab_len = (uint16_t*)malloc(LZW_CODES * sizeof(uint16_t));
+        fd_cache fc = {-1, -1};
+#pragma omp for schedule(dynamic, 1)
+        for (int64_t i = 0; i < n; ++i) {
+            int64_t off = 0;
+            const int64_t sz = lengths[i] < 0 ? AFCODEC_E_FORMAT : stat_range(paths[i], offsets, lengths, i, &off);
+            int64_t r;
+            if (sz < 0 || dstsizes[i] < 0 || dstsizes[i] > 0x7fffffff || (!dsts[i] && dstsizes[i]) || !tab_pos || !tab_len) {
+                r = AFCODEC_E_FORMAT;
+            } else {
+                uint8_t* buf = (uint8_t*)malloc((size_t)(sz ? sz : 1));
+                if (!buf || (sz && read_piece_of(&fc, i, paths[i], buf, sz, off, 0) != sz)) r = AFCODEC_E_FORMAT;
+                else r = lzw_decode_segment(buf, sz, (uint8_t*)dsts[i], dstsizes[i], tab_pos, tab_len, 1) ? AFCODEC_E_CODEC : dstsizes[i];
+                free(buf);
+            }
+            results[i] = r;
+            if (r < 0) bad += 1;
+        }
+        if (fc.fd >= 0) close(fc.fd);
+        free(tab_pos);
+        free(tab_len);
+    }
+    return bad ? fail(AFCODEC_E_CODEC, "lzw_decode_ranges: one or more segments could not be read or are damaged (see results[])") : AFCODEC_OK;
+}

@@ -43,7 +43,7 @@ EXPORTS = (
     "afhip_take_box", "afhip_shuffle_blocks", "afhip_lz4_encode_streams", "afhip_copy_ranges", "afhip_zstd_encode_blocks",
     "afhip_zstd_encode_scratch_bytes", "afhip_place_box_swapped", "afhip_grib_rank_bytes", "afhip_grib_unpack", "afhip_place_box_tlast",
     "afhip_delta_scratch_bytes", "afhip_delta_decode", "afhip_fso_decode", "afhip_grib_complex_scratch_bytes", "afhip_grib_unpack_complex",
-    "afhip_grib_ccsds_scratch_bytes", "afhip_grib_unpack_ccsds",
+    "afhip_grib_ccsds_scratch_bytes", "afhip_grib_unpack_ccsds", "afhip_lzw_decode", "afhip_tiff_place",
 )
 
 
@@ -151,6 +151,8 @@ def load():
     lib.afhip_grib_ccsds_scratch_bytes.restype = i64
     lib.afhip_grib_ccsds_scratch_bytes.argtypes = [i64, i64, i64]
     lib.afhip_grib_unpack_ccsds.argtypes = [vp, i64, vp, i64, i64] + [i64] * 6 + [vp, i32] + [i64] * 6 + [vp, i64, vp, vp]
+    lib.afhip_lzw_decode.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp]
+    lib.afhip_tiff_place.argtypes = [vp, i64, vp, i64, i64, i32, i32, i32, vp] + [i64] * 10 + [vp, vp]
     lib.afhip_zstd_encode_scratch_bytes.restype = i64
     lib.afhip_zstd_encode_scratch_bytes.argtypes = [i64]
     lib.afhip_zstd_scratch_bytes.restype = i64
@@ -393,6 +395,42 @@ def grib_unpack_ccsds(stage, steps, n_steps: int, max_rsis: int, grid, box, cube
                                           int(NY), int(NX), int(y0), int(x0), int(ny), int(nx), cube.data_ptr(), cube.element_size(),
                                           cube.shape[0], cube.shape[1], cube.shape[2], int(t0), int(cy), int(cx), scratch.data_ptr(),
                                           scratch.numel() * scratch.element_size(), errors.data_ptr(), _stream_ptr(cube)))
+
+
+# one record of `afhip_lzw_decode` / `afhip_tiff_place` per segment, a strip or a tile (`afhip_tiff_seg`, include/aggfly_hip.h)
+TIFF_SEG = np.dtype([("src_off", "<i8"), ("src_bytes", "<i8"), ("dec_off", "<i8"), ("dec_bytes", "<i8"), ("rows", "<i4"), ("pitch", "<i4"),
+                     ("t", "<i4"), ("y", "<i4"), ("x", "<i4"), ("bad", "<i4")])
+
+
+def lzw_decode(stage, records, n: int, out, errors):
+    """`afhip_lzw_decode`: the ``n`` TIFF LZW streams staged in the uint8 HBM tensor ``stage`` under the `TIFF_SEG` records of the uint8
+    HBM tensor ``records`` (``src_off`` / ``src_bytes``), decoded into ``dec_off`` / ``dec_bytes`` of the uint8 HBM tensor ``out``, one
+    wave per segment.  A damaged stream, or a record that leaves the stage or ``out``, sets the record's ``bad``, counts in the int32 HBM
+    counter ``errors`` and leaves its decoded bytes untouched.  The work goes to the current stream."""
+    if records.numel() * records.element_size() < int(n) * TIFF_SEG.itemsize:
+        raise ValueError(f"lzw_decode: {n} records need {int(n) * TIFF_SEG.itemsize} bytes")
+    if not (stage.is_contiguous() and out.is_contiguous() and records.is_contiguous()):
+        raise ValueError("lzw_decode: the stage, the records and the decoded buffer must be contiguous")
+    _check(load().afhip_lzw_decode(stage.data_ptr(), stage.numel() * stage.element_size(), records.data_ptr(), int(n), out.data_ptr(),
+                                   out.numel() * out.element_size(), errors.data_ptr(), _stream_ptr(out)))
+
+
+def tiff_place(decoded, records, n: int, max_rows: int, predictor: int, swap: bool, cube, box, at, errors):
+    """`afhip_tiff_place`: the ``n`` decoded segments of the uint8 HBM tensor ``decoded`` under the `TIFF_SEG` records of ``records``
+    (``dec_off``, ``rows``, ``pitch``, ``t``, ``y``, ``x``, ``bad``) into the contiguous 3-D ``cube``, whose element size is the samples':
+    the predictor (1 none, 2 horizontal, 3 floating point) is undone along every row, the samples byte-swapped where ``swap``, and those
+    of the image box ``box = (y0, x0, ny, nx)`` written at ``cube[t0 + t, cy + row - y0, cx + column - x0]``, ``at = (t0, cy, cx)``.
+    ``max_rows``: at least every record's ``rows``.  Bad segments are skipped, unsound records count in ``errors``.  The work goes to the
+    current stream."""
+    if cube.dim() != 3 or not cube.is_contiguous() or not decoded.is_contiguous() or not records.is_contiguous():
+        raise ValueError("tiff_place: the cube must be a contiguous 3-D tensor, the decoded buffer and the records contiguous")
+    if records.numel() * records.element_size() < int(n) * TIFF_SEG.itemsize:
+        raise ValueError(f"tiff_place: {n} records need {int(n) * TIFF_SEG.itemsize} bytes")
+    (y0, x0, ny, nx), (t0, cy, cx) = box, at
+    _check(load().afhip_tiff_place(decoded.data_ptr(), decoded.numel() * decoded.element_size(), records.data_ptr(), int(n), int(max_rows),
+                                   cube.element_size(), int(predictor), int(bool(swap)), cube.data_ptr(), cube.shape[0], cube.shape[1],
+                                   cube.shape[2], int(y0), int(x0), int(ny), int(nx), int(t0), int(cy), int(cx), errors.data_ptr(),
+                                   _stream_ptr(cube)))
 
 
 def lz4_decode_streams(comp, streams, n_streams: int, max_dsize: int, tmp, out, errors):

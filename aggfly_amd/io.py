@@ -850,6 +850,10 @@ GPU_DECODE_AUTO_BYTES_DEFLATE = None
 # measured yet (profiles/blosc_flavours_ingest.txt), so both flavours are opt-in (AGGFLY_HIP_GPU_DECODE=1)
 GPU_DECODE_AUTO_BYTES_BLOSC_BITSHUFFLE = None     # LZ4 / LZ4HC streams under the bit shuffle
 GPU_DECODE_AUTO_BYTES_BLOSC_ZSTD = None           # Zstandard streams, any shuffle
+# TIFF LZW segments (`_TiffSource`, `hip.lzw_decode`): the same rule, on the two LZW layouts of scripts/tiff_ingest_bench.py.  None: measured
+# 64 MiB ... 820 MiB, there is no such size — 1.19-1.38 x the host team's minimum on strips of 8 rows, 1.20-2.64 x on 256 x 256 tiles (one
+# wave walks a tile's 256 KiB code by code; profiles/tiff_ingest.txt) — so the route is opt-in (AGGFLY_HIP_GPU_DECODE=1)
+GPU_DECODE_AUTO_BYTES_LZW = None
 
 
 def _deflate_typesize(kind):
@@ -2312,6 +2316,9 @@ def read_time_coordinate(path, var, timecoord="time"):
     elif _is_grib(path):
         from . import grib
         return grib.open_index(path).select(var).time               # the valid times of the variable's messages, in time order
+    elif _is_tiff(path):
+        from . import tiff
+        return tiff.TiffStack(path).time                            # a single-page file: the step its name gives
     if t is None:
         raise ValueError(f"cannot read a time coordinate from {path}")
     return t if isinstance(t, (pd.DatetimeIndex, CFTimeIndex)) else pd.DatetimeIndex(t)     # (datetime64 values stored as such)
@@ -2741,11 +2748,165 @@ def _open_grib(path, var, xycoords=("longitude", "latitude"), timecoord="time", 
     return DataArray(src.field.file.read(src.field), src.dims, src.coords(), name=var, attrs=src.attrs)
 
 
-def _streamed_source(path, var, xycoords=("longitude", "latitude"), timecoord="time", engine=None, filter_by_keys=None):
+class _TiffSource(_FileSource):
+    """The pages of a stack of GeoTIFF files in time order (`tiff.TiffStack`), from the image file directories alone: ONE source over
+    the whole stack — 365 daily files are one stream into one cube, not 365 parts to join.  ``dtype`` is the stored type, ``attrs`` carry
+    ``_FillValue`` where the files name a nodata value, ``packing`` is None (``keep_packed`` is accepted and ignored).  Whatever
+    `tiff.py` or the kernels refuse raises with its reason: a TIFF has no other route to fall back to."""
+
+    packing, host_route = None, False
+
+    def __init__(self, stack, var, xycoords, timecoord):
+        self.stack, self.path, self.name = stack, stack.paths[0], var
+        self.dims, self.shape, self.dtype, self.attrs = (timecoord, xycoords[1], xycoords[0]), stack.shape, stack.dtype, dict(stack.attrs)
+
+    def takes(self, n_parts, time_window, lat_window) -> bool:
+        return True                                     # (the stack is one source whatever the number of files: a window counts its steps)
+
+    def coords(self):
+        c = self.stack.coords()
+        return {self.dims[0]: c["time"], self.dims[1]: c["latitude"], self.dims[2]: c["longitude"]}
+
+    def to_device(self, device, window, box, keep_packed=False, threads: int = 16, slab_bytes: int = 128 << 20):
+        """A TIFF stack into HBM, as `_Nc3Source.to_device` does it for a classic file.  Step ``t`` is one page, cut into strips or
+        tiles: slabs are whole time steps, and only the segments that touch the requested box are read.  Uncompressed segments are
+        `pread` into the page-locked slab by the native reader's team, Deflate and LZW segments are decoded into it by the same team
+        (`codec.decode_ranges`, `codec.lzw_decode_ranges`); with AGGFLY_HIP_GPU_DECODE=1 the LZW streams of a stack that is LZW
+        throughout cross PCIe compressed instead and `hip.lzw_decode` decodes them into a scratch in HBM, one wave per segment.  Then
+        `hip.tiff_place` undoes the predictor along every segment row, swaps the bytes of a big-endian file and writes the box — the
+        clip included, the padding of partial tiles dropped — into the cube, or into a buffer of the stored type beside it when
+        integers become floats; CF masking of the nodata value follows in HBM as for every other format (`_cf_in_hbm`)."""
+        import torch
+        from . import codec, hip, tiff
+        src = self
+        slab_bytes = _slab_bytes(slab_bytes)
+        post, need_post, out_np, wire = _cf_in_hbm(src.dtype, src.attrs)
+        T, NY, NX = src.shape
+        k_lo, k_hi = src._steps(window)
+        a0, a1, b0, b1 = box if box is not None else (0, NY, 0, NX)
+        pages = src.stack.steps[k_lo:k_hi]
+        n, isz = len(pages), src.dtype.itemsize
+        wire_t, out_t = _torch_dtype(wire), _torch_dtype(out_np)
+        if n == 0 or a1 <= a0 or b1 <= b0:
+            return torch.empty((n, max(a1 - a0, 0), max(b1 - b0, 0)), dtype=out_t, device=device)
+        # the segments of every step that touch the box (pages of one layout share the list), all steps back to back
+        layouts, per = {}, []
+        for pg in pages:
+            key = (pg.tiled, pg.seg_w, pg.seg_h)
+            if key not in layouts:
+                layouts[key] = pg.segments((a0, a1, b0, b1))
+            per.append(layouts[key])
+        nseg = np.array([len(g[0]) for g in per], dtype=np.int64)
+        seg0 = np.concatenate([[0], np.cumsum(nseg)])
+        step_of = np.repeat(np.arange(n, dtype=np.int64), nseg)
+        rec = np.zeros(int(seg0[-1]), dtype=hip.TIFF_SEG)
+        for name, j in (("y", 1), ("x", 2), ("rows", 3), ("pitch", 4), ("dec_bytes", 5)):
+            rec[name] = np.concatenate([g[j] for g in per])
+        f_off = np.concatenate([pg.offsets[g[0]] for pg, g in zip(pages, per)])
+        f_cnt = np.concatenate([pg.counts[g[0]] for pg, g in zip(pages, per)])
+        kind = np.repeat(np.array([0 if pg.compression == tiff.COMPRESSION_NONE else 1 if pg.compression == tiff.COMPRESSION_LZW else 2
+                                   for pg in pages]), nseg)               # 0 as stored, 1 LZW, 2 Deflate
+        f_cnt = np.where(kind == 0, rec["dec_bytes"], f_cnt)                # (an uncompressed segment: the bytes of its samples, no more)
+        undo = np.array([(pg.predictor, pg.byteorder == ">" and isz > 1) for pg in pages], dtype=np.int64)     # per step: predictor, swap
+        paths = [pg.path for pg in pages]
+        file_of = np.unique(np.array(paths), return_inverse=True)[1]          # per step: which file
+        max_rows = int(rec["rows"].max())
+        in_hbm = bool((kind == 1).all()) and os.environ.get("AGGFLY_HIP_GPU_DECODE", "auto") == "1"    # (GPU_DECODE_AUTO_BYTES_LZW is None: opt-in)
+        staged = f_cnt if in_hbm else rec["dec_bytes"]                      # what a segment takes in the slab
+        per_step = lambda v: np.add.reduceat(v, seg0[:-1])                  # (every step has a segment: the box is not empty)
+        row = int(-(-int(per_step(staged).max()) // 8) * 8)
+        dec_row = int(per_step(rec["dec_bytes"]).max())
+        slab = max(1, min(slab_bytes, 1 << 30) // max(row, 1))
+        if in_hbm:
+            slab = max(1, min(slab, (4 * min(slab_bytes, 1 << 30)) // max(dec_row, 1)))     # the decoded scratch: at most four slabs of staged bytes
+        m_max = min(slab, n)
+        decoded = torch.empty(m_max * dec_row, dtype=torch.uint8, device=device) if in_hbm else None
+        # integers that become floats in HBM: the kernel writes the stored type beside the cube, the conversion is the copy into it
+        beside = torch.empty((m_max, a1 - a0, b1 - b0), dtype=wire_t, device=device) if wire_t != out_t else None
+        errors = torch.zeros(1, dtype=torch.int32, device=device)
+        pending = []                                                        # the records of the slab just read, for `place`
+
+        def read(k0, k1, out):
+            s0, s1 = int(seg0[k0]), int(seg0[k1])
+            r = rec[s0:s1].copy()
+            r["t"] = step_of[s0:s1] - k0
+            r["dec_off"] = np.cumsum(r["dec_bytes"]) - r["dec_bytes"]
+            size = staged[s0:s1]
+            at = np.cumsum(size) - size                                      # where a segment's staged bytes begin in the slab
+            st, fo, fc, kd = step_of[s0:s1], f_off[s0:s1], f_cnt[s0:s1], kind[s0:s1]
+            try:
+                if in_hbm or not kd.any():
+                    # bytes as they lie in the files, packed back to back by the reader's team: compressed streams, or stored samples.
+                    # Segments that follow each other in one file — the strips of a page, as a rule — are one range
+                    r["src_off"], r["src_bytes"] = at, size
+                    head = np.ones(len(fo), dtype=bool)
+                    head[1:] = (file_of[st[1:]] != file_of[st[:-1]]) | (fo[1:] != fo[:-1] + fc[:-1])
+                    head = np.flatnonzero(head)
+                    runs = np.add.reduceat(fc, head)
+                    locs = [(paths[t], o, c) for t, o, c in zip(st[head].tolist(), fo[head].tolist(), runs.tolist())]
+                    offs, got = codec.read_packed(locs, out, align=1, threads=threads)
+                    if not np.array_equal(got, runs):
+                        raise OSError(f"{src.path}: a file ends inside the steps {k_lo + k0}..{k_lo + k1} of the stack")
+                else:
+                    locs = [(paths[t], o, c) for t, o, c in zip(st.tolist(), fo.tolist(), fc.tolist())]
+                    bufs = [out[a:a + c] for a, c in zip(at.tolist(), size.tolist())]
+                    for code, decode in ((0, lambda l, b: codec.decode_ranges("raw", l, b, threads=threads)),
+                                         (1, lambda l, b: codec.lzw_decode_ranges(l, b, threads=threads)),
+                                         (2, lambda l, b: codec.decode_ranges("zlib", l, b, threads=threads))):
+                        idx = np.flatnonzero(kd == code).tolist()
+                        if idx:
+                            decode([locs[i] for i in idx], [bufs[i] for i in idx])
+            except codec.CodecError as e:
+                raise ValueError(f"{src.path}: steps {k_lo + k0}..{k_lo + k1} of the stack: {e}") from None
+            pending[:] = [(r, undo[k0:k1])]
+
+        def place(raw, dst, m):
+            r, un = pending[0]
+            into = dst if beside is None else beside[:m]
+            recs = torch.from_numpy(r.view(np.uint8).reshape(-1)).to(dst.device)
+            if in_hbm:
+                hip.lzw_decode(raw, recs, len(r), decoded, errors)
+            # runs of consecutive steps of one predictor and byte order (one, as a rule), each with its records
+            cuts = np.concatenate([[0], np.flatnonzero((un[1:] != un[:-1]).any(axis=1)) + 1, [m]])
+            first = np.searchsorted(r["t"], cuts)
+            for i, lo, hi in zip(cuts[:-1].tolist(), first[:-1].tolist(), first[1:].tolist()):
+                hip.tiff_place(decoded if in_hbm else raw, recs[lo * hip.TIFF_SEG.itemsize:hi * hip.TIFF_SEG.itemsize], hi - lo, max_rows,
+                               int(un[i, 0]), bool(un[i, 1]), into, (a0, b0, a1 - a0, b1 - b0), (0, 0, 0), errors)
+            if beside is not None:
+                dst.copy_(into)
+
+        data = stream_to_device(n, (a1 - a0, b1 - b0), src.dtype, read, slab, device, post if need_post else None, out_np, wire,
+                                place=place, stage_step_bytes=row)
+        if int(errors.item()):
+            raise ValueError(f"{src.path}: {int(errors.item())} segment(s) of the stack were refused by the kernels (LZW streams that are damaged or end "
+                             "before their decoded size; AGGFLY_HIP_GPU_DECODE=0 decodes on the host and names them)")
+        return data
+
+
+def _is_tiff(path) -> bool:
+    from . import tiff
+    return isinstance(path, str) and os.path.isfile(path) and tiff.is_tiff(path)
+
+
+def _tiff_source(paths, var, xycoords=("longitude", "latitude"), timecoord="time", tiff_time=None):
+    """The `_TiffSource` of the stack of the TIFF files ``paths`` (one path, or several in time order).  Whatever `tiff.py` refuses
+    raises here, with its reason."""
+    from . import tiff
+    return _TiffSource(tiff.TiffStack(paths, tiff_time), var, xycoords, timecoord)
+
+
+def _open_tiff(paths, var, xycoords=("longitude", "latitude"), timecoord="time", tiff_time=None):
+    """A TIFF stack on the host: the directories of `tiff.py`, the codec library's decode and numpy's predictors (`TiffStack.read`)."""
+    src = _tiff_source(paths, var, xycoords, timecoord, tiff_time)
+    return DataArray(src.stack.read(), src.dims, src.coords(), name=var, attrs=src.attrs)
+
+
+def _streamed_source(path, var, xycoords=("longitude", "latitude"), timecoord="time", engine=None, filter_by_keys=None, tiff_time=None):
     """The `_StreamedSource` of ``var`` in the store or file ``path`` — the one probe of `dataset_from_path`, `distributed._step_bytes`
     and the CLI — or None when no streaming route takes it.  ``engine``: the reader `dataset_from_path` was asked for, which narrows
     the formats looked for.  A Zarr store or a classic file that cannot be read gives None (the host route then says why), a GRIB file
-    that `grib.py` refuses raises with its reason."""
+    that `grib.py` refuses raises with its reason, and so does a TIFF file that `tiff.py` refuses (``path`` may be the list of a stack's files:
+    they are one source)."""
     if engine == "zarr" or (engine is None and _looks_like_zarr(path)):
         try:
             return _ZarrSource(path, var, xycoords, timecoord)
@@ -2757,6 +2918,8 @@ def _streamed_source(path, var, xycoords=("longitude", "latitude"), timecoord="t
         return _netcdf3_source(path, var, timecoord)
     if engine in (None, "cfgrib") and _is_grib(path):
         return _grib_source(path, var, xycoords, timecoord, filter_by_keys)
+    if engine in (None, "rasterio") and all(_is_tiff(p) for p in (path if isinstance(path, (list, tuple)) else [path])):
+        return _tiff_source(path, var, xycoords, timecoord, tiff_time)
     return None
 
 
@@ -2853,8 +3016,12 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
     paths = sorted(glob.glob(path)) if isinstance(path, str) and "*" in path else (list(path) if isinstance(path, (list, tuple)) else [path])
     if not paths:
         raise FileNotFoundError(path)
-    engine, grib_filter = kwargs.pop("engine", None), _grib_filter(kwargs)
-    first = _streamed_source(paths[0], var, xycoords, timecoord, engine, grib_filter) if device is not None else None
+    engine, grib_filter, tiff_time = kwargs.pop("engine", None), _grib_filter(kwargs), kwargs.get("tiff_time")
+    # the files of a TIFF stack — one raster per day or month — are ONE source and one stream into one cube, not a part per file
+    tiffs = engine in (None, "rasterio") and all(_is_tiff(p) for p in paths)
+    if tiffs:
+        paths = [list(paths)]
+    first = _streamed_source(paths[0], var, xycoords, timecoord, engine, grib_filter, tiff_time) if device is not None else None
     if first is not None and first.takes(len(paths), time_window, lat_window):
         # the streaming routes (`_StreamedSource`): every store or file is probed and streamed into HBM under the same request, the parts
         # are joined along time.  Several — yearly or monthly, each with its own packing — stay packed when each has a packing and all
@@ -2879,7 +3046,9 @@ def dataset_from_path(path, var, xycoords=("longitude", "latitude"), timecoord="
                            preprocess=preprocess, georegions=None if lat_window is not None else georegions, time_fix=time_fix, name=name)
     parts = []
     for p in paths:
-        if engine == "zarr" or (engine is None and _looks_like_zarr(p)):
+        if tiffs:
+            da = _open_tiff(p, var, xycoords, timecoord, tiff_time)
+        elif engine == "zarr" or (engine is None and _looks_like_zarr(p)):
             da = open_zarr(p, var)
         elif p.endswith(".npz"):
             da = _open_npz(p, var)

@@ -180,6 +180,14 @@ int afcodec_decode_ranges(int kind, int64_t n, const char* const* paths, const i
 int afcodec_read_packed(int64_t n, const char* const* paths, const int64_t* offsets, const int64_t* lengths, void* dst, int64_t cap,
                         int64_t align, int nthreads, int64_t* out_off, int64_t* results);
 
+/* TIFF LZW segments (strips or tiles) read and decoded on an OpenMP team, mirroring afcodec_decode_ranges: the stream in
+ * [offsets[i], offsets[i] + lengths[i]) of paths[i] -> dsts[i], which it must fill exactly (dstsizes[i] bytes: a stream ends at
+ * EndOfInformation or at that size).  results[i] = dstsizes[i], or a negative code for a range beyond the file or a damaged stream (a
+ * code above the next free one, no literal after Clear, a span beyond the size, a stream that ends early).  The text of
+ * aggfly_amd/csrc/lzw_passes.h, which afhip_lzw_decode runs on the GPU. */
+int afcodec_lzw_decode_ranges(int64_t n, const char* const* paths, const int64_t* offsets, const int64_t* lengths,
+                              void* const* dsts, const int64_t* dstsizes, int nthreads, int64_t* results);
+
 /* numcodecs' LZ4 codec (Zarr v2 compressor id "lz4"): int32 decoded size + one raw LZ4 block. */
 int64_t afcodec_lz4_decode(const void* src, int64_t n, void* dst, int64_t cap);
 

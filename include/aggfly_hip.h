@@ -303,6 +303,41 @@ int afhip_grib_unpack_ccsds(const void* stage_dev, int64_t stage_bytes, const af
                             void* cube_dev, int cube_elem_size, int64_t cube_nt, int64_t cube_NY, int64_t cube_NX,
                             int64_t t0, int64_t cy, int64_t cx, void* scratch_dev, int64_t scratch_bytes, int32_t* errors_dev, void* stream);
 
+/* TIFF stacks in HBM (aggfly_amd/tiff.py reads the image file directories; aggfly_amd/io.py: `_TiffSource.to_device`).  One
+ * afhip_tiff_seg per staged segment (a strip or a tile) serves both entries.
+ *
+ * afhip_lzw_decode: the n TIFF LZW streams [src_off, src_off + src_bytes) of the stage (codes most significant bit first, 9 to 12
+ * bits, Clear 256, EndOfInformation 257, libtiff's early change; aggfly_amd/csrc/lzw_passes.h has the format, the span table and the
+ * safety contract) decoded into [dec_off, dec_off + dec_bytes) of the decoded buffer, one wave per segment.  A stream ends at
+ * EndOfInformation or at dec_bytes.  Bad — `bad` of the record is set (else cleared), *errors_dev grows by one and the segment's decoded
+ * bytes are left untouched —: ranges that leave the stage or the decoded buffer, dec_bytes above 2^31 - 1, a code above the next free
+ * one, a first code after Clear that is no literal, a span beyond dec_bytes, a stream that ends before dec_bytes.  The records are
+ * written (bad), so they are not const.
+ *
+ * afhip_tiff_place: the n decoded segments — `rows` rows of `pitch` samples of elem_size (1, 2, 4, 8) bytes at dec_off, whose first
+ * sample belongs at row y, column x of image t of the batch — into the cube (NT, NY, NX) of the same element size: the predictor is
+ * undone along every row (1: none; 2: horizontal differencing, a wrapping running sum in the sample's width, after the byte swap; 3:
+ * the floating-point predictor, a running sum mod 256 over the row's pitch * elem_size bytes and a gather of the byte planes, most
+ * significant first — `swap` is not applied), samples are byte-swapped where swap != 0, and the samples of image rows [y0, y0 + ny) and
+ * columns [x0, x0 + nx) are written at cube[t0 + t][cy + row - y0][cx + column - x0]; every other sample (the padding of partial
+ * tiles, what the box cuts off) is dropped.  max_rows >= every record's rows.  A record with bad != 0 is skipped; one whose samples
+ * leave [0, decoded_bytes), whose dec_off is not a multiple of elem_size, whose t is outside [0, NT - t0) or whose rows / pitch / y / x
+ * are negative is not placed and counts in *errors_dev.  AFHIP_E_INVALID: a box that does not fit the cube, an elem_size or predictor
+ * other than those, predictor 3 on 1- or 2-byte samples, pointers on different devices or misaligned.  Nothing is written outside the
+ * box of the cube.  Both entries enqueue on `stream` and retain nothing. */
+typedef struct afhip_tiff_seg {
+    int64_t src_off, src_bytes;      /* afhip_lzw_decode: the compressed stream in the stage */
+    int64_t dec_off, dec_bytes;      /* the decoded segment in the decoded buffer */
+    int32_t rows, pitch;             /* afhip_tiff_place: rows, and samples from one row to the next */
+    int32_t t, y, x;                 /* image of the batch, row and column of the segment's first sample */
+    int32_t bad;
+} afhip_tiff_seg;
+int afhip_lzw_decode(const void* stage_dev, int64_t stage_bytes, afhip_tiff_seg* records_dev, int64_t n, void* out_dev, int64_t out_bytes,
+                     int32_t* errors_dev, void* stream);
+int afhip_tiff_place(const void* decoded_dev, int64_t decoded_bytes, const afhip_tiff_seg* records_dev, int64_t n, int64_t max_rows,
+                     int elem_size, int predictor, int swap, void* cube_dev, int64_t NT, int64_t NY, int64_t NX,
+                     int64_t y0, int64_t x0, int64_t ny, int64_t nx, int64_t t0, int64_t cy, int64_t cx, int32_t* errors_dev, void* stream);
+
 /* Chunk decode in HBM ("or GPU-side decode"; the reference decodes on host threads inside its dask
  * graph, aggfly/dataset/dataset.py:697-728).  Blosc-1 chunks whose streams are LZ4 cross PCIe compressed; the host parses
  * the containers (afcodec_blosc_lz4_plan, include/aggfly_codec.h) into the two record lists below, which travel to HBM with
