@@ -943,6 +943,48 @@ extern "C" int afhip_tiff_place(const void* decoded_dev, int64_t decoded_bytes, 
     return AFHIP_OK;
 }
 
+extern "C" int afhip_tiff_place_bands(const void* decoded_dev, int64_t decoded_bytes, const afhip_tiff_seg* records_dev, int64_t n, int64_t max_rows,
+                                      int64_t bands, int elem_size, int predictor, int swap, void* cube_dev, int64_t NT, int64_t NY, int64_t NX,
+                                      int64_t y0, int64_t x0, int64_t ny, int64_t nx, int64_t t0, int64_t cy, int64_t cx, int32_t* errors_dev,
+                                      void* stream) {
+    if (!decoded_dev || !records_dev || !cube_dev || !errors_dev || decoded_bytes < 0 || n < 0 || max_rows < 0)
+        return fail(AFHIP_E_INVALID, "tiff_place_bands: bad arguments");
+    if (bands < 1 || bands > TBAND_MAX) return fail(AFHIP_E_INVALID, "tiff_place_bands: bands must be 1 .. %d (got %lld)", TBAND_MAX, (long long)bands);
+    if (elem_size != 1 && elem_size != 2 && elem_size != 4 && elem_size != 8)
+        return fail(AFHIP_E_INVALID, "tiff_place_bands: elem_size must be 1, 2, 4 or 8 (got %d)", elem_size);
+    if (predictor < 1 || predictor > 3)
+        return fail(AFHIP_E_INVALID, "tiff_place_bands: predictor must be 1 (none), 2 (horizontal) or 3 (floating point), got %d", predictor);
+    if (predictor == 3 && elem_size != 4 && elem_size != 8) return fail(AFHIP_E_INVALID, "tiff_place_bands: the floating-point predictor needs 4- or 8-byte samples");
+    if (NT < 0 || NY <= 0 || NX <= 0 || NY > 0x7fffffff || NX > 0x7fffffff || y0 < 0 || x0 < 0 || ny < 0 || nx < 0 || t0 < 0 || cy < 0 || cx < 0 ||
+        y0 > 0x7fffffff || x0 > 0x7fffffff || t0 > NT || ny > NY - cy || nx > NX - cx)
+        return fail(AFHIP_E_INVALID, "tiff_place_bands: box outside the cube");
+    if (n > 0x7fffffff) return fail(AFHIP_E_INVALID, "tiff_place_bands: too many segments for one launch");
+    if (((uintptr_t)decoded_dev | (uintptr_t)cube_dev) & (uintptr_t)(elem_size - 1))
+        return fail(AFHIP_E_INVALID, "tiff_place_bands: the decoded buffer and the cube must be aligned to the element size");
+    if ((uintptr_t)records_dev & 7) return fail(AFHIP_E_INVALID, "tiff_place_bands: the records must be 8-byte aligned");
+    const int dev = pointer_device(cube_dev);
+    if (dev < 0 || pointer_device(decoded_dev) != dev || pointer_device(records_dev) != dev || pointer_device(errors_dev) != dev)
+        return fail(AFHIP_E_INVALID, "tiff_place_bands: the decoded buffer, the records, the error counter and the cube must lie on one device");
+    if (n == 0 || max_rows == 0 || ny == 0 || nx == 0 || NT == t0) return AFHIP_OK;
+    GUARD_DEVICE(dev);
+    hipStream_t s = (hipStream_t)stream;
+    // a workgroup per (segment, row, tile of bands); rows beyond the grid's limit are walked by the same workgroups
+    const dim3 grid((unsigned)n, (unsigned)(max_rows < 65535 ? max_rows : 65535), (unsigned)((bands + TBAND_TILE - 1) / TBAND_TILE)), block(TIFF_WG);
+    const TiffBox g{NT, NY, NX, y0, x0, ny, nx, t0, cy, cx};
+#define TIFF_BANDS_AS(TE)                                                                                                                      \
+    hipLaunchKernelGGL(k_tiff_place_bands<TE>, grid, block, 0, s, (const uint8_t*)decoded_dev, decoded_bytes, (const TiffSeg*)records_dev, (int)bands, \
+                       predictor, swap != 0, (TE*)cube_dev, g, errors_dev)
+    switch (elem_size) {
+        case 1: TIFF_BANDS_AS(uint8_t); break;
+        case 2: TIFF_BANDS_AS(uint16_t); break;
+        case 4: TIFF_BANDS_AS(uint32_t); break;
+        default: TIFF_BANDS_AS(uint64_t); break;
+    }
+#undef TIFF_BANDS_AS
+    HIP_TRY(hipGetLastError());
+    return AFHIP_OK;
+}
+
 extern "C" int afhip_lz4_decode_streams(const void* comp_dev, const afhip_lz4_stream* streams_dev, int64_t n_streams, int32_t max_dsize,
                                         void* tmp_dev, void* out_dev, int32_t* errors_dev, void* stream) {
     static_assert(sizeof(afhip_lz4_stream) == sizeof(Lz4Stream) && sizeof(afhip_shuffle_block) == sizeof(ShufBlock), "record layouts");

@@ -43,7 +43,7 @@ EXPORTS = (
     "afhip_take_box", "afhip_shuffle_blocks", "afhip_lz4_encode_streams", "afhip_copy_ranges", "afhip_zstd_encode_blocks",
     "afhip_zstd_encode_scratch_bytes", "afhip_place_box_swapped", "afhip_grib_rank_bytes", "afhip_grib_unpack", "afhip_place_box_tlast",
     "afhip_delta_scratch_bytes", "afhip_delta_decode", "afhip_fso_decode", "afhip_grib_complex_scratch_bytes", "afhip_grib_unpack_complex",
-    "afhip_grib_ccsds_scratch_bytes", "afhip_grib_unpack_ccsds", "afhip_lzw_decode", "afhip_tiff_place",
+    "afhip_grib_ccsds_scratch_bytes", "afhip_grib_unpack_ccsds", "afhip_lzw_decode", "afhip_tiff_place", "afhip_tiff_place_bands",
 )
 
 
@@ -153,6 +153,7 @@ def load():
     lib.afhip_grib_unpack_ccsds.argtypes = [vp, i64, vp, i64, i64] + [i64] * 6 + [vp, i32] + [i64] * 6 + [vp, i64, vp, vp]
     lib.afhip_lzw_decode.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp]
     lib.afhip_tiff_place.argtypes = [vp, i64, vp, i64, i64, i32, i32, i32, vp] + [i64] * 10 + [vp, vp]
+    lib.afhip_tiff_place_bands.argtypes = [vp, i64, vp, i64, i64, i64, i32, i32, i32, vp] + [i64] * 10 + [vp, vp]
     lib.afhip_zstd_encode_scratch_bytes.restype = i64
     lib.afhip_zstd_encode_scratch_bytes.argtypes = [i64]
     lib.afhip_zstd_scratch_bytes.restype = i64
@@ -431,6 +432,23 @@ def tiff_place(decoded, records, n: int, max_rows: int, predictor: int, swap: bo
                                    cube.element_size(), int(predictor), int(bool(swap)), cube.data_ptr(), cube.shape[0], cube.shape[1],
                                    cube.shape[2], int(y0), int(x0), int(ny), int(nx), int(t0), int(cy), int(cx), errors.data_ptr(),
                                    _stream_ptr(cube)))
+
+
+def tiff_place_bands(decoded, records, n: int, max_rows: int, bands: int, predictor: int, swap: bool, cube, box, at, errors):
+    """`afhip_tiff_place_bands`: `tiff_place` for chunky segments of ``bands`` interleaved samples per pixel, every band a time step: a
+    record's segment holds ``rows`` x ``pitch`` x ``bands`` samples, ``pitch`` in pixels, ``t`` the step of its band 0.  The predictor is
+    undone at a stride of ``bands`` samples and sample (row, pixel, band) is written at ``cube[t0 + t + band, cy + y + row - y0,
+    cx + x + pixel - x0]`` when it lies in the box and ``0 <= t + band < cube.shape[0] - t0``; ``t`` may be negative down to
+    ``-(bands - 1)``.  Bad segments are skipped, unsound records count in ``errors``.  The work goes to the current stream."""
+    if cube.dim() != 3 or not cube.is_contiguous() or not decoded.is_contiguous() or not records.is_contiguous():
+        raise ValueError("tiff_place_bands: the cube must be a contiguous 3-D tensor, the decoded buffer and the records contiguous")
+    if records.numel() * records.element_size() < int(n) * TIFF_SEG.itemsize:
+        raise ValueError(f"tiff_place_bands: {n} records need {int(n) * TIFF_SEG.itemsize} bytes")
+    (y0, x0, ny, nx), (t0, cy, cx) = box, at
+    _check(load().afhip_tiff_place_bands(decoded.data_ptr(), decoded.numel() * decoded.element_size(), records.data_ptr(), int(n), int(max_rows),
+                                         int(bands), cube.element_size(), int(predictor), int(bool(swap)), cube.data_ptr(), cube.shape[0],
+                                         cube.shape[1], cube.shape[2], int(y0), int(x0), int(ny), int(nx), int(t0), int(cy), int(cx),
+                                         errors.data_ptr(), _stream_ptr(cube)))
 
 
 def lz4_decode_streams(comp, streams, n_streams: int, max_dsize: int, tmp, out, errors):

@@ -565,7 +565,7 @@ def _pinned_stage(nbytes: int, count: int, device=None):
 
 
 def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: int, device="cuda", post=None, out_dtype=None, wire_dtype=None,
-                     place=None, stage_step_bytes=None):
+                     place=None, stage_step_bytes=None, slabs=None):
     """Fill a (T, *spatial) HBM tensor slab by slab through two cached page-locked staging buffers.
 
     ``read_slab(k0, k1, out)`` fills ``out[:k1-k0]`` with time steps [k0, k1) (a Zarr chunk
@@ -577,7 +577,9 @@ def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: in
     ``place(raw, dst, n)`` with ``stage_step_bytes`` (the NetCDF classic route, `_Nc3Source.to_device`): a slab is then
     ``stage_step_bytes`` raw bytes per step, as they lie in the file — ``read_slab`` fills a uint8 array —, uploaded as they are
     into one HBM staging buffer, and ``place`` (a kernel on the copy stream) writes the ``n`` steps of ``raw`` into ``dst`` =
-    ``cube[k0:k1]``; ``post`` follows as usual.  One HBM buffer serves every slab: upload and kernel are ordered on the copy stream."""
+    ``cube[k0:k1]``; ``post`` follows as usual.  One HBM buffer serves every slab: upload and kernel are ordered on the copy stream.
+    ``slabs`` (with ``place``; the TIFF route, whose pages hold different numbers of steps): the slabs themselves, [(k0, k1, staged
+    bytes)] in step order, in place of slabs of ``slab_steps`` steps of ``stage_step_bytes`` each."""
     import torch
     np_dtype = np.dtype(np_dtype)
     tdt = _torch_dtype(np_dtype if wire_dtype is None else wire_dtype)     # as stored (packed integers stay packed on the wire)
@@ -586,22 +588,26 @@ def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: in
         return cube
     slab_steps = max(1, min(slab_steps, T))
     row = int(np.prod(spatial)) * np_dtype.itemsize if place is None else int(stage_step_bytes)
-    nstage = 2 if T > slab_steps else 1
+    if slabs is None:
+        slabs = [(k0, min(T, k0 + slab_steps), (min(T, k0 + slab_steps) - k0) * row) for k0 in range(0, T, slab_steps)]
+        stage_bytes = slab_steps * row
+    else:
+        stage_bytes = max(max(nb for _, _, nb in slabs), 1)
+    nstage = 2 if len(slabs) > 1 else 1
     if place is None:
         stage_t = [b[:slab_steps * row].view(tdt).reshape((slab_steps,) + tuple(spatial)) for b in _pinned_stage(slab_steps * row, nstage, device)]
         stage = [t.numpy().view(np_dtype) for t in stage_t]
     else:
-        stage_t = [b[:slab_steps * row] for b in _pinned_stage(slab_steps * row, nstage, device)]
+        stage_t = [b[:stage_bytes] for b in _pinned_stage(stage_bytes, nstage, device)]
         stage = [t.numpy() for t in stage_t]
-        raw_dev = torch.empty(slab_steps * row, dtype=torch.uint8, device=device)
+        raw_dev = torch.empty(stage_bytes, dtype=torch.uint8, device=device)
     copy_stream = torch.cuda.Stream(device=device)
     # the cube (and the staging tensors) come from the caching allocator on the CURRENT stream: a block freed there may
     # still be read by queued kernels (the previous HBM window's fused pass) — order the copies behind them
     copy_stream.wait_stream(torch.cuda.current_stream(device))
     done = [None, None]
     uploaded = [None, None]
-    for i, k0 in enumerate(range(0, T, slab_steps)):
-        k1 = min(T, k0 + slab_steps)
+    for i, (k0, k1, nb) in enumerate(slabs):
         b = i % nstage
         if done[b] is not None:
             done[b].synchronize()                       # staging buffer b is free again
@@ -611,8 +617,8 @@ def stream_to_device(T: int, spatial: tuple, np_dtype, read_slab, slab_steps: in
             if place is None:
                 dst.copy_(stage_t[b][:k1 - k0], non_blocking=True)
             else:
-                raw = raw_dev[:(k1 - k0) * row]
-                raw.copy_(stage_t[b][:(k1 - k0) * row], non_blocking=True)
+                raw = raw_dev[:nb]
+                raw.copy_(stage_t[b][:nb], non_blocking=True)
                 place(raw, dst, k1 - k0)
             if post is not None:
                 post(dst)                                # e.g. fill-value masking, applied in HBM
@@ -2750,7 +2756,8 @@ def _open_grib(path, var, xycoords=("longitude", "latitude"), timecoord="time", 
 
 class _TiffSource(_FileSource):
     """The pages of a stack of GeoTIFF files in time order (`tiff.TiffStack`), from the image file directories alone: ONE source over
-    the whole stack — 365 daily files are one stream into one cube, not 365 parts to join.  ``dtype`` is the stored type, ``attrs`` carry
+    the whole stack — 365 daily files are one stream into one cube, not 365 parts to join; every band of a multi-band page is a time
+    step, so are 24 files of 365 bands.  ``dtype`` is the stored type, ``attrs`` carry
     ``_FillValue`` where the files name a nodata value, ``packing`` is None (``keep_packed`` is accepted and ignored).  Whatever
     `tiff.py` or the kernels refuse raises with its reason: a TIFF has no other route to fall back to."""
 
@@ -2768,14 +2775,25 @@ class _TiffSource(_FileSource):
         return {self.dims[0]: c["time"], self.dims[1]: c["latitude"], self.dims[2]: c["longitude"]}
 
     def to_device(self, device, window, box, keep_packed=False, threads: int = 16, slab_bytes: int = 128 << 20):
-        """A TIFF stack into HBM, as `_Nc3Source.to_device` does it for a classic file.  Step ``t`` is one page, cut into strips or
-        tiles: slabs are whole time steps, and only the segments that touch the requested box are read.  Uncompressed segments are
-        `pread` into the page-locked slab by the native reader's team, Deflate and LZW segments are decoded into it by the same team
-        (`codec.decode_ranges`, `codec.lzw_decode_ranges`); with AGGFLY_HIP_GPU_DECODE=1 the LZW streams of a stack that is LZW
-        throughout cross PCIe compressed instead and `hip.lzw_decode` decodes them into a scratch in HBM, one wave per segment.  Then
-        `hip.tiff_place` undoes the predictor along every segment row, swaps the bytes of a big-endian file and writes the box — the
-        clip included, the padding of partial tiles dropped — into the cube, or into a buffer of the stored type beside it when
-        integers become floats; CF masking of the nodata value follows in HBM as for every other format (`_cf_in_hbm`)."""
+        """A TIFF stack into HBM, as `_Nc3Source.to_device` does it for a classic file.  A time step is one band of one page, and what
+        is staged comes in groups: a single-band page, or one band of a planar page (PlanarConfiguration 2: single-band segments of
+        its own), is a group of one step; a chunky multi-band page (PlanarConfiguration 1) is one group of all its steps the window
+        holds, its segments — every band of a pixel interleaved — staged once however many bands are asked for.  Only the segments that
+        touch the requested box are read.  A slab is a whole number of groups: as many as fit ``slab_bytes`` at the size of the largest
+        group, and one where a page of many bands is larger than that — the staging buffers are then sized to that page.  Where the
+        host team decodes, a slab holds no fewer groups than give every thread of the team a segment, up to 1 GiB of staging (the
+        rule of `array_to_device` for chunks): a compressed segment is one stream and one thread's work, and a 365-band page in one
+        tile would otherwise be decoded by one thread while fifteen wait (profiles/tiff_bands_ingest.txt).
+        Uncompressed segments are `pread` into the page-locked slab by the native reader's team, Deflate and LZW segments are decoded
+        into it by the same team (`codec.decode_ranges`, `codec.lzw_decode_ranges`); with AGGFLY_HIP_GPU_DECODE=1 the LZW streams of a
+        stack that is LZW throughout cross PCIe compressed instead and `hip.lzw_decode` decodes them into a scratch in HBM, one wave
+        per segment.  Then `hip.tiff_place` undoes the predictor along every segment row, swaps the bytes of a big-endian file and
+        writes the box — the clip included, the padding of partial tiles dropped — into the cube, or into a buffer of the stored type
+        beside it when integers become floats; the segments of chunky pages go to `hip.tiff_place_bands`, which also takes the bands
+        apart — band b of a segment whose band 0 is step t goes to step t + b, and a window that begins or ends inside a page drops
+        the bands outside it (t is then negative, or t + b beyond the slab).  Runs of groups that share predictor, byte order, band
+        count and configuration share a launch.  CF masking of the nodata value follows in HBM as for every other format
+        (`_cf_in_hbm`)."""
         import torch
         from . import codec, hip, tiff
         src = self
@@ -2784,21 +2802,33 @@ class _TiffSource(_FileSource):
         T, NY, NX = src.shape
         k_lo, k_hi = src._steps(window)
         a0, a1, b0, b1 = box if box is not None else (0, NY, 0, NX)
-        pages = src.stack.steps[k_lo:k_hi]
-        n, isz = len(pages), src.dtype.itemsize
+        n, isz = k_hi - k_lo, src.dtype.itemsize
         wire_t, out_t = _torch_dtype(wire), _torch_dtype(out_np)
         if n == 0 or a1 <= a0 or b1 <= b0:
             return torch.empty((n, max(a1 - a0, 0), max(b1 - b0, 0)), dtype=out_t, device=device)
-        # the segments of every step that touch the box (pages of one layout share the list), all steps back to back
+        # the groups of the window: (page, band or -1 for a chunky page, first step, steps [g_lo, g_hi) of the window it fills)
+        groups = []
+        for k in range(k_lo, k_hi):
+            st = src.stack.steps[k]
+            if not st.page.chunky:
+                groups.append((st.page, st.band, k - k_lo, k - k_lo, k - k_lo + 1))
+            elif not groups or groups[-1][0] is not st.page:
+                groups.append((st.page, -1, k - st.band - k_lo, k - k_lo, min(k - st.band + st.page.bands, k_hi) - k_lo))
+        pages = [g[0] for g in groups]
+        ng = len(groups)
+        t_first = np.array([g[2] for g in groups], dtype=np.int64)            # the step of a group's band 0: negative where the window begins inside a page
+        g_lo, g_hi = np.array([g[3] for g in groups], dtype=np.int64), np.array([g[4] for g in groups], dtype=np.int64)
+        # the segments of every group that touch the box (groups of one layout share the list), all groups back to back
         layouts, per = {}, []
-        for pg in pages:
-            key = (pg.tiled, pg.seg_w, pg.seg_h)
+        for pg, band, *_ in groups:
+            key = (pg.tiled, pg.seg_w, pg.seg_h, pg.width, pg.height, pg.bands if pg.chunky else 1)
             if key not in layouts:
                 layouts[key] = pg.segments((a0, a1, b0, b1))
-            per.append(layouts[key])
+            g = layouts[key]
+            per.append(g if band <= 0 else (g[0] + band * pg.across * pg.down,) + g[1:])
         nseg = np.array([len(g[0]) for g in per], dtype=np.int64)
         seg0 = np.concatenate([[0], np.cumsum(nseg)])
-        step_of = np.repeat(np.arange(n, dtype=np.int64), nseg)
+        group_of = np.repeat(np.arange(ng, dtype=np.int64), nseg)
         rec = np.zeros(int(seg0[-1]), dtype=hip.TIFF_SEG)
         for name, j in (("y", 1), ("x", 2), ("rows", 3), ("pitch", 4), ("dec_bytes", 5)):
             rec[name] = np.concatenate([g[j] for g in per])
@@ -2807,33 +2837,41 @@ class _TiffSource(_FileSource):
         kind = np.repeat(np.array([0 if pg.compression == tiff.COMPRESSION_NONE else 1 if pg.compression == tiff.COMPRESSION_LZW else 2
                                    for pg in pages]), nseg)               # 0 as stored, 1 LZW, 2 Deflate
         f_cnt = np.where(kind == 0, rec["dec_bytes"], f_cnt)                # (an uncompressed segment: the bytes of its samples, no more)
-        undo = np.array([(pg.predictor, pg.byteorder == ">" and isz > 1) for pg in pages], dtype=np.int64)     # per step: predictor, swap
+        # per group: predictor, swap, the bands of a chunky page (0: single-band segments)
+        undo = np.array([(pg.predictor, pg.byteorder == ">" and isz > 1, pg.bands if pg.chunky else 0) for pg in pages], dtype=np.int64)
         paths = [pg.path for pg in pages]
-        file_of = np.unique(np.array(paths), return_inverse=True)[1]          # per step: which file
+        file_of = np.unique(np.array(paths), return_inverse=True)[1]          # per group: which file
         max_rows = int(rec["rows"].max())
         in_hbm = bool((kind == 1).all()) and os.environ.get("AGGFLY_HIP_GPU_DECODE", "auto") == "1"    # (GPU_DECODE_AUTO_BYTES_LZW is None: opt-in)
         staged = f_cnt if in_hbm else rec["dec_bytes"]                      # what a segment takes in the slab
-        per_step = lambda v: np.add.reduceat(v, seg0[:-1])                  # (every step has a segment: the box is not empty)
-        row = int(-(-int(per_step(staged).max()) // 8) * 8)
-        dec_row = int(per_step(rec["dec_bytes"]).max())
-        slab = max(1, min(slab_bytes, 1 << 30) // max(row, 1))
+        per_group = lambda v: np.add.reduceat(v, seg0[:-1])                 # (every group has a segment: the box is not empty)
+        row = int(-(-int(per_group(staged).max()) // 8) * 8)
+        dec_row = int(per_group(rec["dec_bytes"]).max())
+        slab = max(1, min(slab_bytes, 1 << 30) // max(row, 1))              # groups to a slab
         if in_hbm:
             slab = max(1, min(slab, (4 * min(slab_bytes, 1 << 30)) // max(dec_row, 1)))     # the decoded scratch: at most four slabs of staged bytes
-        m_max = min(slab, n)
-        decoded = torch.empty(m_max * dec_row, dtype=torch.uint8, device=device) if in_hbm else None
+        elif kind.any():
+            slab = max(slab, min(-(-threads // int(nseg.min())), (1 << 30) // max(row, 1)))     # a segment for every thread of the team
+        slab = min(slab, ng)
+        cut = list(range(0, ng, slab)) + [ng]
+        slabs = [(int(g_lo[i]), int(g_hi[j - 1]), (j - i) * row) for i, j in zip(cut[:-1], cut[1:])]
+        groups_of_slab = {int(g_lo[i]): (i, j) for i, j in zip(cut[:-1], cut[1:])}
+        m_max = max(k1 - k0 for k0, k1, _ in slabs)
+        decoded = torch.empty(slab * dec_row, dtype=torch.uint8, device=device) if in_hbm else None
         # integers that become floats in HBM: the kernel writes the stored type beside the cube, the conversion is the copy into it
         beside = torch.empty((m_max, a1 - a0, b1 - b0), dtype=wire_t, device=device) if wire_t != out_t else None
         errors = torch.zeros(1, dtype=torch.int32, device=device)
         pending = []                                                        # the records of the slab just read, for `place`
 
         def read(k0, k1, out):
-            s0, s1 = int(seg0[k0]), int(seg0[k1])
+            i0, i1 = groups_of_slab[k0]
+            s0, s1 = int(seg0[i0]), int(seg0[i1])
             r = rec[s0:s1].copy()
-            r["t"] = step_of[s0:s1] - k0
+            r["t"] = t_first[group_of[s0:s1]] - k0
             r["dec_off"] = np.cumsum(r["dec_bytes"]) - r["dec_bytes"]
             size = staged[s0:s1]
             at = np.cumsum(size) - size                                      # where a segment's staged bytes begin in the slab
-            st, fo, fc, kd = step_of[s0:s1], f_off[s0:s1], f_cnt[s0:s1], kind[s0:s1]
+            st, fo, fc, kd = group_of[s0:s1], f_off[s0:s1], f_cnt[s0:s1], kind[s0:s1]
             try:
                 if in_hbm or not kd.any():
                     # bytes as they lie in the files, packed back to back by the reader's team: compressed streams, or stored samples.
@@ -2858,25 +2896,28 @@ class _TiffSource(_FileSource):
                             decode([locs[i] for i in idx], [bufs[i] for i in idx])
             except codec.CodecError as e:
                 raise ValueError(f"{src.path}: steps {k_lo + k0}..{k_lo + k1} of the stack: {e}") from None
-            pending[:] = [(r, undo[k0:k1])]
+            pending[:] = [(r, undo[i0:i1], seg0[i0:i1 + 1] - s0)]
 
         def place(raw, dst, m):
-            r, un = pending[0]
+            r, un, first = pending[0]
             into = dst if beside is None else beside[:m]
             recs = torch.from_numpy(r.view(np.uint8).reshape(-1)).to(dst.device)
             if in_hbm:
                 hip.lzw_decode(raw, recs, len(r), decoded, errors)
-            # runs of consecutive steps of one predictor and byte order (one, as a rule), each with its records
-            cuts = np.concatenate([[0], np.flatnonzero((un[1:] != un[:-1]).any(axis=1)) + 1, [m]])
-            first = np.searchsorted(r["t"], cuts)
-            for i, lo, hi in zip(cuts[:-1].tolist(), first[:-1].tolist(), first[1:].tolist()):
-                hip.tiff_place(decoded if in_hbm else raw, recs[lo * hip.TIFF_SEG.itemsize:hi * hip.TIFF_SEG.itemsize], hi - lo, max_rows,
-                               int(un[i, 0]), bool(un[i, 1]), into, (a0, b0, a1 - a0, b1 - b0), (0, 0, 0), errors)
+            # runs of consecutive groups of one predictor, byte order, band count and configuration (one, as a rule), each with its records
+            cuts = np.concatenate([[0], np.flatnonzero((un[1:] != un[:-1]).any(axis=1)) + 1, [len(un)]])
+            for i, lo, hi in zip(cuts[:-1].tolist(), first[cuts[:-1]].tolist(), first[cuts[1:]].tolist()):
+                some = recs[lo * hip.TIFF_SEG.itemsize:hi * hip.TIFF_SEG.itemsize]
+                args = (int(un[i, 0]), bool(un[i, 1]), into, (a0, b0, a1 - a0, b1 - b0), (0, 0, 0), errors)
+                if un[i, 2]:
+                    hip.tiff_place_bands(decoded if in_hbm else raw, some, hi - lo, max_rows, int(un[i, 2]), *args)
+                else:
+                    hip.tiff_place(decoded if in_hbm else raw, some, hi - lo, max_rows, *args)
             if beside is not None:
                 dst.copy_(into)
 
-        data = stream_to_device(n, (a1 - a0, b1 - b0), src.dtype, read, slab, device, post if need_post else None, out_np, wire,
-                                place=place, stage_step_bytes=row)
+        data = stream_to_device(n, (a1 - a0, b1 - b0), src.dtype, read, m_max, device, post if need_post else None, out_np, wire,
+                                place=place, stage_step_bytes=row, slabs=slabs)
         if int(errors.item()):
             raise ValueError(f"{src.path}: {int(errors.item())} segment(s) of the stack were refused by the kernels (LZW streams that are damaged or end "
                              "before their decoded size; AGGFLY_HIP_GPU_DECODE=0 decodes on the host and names them)")

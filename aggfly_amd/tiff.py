@@ -1,8 +1,9 @@
-"""Header reader for GeoTIFF stacks — one single-band raster per day or month, or one multi-page file: how PRISM, CHIRPS, WorldClim,
-Daymet mosaics and Earth Engine exports arrive —, written from the TIFF 6.0 specification, the BigTIFF design note and the GeoTIFF
-specification (OGC 19-008r4).  It tells where the bytes of every strip or tile of every page lie in the files; no pixel is touched
-here.  `io._TiffSource.to_device` `pread`s those bytes into page-locked memory and kernels (`hip.lzw_decode`, `hip.tiff_place`) decode
-them, undo the predictor and place them in the cube in HBM; `TiffStack.read` is the same on the host, in numpy.
+"""Header reader for GeoTIFF stacks — one single-band raster per day or month, one multi-page file, or files with a band per time step:
+how PRISM, CHIRPS, WorldClim, Daymet mosaics and Earth Engine exports arrive —, written from the TIFF 6.0 specification, the BigTIFF
+design note and the GeoTIFF specification (OGC 19-008r4).  It tells where the bytes of every strip or tile of every page lie in the
+files; no pixel is touched here.  `io._TiffSource.to_device` `pread`s those bytes into page-locked memory and kernels (`hip.lzw_decode`,
+`hip.tiff_place`, `hip.tiff_place_bands`) decode them, undo the predictor and place them in the cube in HBM; `TiffStack.read` is the
+same on the host, in numpy.
 
     header  = byte order ('II' little-endian, 'MM' big-endian) magic (42 classic, 43 BigTIFF) offset of the first IFD
     IFD     = count [tag type count value-or-offset ...] offset of the next IFD (0: the last)
@@ -14,8 +15,19 @@ the first by its difference from the sample before (2; in the sample's width, wr
 most significant bytes first, and differenced those bytes (3).  The predictor is part of the LZW and Deflate codecs: on uncompressed
 segments the tag means nothing, as in libtiff.
 
+A page of SamplesPerPixel = B > 1 holds B bands, and every band of every full-resolution page is one time step, in page order, then
+band order (GDAL's `-separate` merges, Earth Engine's `toBands()` exports, rioxarray's `to_raster` of a (time, y, x) array).
+PlanarConfiguration 1 (chunky, GDAL's INTERLEAVE=PIXEL) interleaves the bands of a pixel: a segment holds rows x pitch x B samples, and
+the predictors run at stride B as libtiff applies them (tif_predict.c) — predictor 2 adds sample i - B to sample i; predictor 3 is a
+running sum over the row's pitch * B * size bytes at stride B, continuing across the byte planes, and sample i = pixel * B + band is
+gathered from the bytes plane * (pitch * B) + i.  PlanarConfiguration 2 (INTERLEAVE=BAND) stores band b as single-band segments of its
+own at indices b * across * down + k.  BitsPerSample and SampleFormat hold one value or B equal ones; ExtraSamples and
+PhotometricInterpretation are ignored (a band is a band).  Parity with a GDAL- or Earth-Engine-written multi-band file is unverified:
+none was at hand; the files tested are an independent writer's and libtiff's through Pillow (chunky uint8, predictor 2).
+
 What is read: compression 1 (none), 5 (LZW) and 8 / 32946 (Deflate: zlib streams); predictors 1, 2 (integers) and 3 (float32 / float64);
-integers of 8 / 16 / 32 / 64 bits of either sign, float32, float64; strips and tiles; one sample per pixel; any number of pages per file.
+integers of 8 / 16 / 32 / 64 bits of either sign, float32, float64; strips and tiles; any number of bands per pixel in either planar
+configuration; any number of pages per file.
 Pages whose NewSubfileType has bit 0 (a reduced-resolution overview) or bit 2 (a mask) set are skipped: every cloud-optimised GeoTIFF
 has them.  Whatever else is met raises ValueError with the reason:
 
@@ -23,14 +35,15 @@ has them.  Whatever else is met raises ValueError with the reason:
     old-style LZW (least significant bit first, a stream that begins 00 01) and FillOrder 2
     bits per sample other than 8 / 16 / 32 / 64; floats of 16 bits; complex samples
     predictor 2 on floats, predictor 3 on integers
-    SamplesPerPixel > 1, in either planar configuration
+    bands of one page that differ in width or format (mixed BitsPerSample / SampleFormat); a PlanarConfiguration other than 1 and 2
     a projected coordinate reference system (GTModelTypeGeoKey 1), rotated or sheared transformations, no georeferencing at all
     pages of one stack that differ in grid, type or nodata value
     offsets or byte counts that leave the file
 
 Coordinates come from ModelPixelScale + ModelTiepoint, or from a ModelTransformation without rotation or shear: cell centres for
 RasterPixelIsArea (the default), the grid points themselves for RasterPixelIsPoint.  Rows stay in stored order (north first, as a rule).
-A TIFF has no time axis: ``tiff_time`` gives one, else the time is read from every file's name (`time_from_name`).
+A TIFF has no time axis: ``tiff_time`` gives one, else the time is read from every file's name (`time_from_name`), or, for a
+single-page multi-band file, from the band descriptions of GDAL_METADATA (tag 42112) where every band has one that holds a date.
 """
 from __future__ import annotations
 
@@ -44,10 +57,10 @@ import pandas as pd
 # the tags that are read (every other entry of an IFD is skipped unread)
 T_SUBFILE, T_WIDTH, T_LENGTH, T_BITS, T_COMPRESSION, T_FILL_ORDER, T_STRIP_OFFSETS, T_SPP, T_ROWS_PER_STRIP = 254, 256, 257, 258, 259, 266, 273, 277, 278
 T_STRIP_COUNTS, T_PLANAR, T_PREDICTOR, T_TILE_WIDTH, T_TILE_LENGTH, T_TILE_OFFSETS, T_TILE_COUNTS, T_SAMPLE_FORMAT = 279, 284, 317, 322, 323, 324, 325, 339
-T_PIXEL_SCALE, T_TIEPOINT, T_TRANSFORMATION, T_GEO_KEYS, T_GDAL_NODATA = 33550, 33922, 34264, 34735, 42113
+T_PIXEL_SCALE, T_TIEPOINT, T_TRANSFORMATION, T_GEO_KEYS, T_GDAL_METADATA, T_GDAL_NODATA = 33550, 33922, 34264, 34735, 42112, 42113
 _READ_TAGS = frozenset((T_SUBFILE, T_WIDTH, T_LENGTH, T_BITS, T_COMPRESSION, T_FILL_ORDER, T_STRIP_OFFSETS, T_SPP, T_ROWS_PER_STRIP, T_STRIP_COUNTS,
                         T_PLANAR, T_PREDICTOR, T_TILE_WIDTH, T_TILE_LENGTH, T_TILE_OFFSETS, T_TILE_COUNTS, T_SAMPLE_FORMAT, T_PIXEL_SCALE,
-                        T_TIEPOINT, T_TRANSFORMATION, T_GEO_KEYS, T_GDAL_NODATA))
+                        T_TIEPOINT, T_TRANSFORMATION, T_GEO_KEYS, T_GDAL_METADATA, T_GDAL_NODATA))
 # field type -> (struct letter, bytes); 2 ASCII and 7 UNDEFINED are bytes; 5 / 10 (rationals) are pairs
 _TYPES = {1: ("B", 1), 2: ("c", 1), 3: ("H", 2), 4: ("I", 4), 5: ("I", 4), 6: ("b", 1), 7: ("c", 1), 8: ("h", 2), 9: ("i", 4), 10: ("i", 4),
           11: ("f", 4), 12: ("d", 8), 13: ("I", 4), 16: ("Q", 8), 17: ("q", 8), 18: ("Q", 8)}
@@ -78,8 +91,16 @@ def time_from_name(path) -> pd.Timestamp:
     ``YYYYMM`` or ``YYYY`` (digits not next to other digits) and is a date between the years 1000 and 2999."""
     base = os.path.basename(str(path))
     base = base[:base.rfind(".")] if "." in base and base.lower().endswith((".tif", ".tiff")) else base
+    found = _date_in(base)
+    if found is None:
+        raise ValueError(f"{path}: no time step can be read from the file name (YYYYMMDD, YYYY-MM-DD, YYYYMM or YYYY); pass tiff_time=")
+    return found
+
+
+def _date_in(text):
+    """The last date `time_from_name`'s patterns find in ``text``, or None."""
     found = None
-    for m in _NAME_DATE.finditer(base):
+    for m in _NAME_DATE.finditer(text):
         y, mo, d, ymd, ym, yy = m.groups()
         if ymd:
             y, mo, d = ymd[:4], ymd[4:6], ymd[6:]
@@ -92,8 +113,6 @@ def time_from_name(path) -> pd.Timestamp:
                 found = pd.Timestamp(year=int(y), month=int(mo), day=int(d))
         except ValueError:
             pass
-    if found is None:
-        raise ValueError(f"{path}: no time step can be read from the file name (YYYYMMDD, YYYY-MM-DD, YYYYMM or YYYY); pass tiff_time=")
     return found
 
 
@@ -111,7 +130,7 @@ class Page:
         self.compression, self.predictor, self.fill_order = one(T_COMPRESSION, 1), one(T_PREDICTOR, 1), one(T_FILL_ORDER, 1)
         self.bits = [int(b) for b in tags.get(T_BITS, (1,))]
         self.sample_format = [int(b) for b in tags.get(T_SAMPLE_FORMAT, (1,))]
-        self.nodata_text = tags.get(T_GDAL_NODATA)
+        self.nodata_text, self.gdal_metadata = tags.get(T_GDAL_NODATA), tags.get(T_GDAL_METADATA)
         self.pixel_scale, self.tiepoint = tags.get(T_PIXEL_SCALE), tags.get(T_TIEPOINT)
         self.transformation, self.geo_keys = tags.get(T_TRANSFORMATION), tags.get(T_GEO_KEYS)
         self.tiled = T_TILE_WIDTH in tags or T_TILE_OFFSETS in tags
@@ -119,8 +138,17 @@ class Page:
             return
         if self.width <= 0 or self.height <= 0 or self.width > 0x7fffffff or self.height > 0x7fffffff:
             raise ValueError(f"{where}: ImageWidth / ImageLength missing or absurd ({self.width} x {self.height})")
-        if self.spp != 1:
-            raise ValueError(f"{where}: SamplesPerPixel = {self.spp} (PlanarConfiguration {self.planar}): multi-band files are not read, one sample per pixel only")
+        B = self.bands = self.spp
+        if B < 1:
+            raise ValueError(f"{where}: SamplesPerPixel = {B}")
+        if self.planar not in (1, 2):
+            raise ValueError(f"{where}: PlanarConfiguration {self.planar} is not read: 1 (chunky) and 2 (planar) are")
+        self.chunky = B > 1 and self.planar == 1                    # (one band: the two configurations are the same file)
+        for what, vals in (("BitsPerSample", self.bits), ("SampleFormat", self.sample_format)):
+            if len(vals) not in (1, B) or len(set(vals)) != 1:
+                if len(vals) > 1 and len(set(vals)) > 1:
+                    raise ValueError(f"{where}: the bands differ in {what} ({', '.join(str(v) for v in vals)}): mixed band types are not read")
+                raise ValueError(f"{where}: {what} holds {len(vals)} values for SamplesPerPixel = {B}: one value, or one per band")
         if self.compression not in (COMPRESSION_NONE, COMPRESSION_LZW) + _DEFLATE_CODES:
             raise ValueError(f"{where}: compression {self.compression} ({COMPRESSION_NAMES.get(self.compression, 'unknown')}) is not read: "
                              "none (1), LZW (5) and Deflate (8, 32946) are")
@@ -154,9 +182,10 @@ class Page:
             self.seg_w, self.seg_h = self.width, max(1, min(one(T_ROWS_PER_STRIP, self.height), self.height))
             offs, cnts = tags.get(T_STRIP_OFFSETS), tags.get(T_STRIP_COUNTS)
         self.across, self.down = -(-self.width // self.seg_w), -(-self.height // self.seg_h)
-        n = self.across * self.down
+        n = self.across * self.down * (1 if self.planar == 1 else B)
+        per = f" (SamplesPerPixel = {B}, PlanarConfiguration {self.planar})" if B > 1 else ""
         if offs is None or cnts is None or len(offs) != n or len(cnts) != n:
-            raise ValueError(f"{where}: {n} {'tiles' if self.tiled else 'strips'} need as many offsets and byte counts "
+            raise ValueError(f"{where}: {n} {'tiles' if self.tiled else 'strips'} need as many offsets and byte counts{per} "
                              f"({0 if offs is None else len(offs)} and {0 if cnts is None else len(cnts)} are there)")
         self.offsets, self.counts = np.asarray(offs, dtype=np.uint64), np.asarray(cnts, dtype=np.uint64)
         if n and (int(self.offsets.max()) > file_size or int(self.counts.max()) > file_size or int((self.offsets + self.counts).max()) > file_size):
@@ -164,14 +193,16 @@ class Page:
             raise ValueError(f"{where}: {'tile' if self.tiled else 'strip'} {k} (offset {int(self.offsets[k])}, {int(self.counts[k])} bytes) "
                              f"leaves the file ({file_size} bytes)")
         self.offsets, self.counts = self.offsets.astype(np.int64), self.counts.astype(np.int64)
-        if (self.seg_h * self.seg_w * E) > 0x7fffffff:
-            raise ValueError(f"{where}: a {'tile' if self.tiled else 'strip'} of {self.seg_h} x {self.seg_w} samples is larger than 2 GiB")
+        Bs = B if self.chunky else 1                                # the samples of a pixel in one segment
+        if (self.seg_h * self.seg_w * E * Bs) > 0x7fffffff:
+            raise ValueError(f"{where}: a {'tile' if self.tiled else 'strip'} of {self.seg_h} x {self.seg_w} samples{per} is larger than 2 GiB")
         if self.compression == COMPRESSION_NONE:
-            k0 = np.arange(n) // self.across
-            need = (np.minimum(self.seg_h, self.height - k0 * self.seg_h) if not self.tiled else self.seg_h) * self.seg_w * E
+            k0 = (np.arange(n) % (self.across * self.down)) // self.across
+            need = (np.minimum(self.seg_h, self.height - k0 * self.seg_h) if not self.tiled else self.seg_h) * self.seg_w * E * Bs
             if (self.counts < need).any():
                 k = int(np.argmax(self.counts < need))
-                raise ValueError(f"{where}: {'tile' if self.tiled else 'strip'} {k} holds {int(self.counts[k])} bytes, its samples need {int(np.broadcast_to(need, (n,))[k])}")
+                raise ValueError(f"{where}: {'tile' if self.tiled else 'strip'} {k} holds {int(self.counts[k])} bytes, its samples{per} need "
+                                 f"{int(np.broadcast_to(need, (n,))[k])}")
         if self.compression == COMPRESSION_LZW and n:
             k = int(np.argmax(self.counts > 1)) if (self.counts > 1).any() else -1
             if k >= 0:
@@ -238,25 +269,73 @@ class Page:
 
     @property
     def n_segments(self):
-        return self.across * self.down
+        """The segments of the page; of a planar page: of all its bands."""
+        return self.across * self.down * (1 if self.planar == 1 else self.bands)
+
+    def band_descriptions(self):
+        """The DESCRIPTION item of every band in GDAL_METADATA (tag 42112), or None where a band has none:
+        ``<Item name="DESCRIPTION" sample="k" role="description">text</Item>``, found by an explicit search for that form — no XML parser
+        reads a file's bytes here."""
+        out = [None] * self.bands
+        for attrs, text in _ITEM.findall(self.gdal_metadata or ""):
+            a = dict(_ATTR.findall(attrs))
+            if a.get("name") == "DESCRIPTION" and a.get("role", "description") == "description" and a.get("sample", "").isdigit():
+                k = int(a["sample"])
+                if k < self.bands and out[k] is None:
+                    out[k] = _unescape(text.strip())
+        return out
 
     def grid_key(self):
         return (self.width, self.height, self.dtype.str, self.nodata, self.longitude.tobytes(), self.latitude.tobytes())
 
-    def segments(self, box=None):
+    def segments(self, box=None, band=0):
         """The segments that touch the stored-axes ``box`` (a0, a1, b0, b1) (None: all), as arrays: index, first row, first column,
-        rows (of a bottom strip: those it holds; of a tile: all, padding included), pitch, decoded bytes."""
+        rows (of a bottom strip: those it holds; of a tile: all, padding included), pitch (in pixels), decoded bytes.  A chunky page's
+        segments hold all its bands (rows x pitch x bands samples); a planar page's are those of ``band``, single-band segments."""
         a0, a1, b0, b1 = box if box is not None else (0, self.height, 0, self.width)
-        k = np.arange(self.n_segments, dtype=np.int64)
+        k = np.arange(self.across * self.down, dtype=np.int64)
         y, x = (k // self.across) * self.seg_h, (k % self.across) * self.seg_w
         rows = np.full_like(k, self.seg_h) if self.tiled else np.minimum(self.seg_h, self.height - y)
         keep = (y < a1) & (y + rows > a0) & (x < b1) & (x + self.seg_w > b0)
         k, y, x, rows = k[keep], y[keep], x[keep], rows[keep]
-        return k, y, x, rows, np.full_like(k, self.seg_w), rows * self.seg_w * self.dtype.itemsize
+        if self.chunky:
+            return k, y, x, rows, np.full_like(k, self.seg_w), rows * self.seg_w * self.dtype.itemsize * self.bands
+        if not 0 <= band < self.bands:
+            raise IndexError(f"band {band} of a page of {self.bands}")
+        return k + band * self.across * self.down, y, x, rows, np.full_like(k, self.seg_w), rows * self.seg_w * self.dtype.itemsize
 
     def __repr__(self):
         return (f"<tiff.Page {self.index} of {self.path!r} {self.width}x{self.height} {getattr(self, 'dtype', '?')} compression={self.compression} "
-                f"predictor={self.predictor} {'tiles' if self.tiled else 'strips'} {self.seg_w}x{getattr(self, 'seg_h', '?')}>")
+                f"predictor={self.predictor} bands={getattr(self, 'bands', '?')} {'tiles' if self.tiled else 'strips'} {self.seg_w}x{getattr(self, 'seg_h', '?')}>")
+
+
+_ITEM = re.compile(r"<Item\b([^>]*)>(.*?)</Item\s*>", re.S)
+_ATTR = re.compile(r"""([A-Za-z_][\w.-]*)\s*=\s*["']([^"']*)["']""")
+
+
+def _unescape(text):
+    for a, b in (("&lt;", "<"), ("&gt;", ">"), ("&quot;", '"'), ("&apos;", "'"), ("&amp;", "&")):
+        text = text.replace(a, b)
+    return text
+
+
+class Step:
+    """One time step of a stack: band ``band`` of ``page``.  What the page says of the image (``compression``, ``predictor``, ``dtype``,
+    ...) reads through; ``segments`` are those that hold the band."""
+
+    __slots__ = ("page", "band")
+
+    def __init__(self, page, band):
+        self.page, self.band = page, band
+
+    def __getattr__(self, name):
+        return getattr(self.page, name)
+
+    def segments(self, box=None):
+        return self.page.segments(box, self.band)
+
+    def __repr__(self):
+        return f"<tiff.Step band {self.band} of {self.page!r}>"
 
 
 class TiffFile:
@@ -349,7 +428,8 @@ def _timestamps(v):
 class TiffStack:
     """The pages of one or many TIFF files in time order, as one (time, latitude, longitude) variable: ``shape``, ``dtype`` (the
     stored type, native byte order), ``nodata``, ``attrs`` (``_FillValue`` where there is a nodata value), ``time``, ``latitude``,
-    ``longitude``, and ``steps``: the `Page` of every time step.  Pages of one stack share grid, type and nodata value."""
+    ``longitude``, and ``steps``: the `Step` (page, band) of every time step — every band of every page, in page order, then band
+    order.  Pages of one stack share grid, type and nodata value; they may differ in band count and planar configuration."""
 
     def __init__(self, paths, tiff_time=None):
         paths = [paths] if isinstance(paths, (str, os.PathLike)) else list(paths)
@@ -357,10 +437,11 @@ class TiffStack:
             raise ValueError("a TIFF stack needs a file")
         self.files = [TiffFile(p) for p in paths]
         self.paths = [f.path for f in self.files]
-        self.steps = [pg for f in self.files for pg in f.pages]
-        first = self.steps[0]
+        self.pages = [pg for f in self.files for pg in f.pages]
+        self.steps = [Step(pg, b) for pg in self.pages for b in range(pg.bands)]
+        first = self.pages[0]
         key = first.grid_key()
-        for pg in self.steps[1:]:
+        for pg in self.pages[1:]:
             if pg.grid_key() != key:
                 what = ("size" if (pg.width, pg.height) != (first.width, first.height) else "type" if pg.dtype != first.dtype else
                         "nodata value" if pg.nodata != first.nodata else "grid coordinates")
@@ -375,17 +456,25 @@ class TiffStack:
     def _time(self, tiff_time):
         n = len(self.steps)
         if tiff_time is None:
-            many = [f.path for f in self.files if len(f.pages) > 1]
-            if many:
-                raise ValueError(f"{many[0]}: a multi-page file has no time axis and its name gives one step: pass tiff_time= "
-                                 "(a sequence of timestamps, or a callable path -> timestamps)")
-            times = [time_from_name(f.path) for f in self.files]
+            times = []
+            for f in self.files:
+                if len(f.pages) == 1 and f.pages[0].bands == 1:
+                    times.append(time_from_name(f.path))
+                    continue
+                got = _times_from_descriptions(f.pages[0]) if len(f.pages) == 1 else None
+                if got is None:
+                    kind = "multi-page" if len(f.pages) > 1 else "multi-band"
+                    raise ValueError(f"{f.path}: a {kind} file has no time axis and its name gives one step: pass tiff_time= "
+                                     "(a sequence of timestamps, or a callable path -> timestamps), or band descriptions that hold a date")
+                times += got
         elif callable(tiff_time):
             times = []
             for f in self.files:
                 got = _timestamps(tiff_time(f.path))
-                if len(got) != len(f.pages):
-                    raise ValueError(f"{f.path}: tiff_time gave {len(got)} timestamp(s) for {len(f.pages)} page(s)")
+                want = sum(pg.bands for pg in f.pages)
+                if len(got) != want:
+                    bands = "" if want == len(f.pages) else f" of {want} band(s) in all"
+                    raise ValueError(f"{f.path}: tiff_time gave {len(got)} timestamp(s) for {len(f.pages)} page(s){bands}")
                 times += got
         else:
             times = _timestamps(tiff_time)
@@ -404,9 +493,15 @@ class TiffStack:
         idx = list(range(self.shape[0])) if steps is None else list(steps)
         _, H, W = self.shape
         out = np.empty((len(idx), H, W), dtype=self.dtype)
+        # what is decoded: a planar or single-band step's own segments; a chunky page's segments once, for all of its bands asked for
+        jobs = {}
         for i, t in enumerate(idx):
-            pg = self.steps[t]
-            k, y, x, rows, pitch, nbytes = pg.segments()
+            st = self.steps[t]
+            jobs.setdefault((id(st.page), st.band if not st.page.chunky else -1), (st, []))[1].append((i, st.band))
+        for st, takes in jobs.values():
+            pg = st.page
+            B = pg.bands if pg.chunky else 1
+            k, y, x, rows, pitch, nbytes = st.segments()
             bufs = [np.empty(int(b), dtype=np.uint8) for b in nbytes]
             locs = [(pg.path, int(pg.offsets[j]), int(pg.counts[j])) for j in k]
             if pg.compression == COMPRESSION_LZW:
@@ -417,9 +512,10 @@ class TiffStack:
                 locs = [(p, o, int(b)) for (p, o, _), b in zip(locs, nbytes)]
                 codec.decode_ranges("raw", locs, bufs, threads=threads)
             for buf, yy, xx, r, p in zip(bufs, y.tolist(), x.tolist(), rows.tolist(), pitch.tolist()):
-                seg = undo_predictor(buf, r, p, pg.dtype, pg.predictor, pg.byteorder)
+                seg = undo_predictor(buf, r, p, pg.dtype, pg.predictor, pg.byteorder, B)
                 hh, ww = min(r, H - yy), min(p, W - xx)
-                out[i, yy:yy + hh, xx:xx + ww] = seg[:hh, :ww]
+                for i, band in takes:
+                    out[i, yy:yy + hh, xx:xx + ww] = seg[:hh, :ww] if B == 1 else seg[:hh, :ww, band]
         return out
 
     def read(self, steps=None, threads: int = 8) -> np.ndarray:
@@ -429,16 +525,26 @@ class TiffStack:
         return _cf_mask_scale(self.read_raw(steps, threads), self.attrs)
 
 
-def undo_predictor(buf: np.ndarray, rows: int, pitch: int, dtype, predictor: int, byteorder: str) -> np.ndarray:
-    """One decoded segment (uint8) -> its (rows, pitch) samples in native byte order, the predictor undone along every row."""
+def _times_from_descriptions(page):
+    """The time steps the band descriptions of ``page`` give (`Page.band_descriptions`, `time_from_name`'s patterns), or None unless
+    every band has a description that holds a date."""
+    times = [None if d is None else _date_in(d) for d in page.band_descriptions()]
+    return None if any(t is None for t in times) else times
+
+
+def undo_predictor(buf: np.ndarray, rows: int, pitch: int, dtype, predictor: int, byteorder: str, bands: int = 1) -> np.ndarray:
+    """One decoded segment (uint8) -> its (rows, pitch) samples — (rows, pitch, bands) of a chunky segment of ``bands`` > 1 — in native
+    byte order, the predictor undone along every row at a stride of ``bands`` samples, as libtiff does it."""
     dtype = np.dtype(dtype)
-    E = dtype.itemsize
+    E, B = dtype.itemsize, int(bands)
+    shape = (rows, pitch) if B == 1 else (rows, pitch, B)
     if predictor == 3:
-        # a running sum over the row's bytes, then sample i is the bytes i, pitch + i, 2 pitch + i, ... — most significant first,
-        # whatever the file's byte order
-        b = np.cumsum(buf.reshape(rows, pitch * E), axis=1, dtype=np.uint8)
-        return np.ascontiguousarray(b.reshape(rows, E, pitch).transpose(0, 2, 1)).view(dtype.newbyteorder(">")).reshape(rows, pitch).astype(dtype)
-    a = buf.view(dtype.newbyteorder(byteorder)).reshape(rows, pitch).astype(dtype)
+        # a running sum over the row's bytes at stride B — the bytes of one band are one chain through all the planes, since pitch * B is
+        # a multiple of B —, then sample i = pixel * B + band is the bytes i, pitch * B + i, 2 pitch * B + i, ... — most significant
+        # first, whatever the file's byte order
+        b = np.cumsum(buf.reshape(rows, pitch * E, B), axis=1, dtype=np.uint8)
+        return np.ascontiguousarray(b.reshape(rows, E, pitch * B).transpose(0, 2, 1)).view(dtype.newbyteorder(">")).reshape(shape).astype(dtype)
+    a = buf.view(dtype.newbyteorder(byteorder)).reshape(rows, pitch, B).astype(dtype)
     if predictor == 2:
         a = np.cumsum(a, axis=1, dtype=dtype)                       # wraps in the sample's width
-    return a
+    return a.reshape(shape)

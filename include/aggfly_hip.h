@@ -338,6 +338,23 @@ int afhip_tiff_place(const void* decoded_dev, int64_t decoded_bytes, const afhip
                      int elem_size, int predictor, int swap, void* cube_dev, int64_t NT, int64_t NY, int64_t NX,
                      int64_t y0, int64_t x0, int64_t ny, int64_t nx, int64_t t0, int64_t cy, int64_t cx, int32_t* errors_dev, void* stream);
 
+/* afhip_tiff_place_bands: afhip_tiff_place for chunky multi-band segments (SamplesPerPixel = bands, PlanarConfiguration 1), every band
+ * a time step.  The same records: a decoded segment holds rows * pitch * bands samples, `pitch` counts pixels, sample
+ * (row, pixel, band) lies at (row * pitch + pixel) * bands + band, and `t` is the step of the segment's band 0.  The predictor is undone
+ * at a stride of `bands` samples as libtiff does it (2: sample i adds sample i - bands, after the byte swap; 3: a running sum mod 256
+ * over the row's pitch * bands * elem_size bytes at stride `bands`, continuing across the byte planes, sample i gathered from the bytes
+ * plane * (pitch * bands) + i, most significant plane first), and the sample goes to
+ * cube[t0 + t + band, cy + y + row - y0, cx + x + pixel - x0] when it lies in the box and 0 <= t + band < NT - t0.  t may be negative
+ * down to -(bands - 1): a time window that begins or ends inside a page's bands drops the bands outside it.  A record is unsound —
+ * not placed, counted in *errors_dev — as for afhip_tiff_place, with rows * pitch * bands samples, or with t <= -bands or
+ * t >= NT - t0.  AFHIP_E_INVALID as for afhip_tiff_place, and bands outside 1 .. 65535.  Nothing is read outside the decoded buffer,
+ * nothing written outside the box.  A tiled transpose through LDS (aggfly_amd/csrc/afhip_tiff_kernels.h: k_tiff_place_bands); planar
+ * files (PlanarConfiguration 2) hold single-band segments and go through afhip_tiff_place.  Parity with a GDAL- or Earth-Engine-written
+ * multi-band file is unverified.  Enqueues on `stream` and retains nothing. */
+int afhip_tiff_place_bands(const void* decoded_dev, int64_t decoded_bytes, const afhip_tiff_seg* records_dev, int64_t n, int64_t max_rows,
+                           int64_t bands, int elem_size, int predictor, int swap, void* cube_dev, int64_t NT, int64_t NY, int64_t NX,
+                           int64_t y0, int64_t x0, int64_t ny, int64_t nx, int64_t t0, int64_t cy, int64_t cx, int32_t* errors_dev, void* stream);
+
 /* Chunk decode in HBM ("or GPU-side decode"; the reference decodes on host threads inside its dask
  * graph, aggfly/dataset/dataset.py:697-728).  Blosc-1 chunks whose streams are LZ4 cross PCIe compressed; the host parses
  * the containers (afcodec_blosc_lz4_plan, include/aggfly_codec.h) into the two record lists below, which travel to HBM with
