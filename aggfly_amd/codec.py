@@ -574,11 +574,21 @@ def zstd_plan(base: np.ndarray, comp_off, comp_size, out_off, out_size, frames: 
     return ZstdPlan(int(nf.value), int(nb.value), int(lit.value), int(nsq.value), int(dec.value), res)
 
 
-def zstd_emulate(base: np.ndarray, frames: np.ndarray, blocks: np.ndarray, plan: ZstdPlan, out: np.ndarray):
+def _emulation_scratch(scratch, nbytes: int) -> np.ndarray:
+    """A fresh zeroed scratch, or the caller's (uint8, contiguous, 16-byte aligned like the device's, at least ``nbytes``) as it is."""
+    if scratch is None:
+        return np.zeros(nbytes, dtype=np.uint8)
+    if scratch.dtype != np.uint8 or not scratch.flags.c_contiguous or scratch.nbytes < nbytes or scratch.ctypes.data % 16:
+        raise ValueError(f"scratch must be a contiguous, 16-byte aligned uint8 array of at least {nbytes} bytes")
+    return scratch
+
+
+def zstd_emulate(base: np.ndarray, frames: np.ndarray, blocks: np.ndarray, plan: ZstdPlan, out: np.ndarray, scratch: np.ndarray | None = None):
     """Run the passes of the GPU decode (`hip.zstd_decode`) on this thread — the host reference of the GPU algorithm, for
-    tests.  -> (errors, pointer-jump rounds)."""
+    tests.  ``scratch``: the passes' scratch (at least ``plan.scratch_bytes()``), whose previous content is not an input; a fresh
+    zeroed array when None.  -> (errors, pointer-jump rounds)."""
     lib = load()
-    scratch = np.zeros(plan.scratch_bytes(), dtype=np.uint8)
+    scratch = _emulation_scratch(scratch, plan.scratch_bytes())
     err, rounds = C.c_int32(0), C.c_int32(0)
     lib.afcodec_zstd_emulate(base.ctypes.data, base.nbytes, frames.ctypes.data, plan.n_frames, blocks.ctypes.data, plan.n_blocks,
                              plan.lit_bytes, plan.n_seqs, plan.dec_bytes, scratch.ctypes.data, out.ctypes.data, C.byref(err),
@@ -681,11 +691,12 @@ def inflate_plan(base: np.ndarray, comp_off, comp_size, out_off, out_size, strea
     return InflatePlan(int(ns.value), int(nsh.value), int(nb.value), int(nsq.value), int(npc.value), int(dec.value), int(tmp.value), max_b, res)
 
 
-def inflate_emulate(base: np.ndarray, streams: np.ndarray, shuf: np.ndarray, plan: InflatePlan, out: np.ndarray):
+def inflate_emulate(base: np.ndarray, streams: np.ndarray, shuf: np.ndarray, plan: InflatePlan, out: np.ndarray,
+                    scratch: np.ndarray | None = None):
     """Run the passes of the GPU decode (`hip.inflate_decode`) on this thread — the host reference of the GPU algorithm, for
-    tests.  -> (errors, pointer-jump rounds)."""
+    tests.  ``scratch`` as for `zstd_emulate`.  -> (errors, pointer-jump rounds)."""
     lib = load()
-    scratch = np.zeros(plan.scratch_bytes(), dtype=np.uint8)
+    scratch = _emulation_scratch(scratch, plan.scratch_bytes())
     err, rounds = C.c_int32(0), C.c_int32(0)
     lib.afcodec_inflate_emulate(base.ctypes.data, base.nbytes, streams.ctypes.data, plan.n_streams, shuf.ctypes.data, plan.n_shuf,
                                 plan.n_pblocks, plan.n_seqs, plan.n_pieces, plan.dec_bytes, plan.tmp_bytes, scratch.ctypes.data,

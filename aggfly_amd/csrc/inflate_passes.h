@@ -244,6 +244,23 @@ AFZ_FN int afi_is_bad(const afi_ctx* c, int64_t s) {
 #endif
 }
 
+/* afz_mark_bad_in_fill / afz_was_bad_before_fill of zstd_passes.h for this context: the fill pass sets 2 and asks for 1. */
+AFZ_FN void afi_mark_bad_in_fill(const afi_ctx* c, int64_t s) {
+#if defined(__HIPCC__)
+    if (atomicExch(&c->bad[s], 2) == 0) atomicAdd(c->errors, 1);
+#else
+    if (c->bad[s] == 0) { c->bad[s] = 2; *c->errors += 1; }
+#endif
+}
+
+AFZ_FN int afi_was_bad_before_fill(const afi_ctx* c, int64_t s) {
+#if defined(__HIPCC__)
+    return __hip_atomic_load(&c->bad[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1;
+#else
+    return c->bad[s] == 1;
+#endif
+}
+
 /* ---- pass 1: the front end of stream s; slot: its table slot (NULL: the one in the scratch) ---- */
 typedef struct afi_emit {
     uint8_t* lit; afz_seq* seq; afi_pblock* pb;
@@ -406,16 +423,31 @@ AFZ_FN void afi_pass_front(const afi_ctx* c, int64_t s, uint8_t* slot) {
     c->want[s] = want;
 }
 
+/* afz_stop_range of zstd_passes.h for this context: src[] of the bytes [p0, p1) that nobody will fill = "a literal". */
+AFZ_FN void afi_stop_range(const afi_ctx* c, int64_t p0, int64_t p1, int l, int nl) {
+    if (p0 < 0) p0 = 0;
+    if (p1 > c->dec_bytes) p1 = c->dec_bytes;
+    for (int64_t p = p0 + l; p < p1; p += nl) c->src[p] = AFZ_LIT;
+}
+
 /* ---- pass 2: src[] of pseudo-block b, lane l of nl ---- */
 AFZ_FN void afi_pass_fill(const afi_ctx* c, int64_t b, int l, int nl) {
     if (b >= c->n_blocks) return;
     const afi_pblock* k = &c->pblocks[b];
-    if (afi_is_bad(c, k->stream)) return;
     const afi_stream* st = &c->streams[k->stream];
+    if (afi_was_bad_before_fill(c, k->stream)) {       /* the front end stopped somewhere: this slot's share of the stream's bytes */
+        const int64_t i = b - st->first_block, n = st->n_blocks > 0 ? st->n_blocks : 1;
+        afi_stop_range(c, st->base + st->dsize / n * i, i == n - 1 ? st->base + st->dsize : st->base + st->dsize / n * (i + 1), l, nl);
+        return;
+    }
     int64_t pos = k->out_pos, lit = k->lit_off;
     for (int32_t i = 0; i < k->nseq; ++i) {
         const afz_seq s = c->seqs[k->seq_off + i];
-        if (s.off <= 0 || s.off > pos + s.ll - st->base) { if (l == 0) afi_mark_bad(c, k->stream); return; }
+        if (s.off <= 0 || s.off > pos + s.ll - st->base) {              /* (the same for every lane) */
+            if (l == 0) afi_mark_bad_in_fill(c, k->stream);
+            afi_stop_range(c, pos, k->out_pos + k->dsize, l, nl);
+            return;
+        }
         for (int64_t j = l; j < s.ll; j += nl) c->src[pos + j] = AFZ_LIT | (uint32_t)(lit + j);
         pos += s.ll; lit += s.ll;
         for (int64_t j = l; j < s.ml; j += nl) c->src[pos + j] = (uint32_t)(pos + j - s.off);

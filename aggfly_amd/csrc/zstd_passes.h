@@ -334,6 +334,24 @@ AFZ_FN int afz_is_bad(const afz_ctx* c, int32_t f) {
 #endif
 }
 
+/* The fill pass is the one pass that both asks for the flag and sets it from another work item of the same frame.  It sets 2 and asks
+ * for 1, so that what a block of the pass does never depends on when a sibling block found its defect. */
+AFZ_FN void afz_mark_bad_in_fill(const afz_ctx* c, int32_t f) {
+#if defined(__HIPCC__)
+    if (atomicExch(&c->bad[f], 2) == 0) atomicAdd(c->errors, 1);
+#else
+    if (c->bad[f] == 0) { c->bad[f] = 2; *c->errors += 1; }
+#endif
+}
+
+AFZ_FN int afz_was_bad_before_fill(const afz_ctx* c, int32_t f) {
+#if defined(__HIPCC__)
+    return __hip_atomic_load(&c->bad[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1;
+#else
+    return c->bad[f] == 1;
+#endif
+}
+
 /* ---- pass 1: tables of block b (b == n_blocks: the predefined FSE tables) ---- */
 AFZ_FN int afz_huffman_table(const afz_ctx* c, const afz_block* k, uint8_t* slot) {
     uint8_t* w = slot + AFZ_SLOT_WORK;
@@ -570,12 +588,25 @@ AFZ_FN void afz_pass_frame(const afz_ctx* c, int64_t f) {
     if (pos - fr->base != fr->size) afz_mark_bad(c, (int32_t)f);
 }
 
+/* src[] of the bytes [p0, p1) that nobody will fill, clipped to the batch: "a literal", where a pointer-jump round stops.  The
+ * rounds visit every byte of the batch, those of a bad frame too; what they find there must not be what the scratch held before
+ * the call (the count of rounds with work is an output, and stale entries would be chased). */
+AFZ_FN void afz_stop_range(const afz_ctx* c, int64_t p0, int64_t p1, int l, int nl) {
+    if (p0 < 0) p0 = 0;
+    if (p1 > c->dec_bytes) p1 = c->dec_bytes;
+    for (int64_t p = p0 + l; p < p1; p += nl) c->src[p] = AFZ_LIT;
+}
+
 /* ---- pass 5: src[] of block b, lane l of nl ---- */
 AFZ_FN void afz_pass_fill(const afz_ctx* c, int64_t b, int l, int nl) {
     if (b >= c->n_blocks) return;
     const afz_block* k = &c->blocks[b];
-    if (afz_is_bad(c, k->frame)) return;
     const afz_frame* fr = &c->frames[k->frame];
+    if (afz_was_bad_before_fill(c, k->frame)) {        /* its block sizes may be unknown: this block's share of the frame's bytes */
+        const int64_t i = b - fr->first_block, n = fr->n_blocks > 0 ? fr->n_blocks : 1;
+        afz_stop_range(c, fr->base + fr->size / n * i, i == n - 1 ? fr->base + fr->size : fr->base + fr->size / n * (i + 1), l, nl);
+        return;
+    }
     int64_t pos = c->out_pos[b], lit = k->lit_off;
     const int32_t* ri = c->rep_in + 3 * b;
     int any = 0;
@@ -583,7 +614,11 @@ AFZ_FN void afz_pass_fill(const afz_ctx* c, int64_t b, int l, int nl) {
         for (int32_t i = 0; i < k->nseq; ++i) {
             const afz_seq s = c->seqs[k->seq_off + i];
             const int64_t off = afz_resolve(s.off, ri);
-            if (off <= 0 || off > pos + s.ll - fr->base) { if (l == 0) afz_mark_bad(c, k->frame); return; }
+            if (off <= 0 || off > pos + s.ll - fr->base) {          /* (the same for every lane) */
+                if (l == 0) afz_mark_bad_in_fill(c, k->frame);
+                afz_stop_range(c, pos, c->out_pos[b] + c->dsize[b], l, nl);
+                return;
+            }
             for (int64_t j = l; j < s.ll; j += nl) c->src[pos + j] = AFZ_LIT | (uint32_t)(lit + j);
             pos += s.ll; lit += s.ll;
             for (int64_t j = l; j < s.ml; j += nl) c->src[pos + j] = (uint32_t)(pos + j - off);

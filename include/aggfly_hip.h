@@ -8,7 +8,8 @@
  * Conventions
  *   - plain pointers and sizes only; no C++/torch types cross this boundary;
  *   - `*_dev` pointers are device (HBM) addresses owned by the caller; tables marked
- *     HOST are read on the host during the call and may be freed afterwards;
+ *     HOST are read on the host during the call and may be freed afterwards; an entry reads no byte of a scratch, a workspace, a
+ *     `tmp` or a slots buffer that it has not written in the same call: their previous content is not an input;
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream); all work is
  *     enqueued on it and the call returns without synchronising unless stated;
  *   - cubes are time-major: element (k, cell) at cube[k * n_cells + cell], cell =
