@@ -1305,7 +1305,14 @@ extern "C" int afhip_transform(const void* x_dev, int x_dtype, int64_t n, int tr
     const int64_t per_block = (int64_t)WG * TRANSFORM_PER_THREAD;
     const int64_t blocks = (n + per_block - 1) / per_block;
     if (blocks > 0x7fffffff) return fail(AFHIP_E_INVALID, "transform: array too large for one launch");
-    hipLaunchKernelGGL(k_transform, dim3((unsigned)blocks), dim3(WG), 0, (hipStream_t)stream, ta);
+    const dim3 grid((unsigned)blocks), block(WG);
+    hipStream_t st = (hipStream_t)stream;
+    switch (ta.tf) {
+        case TF_POWI: hipLaunchKernelGGL(k_transform<TF_POWI>, grid, block, 0, st, ta); break;
+        case TF_POW: hipLaunchKernelGGL(k_transform<TF_POW>, grid, block, 0, st, ta); break;
+        case TF_HINGE: hipLaunchKernelGGL(k_transform<TF_HINGE>, grid, block, 0, st, ta); break;
+        default: hipLaunchKernelGGL(k_transform<TF_INTER>, grid, block, 0, st, ta); break;
+    }
     HIP_TRY(hipGetLastError());
     return AFHIP_OK;
 }

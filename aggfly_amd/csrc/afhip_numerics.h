@@ -31,6 +31,28 @@ __device__ __forceinline__ double clamp_finite(double x) {
 // made finite in place (inf + finite = inf).  (A v_cmp_class on hi and a select — between hi and hi + lo, or on lo — kept two more
 // VGPRs alive in 343 / 441 of the 529 kernels and cost 18 / 36 of them a wave per SIMD; profiles/special_values.txt.)
 __device__ __forceinline__ double powi_finish(double hi, double lo) { return hi + clamp_finite(lo); }
+// ... with the chain's sign.  hi + lo has hi's sign wherever it is not zero (|lo| is a few ulps of hi); where it is zero it is +0 unless
+// both are -0, and hi's sign is the power's.  So hi's sign bit is OR-ed in: two VALU on the high dword, no compare, no select, nothing
+// kept alive.  The mask is a literal of the v_and_b32 itself: as a copysign the compiler parks 0x7fffffff in a scalar register for the
+// whole kernel, which cost one variant its eighth wave (profiles/numerics_exact.txt).  That is one compiler's register allocation:
+// __builtin_copysign(x, hi) computes the same value on every (x, hi) the chain produces and is the form to go back to, resource lines
+// permitting, should a toolchain reject or mis-schedule the assembly.  (An OR, not a copysign: the two differ where x < 0 <= hi, which
+// the chain cannot produce; the host branch below is the same OR.)
+__device__ __forceinline__ double or_sign(double x, double hi) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t hh = (uint32_t)((uint64_t)__double_as_longlong(hi) >> 32);
+    uint32_t s;
+    asm("v_and_b32 %0, 0x80000000, %1" : "=v"(s) : "v"(hh));
+    return __longlong_as_double((long long)((uint64_t)__double_as_longlong(x) | ((uint64_t)s << 32)));
+#else
+    uint64_t xb, hb;
+    __builtin_memcpy(&xb, &x, 8);
+    __builtin_memcpy(&hb, &hi, 8);
+    xb |= hb & 0x8000000000000000ull;
+    __builtin_memcpy(&x, &xb, 8);
+    return x;
+#endif
+}
 
 // x**e for a small integer e, evaluated as a double-double product chain so that the
 // result is the correctly rounded power in all but ~1e-14 of cases — what libm's pow()
@@ -42,9 +64,17 @@ __device__ __forceinline__ double powi_finish(double hi, double lo) { return hi 
 // (one fma) and the small term rounded once (a second fma) — |lo| stays within a few ulps of hi for every exponent lowered to this
 // form (|e| <= 64), so its rounding errors are of order 2^-106 and only the final hi + lo rounds at 2^-53.  Three instructions per
 // step, two for the first (lo = 0), instead of the six of a renormalising step: x^3 6 instructions, x^4 9 (were 13 and 19).
-// ZERO_SIGN (k_transform, held to np.power's signed zeros): a power that underflows is the +-0 of its product chain — hi — where
-// hi + lo may be -0 + +0 = +0; the fused kernels leave it (their power columns are held by value: an outer sum starts at +0.0 and
-// loses the sign anyway).
+// Zeros: a power that underflows is the +-0 of its product chain — hi — where hi + lo may be -0 + +0 = +0, and under a negative
+// exponent that sign is the sign of an infinity ((-0)^-3 and (-1e-200)^-3 are -inf).  The result takes hi's sign bit (or_sign, above) in every form
+// that divides or promises np.power's signed zeros (NEG, ZERO_SIGN: k_transform's chain on a scaled mantissa runs with NEG off).
+//
+// What the chain ON x ITSELF does not reach (tests/numerics_cases.py holds every exponent to exact rational arithmetic):
+// "err = hi x - p exactly" needs err representable, so a power below 2^-969 = 2^(-1022 + 53) in magnitude, whose error terms are
+// subnormal or lost, is within one ulp (one step, 2^-1074, below 2^-1022) of the exact power instead of correctly rounded; and a
+// negative exponent takes the reciprocal of the positive power, whatever became of that: +-0 where it overflowed though the exact
+// power is a subnormal, the reciprocal of a product with few bits left where it was subnormal.  The fused kernels keep that
+// (powi_scaled_vec in all of them cost 17 variants a wave per SIMD and one 208 bytes of scratch: profiles/numerics_exact.txt);
+// k_transform does not (powi_scaled_vec, below).
 template <int N, bool NEG = true, bool ZERO_SIGN = false>
 __device__ __forceinline__ void powi_dd_vec(double (&x)[N], int e) {
     if (e == 0) {
@@ -78,9 +108,9 @@ __device__ __forceinline__ void powi_dd_vec(double (&x)[N], int e) {
         }
 #pragma unroll
         for (int i = 0; i < N; ++i) x[i] = powi_finish(hi[i], lo[i]);
-        if constexpr (ZERO_SIGN) {
+        if constexpr (NEG || ZERO_SIGN) {
 #pragma unroll
-            for (int i = 0; i < N; ++i) x[i] = (x[i] == 0.0) ? hi[i] : x[i];
+            for (int i = 0; i < N; ++i) x[i] = or_sign(x[i], hi[i]);
         }
     }
     if constexpr (NEG) {                // (the lean short-group forms take non-negative exponents only: no division code in them)
@@ -90,6 +120,70 @@ __device__ __forceinline__ void powi_dd_vec(double (&x)[N], int e) {
             for (int i = 0; i < N; ++i) x[i] = 1.0 / x[i];
         }
     }
+}
+
+// frexp as two instructions, without the library's special-case code: v_frexp_mant_f64 / v_frexp_exp_i32_f64 split a finite non-zero
+// x (subnormals included) into f in +-[0.5, 1) and k with x = f 2^k, and return (x, 0) for x = +-0, +-inf and NaN.
+__device__ __forceinline__ double frexp_mant(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_frexp_mant(x);
+#else
+    int k;
+    return (x == 0.0 || x != x || x - x != 0.0) ? x : frexp(x, &k);
+#endif
+}
+__device__ __forceinline__ int frexp_exp(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_frexp_exp(x);
+#else
+    int k = 0;
+    if (!(x == 0.0 || x != x || x - x != 0.0)) (void)frexp(x, &k);
+    return k;
+#endif
+}
+// The library's pow(x, y), except where x = +-2^m and m y is an integer: that power is +-2^(m y) exactly, by v_ldexp_f64 — the
+// library's pow is within an ulp or two and gave the neighbour of 2^130 for 4^65 (tests/test_gpu_numerics.py: the lowering boundary).
+// m y is formed without a rounding (the fma's remainder is zero) or the library's value stands; a negative x needs an integer y,
+// whose parity gives the sign; +-0, +-inf and NaN have no mantissa of +-0.5 and keep the library's answers.  k_transform's form.
+__device__ __forceinline__ double pow_exact_pow2(double x, double y) {
+    double r = pow(x, y);
+    const double f = frexp_mant(x);
+    if (f == 0.5 || f == -0.5) {
+        const double m = (double)(frexp_exp(x) - 1);
+        const double my = m * y;
+        const bool whole = my == floor(my) && __fma_rn(m, y, -my) == 0.0 && fabs(my) < 4096.0;
+        if (whole && (x > 0.0 || y == floor(y))) {
+            const bool neg = x < 0.0 && 0.5 * y != floor(0.5 * y);          // an odd integer y (from 2^53 on every double is even)
+            r = ldexp(neg ? -1.0 : 1.0, (int)my);
+        }
+    }
+    return r;
+}
+
+// x**e as powi_dd_vec<N, true, true> gives it, for every x: for |e| >= 3 and e = -2 the chain runs on frexp's mantissa f — every
+// product in [2^-64, 1), every error term normal or zero, nothing overflows — and x^e = f^e 2^(k e) by one v_ldexp_f64, which is exact
+// where the result is normal, rounds once more where it is subnormal (within one step, 2^-1074, of the exact power) and saturates to
+// +-inf / +-0.  So a positive power is correctly rounded down to 2^-1022, (2^20)^-52 is 2^-1040 instead of the reciprocal of an
+// infinity, and a negative power is within one ulp whatever the size of the positive one.  Four more instructions per element and an
+// int register each: k_transform's form, a plain HBM stream with VALU to spare.  x^2 and x^-1 stay single IEEE operations.
+template <int N>
+__device__ __forceinline__ void powi_scaled_vec(double (&x)[N], int e) {
+    const int n = e < 0 ? -e : e;
+    if (n < 2 || e == 2) {
+        powi_dd_vec<N, true, true>(x, e);
+        return;
+    }
+    int k[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) { k[i] = frexp_exp(x[i]) * e; x[i] = frexp_mant(x[i]); }
+    powi_dd_vec<N, false, true>(x, n);
+    if (e < 0) {
+        KEEP_BRANCH();
+#pragma unroll
+        for (int i = 0; i < N; ++i) x[i] = 1.0 / x[i];
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) x[i] = ldexp(x[i], k[i]);
 }
 __device__ __forceinline__ double powi_dd(double x, int e) {
     double v[1] = {x};
@@ -122,8 +216,12 @@ __device__ __forceinline__ double rcp_range(double x) {
 }
 // a / b given y ~ 1/b (Markstein): q0 = a*y, r = a - b*q0 exactly (fma), q = q0 + r*y.  With y the
 // CORRECTLY rounded reciprocal (the host's 1.0/n for a group length n) q is the correctly rounded
-// quotient — bit-identical to a true division (checked against exact rational arithmetic,
-// DESIGN.md §5); with a faithful y it is within 1 ulp.  v_div_fixup restores the IEEE results for
+// quotient — bit-identical to a true division — wherever |a / b| >= 2^-1022; a SUBNORMAL quotient is
+// within one step (2^-1074) of it: r is exact, but q0 + r*y then rounds a value that is not a / b, and
+// on an exact tie (2856 * 2^-1074 / 48 = 59.5 steps) the rounded y decides the direction instead of
+// ties-to-even.  Checked against exact rational arithmetic over group lengths 1 .. 48 in
+// tests/test_numerics_host.py (the emulated text) and tests/test_gpu_numerics.py (the kernels);
+// DESIGN.md §5.  With a faithful y it is within 1 ulp.  v_div_fixup restores the IEEE results for
 // inf / NaN / zero operands.
 __device__ __forceinline__ double div_by_finite(double a, double b, double y) {   // finite a, normal b
     const double q0 = a * y;

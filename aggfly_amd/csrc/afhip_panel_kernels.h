@@ -756,6 +756,10 @@ struct TransformArgs {
     double arg;
 };
 
+// One instantiation per transform (TF = a.tf): the library's pow needs 86 VGPRs, and as one kernel its registers were every
+// transform's — five waves per SIMD instead of eight cost the float32 hinge and integer powers a fifth of their rate
+// (profiles/numerics_exact.txt).
+template <int TF>
 __global__ __launch_bounds__(WG) void k_transform(const TransformArgs a) {
     const int64_t base = (int64_t)blockIdx.x * (WG * TRANSFORM_PER_THREAD) + threadIdx.x;
     double v[TRANSFORM_PER_THREAD], o[TRANSFORM_PER_THREAD];
@@ -765,15 +769,15 @@ __global__ __launch_bounds__(WG) void k_transform(const TransformArgs a) {
         const int64_t ic = i < a.n ? i : a.n - 1;                     // clamped: the tail re-reads the last element
         v[u] = a.x_f32 ? (double)((const float*)a.x)[ic] : ((const double*)a.x)[ic];
         o[u] = 1.0;
-        if (a.tf == TF_INTER) o[u] = a.other_f32 ? (double)((const float*)a.other)[ic] : ((const double*)a.other)[ic];
+        if (TF == TF_INTER) o[u] = a.other_f32 ? (double)((const float*)a.other)[ic] : ((const double*)a.other)[ic];
     }
     const bool all_f32 = a.x_f32 && a.out_f32;
-    if (a.tf == TF_POWI) {
-        powi_dd_vec<TRANSFORM_PER_THREAD, true, true>(v, a.iarg);       // signed zeros as np.power's
-    } else if (a.tf == TF_POW) {
+    if constexpr (TF == TF_POWI) {
+        powi_scaled_vec<TRANSFORM_PER_THREAD>(v, a.iarg);               // signed zeros as np.power's; exact down to the subnormals
+    } else if constexpr (TF == TF_POW) {
 #pragma unroll
-        for (int u = 0; u < TRANSFORM_PER_THREAD; ++u) v[u] = pow(v[u], a.arg);
-    } else if (a.tf == TF_HINGE) {
+        for (int u = 0; u < TRANSFORM_PER_THREAD; ++u) v[u] = pow_exact_pow2(v[u], a.arg);
+    } else if constexpr (TF == TF_HINGE) {
         if (all_f32) {
             const float kf = (float)a.arg;
 #pragma unroll
